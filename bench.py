@@ -5,7 +5,9 @@
 
 Workload = BASELINE.json configs[1]: batch 64 (8 synthetic 256x256 scenes x 8 targets) per GPU, ResNet-18, fp32,
 stealth loss camdE_caml2, d_thr 5, targeted.  A "step" is one pass of the loop body
-(/root/reference/src/python/projector_based_attack.py:264-328) over the batch, inputs resident in HBM.
+(the reference's src/python/projector_based_attack.py:264-328) over the batch, inputs resident in HBM.  `--steps K` times
+exactly K steps after the W warm-up steps; `ms_per_step` is the timed region over K.  `--dump-outputs DIR` writes the last
+timed step's outputs as DIR/<name>.npy (the inputs are synthetic and seeded: the same arguments give the same inputs).
 N > 1: every rank attacks its own 64 samples (weak scaling, no data-path collective); the only exchange is the final
 result gather, timed separately (`gather_ms`).  `--gpus N` without a torchrun environment starts the N ranks itself
 (before anything touches the GPU).  Prints ONE JSON line on rank 0.
@@ -77,6 +79,37 @@ def build_attack(rank, batch, size, n_scenes, dev, classifier='resnet18', storag
     hp = dict(targeted=True, d_thr=5, adv_lr=2, col_lr=1, p_thresh=0.9)
     st.step = lambda: st.iteration(**hp)
     return st, sd, csd, setup, scenes, targets
+
+
+DUMP_BUDGET_BYTES = 60 * 2 ** 20   # --dump-outputs: at most this much array data in all (64 MB with headroom for the .npy headers)
+
+
+def step_outputs(st, attack):
+    """What the timed path computed in its last step, as [B, 3, H, W] float32 GPU tensors: the arrays a caller of the loop receives
+    (spaa(): cam_infer_best, prj_adv_best; PerC-AL: the best adversarial image) and the step's own current images."""
+    from spaa_amd.models import to_nchw
+    with torch.cuda.device(st.x.device):
+        if attack == 'perc_al':
+            return {'x_adv_best': st.result(), 'x_adv': to_nchw(st.x)}
+        cam_best, prj_best = st.results()
+        return {'cam_infer_best': cam_best, 'prj_adv_best': prj_best, 'prj_adv': to_nchw(st.x),
+                'cam_infer': to_nchw(st._y.float().contiguous())}
+
+
+def dump_outputs(outs, out_dir, budget=DUMP_BUDGET_BYTES):
+    """Writes `out_dir/<name>.npy` (float32) for every array of `outs`.  When the batch does not fit `budget`, every array keeps the
+    same fixed, seeded sample of its samples (rows): the same arguments dump the same rows.  Returns a summary for the result line."""
+    import numpy as np
+    b = next(iter(outs.values())).shape[0]
+    row_bytes = sum(t[0].numel() * 4 for t in outs.values())
+    n = max(1, min(b, budget // row_bytes))
+    rows = np.arange(b) if n == b else np.sort(np.random.default_rng(0).choice(b, n, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    idx = torch.from_numpy(rows).to(next(iter(outs.values())).device)
+    for name, t in outs.items():
+        np.save(os.path.join(out_dir, name + '.npy'), t.index_select(0, idx).float().cpu().numpy())
+    return {'dir': out_dir, 'arrays': {k: [int(n)] + list(t.shape[1:]) for k, t in outs.items()}, 'dtype': 'float32',
+            'rows': [int(r) for r in rows] if n < b else 'all'}
 
 
 def usable_cores():
@@ -493,9 +526,14 @@ def main():
     ap.add_argument('--no-modes', action='store_true',
                     help='skip the extra configurations timed after the headline (f16 storage, Inception-v3, VGG-16 + PerC-AL)')
     ap.add_argument('--profile-out', default=None, help='write the per-layer tapconv timing table (JSON) here')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help="after the timed steps, write what rank 0's last timed step computed as DIR/<name>.npy (float32, at most "
+                         '64 MB in all: a fixed, seeded sample of the batch when it is larger), for output-for-output comparisons')
     ap.add_argument('--rehearse-glue', action='store_true',
                     help='CPU/gloo rehearsal of the multi-rank glue with a stand-in step (tests/); not a measurement')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
 
     world_env = os.environ.get('WORLD_SIZE')
     if args.gpus > 1 and world_env is None:
@@ -570,6 +608,8 @@ def main():
     # final result gather (the path's only exchange, once per attack): prj_adv_best + cam_infer_best of every rank
     cam, prj = st.results()
     gather_ms, _ = gather_final(cam, prj, dist, world, torch.cuda.synchronize)
+    # the last timed step's outputs, before the instrumented passes below run further steps on the same state
+    dumped = dump_outputs(step_outputs(st, args.attack), args.dump_outputs) if args.dump_outputs and rank == 0 else None
 
     # instrumented passes: HIP events around every launch (same stream) -> per-kernel rooflines
     from spaa_amd import convplan
@@ -688,6 +728,8 @@ def main():
         }
         if gather_ms is not None:
             out['gather_ms'] = round(gather_ms, 3)
+        if dumped is not None:
+            out['dump_outputs'] = dumped
         # what the process group and the runtime saw (the driver can check that RCCL really ran N ranks on N devices)
         out['ranks_seen'] = {'world_size': dist.get_world_size() if dist is not None else 1,
                              'backend': dist.get_backend() if dist is not None else None,

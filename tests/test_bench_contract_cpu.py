@@ -74,6 +74,31 @@ def test_rocprof_summary_agrees_with_bench_roofline():
     assert abs(avg_us - b['roofline']['avg_launch_us']) < 0.05 * avg_us, (avg_us, b['roofline']['avg_launch_us'])
 
 
+def test_dump_outputs_writes_a_fixed_sample_within_budget(tmp_path):
+    """`bench.py --dump-outputs DIR`: float32 .npy files; a batch larger than the budget keeps the same seeded rows in every array
+    and from run to run; a batch that fits is written whole."""
+    import numpy as np
+    import torch
+    import bench
+    g = torch.Generator().manual_seed(0)
+    outs = {'a': torch.rand(64, 3, 16, 16, generator=g), 'b': torch.rand(64, 3, 16, 16, generator=g)}
+    row_bytes = 2 * 3 * 16 * 16 * 4
+    s1 = bench.dump_outputs(outs, str(tmp_path / 'd1'), budget=10 * row_bytes + 100)
+    s2 = bench.dump_outputs(outs, str(tmp_path / 'd2'), budget=10 * row_bytes + 100)
+    rows = s1['rows']
+    assert rows == s2['rows'] and len(rows) == 10 and rows == sorted(set(rows)) and all(0 <= r < 64 for r in rows)
+    total = 0
+    for name, t in outs.items():
+        a1, a2 = np.load(tmp_path / 'd1' / f'{name}.npy'), np.load(tmp_path / 'd2' / f'{name}.npy')
+        assert a1.dtype == np.float32 and a1.shape == (10, 3, 16, 16) and np.array_equal(a1, a2)
+        assert np.array_equal(a1, t.numpy()[rows])
+        total += a1.nbytes
+    assert total <= 10 * row_bytes + 100
+    s3 = bench.dump_outputs(outs, str(tmp_path / 'd3'))
+    assert s3['rows'] == 'all' and np.array_equal(np.load(tmp_path / 'd3' / 'a.npy'), outs['a'].numpy())
+    assert bench.DUMP_BUDGET_BYTES <= 64 * 10 ** 6
+
+
 def test_gpus_flag_launches_that_many_ranks():
     """`python bench.py --gpus 2` (no torchrun environment) must start 2 ranks itself and print ONE line with n_gpus 2:
     rehearsed here on gloo with a stand-in step (`--rehearse-glue`: launcher, rendezvous, barrier-bracketed timed region,

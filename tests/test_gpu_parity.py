@@ -3711,3 +3711,29 @@ def test_rccl_path_single_rank():
     line = json.loads(r.stdout.strip().splitlines()[-1])
     assert line['n_gpus'] == 1 and line['value'] > 0 and line['gather_ms'] is not None and line['gather_ms'] > 0
     print(f"bench.py under the nccl process group (1 rank): {line['value']} it/s, gather {line['gather_ms']} ms")
+
+
+def test_bench_dump_outputs(tmp_path):
+    """`bench.py --steps K --dump-outputs DIR` (fresh child process): the result line times exactly K steps, and DIR holds the last
+    timed step's images as float32 .npy files, a seeded sample of the batch within 64 MB."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = tmp_path / 'dump'
+    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--steps', '3', '--warmup', '1', '--no-cpu-baseline', '--no-modes',
+                        '--dump-outputs', str(out)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-4000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line['steps'] == 3 and abs(line['value'] - 1e3 / line['ms_per_step']) < 0.01 * line['value']
+    d = line['dump_outputs']
+    assert sorted(d['arrays']) == ['cam_infer', 'cam_infer_best', 'prj_adv', 'prj_adv_best']
+    total = 0
+    for name, shape in d['arrays'].items():
+        a = np.load(out / f'{name}.npy')
+        assert a.dtype == np.float32 and list(a.shape) == shape and a.shape[1:] == (3, 256, 256) and np.isfinite(a).all(), name
+        total += a.nbytes
+    assert total <= 64 * 10 ** 6 and len(d['rows']) == d['arrays']['prj_adv'][0]
+    for name in ('cam_infer', 'cam_infer_best', 'prj_adv_best'):
+        a = np.load(out / f'{name}.npy')
+        assert a.min() >= 0.0 and a.max() <= 1.0, name
