@@ -10,24 +10,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/spaa_hip.h"
+#include "device_util.hpp"
 
 namespace {
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
-
-// fixed-order block reduction (256 threads); result valid in every thread
-__device__ __forceinline__ float block_sum(float v, float* red) {
-    v = wave_sum(v);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane == 0) red[wave] = v;
-    __syncthreads();
-    return red[0] + red[1] + red[2] + red[3];
-}
 
 // state: [B][4] = succ, best_adv, best, top1      stats: [B][8] = p1, caml2, camdE, col_loss, prjl2, col_loss_best,
 // target logit, reserved

@@ -13,6 +13,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/spaa_hip.h"
+#include "device_util.hpp"
 
 namespace {
 
@@ -347,17 +348,6 @@ __device__ __forceinline__ float de_rgb_grad(float r, float g, float b, float L2
     return d.de;
 }
 
-__device__ __forceinline__ float block_sum_256(float v, float* red) {
-    // wave64 shuffle reduction then 4 partials through LDS, fixed order
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane == 0) red[wave] = v;
-    __syncthreads();
-    return red[0] + red[1] + red[2] + red[3];
-}
-
 // grid: (nblk, B); block 256 px
 __global__ __launch_bounds__(256) void stealth_loss_kernel(const float4* __restrict__ y,
                                                            const float4* __restrict__ scene,
@@ -404,9 +394,9 @@ __global__ __launch_bounds__(256) void stealth_loss_kernel(const float4* __restr
         g_y[idx] = make_float4(g0 * gscale, g1 * gscale, g2 * gscale, 0.f);
         if (de_map != nullptr) de_map[idx] = de;
     }
-    const float s_l2 = block_sum_256(l2, red);
-    const float s_de = block_sum_256(de, red);
-    const float s_de2 = block_sum_256(de * de, red);
+    const float s_l2 = block_sum(l2, red);
+    const float s_de = block_sum(de, red);
+    const float s_de2 = block_sum(de * de, red);
     if (threadIdx.x == 0) {
         float* p = partial + 3 * ((size_t)b * gridDim.x + blockIdx.x);
         p[0] = s_l2;
@@ -438,8 +428,8 @@ __global__ __launch_bounds__(256) void img_dists_kernel(const float4* __restrict
         rgb_to_lab(b.x, b.y, b.z, L2, A2, B2);
         de = ciede2000<false>(L1, A1, B1, L2, A2, B2).de;
     }
-    const float s0 = block_sum_256(sq, red), s1 = block_sum_256(l2, red), s2 = block_sum_256(li, red),
-                s3 = block_sum_256(de, red);
+    const float s0 = block_sum(sq, red), s1 = block_sum(l2, red), s2 = block_sum(li, red),
+                s3 = block_sum(de, red);
     if (threadIdx.x == 0) {
         partial[4 * blockIdx.x + 0] = s0;
         partial[4 * blockIdx.x + 1] = s1;
@@ -493,7 +483,7 @@ __global__ __launch_bounds__(256) void ssim_kernel(const float4* __restrict__ x,
                  ((m11 + m22 + C1) * ((s11[ch] - m11) + (s22[ch] - m22) + C2));
         }
     }
-    const float s = block_sum_256(v, red);
+    const float s = block_sum(v, red);
     if (threadIdx.x == 0) partial[((size_t)b * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = s;
 }
 
@@ -572,7 +562,7 @@ __global__ __launch_bounds__(256) void train_loss_stats_kernel(const float4* __r
             M12[o] = make_float4(m12[0], m12[1], m12[2], 0.f);
         }
     }
-    const float r0 = block_sum_256(s_sum, red), r1 = block_sum_256(l1, red), r2 = block_sum_256(l2, red);
+    const float r0 = block_sum(s_sum, red), r1 = block_sum(l1, red), r2 = block_sum(l2, red);
     if (threadIdx.x == 0) {
         float* pp = partial + 3 * (((size_t)b * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x);
         pp[0] = r0;

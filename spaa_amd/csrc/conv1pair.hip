@@ -16,11 +16,7 @@
 #include <stdlib.h>
 #include <type_traits>
 #include "../../include/spaa_hip.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f2 __attribute__((ext_vector_type(2)));
-typedef float f4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+#include "device_util.hpp"
 
 namespace {
 
@@ -31,7 +27,6 @@ constexpr int NPIX = PH * PW;                  // 1105 staged pixels of 16 B per
 constexpr int NPIECE = (NPIX + 63) / 64;       // 18 one-KiB DMA pieces per source
 constexpr int SRC_BYTES = NPIECE * 1024;
 constexpr int LDS_BYTES = 2 * SRC_BYTES;       // 36 KiB
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
 struct c1p_args {
     const float* xw;
@@ -46,26 +41,15 @@ struct c1p_args {
     int B, H, W, Hm, Wm, tiles_x, tiles_y;
 };
 
-__device__ __forceinline__ void dma16(const __amdgpu_buffer_rsrc_t rsrc, unsigned char* dst, int voff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_ptr_t)dst, 16, voff, 0, 0, 0);
-}
 __device__ __forceinline__ f32x16 mfma2(float a, float b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
 }
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const float* ptr, uint32_t bytes) {
-    const uint64_t addr = reinterpret_cast<uint64_t>(ptr);
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)addr);
-    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(addr >> 32));
-    return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<float*>(((uint64_t)hi << 32) | lo), 0,
-                                             (int)__builtin_amdgcn_readfirstlane(bytes), 0x00020000);
-}
-
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t row_rsrc(const void* base, const size_t byte_off, const int bytes) {
     const uint64_t addr = reinterpret_cast<uint64_t>(base) + byte_off;
     const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)addr);
     const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(addr >> 32));
     return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((uint64_t)hi << 32) | lo), 0,
-                                             (int)__builtin_amdgcn_readfirstlane(bytes), 0x00020000);
+                                             (int)__builtin_amdgcn_readfirstlane(bytes), BUF_RSRC_FLAGS);
 }
 // nibble q of u (q = 0..3) -> byte q: the gate format is one byte per 4 channels
 __device__ __forceinline__ uint32_t spread_nibbles(const uint32_t u) {
@@ -106,7 +90,7 @@ __global__ __launch_bounds__(256, 2) void conv1pair_kernel(const c1p_args p) {
     // ---- stage the two input patches: rows 2 y0 - 1 .., columns 2 x0 - 1 .. (one 16-byte pixel per lane)
     {
         const uint32_t bytes = (uint32_t)p.B * (uint32_t)(p.H * p.W) * 16u;
-        const auto rx = make_rsrc(p.xw, bytes), rs = make_rsrc(p.s, bytes);
+        const auto rx = wave_rsrc(p.xw, bytes), rs = wave_rsrc(p.s, bytes);
         for (int i = wave; i < NPIECE; i += 4) {
             const int q = i * 64 + lane;
             const int py = q / PW, px = q - py * PW;
@@ -205,47 +189,6 @@ __global__ __launch_bounds__(256, 2) void conv1pair_kernel(const c1p_args p) {
 //       of this library): 36 v_mfma_f32_16x16x32_bf16 per 16 pixels
 // instead of 54 v_mfma_f32_32x32x2_f32 of four times the length (46 us of matrix time on 5.4 GFLOP in the kernel above).  The epilogue
 // writes a lane's four channels of a pixel as one 8- / 16-byte store and one gate byte.
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ unsigned int cvt2(float a, float b) {
-    f2 v = {a, b};
-    return __builtin_bit_cast(unsigned int, __builtin_convertvector(v, bf16x2));
-}
-__device__ __forceinline__ float lo_f(unsigned int p) { return __builtin_bit_cast(float, p << 16); }
-__device__ __forceinline__ float hi_f(unsigned int p) { return __builtin_bit_cast(float, p & 0xffff0000u); }
-// 8 fp32 -> three bf16x8 with x == h + m + l exactly
-__device__ __forceinline__ void split8(const f4 a, const f4 b, bf16x8& h, bf16x8& m, bf16x8& l) {
-    const float x[8] = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-    u4 hh, mm, ll;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const unsigned int ph = cvt2(x[2 * i], x[2 * i + 1]);
-        const float r0 = x[2 * i] - lo_f(ph), r1 = x[2 * i + 1] - hi_f(ph);
-        const unsigned int pm = cvt2(r0, r1);
-        const float s0 = r0 - lo_f(pm), s1 = r1 - hi_f(pm);
-        hh[i] = ph;
-        mm[i] = pm;
-        ll[i] = cvt2(s0, s1);
-    }
-    h = __builtin_bit_cast(bf16x8, hh);
-    m = __builtin_bit_cast(bf16x8, mm);
-    l = __builtin_bit_cast(bf16x8, ll);
-}
-// six of the nine partial products of (w0 + w1 + w2) . (p0 + p1 + p2), small terms first
-__device__ __forceinline__ f32x4 mfma6(const bf16x8 (&w)[3], const bf16x8 (&q)[3], f32x4 acc) {
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[2], q[0], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[0], q[2], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[1], q[1], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[1], q[0], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[0], q[1], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[0], q[0], acc, 0, 0, 0);
-    return acc;
-}
 
 template <bool F16>
 __global__ __launch_bounds__(256, 2) void conv1pair_mfma_kernel(const c1p_args p) {
@@ -266,7 +209,7 @@ __global__ __launch_bounds__(256, 2) void conv1pair_mfma_kernel(const c1p_args p
     const int y0 = ty * TH, x0 = tx * TW;
     {   // the two input patches, as the kernel above stages them
         const uint32_t bytes = (uint32_t)p.B * (uint32_t)(p.H * p.W) * 16u;
-        const auto rx = make_rsrc(p.xw, bytes), rs = make_rsrc(p.s, bytes);
+        const auto rx = wave_rsrc(p.xw, bytes), rs = wave_rsrc(p.s, bytes);
         for (int i = wave; i < NPIECE; i += 4) {
             const int q = i * 64 + lane;
             const int py = q / PW, px = q - py * PW;

@@ -4,10 +4,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/spaa_hip.h"
+#include "device_util.hpp"
 
 namespace {
-
-typedef float f4 __attribute__((ext_vector_type(4)));
 
 // 4 consecutive elements of a tensor stored as fp32 or as fp16 (fp16-STORAGE mode: spaa_tapconv_t.io_dtype)
 template <typename T>
@@ -23,7 +22,6 @@ struct io4<float> {
     static __device__ __forceinline__ float ld1(const void* base, size_t idx) { return reinterpret_cast<const float*>(base)[idx]; }
     static __device__ __forceinline__ void st1(void* base, size_t idx, float v) { reinterpret_cast<float*>(base)[idx] = v; }
 };
-typedef _Float16 h4 __attribute__((ext_vector_type(4)));
 template <>
 struct io4<_Float16> {
     static __device__ __forceinline__ f4 ld(const void* base, size_t idx) {
@@ -208,20 +206,12 @@ __device__ __forceinline__ void store4_pre(const spaa_tapconv_t& p, const size_t
 // (loads give 0, stores are dropped) and out-of-range pixels / channels use the out-of-bounds offset, so that a kernel can keep
 // the operand loads of several pixels per lane in flight -- the conditional loads of epi_load() make the compiler wait for
 // each one (s_waitcnt vmcnt(0) at every join).  32-bit byte offsets: fits_32bit_offsets().
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 struct fast_epi_t {
     __amdgpu_buffer_rsrc_t out, add, gbits, g2bits, mask, aux, rbias;
     float bias[4];
     bool has_gate, relu;
     bool out_sc1;   // `out` is written with agent-scope (sc1) stores: K-range partial sums another XCD's workgroup reads back (fast_epi_store<.., SC1 = true>)
 };
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc_or_empty(const void* ptr, const int64_t bytes) {
-    const uint64_t a = reinterpret_cast<uint64_t>(ptr);
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)a), hi = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
-    const int n = ptr != nullptr ? (int)bytes : 0;
-    return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((uint64_t)hi << 32) | lo), 0, __builtin_amdgcn_readfirstlane(n), 0x00020000);
-}
 // (the launcher checks that every operand of the fast path is below 2 GiB: fits_32bit_offsets)
 __device__ __forceinline__ bool fits_32bit_offsets(const spaa_tapconv_t& p) {
     const int64_t npix = (int64_t)p.B * p.Hout * p.Wout;

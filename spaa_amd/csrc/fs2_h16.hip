@@ -23,15 +23,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/spaa_hip.h"
+#include "device_util.hpp"
 #include "launch_util.hpp"
 
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 namespace {
-
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
 struct fs2_args {
     const _Float16* in;      // [B, Hi, Wi, in_cstride], channels [0, Cin)
@@ -62,16 +57,10 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 3 : 1) void fs2_h16_kernel(const
     // ---- prologue: the weight images into LDS as they are (1 KB pieces, LDS-DMA)
     const int n1 = p.ks1 * 9 * NRB, n2 = p.ks2 * NRB;      // pieces
     {
-        const uint64_t a1 = reinterpret_cast<uint64_t>(p.w_img);
-        const auto r1 = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(a1 >> 32)) << 32) |
-                                                                                  (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)a1)),
-                                                          0, n1 * 1024, 0x00020000);
+        const auto r1 = wave_rsrc(p.w_img, n1 * 1024);
         for (int i = wave; i < n1; i += NW) __builtin_amdgcn_raw_ptr_buffer_load_lds(r1, (lds_ptr_t)(smem + i * 1024), 16, lane * 16, i * 1024, 0, 0);
         if (n2 > 0) {
-            const uint64_t a2 = reinterpret_cast<uint64_t>(p.w2_img);
-            const auto r2 = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(a2 >> 32)) << 32) |
-                                                                                      (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)a2)),
-                                                              0, n2 * 1024, 0x00020000);
+            const auto r2 = wave_rsrc(p.w2_img, n2 * 1024);
             for (int i = wave; i < n2; i += NW)
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(r2, (lds_ptr_t)(smem + (n1 + i) * 1024), 16, lane * 16, i * 1024, 0, 0);
         }
@@ -87,23 +76,15 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 3 : 1) void fs2_h16_kernel(const
     // every tensor through a buffer descriptor with 32-bit byte offsets: a pixel that does not exist is the out-of-range offset (loads give
     // zero, stores are dropped) -- no branch around any memory operation, so that the waits on them are counted, not drained
     constexpr int OOB = (int)0x80000000;
-    auto mk = [](const void* ptr, const int64_t bytes) {
-        const uint64_t a = reinterpret_cast<uint64_t>(ptr);
-        const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)a), hi = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
-        return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((uint64_t)hi << 32) | lo), 0,
-                                                 __builtin_amdgcn_readfirstlane(ptr != nullptr ? (int)bytes : 0), 0x00020000);
-    };
     const int64_t npx_o = (int64_t)p.B * Ho * Wo;
-    const auto r_in = mk(p.in, (int64_t)p.B * p.Hi * p.Wi * p.in_cstride * 2);
-    const auto r_in2 = mk(p.in2, npx_o * p.in2_cstride * 2);
-    const auto r_add = mk(p.add, npx_o * COUT * 2);
-    const auto r_gate = mk(p.gate_bits, npx_o * (COUT / 4));
-    const auto r_out = mk(p.out, npx_o * COUT * 2);
-    const auto r_mask = mk(p.mask_out, npx_o * (COUT / 4));
-    const auto r_bias = mk(p.bias, COUT * 4);
+    const auto r_in = rsrc_or_empty(p.in, (int64_t)p.B * p.Hi * p.Wi * p.in_cstride * 2);
+    const auto r_in2 = rsrc_or_empty(p.in2, npx_o * p.in2_cstride * 2);
+    const auto r_add = rsrc_or_empty(p.add, npx_o * COUT * 2);
+    const auto r_gate = rsrc_or_empty(p.gate_bits, npx_o * (COUT / 4));
+    const auto r_out = rsrc_or_empty(p.out, npx_o * COUT * 2);
+    const auto r_mask = rsrc_or_empty(p.mask_out, npx_o * (COUT / 4));
+    const auto r_bias = rsrc_or_empty(p.bias, COUT * 4);
     const bool has_gate = p.gate_bits != nullptr;
-    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-    typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
     const int pxb = p.in_cstride * 2, pxb2 = p.in2_cstride * 2;     // bytes per pixel
 
     for (int t = wid; t < ntask; t += nwv) {

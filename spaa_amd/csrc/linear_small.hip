@@ -8,10 +8,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/spaa_hip.h"
+#include "device_util.hpp"
 
 namespace {
-
-typedef float f4 __attribute__((ext_vector_type(4)));
 
 // sum over the 64 lanes in a fixed order, on the VALU's cross-lane data paths (no LDS round trips); the total lands in lane 63
 template <int CTRL, int ROW_MASK, bool BOUND>
@@ -27,12 +26,6 @@ __device__ __forceinline__ float wave_sum63(float v) {
     v += dpp_term<0x143, 0xC, false>(v);   // row_bcast31 into rows 2 and 3
     return v;
 }
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc_of(const float* ptr, const uint32_t bytes) {
-    const uint64_t a = reinterpret_cast<uint64_t>(ptr);
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)a), hi = __builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
-    return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((uint64_t)hi << 32) | lo), 0, (int)__builtin_amdgcn_readfirstlane(bytes), 0x00020000);
-}
 __device__ __forceinline__ f4 load4(const __amdgpu_buffer_rsrc_t r, const int off) {   // (out-of-range offset: zeros, no branch)
     return __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0));
 }
@@ -45,7 +38,7 @@ __global__ __launch_bounds__(256) void linear_small_kernel(const float* __restri
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int n0 = blockIdx.x * NPW;
     constexpr int OOB = (int)0x80000000;
-    const auto rx = rsrc_of(x, (uint32_t)M * (uint32_t)ldx * 4u), rw = rsrc_of(w, (uint32_t)N * (uint32_t)ldw * 4u);
+    const auto rx = wave_rsrc(x, (uint32_t)M * (uint32_t)ldx * 4u), rw = wave_rsrc(w, (uint32_t)N * (uint32_t)ldw * 4u);
     f4 wr[NPW][KV];
 #pragma unroll
     for (int j = 0; j < NPW; ++j)

@@ -10,6 +10,7 @@
 
 namespace {
 
+// device_util.hpp's block_sum computes the same sums, but its form (wave_sum inlined) schedules this file's kernels differently
 __device__ __forceinline__ float block_sum(float v, float* red) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
@@ -19,7 +20,6 @@ __device__ __forceinline__ float block_sum(float v, float* red) {
     __syncthreads();
     return red[0] + red[1] + red[2] + red[3];
 }
-
 __device__ __forceinline__ float block_max(float v, float* red) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_down(v, off, 64));

@@ -17,17 +17,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/spaa_hip.h"
+#include "device_util.hpp"
 #include "launch_util.hpp"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-
 namespace {
-
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
 struct s2fx_args {
     const float* in;           // [B, Hi, Wi, in_cstride], channels [0, Cin)
@@ -40,45 +33,6 @@ struct s2fx_args {
     int B, Hi, Wi, in_cstride, ks1, relu, nseg;
 };
 
-__device__ __forceinline__ unsigned int cvt2(float a, float b) {
-    f2 v = {a, b};
-    return __builtin_bit_cast(unsigned int, __builtin_convertvector(v, bf16x2));
-}
-__device__ __forceinline__ float lo_f(unsigned int p) { return __builtin_bit_cast(float, p << 16); }
-__device__ __forceinline__ float hi_f(unsigned int p) { return __builtin_bit_cast(float, p & 0xffff0000u); }
-
-// 8 fp32 -> three bf16x8 with x == h + m + l exactly (as csrc/tapconv_wino.hip: split8)
-__device__ __forceinline__ void split8(const u32x4 a, const u32x4 b, bf16x8& h, bf16x8& m, bf16x8& l) {
-    const float x[8] = {__uint_as_float(a[0]), __uint_as_float(a[1]), __uint_as_float(a[2]), __uint_as_float(a[3]),
-                        __uint_as_float(b[0]), __uint_as_float(b[1]), __uint_as_float(b[2]), __uint_as_float(b[3])};
-    u32x4 hh, mm, ll;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const unsigned int ph = cvt2(x[2 * i], x[2 * i + 1]);
-        const float r0 = x[2 * i] - lo_f(ph), r1 = x[2 * i + 1] - hi_f(ph);
-        const unsigned int pm = cvt2(r0, r1);
-        const float s0 = r0 - lo_f(pm), s1 = r1 - hi_f(pm);
-        hh[i] = ph;
-        mm[i] = pm;
-        ll[i] = cvt2(s0, s1);
-    }
-    h = __builtin_bit_cast(bf16x8, hh);
-    m = __builtin_bit_cast(bf16x8, mm);
-    l = __builtin_bit_cast(bf16x8, ll);
-}
-
-// six of the nine partial products of (w0 + w1 + w2) . (p0 + p1 + p2), small terms first (csrc/tapconv_x6d.hip)
-__device__ __forceinline__ f32x4 mfma6(const bf16x8 w0, const bf16x8 w1, const bf16x8 w2, const bf16x8 p0, const bf16x8 p1, const bf16x8 p2,
-                                       f32x4 acc) {
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w2, p0, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w0, p2, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1, p1, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1, p0, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w0, p1, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w0, p0, acc, 0, 0, 0);
-    return acc;
-}
-
 template <int COUT, int NW>
 __global__ __launch_bounds__(64 * NW, 1) void s2f_x6_kernel(const s2fx_args p) {
     constexpr int NRB = COUT / 16, NP = NRB / 2;
@@ -89,10 +43,7 @@ __global__ __launch_bounds__(64 * NW, 1) void s2f_x6_kernel(const s2fx_args p) {
     // ---- prologue: the weight image into LDS as it is (1 KB pieces, LDS-DMA)
     const int n1 = p.ks1 * 9 * 3 * NRB;
     {
-        const uint64_t a1 = reinterpret_cast<uint64_t>(p.w_img);
-        const auto r1 = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(a1 >> 32)) << 32) |
-                                                                                  (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)a1)),
-                                                          0, n1 * 1024, 0x00020000);
+        const auto r1 = wave_rsrc(p.w_img, n1 * 1024);
         for (int i = wave; i < n1; i += NW) __builtin_amdgcn_raw_ptr_buffer_load_lds(r1, (lds_ptr_t)(smem + i * 1024), 16, lane * 16, i * 1024, 0, 0);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
@@ -102,22 +53,16 @@ __global__ __launch_bounds__(64 * NW, 1) void s2f_x6_kernel(const s2fx_args p) {
     // every tensor through a buffer descriptor with 32-bit byte offsets: a pixel that does not exist is the out-of-range offset (loads give
     // zero, stores are dropped) -- no branch around any memory operation, so that the waits on them are counted, not drained
     constexpr int OOB = (int)0x80000000;
-    auto mk = [](const void* ptr, const int64_t bytes) {
-        const uint64_t a = reinterpret_cast<uint64_t>(ptr);
-        const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)a), hi = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
-        return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((uint64_t)hi << 32) | lo), 0,
-                                                 __builtin_amdgcn_readfirstlane(ptr != nullptr ? (int)bytes : 0), 0x00020000);
-    };
     const int Ho = p.Hi >> 1, Wo = p.Wi >> 1;
     const int ntask = p.B * Ho * p.nseg;
     const int wid = blockIdx.x * NW + wave, nwv = gridDim.x * NW;
     const int64_t npx_o = (int64_t)p.B * Ho * Wo;
-    const auto r_in = mk(p.in, (int64_t)p.B * p.Hi * p.Wi * p.in_cstride * 4);
-    const auto r_add = mk(p.add, npx_o * COUT * 4);
-    const auto r_gate = mk(p.gate_bits, npx_o * (COUT / 4));
-    const auto r_out = mk(p.out, npx_o * COUT * 4);
-    const auto r_mask = mk(p.mask_out, npx_o * (COUT / 4));
-    const auto r_bias = mk(p.bias, COUT * 4);
+    const auto r_in = rsrc_or_empty(p.in, (int64_t)p.B * p.Hi * p.Wi * p.in_cstride * 4);
+    const auto r_add = rsrc_or_empty(p.add, npx_o * COUT * 4);
+    const auto r_gate = rsrc_or_empty(p.gate_bits, npx_o * (COUT / 4));
+    const auto r_out = rsrc_or_empty(p.out, npx_o * COUT * 4);
+    const auto r_mask = rsrc_or_empty(p.mask_out, npx_o * (COUT / 4));
+    const auto r_bias = rsrc_or_empty(p.bias, COUT * 4);
     const bool has_gate = p.gate_bits != nullptr;
     const int pxb = p.in_cstride * 4;
 

@@ -17,61 +17,16 @@
 #include "launch_util.hpp"
 #include <stdint.h>
 #include "../../include/spaa_hip.h"
+#include "device_util.hpp"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f2 __attribute__((ext_vector_type(2)));
 typedef float f16v __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u4 __attribute__((ext_vector_type(4)));
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h4 __attribute__((ext_vector_type(4)));
 typedef _Float16 h2 __attribute__((ext_vector_type(2)));
 typedef _Float16 h16v __attribute__((ext_vector_type(16)));
 typedef const __attribute__((address_space(4))) h16v* ch16_ptr;
 
 namespace {
 
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
 typedef const __attribute__((address_space(4))) f16v* cf16_ptr;
-
-__device__ __forceinline__ unsigned int cvt2(float a, float b) {
-    f2 v = {a, b};
-    return __builtin_bit_cast(unsigned int, __builtin_convertvector(v, bf16x2));
-}
-__device__ __forceinline__ float lo_f(unsigned int p) { return __builtin_bit_cast(float, p << 16); }
-__device__ __forceinline__ float hi_f(unsigned int p) { return __builtin_bit_cast(float, p & 0xffff0000u); }
-
-// 8 fp32 -> three bf16x8 with x == h + m + l exactly
-__device__ __forceinline__ void split8(const f32x4 a, const f32x4 b, bf16x8& h, bf16x8& m, bf16x8& l) {
-    const float x[8] = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-    u4 hh, mm, ll;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const unsigned int ph = cvt2(x[2 * i], x[2 * i + 1]);
-        const float r0 = x[2 * i] - lo_f(ph), r1 = x[2 * i + 1] - hi_f(ph);
-        const unsigned int pm = cvt2(r0, r1);
-        const float s0 = r0 - lo_f(pm), s1 = r1 - hi_f(pm);
-        hh[i] = ph;
-        mm[i] = pm;
-        ll[i] = cvt2(s0, s1);
-    }
-    h = __builtin_bit_cast(bf16x8, hh);
-    m = __builtin_bit_cast(bf16x8, mm);
-    l = __builtin_bit_cast(bf16x8, ll);
-}
-
-// six of the nine partial products of (w0 + w1 + w2) . (p0 + p1 + p2), small terms first
-__device__ __forceinline__ f32x4 mfma6(const bf16x8 w0, const bf16x8 w1, const bf16x8 w2, const bf16x8 p0, const bf16x8 p1,
-                                       const bf16x8 p2, f32x4 acc) {
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w2, p0, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w0, p2, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1, p1, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1, p0, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w0, p1, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w0, p0, acc, 0, 0, 0);
-    return acc;
-}
 
 // Workgroup barrier for LDS hand-overs inside the tile loops: waits for this wave's LDS operations only.  __syncthreads() also drains
 // vmcnt -- every global load requested ahead (the next tile's operands, the residual, the gate bytes) and, on gfx950, every STORE of the
@@ -89,12 +44,11 @@ __device__ __forceinline__ void lds_barrier() {
 // insertion joined the paths conservatively and waited for the NEXT tile's operands at the first product of the current one -- one exposed
 // HBM round trip per tile and wave.)
 constexpr int OOB = (int)0x80000000;
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t img_rsrc(const void* base, const int img, const int64_t img_bytes) {
     const uint64_t a = reinterpret_cast<uint64_t>(base) + (uint64_t)(int64_t)img * (uint64_t)img_bytes;
     const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)a), hi = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
     return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((uint64_t)hi << 32) | lo), 0,
-                                             __builtin_amdgcn_readfirstlane(base != nullptr ? (int)img_bytes : 0), 0x00020000);
+                                             __builtin_amdgcn_readfirstlane(base != nullptr ? (int)img_bytes : 0), BUF_RSRC_FLAGS);
 }
 __device__ __forceinline__ f32x4 ld_f4(const __amdgpu_buffer_rsrc_t r, const int off) {
     const u32x4 u = __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0);
@@ -114,10 +68,7 @@ constexpr int T_BYTES = 8 * PLANE;
 
 // stage [3][128][64] bf16 weight planes (rows of 128 B) into LDS; 16-byte chunk c of row r sits at chunk c ^ ((r >> 1) & 7)
 __device__ __forceinline__ void stage_planes(const uint16_t* w, unsigned char* dst, const int wave, const int lane) {
-    const uint64_t addr = reinterpret_cast<uint64_t>(w);
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)addr);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(addr >> 32));
-    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((uint64_t)hi << 32) | lo), 0, W_BYTES, 0x00020000);
+    const auto rsrc = wave_rsrc(w, W_BYTES);
     for (int piece = wave; piece < W_BYTES / 1024; piece += 8) {   // 8 rows per piece
         const int r = piece * 8 + (lane >> 3);
         const int c = (lane & 7) ^ ((r >> 1) & 7);
@@ -176,10 +127,7 @@ __global__ __launch_bounds__(64 * FWD_WAVES, sizeof(T6) == 2 ? 8 : 1) void shadi
         }
     }
     {   // weight planes (rows of 128 B; chunk c of row r at chunk c ^ ((r >> 1) & 7)): 48 pieces over 16 waves
-        const uint64_t addr = reinterpret_cast<uint64_t>(w2s);
-        const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)addr);
-        const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(addr >> 32));
-        const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((uint64_t)hi << 32) | lo), 0, W_BYTES, 0x00020000);
+        const auto rsrc = wave_rsrc(w2s, W_BYTES);
         // (fp16 storage: ONE plane of fp16 weights, same rows and swizzle; the descriptor still covers three planes' worth of bytes, of
         // which the first third is read)
         for (int piece = wave; piece < (H16 ? W_BYTES / 3 : W_BYTES) / 1024; piece += FWD_WAVES) {
@@ -447,10 +395,7 @@ __global__ __launch_bounds__(1024, sizeof(T6) == 2 ? 8 : 1) void shading_head_bw
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int H = 2 * H2, W = 2 * W2;
     {   // stage [3][64][128] bf16 planes: rows of 256 B, 16 chunks; chunk c of row r at chunk c ^ (r & 15)
-        const uint64_t addr = reinterpret_cast<uint64_t>(w2ts);
-        const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)addr);
-        const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(addr >> 32));
-        const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((uint64_t)hi << 32) | lo), 0, WB_BYTES, 0x00020000);
+        const auto rsrc = wave_rsrc(w2ts, WB_BYTES);
         for (int piece = wave; piece < (H16 ? WB_BYTES / 3 : WB_BYTES) / 1024; piece += 16) {   // 4 rows per piece
             const int r = piece * 4 + (lane >> 4);
             const int c = (lane & 15) ^ (r & 15);

@@ -21,19 +21,12 @@
 #include "../../include/spaa_hip.h"
 #include "epilogue.hpp"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f2 __attribute__((ext_vector_type(2)));
-
 namespace {
 
 constexpr int TW = 32, TH = 8;
 constexpr int MAXT = 9;  // taps held in registers
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
 typedef const __attribute__((address_space(4))) int* cint_ptr;
 
-__device__ __forceinline__ void dma16(const __amdgpu_buffer_rsrc_t rsrc, unsigned char* dst, int voff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_ptr_t)dst, 16, voff, 0, 0, 0);
-}
 __device__ __forceinline__ f32x16 mfma2(float a, float b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
 }
@@ -66,12 +59,7 @@ __global__ __launch_bounds__(256) void smallcin_kernel(const spaa_tapconv_t p, c
     // ---- stage the input patch: rows y0*s_in + dymin .., columns x0*s_in + dxmin ..
     {
         const uint32_t in_bytes = (uint32_t)p.B * (uint32_t)(p.Hin * p.Win) * (uint32_t)p.in_cstride * 4u;
-        const uint64_t in_addr = reinterpret_cast<uint64_t>(p.in);
-        const uint32_t in_lo = __builtin_amdgcn_readfirstlane((uint32_t)in_addr);
-        const uint32_t in_hi = __builtin_amdgcn_readfirstlane((uint32_t)(in_addr >> 32));
-        const auto rsrc_in = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<float*>(((uint64_t)in_hi << 32) | in_lo),
-                                                                0, (int)__builtin_amdgcn_readfirstlane(in_bytes),
-                                                                0x00020000);
+        const auto rsrc_in = wave_rsrc(p.in, in_bytes);
         const int npix = PH * PW;
         const int npieces = (npix + PIX_PER_PIECE - 1) / PIX_PER_PIECE;
         const int row_bytes = p.in_cstride * 4;

@@ -17,6 +17,7 @@
 #include "launch_util.hpp"
 #include <stdint.h>
 #include "../../include/spaa_hip.h"
+#include "device_util.hpp"
 
 int spaa_launch_tapconv_x6(const spaa_tapconv_t& d, int tile, hipStream_t stream);   // tapconv_x6.hip
 int spaa_launch_tapconv_x6d(const spaa_tapconv_t& d, int tile, hipStream_t stream);  // tapconv_x6d.hip
@@ -28,9 +29,6 @@ int spaa_launch_tapconv_x6p(const spaa_tapconv_t& d, hipStream_t stream);       
 int spaa_launch_tapconv_c3(const spaa_tapconv_t& d, hipStream_t stream);            // tapconv_c3.hip
 int spaa_launch_thinpatch(const spaa_tapconv_t& d, hipStream_t stream);               // thinpatch.hip
 int spaa_launch_smallcin(const spaa_tapconv_t& d, hipStream_t stream);                // smallcin.hip
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
@@ -102,15 +100,10 @@ __global__ __launch_bounds__(256, 2) void tapconv_kernel(const spaa_tapconv_t p,
     const uint32_t in_bytes = (uint32_t)p.B * (uint32_t)(p.Hin * p.Win) * (uint32_t)p.in_cstride * 4u;
     // descriptor inputs forced wave-uniform (readfirstlane) so hipcc keeps the SRD in SGPRs instead of wrapping
     // every buffer_load in a waterfall loop
-    const uint64_t in_addr = reinterpret_cast<uint64_t>(p.in);
-    const uint32_t in_lo = __builtin_amdgcn_readfirstlane((uint32_t)in_addr);
-    const uint32_t in_hi = __builtin_amdgcn_readfirstlane((uint32_t)(in_addr >> 32));
-    float* in_uniform = reinterpret_cast<float*>(((uint64_t)in_hi << 32) | in_lo);
-    const auto rsrc_in = __builtin_amdgcn_make_buffer_rsrc(
-        in_uniform, 0, (int)__builtin_amdgcn_readfirstlane(in_bytes), 0x00020000);
+    const auto rsrc_in = wave_rsrc(p.in, in_bytes);
     const int npad = (p.Cout + 127) & ~127;
     const auto rsrc_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.weights + cl.w_off), 0,
-                                                           npad * cl.Kpad * 4, 0x00020000);
+                                                           npad * cl.Kpad * 4, BUF_RSRC_FLAGS);
     int w_off[B_LD];
 #pragma unroll
     for (int i = 0; i < B_LD; ++i) w_off[i] = ((n_blk + (tid >> 3) + 32 * i) * cl.Kpad + 4 * kq) * 4;
@@ -286,11 +279,7 @@ __global__ __launch_bounds__(256) void directconv_kernel(const spaa_tapconv_t p)
     const int x = r - y * p.Wm;
 
     const uint32_t in_bytes = (uint32_t)p.B * (uint32_t)(p.Hin * p.Win) * (uint32_t)p.in_cstride * 4u;
-    const uint64_t in_addr = reinterpret_cast<uint64_t>(p.in);
-    const uint32_t in_lo = __builtin_amdgcn_readfirstlane((uint32_t)in_addr);
-    const uint32_t in_hi = __builtin_amdgcn_readfirstlane((uint32_t)(in_addr >> 32));
-    const auto rsrc_in = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<float*>(((uint64_t)in_hi << 32) | in_lo), 0,
-                                                            (int)__builtin_amdgcn_readfirstlane(in_bytes), 0x00020000);
+    const auto rsrc_in = wave_rsrc(p.in, in_bytes);
     const float* __restrict__ W = p.weights + cl.w_off;  // [Npad][Kpad], K contiguous
     const int Kpad = cl.Kpad;
     const int Cin = p.Cin;
@@ -393,11 +382,7 @@ __global__ __launch_bounds__(256) void thinconv_kernel(const spaa_tapconv_t p) {
     const int M = p.B * HWm;
 
     const uint32_t in_bytes = (uint32_t)p.B * (uint32_t)(p.Hin * p.Win) * (uint32_t)p.in_cstride * 4u;
-    const uint64_t in_addr = reinterpret_cast<uint64_t>(p.in);
-    const uint32_t in_lo = __builtin_amdgcn_readfirstlane((uint32_t)in_addr);
-    const uint32_t in_hi = __builtin_amdgcn_readfirstlane((uint32_t)(in_addr >> 32));
-    const auto rsrc_in = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<float*>(((uint64_t)in_hi << 32) | in_lo), 0,
-                                                            (int)__builtin_amdgcn_readfirstlane(in_bytes), 0x00020000);
+    const auto rsrc_in = wave_rsrc(p.in, in_bytes);
     // XCD-aware order: the workgroups of one XCD (blockIdx.x % 8) take a contiguous range of pixel blocks, so the rows
     // above / below a block (the other taps) are served by that XCD's L2 instead of being fetched 3x from HBM
     int blk;

@@ -20,42 +20,7 @@
 #include "../../include/spaa_hip.h"
 #include "epilogue.hpp"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u4 __attribute__((ext_vector_type(4)));
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-
 namespace {
-
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-__device__ __forceinline__ void dma16(const __amdgpu_buffer_rsrc_t rsrc, unsigned char* dst, int voff, int soff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_ptr_t)dst, 16, voff, soff, 0, 0);
-}
-__device__ __forceinline__ unsigned int cvt2(float a, float b) {
-    f2 v = {a, b};
-    return __builtin_bit_cast(unsigned int, __builtin_convertvector(v, bf16x2));
-}
-__device__ __forceinline__ float lo_f(unsigned int p) { return __builtin_bit_cast(float, p << 16); }
-__device__ __forceinline__ float hi_f(unsigned int p) { return __builtin_bit_cast(float, p & 0xffff0000u); }
-// 8 fp32 -> three bf16x8 with x == h + m + l exactly
-__device__ __forceinline__ void split8(const float (&x)[8], bf16x8& h, bf16x8& m, bf16x8& l) {
-    u4 hh, mm, ll;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const unsigned int ph = cvt2(x[2 * i], x[2 * i + 1]);
-        const float r0 = x[2 * i] - lo_f(ph), r1 = x[2 * i + 1] - hi_f(ph);
-        const unsigned int pm = cvt2(r0, r1);
-        const float s0 = r0 - lo_f(pm), s1 = r1 - hi_f(pm);
-        hh[i] = ph;
-        mm[i] = pm;
-        ll[i] = cvt2(s0, s1);
-    }
-    h = __builtin_bit_cast(bf16x8, hh);
-    m = __builtin_bit_cast(bf16x8, mm);
-    l = __builtin_bit_cast(bf16x8, ll);
-}
 
 constexpr int OH = 16, OW = 32, NW = 8;
 __device__ __forceinline__ int swz_w16(int n) { return ((n >> 3) & 1) << 1; }
@@ -161,15 +126,7 @@ __global__ __launch_bounds__(512, 4) void c3conv_tile_kernel(const spaa_tapconv_
             const bf16x8 w1 = *reinterpret_cast<const bf16x8*>(wc + BN * 64);
             const bf16x8 w2 = *reinterpret_cast<const bf16x8*>(wc + 2 * BN * 64);
 #pragma unroll
-            for (int b = 0; b < 4; ++b) {   // small terms first (tapconv_x6d.hip: X6D_MFMA6)
-                f32x4 a = acc[b][j];
-                a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w2, pf[b][0], a, 0, 0, 0);
-                a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w0, pf[b][2], a, 0, 0, 0);
-                a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1, pf[b][1], a, 0, 0, 0);
-                a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1, pf[b][0], a, 0, 0, 0);
-                a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w0, pf[b][1], a, 0, 0, 0);
-                acc[b][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w0, pf[b][0], a, 0, 0, 0);
-            }
+            for (int b = 0; b < 4; ++b) acc[b][j] = mfma6(w0, w1, w2, pf[b][0], pf[b][1], pf[b][2], acc[b][j]);
         }
     }
 
@@ -343,15 +300,7 @@ __global__ __launch_bounds__(512, 2) void c3conv_kernel(const spaa_tapconv_t p, 
                     const bf16x8 w1 = *reinterpret_cast<const bf16x8*>(wc + BN * 64);
                     const bf16x8 w2 = *reinterpret_cast<const bf16x8*>(wc + 2 * BN * 64);
 #pragma unroll
-                    for (int bb = 0; bb < 2; ++bb) {   // small terms first (tapconv_x6d.hip: X6D_MFMA6)
-                        f32x4 a = acc[2 * bp + bb][j];
-                        a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w2, pf[bb][0], a, 0, 0, 0);
-                        a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w0, pf[bb][2], a, 0, 0, 0);
-                        a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1, pf[bb][1], a, 0, 0, 0);
-                        a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1, pf[bb][0], a, 0, 0, 0);
-                        a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w0, pf[bb][1], a, 0, 0, 0);
-                        acc[2 * bp + bb][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w0, pf[bb][0], a, 0, 0, 0);
-                    }
+                    for (int bb = 0; bb < 2; ++bb) acc[2 * bp + bb][j] = mfma6(w0, w1, w2, pf[bb][0], pf[bb][1], pf[bb][2], acc[2 * bp + bb][j]);
                 }
             }
         }

@@ -23,16 +23,7 @@
 #include "../../include/spaa_hip.h"
 #include "epilogue.hpp"
 
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 namespace {
-
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-
-__device__ __forceinline__ void dma16(const __amdgpu_buffer_rsrc_t rsrc, unsigned char* dst, int voff, int soff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_ptr_t)dst, 16, voff, soff, 0, 0);
-}
 
 // chunk swizzle of a 64-byte row (4 chunks): see tapconv_x6d.hip swz_w<16>
 __device__ __forceinline__ int swz64(int r) { return ((r >> 3) & 1) << 1; }
@@ -72,13 +63,7 @@ __global__ __launch_bounds__(64 * NW, (NW > 4 || NS > 2) ? 1 : 2) void tapconv_h
     cint_ptr ctaps = (cint_ptr)(uintptr_t)(p.taps + 2 * cl.tap_off);
 
     const uint32_t in_bytes = (uint32_t)p.B * (uint32_t)(p.Hin * p.Win) * (uint32_t)row_bytes;
-    const uint64_t in_addr = reinterpret_cast<uint64_t>(p.in);
-    // (readfirstlane returns a SIGNED int: keep the halves in uint32_t, or a low word with bit 31 set sign-extends into
-    // the high word of the base address)
-    const uint32_t in_lo = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)in_addr);
-    const uint32_t in_hi = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(in_addr >> 32));
-    const auto rsrc_in = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((uint64_t)in_hi << 32) | in_lo), 0,
-                                                            (int)__builtin_amdgcn_readfirstlane(in_bytes), 0x00020000);
+    const auto rsrc_in = wave_rsrc(p.in, in_bytes);
     const int K64 = (cl.K + 63) & ~63;
     const int npad = (p.Cout * (p.nfold > 1 ? p.nfold : 1) + 127) & ~127;
     uint64_t wh_off = 0;  // fp16 plane of class c: [npad][K64_c], classes back to back
@@ -88,7 +73,7 @@ __global__ __launch_bounds__(64 * NW, (NW > 4 || NS > 2) ? 1 : 2) void tapconv_h
     const uint32_t w_hi = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(w_addr >> 32));
     const auto rsrc_w = __builtin_amdgcn_make_buffer_rsrc(
         reinterpret_cast<void*>(((uint64_t)w_hi << 32) | w_lo), 0,
-        (int)__builtin_amdgcn_readfirstlane((uint32_t)npad * (uint32_t)K64 * 2u), 0x00020000);
+        (int)__builtin_amdgcn_readfirstlane((uint32_t)npad * (uint32_t)K64 * 2u), BUF_RSRC_FLAGS);
 
     // ---- this wave's pixel rows: piece ib (16 rows) -> lane holds row 32 wave + 16 ib + (lane >> 2), physical chunk lane & 3
     int a_off[2];

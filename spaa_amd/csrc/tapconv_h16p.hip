@@ -21,16 +21,8 @@
 #include "../../include/spaa_hip.h"
 #include "epilogue.hpp"
 
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 namespace {
 
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-
-__device__ __forceinline__ void dma16(const __amdgpu_buffer_rsrc_t rsrc, unsigned char* dst, int voff, int soff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_ptr_t)dst, 16, voff, soff, 0, 0);
-}
 // chunk swizzle of a 64-byte row (four 16-byte chunks): rows 8 apart swap chunk pairs (tapconv_h16.hip swz64)
 __device__ __forceinline__ int swz64(int r) { return ((r >> 3) & 1) << 1; }
 
@@ -136,7 +128,7 @@ __global__ __launch_bounds__(512, LEAN ? 4 : 1) void h16p_kernel(const spaa_tapc
     const uint32_t in_lo = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)in_addr);
     const uint32_t in_hi = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(in_addr >> 32));
     const auto rsrc_in = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((uint64_t)in_hi << 32) | in_lo), 0,
-                                                            (int)__builtin_amdgcn_readfirstlane(in_bytes), 0x00020000);
+                                                            (int)__builtin_amdgcn_readfirstlane(in_bytes), BUF_RSRC_FLAGS);
     const int K64 = (cl.K + 63) & ~63;
     const int nfold = p.nfold > 1 ? p.nfold : 1;
     const int ntaps = cl.ntaps;
@@ -146,7 +138,7 @@ __global__ __launch_bounds__(512, LEAN ? 4 : 1) void h16p_kernel(const spaa_tapc
     const uint32_t w_lo = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)w_addr);
     const uint32_t w_hi = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(w_addr >> 32));
     const auto rsrc_w = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((uint64_t)w_hi << 32) | w_lo), 0,
-                                                           (int)__builtin_amdgcn_readfirstlane((uint32_t)npad * (uint32_t)K64 * 2u), 0x00020000);
+                                                           (int)__builtin_amdgcn_readfirstlane((uint32_t)npad * (uint32_t)K64 * 2u), BUF_RSRC_FLAGS);
     typedef const __attribute__((address_space(4))) int* cint_ptr;
     cint_ptr ctaps = (cint_ptr)(uintptr_t)(p.taps + 2 * cl.tap_off);
 

@@ -23,44 +23,7 @@
 #include "../../include/spaa_hip.h"
 #include "epilogue.hpp"
 
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u4 __attribute__((ext_vector_type(4)));
-
 namespace {
-
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-__device__ __forceinline__ void dma16(const __amdgpu_buffer_rsrc_t rsrc, unsigned char* dst, int voff, int soff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_ptr_t)dst, 16, voff, soff, 0, 0);
-}
-
-__device__ __forceinline__ unsigned int cvt2(float a, float b) {
-    f2 v = {a, b};
-    return __builtin_bit_cast(unsigned int, __builtin_convertvector(v, bf16x2));
-}
-__device__ __forceinline__ float lo_f(unsigned int p) { return __builtin_bit_cast(float, p << 16); }
-__device__ __forceinline__ float hi_f(unsigned int p) { return __builtin_bit_cast(float, p & 0xffff0000u); }
-// 8 fp32 -> three bf16x8 with x == h + m + l exactly (tapconv_x6d.hip: split8)
-__device__ __forceinline__ void split8(const f32x4 x0, const f32x4 x1, bf16x8& h, bf16x8& m, bf16x8& l) {
-    const float x[8] = {x0[0], x0[1], x0[2], x0[3], x1[0], x1[1], x1[2], x1[3]};
-    u4 hh, mm, ll;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const unsigned int ph = cvt2(x[2 * i], x[2 * i + 1]);
-        const float r0 = x[2 * i] - lo_f(ph), r1 = x[2 * i + 1] - hi_f(ph);
-        const unsigned int pm = cvt2(r0, r1);
-        const float s0 = r0 - lo_f(pm), s1 = r1 - hi_f(pm);
-        hh[i] = ph;
-        mm[i] = pm;
-        ll[i] = cvt2(s0, s1);
-    }
-    h = __builtin_bit_cast(bf16x8, hh);
-    m = __builtin_bit_cast(bf16x8, mm);
-    l = __builtin_bit_cast(bf16x8, ll);
-}
 
 constexpr int TW = 32;   // class-grid columns of a workgroup (rows: 4 RW, RW = rows of a wave: template parameter)
 constexpr int NW = 8;
@@ -110,20 +73,11 @@ __global__ __launch_bounds__(512, PDB ? 1 : 2) void thinmf_kernel(const spaa_tap
     }
     const int EB = HIN ? 2 : 4;
     const int row_bytes = p.in_cstride * EB;
-    const uint64_t in_addr = reinterpret_cast<uint64_t>(p.in);
-    const uint32_t in_lo = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)in_addr);
-    const uint32_t in_hi = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(in_addr >> 32));
-    const auto rsrc_in = __builtin_amdgcn_make_buffer_rsrc(
-        reinterpret_cast<void*>(((uint64_t)in_hi << 32) | in_lo), 0,
-        (int)__builtin_amdgcn_readfirstlane((uint32_t)p.B * (uint32_t)(p.Hin * p.Win) * (uint32_t)row_bytes), 0x00020000);
+    const auto rsrc_in = wave_rsrc(p.in, (uint32_t)p.B * (uint32_t)(p.Hin * p.Win) * (uint32_t)row_bytes);
     const int nkb = p.Cin >> 5;
     const int nsteps = nkb * TBW;
     const void* wptr = HIN ? p.w_half : (const void*)p.w_split;
-    const uint64_t w_addr = reinterpret_cast<uint64_t>(wptr);
-    const uint32_t w_lo = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)w_addr);
-    const uint32_t w_hi = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(w_addr >> 32));
-    const auto rsrc_w = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((uint64_t)w_hi << 32) | w_lo), 0,
-                                                           (int)__builtin_amdgcn_readfirstlane((uint32_t)(nsteps * WST * 1024)), 0x00020000);
+    const auto rsrc_w = wave_rsrc(wptr, (uint32_t)(nsteps * WST * 1024));
 
     // ---- patch staging: piece i of this wave = piece wave + 8 i = PPP consecutive patch pixels; lane -> (pixel, physical chunk)
     int pvoff[PPWMAX];
@@ -267,16 +221,7 @@ __global__ __launch_bounds__(512, PDB ? 1 : 2) void thinmf_kernel(const spaa_tap
 #pragma unroll
                 for (int pl = 0; pl < 3; ++pl) wf[pl] = *reinterpret_cast<const bf16x8*>(wbase + (pl * TBH + dyi) * 1024);
 #pragma unroll
-                for (int r = 0; r < RW; ++r) {   // small terms first (tapconv_x6d.hip: X6D_MFMA6)
-                    f32x4 a = acc[r];
-                    a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[2], bfr[r + dyi][0], a, 0, 0, 0);
-                    a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[0], bfr[r + dyi][2], a, 0, 0, 0);
-                    a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[1], bfr[r + dyi][1], a, 0, 0, 0);
-                    a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[1], bfr[r + dyi][0], a, 0, 0, 0);
-                    a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[0], bfr[r + dyi][1], a, 0, 0, 0);
-                    a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[0], bfr[r + dyi][0], a, 0, 0, 0);
-                    acc[r] = a;
-                }
+                for (int r = 0; r < RW; ++r) acc[r] = mfma6(wf, bfr[r + dyi], acc[r]);
             }
         }
     }

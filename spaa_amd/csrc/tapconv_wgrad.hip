@@ -13,8 +13,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/spaa_hip.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+#include "device_util.hpp"
 
 namespace {
 

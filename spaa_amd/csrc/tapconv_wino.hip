@@ -29,43 +29,7 @@
 #include "../../include/spaa_hip.h"
 #include "epilogue.hpp"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u4 __attribute__((ext_vector_type(4)));
-
 namespace {
-
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-
-__device__ __forceinline__ void dma16(const __amdgpu_buffer_rsrc_t rsrc, unsigned char* dst, int voff, int soff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_ptr_t)dst, 16, voff, soff, 0, 0);
-}
-__device__ __forceinline__ unsigned int cvt2(float a, float b) {
-    f2 v = {a, b};
-    return __builtin_bit_cast(unsigned int, __builtin_convertvector(v, bf16x2));
-}
-__device__ __forceinline__ float lo_f(unsigned int p) { return __builtin_bit_cast(float, p << 16); }
-__device__ __forceinline__ float hi_f(unsigned int p) { return __builtin_bit_cast(float, p & 0xffff0000u); }
-
-// 8 fp32 -> three bf16x8 with x == h + m + l exactly
-__device__ __forceinline__ void split8(const float (&x)[8], bf16x8& h, bf16x8& m, bf16x8& l) {
-    u4 hh, mm, ll;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const unsigned int ph = cvt2(x[2 * i], x[2 * i + 1]);
-        const float r0 = x[2 * i] - lo_f(ph), r1 = x[2 * i + 1] - hi_f(ph);
-        const unsigned int pm = cvt2(r0, r1);
-        const float s0 = r0 - lo_f(pm), s1 = r1 - hi_f(pm);
-        hh[i] = ph;
-        mm[i] = pm;
-        ll[i] = cvt2(s0, s1);
-    }
-    h = __builtin_bit_cast(bf16x8, hh);
-    m = __builtin_bit_cast(bf16x8, mm);
-    l = __builtin_bit_cast(bf16x8, ll);
-}
 
 constexpr int TY = 8, TX = 16;                 // Winograd tiles per workgroup (rows x columns): 16 x 32 output pixels
 constexpr int PH = 2 * TY + 2, PW = 2 * TX + 2;  // input patch 18 x 34 pixels
@@ -173,21 +137,13 @@ __global__ __launch_bounds__(64 * NWT, NWT == 4 ? 2 : 1) void wino_x6_kernel(con
     }
     const int row_bytes = p.in_cstride * 4;
     const uint32_t in_bytes = (uint32_t)p.B * (uint32_t)(H * W) * (uint32_t)row_bytes;
-    const uint64_t in_addr = reinterpret_cast<uint64_t>(p.in);
-    const uint32_t in_lo = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)in_addr);
-    const uint32_t in_hi = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(in_addr >> 32));
-    const auto rsrc_in = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((uint64_t)in_hi << 32) | in_lo), 0,
-                                                            (int)__builtin_amdgcn_readfirstlane(in_bytes), 0x00020000);
+    const auto rsrc_in = wave_rsrc(p.in, in_bytes);
     const int kb1 = TWO ? (Cin - p.Cin2) >> 5 : 0x7fffffff;   // first channel block of the second source
     const int row_bytes2 = TWO ? p.in2_cstride * 4 : 0;
     const auto rsrc_in2 = TWO ? rsrc_or_empty(p.in2, (int64_t)p.B * (H * W) * row_bytes2) : rsrc_in;
     const int npad = (p.Cout + 127) & ~127;
     const int plane_bytes = npad * cl.Kpad * 2;
-    const uint64_t w_addr = reinterpret_cast<uint64_t>(p.w_split);
-    const uint32_t w_lo = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)w_addr);
-    const uint32_t w_hi = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(w_addr >> 32));
-    const auto rsrc_w = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((uint64_t)w_hi << 32) | w_lo), 0,
-                                                           (int)__builtin_amdgcn_readfirstlane(3u * (uint32_t)plane_bytes), 0x00020000);
+    const auto rsrc_w = wave_rsrc(p.w_split, 3u * (uint32_t)plane_bytes);
 
     // ---- patch staging: piece i (8 consecutive pixel SLOTS) -> wave i % 8; lane -> (slot lane >> 3, physical chunk lane & 7).
     // LDS layout (bank-conflict-free for a wave's reads: 16 tiles = patch columns 2 apart, 4 channel chunks):
@@ -369,16 +325,7 @@ __global__ __launch_bounds__(64 * NWT, NWT == 4 ? 2 : 1) void wino_x6_kernel(con
                             for (int k = 0; k < 3; ++k)
                                 wf[(j + 1) & 1][k] = *reinterpret_cast<const bf16x8*>(wc + (j + 1) * 1024 + k * W_PLANE);
                         }
-                        const bf16x8 w0 = wf[j & 1][0], w1 = wf[j & 1][1], w2 = wf[j & 1][2];
-                        const f32x4 zero = f32x4{0.f, 0.f, 0.f, 0.f};
-                        {
-                            f32x4 m = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w2, pf[0], zero, 0, 0, 0);
-                            m = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w0, pf[2], m, 0, 0, 0);
-                            m = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1, pf[1], m, 0, 0, 0);
-                            m = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1, pf[0], m, 0, 0, 0);
-                            m = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w0, pf[1], m, 0, 0, 0);
-                            mm[j & 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w0, pf[0], m, 0, 0, 0);
-                        }
+                        mm[j & 1] = mfma6(wf[j & 1], pf, f32x4{0.f, 0.f, 0.f, 0.f});
                     }
                     if (j > 0) {
                         const f32x4 mp = mm[(j - 1) & 1];

@@ -21,12 +21,6 @@
 #include "../../include/spaa_hip.h"
 #include "epilogue.hpp"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f4 __attribute__((ext_vector_type(4)));
-typedef float f2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u2 __attribute__((ext_vector_type(2)));
 
 namespace {
@@ -34,13 +28,6 @@ namespace {
 constexpr int BK = 32;
 constexpr int ROWB = 80;  // LDS row pitch in bytes: 32 bf16 (64 B) + 16 B pad
 constexpr int TAP_BYTES = 16 * (SPAA_MAX_TAPS + 4);
-
-__device__ __forceinline__ unsigned int cvt2(float a, float b) {
-    f2 v = {a, b};
-    return __builtin_bit_cast(unsigned int, __builtin_convertvector(v, bf16x2));
-}
-__device__ __forceinline__ float lo_f(unsigned int p) { return __builtin_bit_cast(float, p << 16); }
-__device__ __forceinline__ float hi_f(unsigned int p) { return __builtin_bit_cast(float, p & 0xffff0000u); }
 
 // x == h + m + l exactly, 4 values at a time, packed as 4 bf16 (8 bytes) per part
 __device__ __forceinline__ void split4(const f4 x, u2& h, u2& m, u2& l) {
@@ -111,11 +98,7 @@ __global__ __launch_bounds__(256, 2) void tapconv_x6_kernel(const spaa_tapconv_t
         a_pix[i] = (b * p.Hin + y * p.s_in) * p.Win + x * p.s_in;
     }
     const uint32_t in_bytes = (uint32_t)p.B * (uint32_t)(p.Hin * p.Win) * (uint32_t)p.in_cstride * 4u;
-    const uint64_t in_addr = reinterpret_cast<uint64_t>(p.in);
-    const uint32_t in_lo = __builtin_amdgcn_readfirstlane((uint32_t)in_addr);
-    const uint32_t in_hi = __builtin_amdgcn_readfirstlane((uint32_t)(in_addr >> 32));
-    const auto rsrc_in = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<float*>(((uint64_t)in_hi << 32) | in_lo), 0,
-                                                            (int)__builtin_amdgcn_readfirstlane(in_bytes), 0x00020000);
+    const auto rsrc_in = wave_rsrc(p.in, in_bytes);
     // split weights of this class: [3][Npad][Kpad] bf16
     const int npad = (p.Cout + 127) & ~127;
     const int plane_bytes = npad * cl.Kpad * 2;
@@ -124,7 +107,7 @@ __global__ __launch_bounds__(256, 2) void tapconv_x6_kernel(const spaa_tapconv_t
     const uint32_t w_hi = __builtin_amdgcn_readfirstlane((uint32_t)(w_addr >> 32));
     const auto rsrc_w = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((uint64_t)w_hi << 32) | w_lo), 0,
                                                            (int)__builtin_amdgcn_readfirstlane(3u * (uint32_t)plane_bytes),
-                                                           0x00020000);
+                                                           BUF_RSRC_FLAGS);
 
     const int wm0 = (wave / WAVES_N) * 32;
     const int wn0 = (wave % WAVES_N) * 32;
@@ -355,11 +338,7 @@ __global__ __launch_bounds__(256, 2) void tapconv_x6v2_kernel(const spaa_tapconv
         a_pix[i] = (b * p.Hin + y * p.s_in) * p.Win + x * p.s_in;
     }
     const uint32_t in_bytes = (uint32_t)p.B * (uint32_t)(p.Hin * p.Win) * (uint32_t)p.in_cstride * 4u;
-    const uint64_t in_addr = reinterpret_cast<uint64_t>(p.in);
-    const uint32_t in_lo = __builtin_amdgcn_readfirstlane((uint32_t)in_addr);
-    const uint32_t in_hi = __builtin_amdgcn_readfirstlane((uint32_t)(in_addr >> 32));
-    const auto rsrc_in = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<float*>(((uint64_t)in_hi << 32) | in_lo), 0,
-                                                            (int)__builtin_amdgcn_readfirstlane(in_bytes), 0x00020000);
+    const auto rsrc_in = wave_rsrc(p.in, in_bytes);
     const int npad = (p.Cout + 127) & ~127;
     const int plane_bytes = npad * cl.Kpad * 2;
     const uint64_t w_addr = reinterpret_cast<uint64_t>(p.w_split) + (uint64_t)cl.w_off * 6u;
@@ -367,7 +346,7 @@ __global__ __launch_bounds__(256, 2) void tapconv_x6v2_kernel(const spaa_tapconv
     const uint32_t w_hi = __builtin_amdgcn_readfirstlane((uint32_t)(w_addr >> 32));
     const auto rsrc_w = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((uint64_t)w_hi << 32) | w_lo), 0,
                                                            (int)__builtin_amdgcn_readfirstlane(3u * (uint32_t)plane_bytes),
-                                                           0x00020000);
+                                                           BUF_RSRC_FLAGS);
     // weight staging: thread -> (row = tid>>2 (+64 j), 16-byte piece q = tid&3) of each plane
     const int bq = tid & 3;
     int b_goff[B_LD];
@@ -627,11 +606,7 @@ __global__ __launch_bounds__(256, 2) void tapconv_x6v3_kernel(const spaa_tapconv
         a_pix[i] = (b * p.Hin + y * p.s_in) * p.Win + x * p.s_in;
     }
     const uint32_t in_bytes = (uint32_t)p.B * (uint32_t)(p.Hin * p.Win) * (uint32_t)p.in_cstride * 4u;
-    const uint64_t in_addr = reinterpret_cast<uint64_t>(p.in);
-    const uint32_t in_lo = __builtin_amdgcn_readfirstlane((uint32_t)in_addr);
-    const uint32_t in_hi = __builtin_amdgcn_readfirstlane((uint32_t)(in_addr >> 32));
-    const auto rsrc_in = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<float*>(((uint64_t)in_hi << 32) | in_lo), 0,
-                                                            (int)__builtin_amdgcn_readfirstlane(in_bytes), 0x00020000);
+    const auto rsrc_in = wave_rsrc(p.in, in_bytes);
     const int npad = (p.Cout + 127) & ~127;
     const int plane_bytes = npad * cl.Kpad * 2;
     const uint64_t w_addr = reinterpret_cast<uint64_t>(p.w_split) + (uint64_t)cl.w_off * 6u;
@@ -639,7 +614,7 @@ __global__ __launch_bounds__(256, 2) void tapconv_x6v3_kernel(const spaa_tapconv
     const uint32_t w_hi = __builtin_amdgcn_readfirstlane((uint32_t)(w_addr >> 32));
     const auto rsrc_w = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((uint64_t)w_hi << 32) | w_lo), 0,
                                                            (int)__builtin_amdgcn_readfirstlane(3u * (uint32_t)plane_bytes),
-                                                           0x00020000);
+                                                           BUF_RSRC_FLAGS);
     // weight staging: thread -> (row = tid>>2 (+64 j), 16-byte piece q = tid&3) of each plane
     const int bq = tid & 3;
     int b_goff[B_LD];

@@ -18,50 +18,9 @@
 #include "../../include/spaa_hip.h"
 #include "epilogue.hpp"
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 namespace {
 
 constexpr int BK = 32;
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-
-__device__ __forceinline__ unsigned int cvt2(float a, float b) {
-    f2 v = {a, b};
-    return __builtin_bit_cast(unsigned int, __builtin_convertvector(v, bf16x2));
-}
-__device__ __forceinline__ float lo_f(unsigned int p) { return __builtin_bit_cast(float, p << 16); }
-__device__ __forceinline__ float hi_f(unsigned int p) { return __builtin_bit_cast(float, p & 0xffff0000u); }
-
-// One LDS-DMA piece: 64 lanes x 16 bytes, global (buffer, per-lane byte offset `voff` + uniform `soff`) -> LDS at the
-// wave-uniform address `dst` + 16 * lane.  An out-of-range offset writes zeros.  (A __device__ helper: the builtin has no
-// host-side meaning and would silently drop the kernel's host stub if it sat in the kernel template itself.)
-__device__ __forceinline__ void dma16(const __amdgpu_buffer_rsrc_t rsrc, unsigned char* dst, int voff, int soff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_ptr_t)dst, 16, voff, soff, 0, 0);
-}
-
-// 8 fp32 -> three bf16x8 with x == h + m + l exactly
-__device__ __forceinline__ void split8(const f4 x0, const f4 x1, bf16x8& h, bf16x8& m, bf16x8& l) {
-    const float x[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
-    u4 hh, mm, ll;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const unsigned int ph = cvt2(x[2 * i], x[2 * i + 1]);
-        const float r0 = x[2 * i] - lo_f(ph), r1 = x[2 * i + 1] - hi_f(ph);
-        const unsigned int pm = cvt2(r0, r1);
-        const float s0 = r0 - lo_f(pm), s1 = r1 - hi_f(pm);
-        hh[i] = ph;
-        mm[i] = pm;
-        ll[i] = cvt2(s0, s1);
-    }
-    h = __builtin_bit_cast(bf16x8, hh);
-    m = __builtin_bit_cast(bf16x8, mm);
-    l = __builtin_bit_cast(bf16x8, ll);
-}
 
 // LDS chunk swizzles.  A b128 LDS read is served in groups of 16 lanes ({0-3,12-15,20-27}, {4-11,16-19,28-31}, ...); the
 // 16 lanes of a group must hit 16 different 16-byte bank groups.  With 32x32x16 fragments (SH = 32) a group holds 16
@@ -125,11 +84,7 @@ __global__ __launch_bounds__(64 * NW, 2) void tapconv_x6d_kernel(const spaa_tapc
     int a_off[4];
     uint32_t a_mlo[4], a_mhi[4];
     const uint32_t in_bytes = (uint32_t)p.B * (uint32_t)(p.Hin * p.Win) * (uint32_t)row_bytes;
-    const uint64_t in_addr = reinterpret_cast<uint64_t>(p.in);
-    const uint32_t in_lo = __builtin_amdgcn_readfirstlane((uint32_t)in_addr);
-    const uint32_t in_hi = __builtin_amdgcn_readfirstlane((uint32_t)(in_addr >> 32));
-    const auto rsrc_in = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<float*>(((uint64_t)in_hi << 32) | in_lo), 0,
-                                                            (int)__builtin_amdgcn_readfirstlane(in_bytes), 0x00020000);
+    const auto rsrc_in = wave_rsrc(p.in, in_bytes);
     // ---- weight staging: piece q = wave * WPW + i -> (plane, 16-row block); lane -> (row, physical chunk)
     const int npad = (p.Cout * (p.nfold > 1 ? p.nfold : 1) + 127) & ~127;
     const int plane_bytes = npad * cl.Kpad * 2;
@@ -138,7 +93,7 @@ __global__ __launch_bounds__(64 * NW, 2) void tapconv_x6d_kernel(const spaa_tapc
     const uint32_t w_hi = __builtin_amdgcn_readfirstlane((uint32_t)(w_addr >> 32));
     const auto rsrc_w = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((uint64_t)w_hi << 32) | w_lo), 0,
                                                            (int)__builtin_amdgcn_readfirstlane(3u * (uint32_t)plane_bytes),
-                                                           0x00020000);
+                                                           BUF_RSRC_FLAGS);
     int w_goff[WPW];
 
     const int nk_all = cl.Kpad / BK;

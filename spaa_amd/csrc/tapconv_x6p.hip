@@ -25,44 +25,7 @@
 #include "../../include/spaa_hip.h"
 #include "epilogue.hpp"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u4 __attribute__((ext_vector_type(4)));
-
 namespace {
-
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-
-__device__ __forceinline__ void dma16(const __amdgpu_buffer_rsrc_t rsrc, unsigned char* dst, int voff, int soff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_ptr_t)dst, 16, voff, soff, 0, 0);
-}
-__device__ __forceinline__ unsigned int cvt2(float a, float b) {
-    f2 v = {a, b};
-    return __builtin_bit_cast(unsigned int, __builtin_convertvector(v, bf16x2));
-}
-__device__ __forceinline__ float lo_f(unsigned int p) { return __builtin_bit_cast(float, p << 16); }
-__device__ __forceinline__ float hi_f(unsigned int p) { return __builtin_bit_cast(float, p & 0xffff0000u); }
-
-// 8 fp32 -> three bf16x8 with x == h + m + l exactly
-__device__ __forceinline__ void split8(const f32x4 a, const f32x4 b, bf16x8& h, bf16x8& m, bf16x8& l) {
-    const float x[8] = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-    u4 hh, mm, ll;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const unsigned int ph = cvt2(x[2 * i], x[2 * i + 1]);
-        const float r0 = x[2 * i] - lo_f(ph), r1 = x[2 * i + 1] - hi_f(ph);
-        const unsigned int pm = cvt2(r0, r1);
-        const float s0 = r0 - lo_f(pm), s1 = r1 - hi_f(pm);
-        hh[i] = ph;
-        mm[i] = pm;
-        ll[i] = cvt2(s0, s1);
-    }
-    h = __builtin_bit_cast(bf16x8, hh);
-    m = __builtin_bit_cast(bf16x8, mm);
-    l = __builtin_bit_cast(bf16x8, ll);
-}
 
 // A workgroup = FOUR waves (one per SIMD), TWO workgroups per compute unit (79 KB of LDS each): the two waves of a SIMD belong
 // to different workgroups, so one's fragment splits, barriers, prologue and epilogue (256 KB of stores per workgroup) run under
@@ -144,19 +107,11 @@ __global__ __launch_bounds__(64 * NW, 2) void x6p_kernel(const spaa_tapconv_t p,
 #endif
     const int row_bytes = p.in_cstride * 4;
     const uint32_t in_bytes = (uint32_t)p.B * (uint32_t)(H * W) * (uint32_t)row_bytes;
-    const uint64_t in_addr = reinterpret_cast<uint64_t>(p.in);
-    const uint32_t in_lo = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)in_addr);
-    const uint32_t in_hi = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(in_addr >> 32));
-    const auto rsrc_in = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((uint64_t)in_hi << 32) | in_lo), 0,
-                                                            (int)__builtin_amdgcn_readfirstlane(in_bytes), 0x00020000);
+    const auto rsrc_in = wave_rsrc(p.in, in_bytes);
     const int npad = (p.Cout + 127) & ~127;
     // the four classes' weight planes sit back to back in w_split: class c at element 3 * cls[c].w_off, [3][Npad][Kpad_c]
     const int64_t w_total = p.cls[3].w_off + (int64_t)npad * p.cls[3].Kpad;
-    const uint64_t w_addr = reinterpret_cast<uint64_t>(p.w_split);
-    const uint32_t w_lo = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)w_addr);
-    const uint32_t w_hi = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(w_addr >> 32));
-    const auto rsrc_w = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((uint64_t)w_hi << 32) | w_lo), 0,
-                                                           (int)__builtin_amdgcn_readfirstlane((uint32_t)(6 * w_total)), 0x00020000);
+    const auto rsrc_w = wave_rsrc(p.w_split, (uint32_t)(6 * w_total));
     typedef const __attribute__((address_space(4))) int* cint_ptr;
     cint_ptr ctaps = (cint_ptr)(uintptr_t)p.taps;
     const int dy_min = p.tap_range[0], dx_min = p.tap_range[2];
@@ -258,7 +213,7 @@ __global__ __launch_bounds__(64 * NW, 2) void x6p_kernel(const spaa_tapconv_t p,
 #pragma unroll
             for (int j = 0; j < TJ; ++j) acc[c][b][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    // one combo's products: two pixel blocks x TJ channel blocks x six bf16 MFMAs (small terms first, tapconv_x6d.hip X6D_MFMA6)
+    // one combo's products: two pixel blocks x TJ channel blocks x six bf16 MFMAs (mfma6)
 #define X6P_MFMA(c_, wbase)                                                                                        \
     {                                                                                                              \
         /* (the weight fragments of channel block j + 1 are requested before block j's MFMAs are issued) */         \
@@ -270,16 +225,7 @@ __global__ __launch_bounds__(64 * NW, 2) void x6p_kernel(const spaa_tapconv_t p,
                 _Pragma("unroll") for (int k = 0; k < 3; ++k)                                                       \
                     wf_[(j + 1) & 1][k] = *reinterpret_cast<const bf16x8*>((wbase) + (j + 1) * 1024 + k * W_PLANE); \
             }                                                                                                      \
-            const bf16x8 w0 = wf_[j & 1][0], w1 = wf_[j & 1][1], w2 = wf_[j & 1][2];                                \
-            _Pragma("unroll") for (int b = 0; b < 2; ++b) {                                                         \
-                f32x4 a_ = acc[c_][b][j];                                                                           \
-                a_ = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w2, pf[b][0], a_, 0, 0, 0);                            \
-                a_ = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w0, pf[b][2], a_, 0, 0, 0);                            \
-                a_ = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1, pf[b][1], a_, 0, 0, 0);                            \
-                a_ = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1, pf[b][0], a_, 0, 0, 0);                            \
-                a_ = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w0, pf[b][1], a_, 0, 0, 0);                            \
-                acc[c_][b][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w0, pf[b][0], a_, 0, 0, 0);                 \
-            }                                                                                                      \
+            _Pragma("unroll") for (int b = 0; b < 2; ++b) acc[c_][b][j] = mfma6(wf_[j & 1], pf[b], acc[c_][b][j]); \
             /* order: [the next block's three fragment reads,] then this block's twelve MFMAs, each with two VALU    \
                instructions in its shadow where there are any (class 3: the split of the next position's fragments) */ \
             if (j + 1 < TJ) __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);                                      \
@@ -301,11 +247,7 @@ __global__ __launch_bounds__(64 * NW, 2) void x6p_kernel(const spaa_tapconv_t p,
     }
     if (nkb2 > 0) {
         // weights of the second source: [3][Npad][Cin2] bf16 planes, one "combo" per 32-channel block, into the ring's last stages
-        const uint64_t w2_addr = reinterpret_cast<uint64_t>(p.w2_split);
-        const uint32_t w2_lo = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)w2_addr);
-        const uint32_t w2_hi = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(w2_addr >> 32));
-        const auto rsrc_w2 = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((uint64_t)w2_hi << 32) | w2_lo), 0,
-                                                                (int)__builtin_amdgcn_readfirstlane((uint32_t)(6 * npad * p.Cin2)), 0x00020000);
+        const auto rsrc_w2 = wave_rsrc(p.w2_split, (uint32_t)(6 * npad * p.Cin2));
         for (int k2 = 0; k2 < nkb2; ++k2) {
 #pragma unroll
             for (int i = 0; i < WPW; ++i) {

@@ -17,22 +17,15 @@
 #include "launch_util.hpp"
 #include <stdint.h>
 #include "../../include/spaa_hip.h"
+#include "device_util.hpp"
 
-typedef float f4 __attribute__((ext_vector_type(4)));
-typedef float f2 __attribute__((ext_vector_type(2)));
 typedef float f16v __attribute__((ext_vector_type(16)));
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 
 namespace {
 
 constexpr int TW = 32, TH1 = 8;  // pixel tile of a workgroup (class-grid coordinates): TW x (TH1 * P), P pixels per lane
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
 typedef const __attribute__((address_space(4))) int* cint_ptr;
 typedef const __attribute__((address_space(4))) f16v* cf16_ptr;
-
-__device__ __forceinline__ void dma16(const __amdgpu_buffer_rsrc_t rsrc, unsigned char* dst, int voff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_ptr_t)dst, 16, voff, 0, 0, 0);
-}
 
 constexpr int MAXCLS = SPAA_MAX_CLASSES;
 
@@ -70,11 +63,7 @@ __global__ __launch_bounds__(256) void thinpatch_kernel(const spaa_tapconv_t p, 
     const int y0 = ty * TH, x0 = tx * TW;
 
     const uint32_t in_bytes = (uint32_t)p.B * (uint32_t)(p.Hin * p.Win) * (uint32_t)p.in_cstride * (uint32_t)EB;
-    const uint64_t in_addr = reinterpret_cast<uint64_t>(p.in);
-    const uint32_t in_lo = __builtin_amdgcn_readfirstlane((uint32_t)in_addr);
-    const uint32_t in_hi = __builtin_amdgcn_readfirstlane((uint32_t)(in_addr >> 32));
-    const auto rsrc_in = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<float*>(((uint64_t)in_hi << 32) | in_lo), 0,
-                                                            (int)__builtin_amdgcn_readfirstlane(in_bytes), 0x00020000);
+    const auto rsrc_in = wave_rsrc(p.in, in_bytes);
     const int npix = PH * PW;
     const int npieces = (npix + PIX_PER_PIECE - 1) / PIX_PER_PIECE;
     const int row_bytes = p.in_cstride * EB;

@@ -6,19 +6,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/spaa_hip.h"
+#include "device_util.hpp"
 #include "warp_common.hpp"
 
 namespace {
-
-__device__ __forceinline__ float block_sum(float v, float* red) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane == 0) red[wave] = v;
-    __syncthreads();
-    return red[0] + red[1] + red[2] + red[3];
-}
 
 // d loss / d fine_grid, summed over the batch (the reference repeats one grid B times, models.py:172: the sum is what
 // reaches the shared parameters).  g_xw is the gradient w.r.t. the MASKED warped image; grid_sampler_2d_backward w.r.t. the
