@@ -308,6 +308,16 @@ int spaa_warp_finish_grid_bwd(const float* g_fine, const float* coarse, const fl
  * partial: ceil(Hout*Wout/256) * (6 + 2 (T+2)) floats of scratch (block sums, added in order) */
 int spaa_warp_coarse_grid_bwd(const float* g_coarse, const float* affine6, const float* theta, const float* ctrl, int T, int Hin,
                               int Win, int Hout, int Wout, float* partial, float* g_params, spaa_stream_t stream);
+/* ---- CompenNet++ training step (train_network.py:130-232), csrc/compennet_train.hip ----------------------------
+ * out[0] = (act[0] > 0) * sum_b g[b] over the first C channels of NHWC tensors with channel stride `cstride`: g [B,H,W,cstride],
+ * act / out [1,H,W,cstride] (act NULL: no gate); C % 4 == 0, cstride % 4 == 0, C <= cstride.  The sum runs b = 0 .. B-1 in
+ * order (no atomics).  The gradient of the batch-1 surface branch from the backbone gradients it feeds (models.py:74-81). */
+int spaa_batch_sum_gate(const float* g, const float* act, float* out, int B, int H, int W, int C, int cstride, spaa_stream_t stream);
+/* grid gradient of TWO sources sampled through one grid (no mask), written (not accumulated): g_grid [Hc,Wc,4] =
+ * d/d grid of source a (g_a [B_a,Hc,Wc,4] gradient w.r.t. the warped image, x_a [B_a,Hp,Wp,4]) plus source b (g_b [B_b,Hc,Wc,4],
+ * x_b [B_b,Hp,Wp,4]); Hp x Wp is the source size, Hc x Wc the grid's (models.py:204-212: camera image and scene) */
+int spaa_warp_bwd_grid2(const float* g_a, const float* x_a, int B_a, const float* g_b, const float* x_b, int B_b, const float* grid,
+                        float* g_grid, int Hp, int Wp, int Hc, int Wc, spaa_stream_t stream);
 /* ---- fused tail / head of ShadingNetSPAA (/root/reference/src/python/models.py:296-300) --------------------------
  * forward:   Ypre = relu(conv6(relu(transConv2(X6) + bias2)) + bias6 + res1),  Y = min(Ypre, 1); the activation between
  *            the two layers (X7, 32 channels at camera resolution) stays in LDS, only its ReLU gate bytes reach HBM.

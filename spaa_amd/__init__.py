@@ -27,6 +27,9 @@ def __getattr__(name):
     if name in ('PerC_AL', 'perc_al_compennet_pp'):
         from . import perc_al
         return getattr(perc_al, name)
+    if name in ('PCNetTrainer', 'train_pcnet', 'CompenNetTrainer', 'train_compennet_pp', 'init_compennet', 'evaluate_model'):
+        from . import train_network
+        return getattr(train_network, name)
     if name == 'calc_img_dists':
         from . import metrics
         return metrics.calc_img_dists

@@ -982,8 +982,8 @@ def _warp_backward_impl(saved, gy):
 
 
 # ----------------------------------------------------------------------------------------------------------------
-# CompenNet / CompenNet++ (models.py:11-94, :188-212): forward only — used once, after the PerC-AL loop, to turn the
-# adversarial camera image into a projector image (projector_based_attack.py:357).
+# CompenNet / CompenNet++ (models.py:11-94, :188-212): the forward pass turns the adversarial camera image into a projector
+# image after the PerC-AL loop (projector_based_attack.py:357); training is CompenNetTrainer's (spaa_amd/train_network.py).
 class CompenNet(nn.Module):
     def __init__(self):
         super().__init__()
@@ -1017,6 +1017,10 @@ class CompenNet(nn.Module):
             f['transConv2'] = cp.deconv_fwd_plan(self.transConv2.weight, self.transConv2.bias, 2, 0, dev, 'compen.tc2')
             self._plans = (dev, f)
         return self._plans[1]
+
+    def invalidate(self):
+        """Call after changing parameters in place (the packed weights of `plans()` are cached)."""
+        self._plans = None
 
     def forward_nhwc4(self, x4, s4):
         """models.py:74-94 on NHWC4 tensors [B,H,W,4] (H, W divisible by 4)."""
@@ -1071,6 +1075,11 @@ class CompenNetPlusplus(nn.Module):
         self.warping_net = unwrap(warping_net) if warping_net is not None else WarpingNet()
         self.compen_net = unwrap(compen_net) if compen_net is not None else CompenNet()
         self._grid = None
+
+    def invalidate(self):
+        """Call after changing parameters in place (the fine grid and the packed weights are cached)."""
+        self._grid = None
+        self.compen_net.invalidate()
 
     def load_state_dict(self, state_dict, strict=True):
         self._grid = None

@@ -1,4 +1,5 @@
-"""PCNet training step on HIP.
+"""PCNet and CompenNet++ training steps on HIP.  CompenNet++: `CompenNetTrainer`,
+`train_compennet_pp`, `init_compennet`, `evaluate_model` at the end of this file (train_network.py:98-232, :395-441).
 
 Mirrors `train_pcnet` of /root/reference/src/python/train_network.py:235-363 and `compute_loss` :367-392: one iteration =
 forward of PCNet (WarpingNet with its CURRENT parameters: the sampling grid is rebuilt every step, models.py:163-185) ->
@@ -16,6 +17,7 @@ PyTorch supplies device memory and index plumbing (re-packing a changed paramete
 precomputed index maps).  No CPU fallback.
 """
 import math
+import os
 import random
 
 import torch
@@ -355,3 +357,474 @@ def train_pcnet(model, train_data, valid_data, cfg):
         valid_psnr, valid_rmse, valid_ssim = (metrics.psnr(infer, valid_data['cam_valid']), metrics.rmse(infer, valid_data['cam_valid']),
                                               metrics.ssim(infer, valid_data['cam_valid']))
     return model, valid_psnr, valid_rmse, valid_ssim
+
+
+# ================================================================================================================
+# CompenNet++ training (train_network.py:98-232)
+# ================================================================================================================
+# CompenNet's convolutions (models.py:17-45): module name -> (stride, padding); the transposed ones are k2 / s2 / p0
+_COMPEN_CONV = {
+    'conv1': (2, 1), 'conv2': (2, 1), 'conv3': (1, 1), 'conv4': (1, 1), 'conv5': (1, 1), 'conv1_s': (2, 1), 'conv2_s': (2, 1),
+    'conv3_s': (1, 1), 'conv4_s': (1, 1), 'conv6': (1, 1), 'skipConv2': (1, 0), 'skipConv3': (1, 0), 'skipConv1.0': (1, 1),
+    'skipConv1.2': (1, 1), 'skipConv1.4': (1, 1)}
+_COMPEN_DECONV = ('transConv1', 'transConv2')
+
+
+class _CompenNetEngine:
+    """CompenNet's forward and backward pass for training, workspaces kept across steps.
+
+    The backbone runs at batch B.  The surface branch (conv1_s .. conv4_s) runs once, at batch 1: the scene is one image
+    expanded to the batch (train_network.py:139), so every sample's branch is the same.  Its outputs are broadcast into the
+    backbone's residual inputs; its gradient is the batch sum of the backbone pre-activation gradients it feeds
+    (spaa_batch_sum_gate), the same gradient as the reference's up to summation order.  Packed weights are refreshed on the
+    device each step (attach_maps / ConvPlan.refresh).  `input_grad`: also produce the gradients w.r.t. both inputs (the
+    warped camera image and the warped scene: CompenNet++ needs them for the grid)."""
+
+    def __init__(self, cn, B, H, W, dev, input_grad):
+        self.cn, self.B, self.H, self.W, self.dev, self.input_grad = cn, B, H, W, dev, input_grad
+        self.maps = []   # (plan, weight parameter, bias parameter or None) of every plan whose packed weights must follow training
+        self.f, self.d, self.wg = {}, {}, {}
+        need_d = set(_COMPEN_CONV) | set(_COMPEN_DECONV)
+        if not input_grad:
+            need_d -= {'conv1', 'conv1_s', 'skipConv1.0'}
+        for nm, (st, pad) in _COMPEN_CONV.items():
+            mod = cn.get_submodule(nm)
+            fb = (lambda w, st=st, pad=pad: cp.conv_fwd_plan(w, None, st, pad, 'cpu'))
+            self.f[nm] = self._reg(cp.conv_fwd_plan(mod.weight, mod.bias, st, pad, dev, 'train.' + nm), fb, mod, True)
+            self.wg[nm] = self._wg_plan(mod, fb)
+            if nm in need_d:
+                db = (lambda w, st=st, pad=pad: cp.conv_dgrad_plan(w, st, pad, 'cpu'))
+                self.d[nm] = self._reg(cp.conv_dgrad_plan(mod.weight, st, pad, dev, 'train.' + nm + '_dgrad'), db, mod, False)
+        for nm in _COMPEN_DECONV:
+            mod = cn.get_submodule(nm)
+            fb = (lambda w: cp.deconv_fwd_plan(w, None, 2, 0, 'cpu'))
+            self.f[nm] = self._reg(cp.deconv_fwd_plan(mod.weight, mod.bias, 2, 0, dev, 'train.' + nm), fb, mod, True)
+            self.wg[nm] = self._wg_plan(mod, lambda w: cp.deconv_fwd_plan(w, None, 2, 0, 'cpu', fold=False))
+            db = (lambda w: cp.deconv_dgrad_plan(w, 2, 0, 'cpu'))
+            self.d[nm] = self._reg(cp.deconv_dgrad_plan(mod.weight, 2, 0, dev, 'train.' + nm + '_dgrad'), db, mod, False)
+        H2, W2, H4, W4 = H // 2, W // 2, H // 4, W // 4
+
+        def z(*shape):
+            return torch.zeros(*shape, device=dev)
+
+        shp = {'S1': (H2, W2, 32), 'S2': (H4, W4, 64), 'S3': (H4, W4, 128), 'S4': (H4, W4, 256)}
+        self.a = {k: z(1, *v) for k, v in shp.items()}                                   # surface branch, batch 1
+        self.a.update({'b' + k: z(B, *v) for k, v in shp.items()})                       # ... broadcast to the batch
+        self.a.update(t0=z(B, H, W, 4), t1=z(B, H, W, 4), R1=z(B, H, W, 4), X1=z(B, H2, W2, 32), R2=z(B, H2, W2, 64),
+                      X2=z(B, H4, W4, 64), R3=z(B, H4, W4, 128), X3=z(B, H4, W4, 128), X4=z(B, H4, W4, 256), X5=z(B, H4, W4, 128),
+                      X6=z(B, H2, W2, 64), X7=z(B, H, W, 32), Y=z(B, H, W, 4), Ypre=z(B, H, W, 4))
+        self.g = dict(P7=z(B, H, W, 32), P6=z(B, H2, W2, 64), P5=z(B, H4, W4, 128), P4=z(B, H4, W4, 256), P3=z(B, H4, W4, 128),
+                      t2=z(B, H4, W4, 64), P2=z(B, H4, W4, 64), t1s=z(B, H2, W2, 32), P1=z(B, H2, W2, 32), r1=z(B, H, W, 4),
+                      t1=z(B, H, W, 4), t0=z(B, H, W, 4), xs=z(B, H, W, 4), xw=z(B, H, W, 4),
+                      S4=z(1, H4, W4, 256), sum3=z(1, H4, W4, 128), S3=z(1, H4, W4, 128), sum2=z(1, H4, W4, 64), S2=z(1, H4, W4, 64),
+                      sum1=z(1, H2, W2, 32), S1=z(1, H2, W2, 32), sw=z(1, H, W, 4))
+
+    def _reg(self, plan, builder, mod, with_bias):
+        cp.attach_maps(plan, builder, mod.weight.detach().cpu())
+        self.maps.append((plan, mod.weight, mod.bias if with_bias else None))
+        return plan
+
+    def _wg_plan(self, mod, builder):
+        """A plan used for its geometry only (taps, classes, packing layout): tap list on the device, unpack map attached."""
+        w = mod.weight.detach().cpu()
+        pl = builder(w)
+        pl.weights, pl.taps, pl.w_split = pl.weights.to(self.dev), pl.taps.to(self.dev), None
+        cp.attach_maps(pl, builder, w)
+        return pl
+
+    def refresh(self):
+        for plan, w, b in self.maps:
+            plan.refresh(w, b)
+
+    def forward(self, xw, sw):
+        """models.py:74-94: xw [B,H,W,4] the (warped) image, sw [1,H,W,4] the (warped) scene.  Returns (Y, Ypre) [B,H,W,4]:
+        the output and relu(pre-activation) of conv6 (its clamp gate)."""
+        a, f = self.a, self.f
+        R, N = _lib.ACT_RELU, _lib.ACT_NONE
+        f['conv1_s'].run(sw, a['S1'], act=R)
+        f['conv2_s'].run(a['S1'], a['S2'], act=R)
+        f['conv3_s'].run(a['S2'], a['S3'], act=R)
+        f['conv4_s'].run(a['S3'], a['S4'], act=R)
+        for k in ('S1', 'S2', 'S3', 'S4'):
+            a['b' + k].copy_(a[k].expand_as(a['b' + k]))
+        f['skipConv1.0'].run(xw, a['t0'], act=R)
+        f['skipConv1.2'].run(a['t0'], a['t1'], act=R)
+        f['skipConv1.4'].run(a['t1'], a['R1'], act=R)
+        f['conv1'].run(xw, a['X1'], add=a['bS1'], act=R)
+        f['skipConv2'].run(a['X1'], a['R2'], act=N)
+        f['conv2'].run(a['X1'], a['X2'], add=a['bS2'], act=R)
+        f['skipConv3'].run(a['X2'], a['R3'], act=N)
+        f['conv3'].run(a['X2'], a['X3'], add=a['bS3'], act=R)
+        f['conv4'].run(a['X3'], a['X4'], add=a['bS4'], act=R)
+        f['conv5'].run(a['X4'], a['X5'], add=a['R3'], act=R)
+        f['transConv1'].run(a['X5'], a['X6'], add=a['R2'], act=R)
+        f['transConv2'].run(a['X6'], a['X7'], act=R)
+        f['conv6'].run(a['X7'], a['Y'], add=a['R1'], act=_lib.ACT_RELU_CLAMP1, aux_out=a['Ypre'])
+        return a['Y'], a['Ypre']
+
+    def backward(self, gP, xw, sw, grads, prefix):
+        """gP: gradient w.r.t. conv6's pre-activation (clamp gate applied) [B,H,W,4].  Fills `grads` with every parameter's
+        gradient (names `prefix` + parameter name); with `input_grad`, returns (g_xw [B,H,W,4], g_sw [1,H,W,4])."""
+        a, g, d = self.a, self.g, self.d
+        p = _lib.ptr
+
+        def wgrad(nm, inp, gout):
+            dw, db = self.wg[nm].wgrad(inp, gout)
+            grads[prefix + nm + '.weight'] = self.wg[nm].unpack_grad(dw)
+            grads[prefix + nm + '.bias'] = db
+
+        def bsum(gb, act, out):
+            _lib.call('spaa_batch_sum_gate', p(gb), p(act), p(out), self.B, gb.shape[1], gb.shape[2], gb.shape[3], gb.shape[3])
+
+        # backbone (batch B)
+        wgrad('conv6', a['X7'], gP)
+        _lib.call('spaa_relu_gate', p(gP), p(a['R1']), p(g['r1']), gP.numel())          # res1 = relu(skipConv1.4(.))
+        d['conv6'].run(gP, g['P7'], gate=a['X7'])
+        wgrad('transConv2', a['X6'], g['P7'])
+        d['transConv2'].run(g['P7'], g['P6'], gate=a['X6'])
+        wgrad('transConv1', a['X5'], g['P6'])
+        wgrad('skipConv2', a['X1'], g['P6'])                                           # res2 enters transConv1's sum
+        d['transConv1'].run(g['P6'], g['P5'], gate=a['X5'])
+        wgrad('conv5', a['X4'], g['P5'])
+        wgrad('skipConv3', a['X2'], g['P5'])                                           # res3 enters conv5's sum
+        d['conv5'].run(g['P5'], g['P4'], gate=a['X4'])
+        wgrad('conv4', a['X3'], g['P4'])
+        d['conv4'].run(g['P4'], g['P3'], gate=a['X3'])
+        wgrad('conv3', a['X2'], g['P3'])
+        d['skipConv3'].run(g['P5'], g['t2'])
+        d['conv3'].run(g['P3'], g['P2'], add=g['t2'], gate=a['X2'])
+        wgrad('conv2', a['X1'], g['P2'])
+        d['skipConv2'].run(g['P6'], g['t1s'])
+        d['conv2'].run(g['P2'], g['P1'], add=g['t1s'], gate=a['X1'])
+        wgrad('conv1', xw, g['P1'])
+        # skipConv1 chain (on the image)
+        wgrad('skipConv1.4', a['t1'], g['r1'])
+        d['skipConv1.4'].run(g['r1'], g['t1'], gate=a['t1'])
+        wgrad('skipConv1.2', a['t0'], g['t1'])
+        d['skipConv1.2'].run(g['t1'], g['t0'], gate=a['t0'])
+        wgrad('skipConv1.0', xw, g['t0'])
+        # surface branch (batch 1): res_k_s = relu(conv_k_s(.)) enters relu(conv_k(x) + res_k_s) of every sample
+        bsum(g['P4'], a['S4'], g['S4'])
+        wgrad('conv4_s', a['S3'], g['S4'])
+        bsum(g['P3'], a['S3'], g['sum3'])
+        d['conv4_s'].run(g['S4'], g['S3'], add=g['sum3'], gate=a['S3'])
+        wgrad('conv3_s', a['S2'], g['S3'])
+        bsum(g['P2'], a['S2'], g['sum2'])
+        d['conv3_s'].run(g['S3'], g['S2'], add=g['sum2'], gate=a['S2'])
+        wgrad('conv2_s', a['S1'], g['S2'])
+        bsum(g['P1'], a['S1'], g['sum1'])
+        d['conv2_s'].run(g['S2'], g['S1'], add=g['sum1'], gate=a['S1'])
+        wgrad('conv1_s', sw, g['S1'])
+        if not self.input_grad:
+            return None
+        d['skipConv1.0'].run(g['t0'], g['xs'])
+        d['conv1'].run(g['P1'], g['xw'], add=g['xs'])
+        d['conv1_s'].run(g['S1'], g['sw'])
+        return g['xw'], g['sw']
+
+
+class CompenNetTrainer:
+    """State of one CompenNet++ (or bare CompenNet) training run: engine, Adam moments, learning rate.  `step(cam_batch,
+    prj_batch)` is one iteration of the reference's loop body (train_network.py:180-192) plus its scheduler step (:226):
+    one torch.optim.Adam over ALL parameters (WarpingNet included) with L2 weight decay `l2_reg`, StepLR(lr_drop_rate,
+    lr_drop_ratio).  Everything arithmetic runs in libspaa_hip.so:
+      grid (current parameters)      spaa_warp_coarse_grid, refine-net tapconv plans, spaa_warp_finish_grid
+      warps (image and scene)        spaa_warp_fwd
+      CompenNet forward / backward   tapconv plans (_CompenNetEngine), spaa_tapconv_wgrad, spaa_batch_sum_gate, spaa_relu_gate
+      loss + its gradient            spaa_train_loss_fwd_bwd, spaa_select_grad (clamp gate)
+      grid / affine / TPS gradients  spaa_warp_bwd_grid2, spaa_warp_finish_grid_bwd, spaa_warp_coarse_grid_bwd
+      optimiser                      spaa_adam_step
+    PyTorch supplies device memory and index plumbing.  No CPU fallback."""
+
+    def __init__(self, model, cam_scene, batch_size, lr=1e-3, l2_reg=1e-4, lr_drop_rate=800, lr_drop_ratio=0.2, device='cuda'):
+        from .models import CompenNet, CompenNetPlusplus
+        if isinstance(model, CompenNetPlusplus):
+            self.pp, cn, wn = True, model.compen_net, model.warping_net
+        elif isinstance(model, CompenNet):
+            self.pp, cn, wn = False, model, None
+        else:
+            raise TypeError('CompenNetTrainer needs a spaa_amd.CompenNetPlusplus or spaa_amd.CompenNet')
+        dev = torch.device(device)
+        if dev.type != 'cuda':
+            raise RuntimeError('spaa_amd training runs on the GPU only (no CPU fallback)')
+        if dev.index is None:
+            dev = torch.device('cuda', torch.cuda.current_device())
+        for n, prm in model.named_parameters():
+            if prm.device != dev or prm.dtype != torch.float32:
+                raise ValueError(f'CompenNetTrainer: parameter {n} is {prm.dtype} on {prm.device}; move the model to {dev} first')
+        if wn is not None and not wn.with_refine:
+            raise NotImplementedError('CompenNet++ training covers WarpingNet with the grid-refine net (with_refine=True)')
+        s = cam_scene.detach().float()
+        while s.ndim < 4:
+            s = s[None]
+        if s.shape[0] != 1 or s.shape[1] != 3:
+            raise ValueError(f'cam_scene must be one [3,H,W] / [1,3,H,W] image, got {tuple(cam_scene.shape)}')
+        self.Hs, self.Ws = s.shape[-2:]                         # source size of the warp (camera), = output size without it
+        self.H, self.W = wn.out_size if self.pp else (self.Hs, self.Ws)
+        if self.H % 4 or self.W % 4:
+            raise ValueError(f'CompenNet training needs an output (projector) size divisible by 4, got {self.H}x{self.W}')
+        self.model, self.cn, self.wn, self.dev, self.B = model, cn, wn, dev, int(batch_size)
+        self.lr, self.l2_reg = float(lr), float(l2_reg)
+        self.lr_drop_rate, self.gamma = int(lr_drop_rate), float(lr_drop_ratio)
+        self.prefix = 'compen_net.' if self.pp else ''
+        self.params = dict(model.named_parameters())
+        with _lib.on_device(dev):
+            self.scene4 = to_nhwc4(s.to(dev))
+            self.window = _window().to(dev)
+            self.m = {n: torch.zeros_like(p) for n, p in self.params.items()}
+            self.v = {n: torch.zeros_like(p) for n, p in self.params.items()}
+            self.eng = _CompenNetEngine(cn, self.B, self.H, self.W, dev, input_grad=self.pp)
+            if self.pp:
+                self._build_warp()
+
+            def z(*shape):
+                return torch.zeros(*shape, device=dev)
+
+            B, H, W = self.B, self.H, self.W
+            nblk = ((H + 15) // 16) * ((W + 15) // 16)
+            self.loss_ws = dict(mmu=z(B, H, W, 4), m11=z(B, H, W, 4), m12=z(B, H, W, 4), partial=z(B * nblk, 3), gY=z(B, H, W, 4),
+                                gP=z(B, H, W, 4))
+            self.ones_state = torch.ones(B, 4, dtype=torch.int32, device=dev)
+        self.grads = {}
+        self.iters = 0
+
+    # ------------------------------------------------------------------------------------------------------------
+    def _build_warp(self):
+        """Plans of the grid-refine net (models.py:123-134): forward, input-gradient, weight-gradient; grid workspaces."""
+        wn, dev, eng = self.wn, self.dev, self.eng
+        g = wn.grid_refine_net
+        self.rf, self.rd, self.rwg = {}, {}, {}
+        for i, kind in ((0, 'conv'), (2, 'conv'), (4, 'deconv'), (6, 'deconv')):
+            mod = g[i]
+            if kind == 'conv':
+                fb = (lambda w: cp.conv_fwd_plan(w, None, 2, 1, 'cpu'))
+                db = (lambda w: cp.conv_dgrad_plan(w, 2, 1, 'cpu'))
+                self.rf[i] = cp.conv_fwd_plan(mod.weight, mod.bias, 2, 1, dev, f'refine{i}')
+                self.rd[i] = cp.conv_dgrad_plan(mod.weight, 2, 1, dev, f'refine{i}_dgrad')
+                wb = fb
+            else:
+                fb = (lambda w: cp.deconv_fwd_plan(w, None, 2, 0, 'cpu'))
+                db = (lambda w: cp.deconv_dgrad_plan(w, 2, 0, 'cpu'))
+                self.rf[i] = cp.deconv_fwd_plan(mod.weight, mod.bias, 2, 0, dev, f'refine{i}')
+                self.rd[i] = cp.deconv_dgrad_plan(mod.weight, 2, 0, dev, f'refine{i}_dgrad')
+                wb = (lambda w: cp.deconv_fwd_plan(w, None, 2, 0, 'cpu', fold=False))
+            eng._reg(self.rf[i], fb, mod, True)
+            eng._reg(self.rd[i], db, mod, False)
+            self.rwg[i] = eng._wg_plan(mod, wb)
+        H, W, B = self.H, self.W, self.B
+
+        def z(*shape):
+            return torch.zeros(*shape, device=dev)
+
+        ncol = 6 + 2 * (wn.nctrl + 2)
+        self.grid_ws = dict(coarse=z(1, H, W, 4), r0=z(1, H // 2, W // 2, 32), r2=z(1, H // 4, W // 4, 64),
+                            r4=z(1, H // 2, W // 2, 32), refine=z(1, H, W, 4), fine=z(H, W, 4),
+                            g_fine=z(H, W, 4), g_sum=z(1, H, W, 4), g_r6=z(1, H, W, 4), g_r4=z(1, H // 2, W // 2, 32),
+                            g_r2=z(1, H // 4, W // 4, 64), g_r0=z(1, H // 2, W // 2, 32), g_c0=z(1, H, W, 4),
+                            partial=z(((H * W + 255) // 256) * ncol), g_params=z(ncol))
+        self.xw, self.sw = z(B, H, W, 4), z(1, H, W, 4)
+
+    def _grid_forward(self):
+        """models.py:168-178 with the current parameters, keeping every intermediate for the backward pass."""
+        wn, ws = self.wn, self.grid_ws
+        H, W = self.H, self.W
+        self._aff = wn.affine_mat.detach().float().contiguous().view(-1)
+        self._theta = wn.theta.detach().float().contiguous().view(-1)
+        self._ctrl = wn.ctrl_pts.detach().float().contiguous().view(-1)
+        _lib.call('spaa_warp_coarse_grid', _lib.ptr(self._aff), _lib.ptr(self._theta), _lib.ptr(self._ctrl), wn.nctrl, self.Hs,
+                  self.Ws, H, W, _lib.ptr(ws['coarse']))
+        R, L = _lib.ACT_RELU, _lib.ACT_LEAKY01
+        self.rf[0].run(ws['coarse'], ws['r0'], act=R)
+        self.rf[2].run(ws['r0'], ws['r2'], act=R)
+        self.rf[4].run(ws['r2'], ws['r4'], act=R)
+        self.rf[6].run(ws['r4'], ws['refine'], act=L)
+        _lib.call('spaa_warp_finish_grid', _lib.ptr(ws['coarse']), _lib.ptr(ws['refine']), _lib.ptr(ws['fine']), H * W)
+        return ws['fine']
+
+    def _grid_backward(self, g_xw, cam4, g_sw):
+        """Gradient of the loss w.r.t. the WarpingNet parameters from the gradients w.r.t. BOTH warped images (models.py:208-209)."""
+        p, ws, wn, gr = _lib.ptr, self.grid_ws, self.wn, self.grads
+        H, W = self.H, self.W
+        _lib.call('spaa_warp_bwd_grid2', p(g_xw), p(cam4), self.B, p(g_sw), p(self.scene4), 1, p(ws['fine']), p(ws['g_fine']),
+                  self.Hs, self.Ws, H, W)
+        _lib.call('spaa_warp_finish_grid_bwd', p(ws['g_fine']), p(ws['coarse']), p(ws['refine']), p(ws['g_sum']), p(ws['g_r6']),
+                  H * W)
+        wp = 'warping_net.grid_refine_net.'
+
+        def rwgrad(i, inp, gout):
+            dw, db = self.rwg[i].wgrad(inp, gout)
+            gr[wp + f'{i}.weight'] = self.rwg[i].unpack_grad(dw)
+            gr[wp + f'{i}.bias'] = db
+
+        rwgrad(6, ws['r4'], ws['g_r6'])
+        self.rd[6].run(ws['g_r6'], ws['g_r4'], gate=ws['r4'])
+        rwgrad(4, ws['r2'], ws['g_r4'])
+        self.rd[4].run(ws['g_r4'], ws['g_r2'], gate=ws['r2'])
+        rwgrad(2, ws['r0'], ws['g_r2'])
+        self.rd[2].run(ws['g_r2'], ws['g_r0'], gate=ws['r0'])
+        rwgrad(0, ws['coarse'], ws['g_r0'])
+        self.rd[0].run(ws['g_r0'], ws['g_c0'], add=ws['g_sum'])               # + the skip connection (models.py:176)
+        _lib.call('spaa_warp_coarse_grid_bwd', p(ws['g_c0']), p(self._aff), p(self._theta), p(self._ctrl), wn.nctrl, self.Hs,
+                  self.Ws, H, W, p(ws['partial']), p(ws['g_params']))
+        gr['warping_net.affine_mat'] = ws['g_params'][:6].view(1, 2, 3)
+        gr['warping_net.theta'] = ws['g_params'][6:].view(1, wn.nctrl + 2, 2)
+
+    # ------------------------------------------------------------------------------------------------------------
+    def step(self, cam_batch, prj_batch, loss='l1+ssim'):
+        """One training iteration (train_network.py:180-192, :226): `cam_batch` [B,3,Hc,Wc] the model input, `prj_batch`
+        [B,3,Hp,Wp] the target.  Returns (loss value, l2 (MSE) value) as Python floats."""
+        if loss == '':
+            raise TypeError('Loss type not specified')                            # compute_loss :368-369
+        if 'l2' in loss or 'huber' in loss:
+            raise NotImplementedError("spaa_amd CompenNet++ training implements the losses 'l1', 'ssim' and 'l1+ssim'")
+        if 'l1' not in loss and 'ssim' not in loss:
+            raise ValueError(f'unknown loss option {loss!r}')
+        B = self.B
+        if tuple(cam_batch.shape) != (B, 3, self.Hs, self.Ws) or tuple(prj_batch.shape) != (B, 3, self.H, self.W):
+            raise ValueError(f'expected cam_batch [{B},3,{self.Hs},{self.Ws}] and prj_batch [{B},3,{self.H},{self.W}], got '
+                             f'{tuple(cam_batch.shape)} and {tuple(prj_batch.shape)}')
+        with _lib.on_device(self.dev):
+            return self._step(cam_batch, prj_batch, loss)
+
+    def _step(self, cam_batch, prj_batch, loss):
+        p = _lib.ptr
+        B, H, W, eng = self.B, self.H, self.W, self.eng
+        cam4 = to_nhwc4(cam_batch.to(self.dev))
+        t4 = to_nhwc4(prj_batch.to(self.dev))
+        # ---- forward with the current parameters (model(cam, scene) :185)
+        eng.refresh()
+        if self.pp:
+            fine = self._grid_forward()
+            _lib.call('spaa_warp_fwd', p(cam4), p(fine), None, None, p(self.xw), None, B, self.Hs, self.Ws, H, W, 0)
+            _lib.call('spaa_warp_fwd', p(self.scene4), p(fine), None, None, p(self.sw), None, 1, self.Hs, self.Ws, H, W, 0)
+            xw, sw = self.xw, self.sw
+        else:
+            xw, sw = cam4, self.scene4
+        y4, ypre = eng.forward(xw, sw)
+        # ---- loss and its gradient w.r.t. the output (compute_loss :367-392), then the clamp / ReLU gate of conv6
+        lw = self.loss_ws
+        l1_w, ssim_w = (1.0 if 'l1' in loss else 0.0), (1.0 if 'ssim' in loss else 0.0)
+        _lib.call('spaa_train_loss_fwd_bwd', p(y4), p(t4), p(self.window), l1_w, ssim_w, p(lw['mmu']), p(lw['m11']), p(lw['m12']),
+                  p(lw['partial']), p(lw['gY']), B, H, W)
+        _lib.call('spaa_select_grad', p(lw['gY']), p(lw['gY']), p(self.ones_state), p(ypre), p(lw['gP']), B, H * W)
+        # ---- backward
+        gin = eng.backward(lw['gP'], xw, sw, self.grads, self.prefix)
+        if self.pp:
+            self._grid_backward(gin[0], cam4, gin[1])
+        # ---- Adam over all parameters (:190-192), then StepLR (:226)
+        self.iters += 1
+        for n, prm in self.params.items():
+            gt = self.grads[n].contiguous()
+            assert gt.numel() == prm.numel(), n
+            _lib.call('spaa_adam_step', p(prm.data.view(-1)), p(gt.view(-1)), p(self.m[n].view(-1)), p(self.v[n].view(-1)),
+                      prm.numel(), self.lr, 0.9, 0.999, 1e-8, self.l2_reg, self.iters)
+        if self.iters % self.lr_drop_rate == 0:
+            self.lr *= self.gamma
+        self.model.invalidate()
+        part = lw['partial'].sum(dim=0).cpu()
+        n_el = 3.0 * B * H * W
+        l1, l2 = float(part[1]) / n_el, float(part[2]) / n_el
+        return l1_w * l1 + ssim_w * (1.0 - float(part[0]) / n_el), l2
+
+
+def _cfg_getter(cfg):
+    return (lambda k, d=None: cfg[k] if k in cfg else d) if isinstance(cfg, dict) else (lambda k, d=None: getattr(cfg, k, d))
+
+
+def _model_name(model):
+    return model.name if hasattr(model, 'name') else model.module.name
+
+
+def evaluate_model(model, valid_data, chunk_sz=10):
+    """train_network.py:395-441: (psnr, rmse, ssim, inference on the host) over `valid_data` (cam_scene, cam_valid,
+    prj_valid), the metrics of each of `chunk_sz` chunks (metrics.calc_img_dists) weighted by its size.  PCNet maps the
+    projector image to the camera image; CompenNet++ (and a bare CompenNet) the camera image to the projector image."""
+    from . import metrics
+    cam_scene, cam_valid, prj_valid = valid_data['cam_scene'], valid_data['cam_valid'], valid_data['prj_valid']
+    name = _model_name(model)
+    if 'PCNet' in name:
+        model_in, gt = prj_valid, cam_valid
+    elif 'CompenNet' in name:
+        model_in, gt = cam_valid, prj_valid
+    else:
+        raise ValueError(f'evaluate_model: unknown model {name!r}')
+    dev = next(model.parameters()).device
+    num_valid = cam_valid.shape[0]
+    if cam_scene.ndim == 3:
+        cam_scene = cam_scene[None]
+    if cam_scene.shape[0] == 1:
+        cam_scene = cam_scene.expand(num_valid, -1, -1, -1)
+    valid_psnr, valid_rmse, valid_ssim = 0., 0., 0.
+    with torch.no_grad():
+        model.eval()
+        infer = torch.zeros(gt.shape)
+        for idx in torch.chunk(torch.arange(num_valid), chunk_sz):
+            out = model(model_in[idx].to(dev), cam_scene[idx].to(dev))
+            if isinstance(out, tuple):
+                out = out[0]
+            infer[idx] = out.detach().cpu()
+            m = metrics.calc_img_dists(out, gt[idx].to(dev))
+            valid_psnr += m[0] * len(idx) / num_valid
+            valid_rmse += m[1] * len(idx) / num_valid
+            valid_ssim += m[2] * len(idx) / num_valid
+    return valid_psnr, valid_rmse, valid_ssim, infer
+
+
+def train_compennet_pp(model, train_data, valid_data, cfg):
+    """train_network.py:130-232 (without the visdom plots): `train_data` = dict(cam_scene [1,3,H,W], cam_train, prj_train),
+    `cfg` (dict or attribute object) with device, max_iters, batch_size, num_train, lr, l2_reg, lr_drop_rate, lr_drop_ratio,
+    loss; with data_root, the trained state dict is saved as `<data_root>/../checkpoint/<io.opt_to_string(cfg)>.pth` like the
+    reference's.  Batch indices are random.sample(range(num_train), batch_size) as in the reference.  Validation (when
+    `valid_data` is given) runs after the last iteration.  Returns (model, valid_psnr, valid_rmse, valid_ssim)."""
+    get = _cfg_getter(cfg)
+    dev = torch.device(get('device', 'cuda'))
+    loss_opt = get('loss', 'l1+ssim')
+    bsz, num_train, max_iters = get('batch_size'), get('num_train'), get('max_iters')
+    tr = CompenNetTrainer(model, train_data['cam_scene'], bsz, get('lr', 1e-3), get('l2_reg', 1e-4), get('lr_drop_rate', 800),
+                          get('lr_drop_ratio', 0.2), dev)
+    cam_train, prj_train = train_data['cam_train'], train_data['prj_train']
+    for it in range(max_iters):
+        idx = random.sample(range(num_train), bsz)                                # :178
+        loss, l2 = tr.step(cam_train[idx], prj_train[idx], loss_opt)
+        if get('verbose', False) and (it % 50 == 0 or it == max_iters - 1):
+            print(f'Iter:{it:5d} | Train Loss: {loss:.4f} | Train RMSE: {math.sqrt(l2 * 3):.4f} | Learn Rate: {tr.lr:.5f}')
+    valid_psnr = valid_rmse = valid_ssim = 0.0
+    if valid_data is not None:
+        valid_psnr, valid_rmse, valid_ssim, _ = evaluate_model(model, valid_data)
+    if get('data_root') is not None:                                                # :229-230
+        from . import io
+        opt = {k: get(k) for k in ('setup_name', 'model_name', 'loss', 'num_train', 'batch_size', 'max_iters', 'lr', 'lr_drop_ratio',
+                                   'lr_drop_rate', 'l2_reg')}
+        if opt['model_name'] is None:
+            opt['model_name'] = _model_name(model)
+        io.save_checkpoint(os.path.join(get('data_root'), '../checkpoint'), model, io.opt_to_string(opt))
+    return model, valid_psnr, valid_rmse, valid_ssim
+
+
+def _init_cfg(data_root, device, model_name, max_iters=500, batch_size=48, num_train=500):
+    """init_cfg of train_network.py:118-120 (+ the model name train_compennet_pp adds, :160)."""
+    return dict(data_root=data_root, setup_name='init', num_dataset=1, device=device, max_epochs=2000, max_iters=max_iters,
+                batch_size=batch_size, lr=1e-3, lr_drop_ratio=0.2, lr_drop_rate=800, loss='l1+ssim', l2_reg=1e-4, plot_on=True,
+                train_plot_rate=50, valid_rate=200, num_train=num_train, model_name=model_name)
+
+
+def init_compennet(compennet, data_root, cfg, *, max_iters=500, batch_size=48, num_train=500):
+    """train_network.py:98-127: initialise a bare CompenNet to |x - s| without actual projections.  Loads
+    `<data_root>/../checkpoint/init_CompenNet_...pth` if it exists; otherwise trains on `prj_share/init` (scene) and
+    `prj_share/train` (target prj, input |prj - 0.3 scene|) with the reference's init_cfg and saves that checkpoint.  The
+    keyword-only extras shrink the run (tests); their defaults are the reference's."""
+    from . import io
+    init_cfg = _init_cfg(data_root, _cfg_getter(cfg)('device', 'cuda'), _model_name(compennet), max_iters, batch_size, num_train)
+    ckpt_file = os.path.join(data_root, '../checkpoint', io.opt_to_string(init_cfg) + '.pth')   # the name :100 spells out
+    if os.path.exists(ckpt_file):
+        dev = next(compennet.parameters()).device
+        compennet.load_state_dict(torch.load(ckpt_file, map_location=dev))
+        compennet.invalidate()
+        print('CompenNet state dict found! Loading...')
+        return compennet
+    print('CompenNet state dict not found! Initializing...')
+    cam_scene = io.torch_imread_mt(os.path.join(data_root, 'prj_share/init'))
+    prj_train = io.torch_imread_mt(os.path.join(data_root, 'prj_share/train'))
+    init_data = dict(cam_scene=cam_scene, cam_train=torch.abs(prj_train - 0.3 * cam_scene.expand_as(prj_train)), prj_train=prj_train)
+    compennet, _, _, _ = train_compennet_pp(compennet, init_data, None, init_cfg)
+    return compennet
