@@ -542,6 +542,17 @@ int spaa_perc_decide(const float* logits, int ncls, const int32_t* label, int mo
 /* dst_b = src_b where state[b][0] != 0 (:244-245) */
 int spaa_track_where(const float* src, float* dst, const int32_t* state, int B, int HW, spaa_stream_t stream);
 
+/* One-pixel DE attacker (one_pixel_attacker/__init__.py:18-99).  base: the quantised image [H][W][4], u8 / 255.0f; cand: int32
+ * [P][5*npix] (row, col, r, g, b per square, squares painted in order, the last one wins).  out [P][oh][ow][4] = bitwise
+ * spaa_preproc_fwd of base with candidate p's squares (side 2*(pixel_size/2)+1) painted (perturb_image :18-44, classifier.py:59) */
+int spaa_onepixel_preproc(const float* base, const int32_t* cand, int P, int npix, int pixel_size, float* out, int H, int W,
+                          int cy0, int cx0, int ch, int cw, int oh, int ow, const float* mean3, const float* std3,
+                          spaa_stream_t stream);
+/* per row of logits [P][ncls]: p = softmax (classifier.py:64); energy = p[target], targeted 1 - p[target] (fp32, :91-95);
+ * argmax = first index of the largest p (numpy.argmax, :68-72); pmax = that p */
+int spaa_onepixel_score(const float* logits, int ncls, int target, int targeted, float* energy, int32_t* argmax, float* pmax,
+                        int P, spaa_stream_t stream);
+
 /* misc */
 int spaa_zero(void* p, int64_t bytes, spaa_stream_t stream);
 const char* spaa_version(void);

@@ -30,6 +30,9 @@ def __getattr__(name):
     if name in ('PCNetTrainer', 'train_pcnet', 'CompenNetTrainer', 'train_compennet_pp', 'init_compennet', 'evaluate_model'):
         from . import train_network
         return getattr(train_network, name)
+    if name in ('DigitalOnePixelAttacker', 'perturb_image'):
+        from . import one_pixel_attacker
+        return getattr(one_pixel_attacker, name)
     if name == 'calc_img_dists':
         from . import metrics
         return metrics.calc_img_dists

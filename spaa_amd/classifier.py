@@ -412,6 +412,15 @@ class ClassifierEngine:
                   self.ch, self.cw, self.oh, self.ow, self._mean, self._std)
         return self.body.forward(self.pre)
 
+    def forward_pre(self):
+        """The body's forward pass on `pre` as the caller filled it (the One-pixel attacker's spaa_onepixel_preproc writes its
+        candidates there): logits [B, ncls].  A decision-only pass, as forward(need_grad=False)."""
+        self.version += 1
+        self._grad_ready = False
+        if hasattr(self.body, 'write_masks'):
+            self.body.write_masks = False
+        return self.body.forward(self.pre)
+
     def backward(self, g_logits):
         if not getattr(self, '_grad_ready', False):
             # (a need_grad=False pass overwrote the activations but left the ReLU-gate masks / pool arg-max bytes of the pass before it)
