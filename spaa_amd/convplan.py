@@ -715,6 +715,9 @@ class ConvPlan:
                 d.reserved1 |= 64
                 pool_fused = True
         self.last_pool_fused = pool_fused
+        # (for tests and reports, next to last_tile: the K split this launch runs with -- 1 none, k > 1 that many K ranges (x6d split-K,
+        # fp16 split-K, the Winograd / tile-68 K-range forms), -1 stream-K)
+        self.last_ksplit = d.ksplit if d.ksplit else 1
         tid = 0
         if PROFILE is not None:
             tid = d.tile + 100 * (d.ksplit if d.ksplit > 1 else (9 if d.ksplit == -1 else 0))
@@ -1101,6 +1104,7 @@ class SmallLinearPlan:
         self.bias = bias.detach().float().contiguous().to(device) if bias is not None else None
         self.n, self.k = self.w.shape
         self.last_tile = -1
+        self.last_ksplit = 1
 
     def applies(self, inp, out, kw):
         m = inp.shape[0] * inp.shape[1] * inp.shape[2]
@@ -1110,13 +1114,13 @@ class SmallLinearPlan:
     def run(self, inp, out, **kw):
         if not self.applies(inp, out, kw):
             r = self.conv.run(inp, out, **kw)
-            self.last_tile = self.conv.last_tile
+            self.last_tile, self.last_ksplit = self.conv.last_tile, self.conv.last_ksplit
             return r
         _lib.check_dev(inp, out)
         m = inp.shape[0] * inp.shape[1] * inp.shape[2]
         _lib.call('spaa_linear_small', _lib.ptr(inp), _lib.ptr(self.w), _lib.ptr(self.bias) if self.bias is not None else None, _lib.ptr(out),
                   m, self.k, self.n, self.k, self.k, self.n)
-        self.last_tile = 75
+        self.last_tile, self.last_ksplit = 75, 1
         return out
 
     def refresh(self, weight, bias=None):

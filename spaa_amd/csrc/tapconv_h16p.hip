@@ -813,6 +813,9 @@ int spaa_launch_tapconv_h16p(const spaa_tapconv_t& d, hipStream_t stream) {
                   (int64_t)pl.ksplit * d.B * d.Hout * d.Wout * ((d.Cout + 127) & ~127) * 4 < ((int64_t)1 << 31);
         spaa_tapconv_t dd = d;
         dd.ksplit = pl.ksplit;
+        // (bit 8 asked for the in-kernel fix-up but the launch declined it: the caller's workspace still begins with the counter header --
+        // the partial sums and the second pass go past it, and the counters stay zero for the next launch that takes the fix-up)
+        if (pl.ksplit > 1 && (d.reserved1 & 256) && !geo.fix) dd.splitk_ws = d.splitk_ws + SPAA_SPLITK_HDR_FLOATS;
 #define H16P_LAUNCH_CV(N, SLOT)                                                                                            \
     {                                                                                                                      \
         typedef h16p_geo<1> G;                                                                                             \

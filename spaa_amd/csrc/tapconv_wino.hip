@@ -758,6 +758,9 @@ int spaa_launch_tapconv_wino(const spaa_tapconv_t& d, hipStream_t stream) {
     if (cv && (int64_t)d.B * d.Hout * d.Wout >= ((int64_t)1 << 24)) return hipErrorInvalidValue;   // (the plan never asks for it: wino_make_plan)
     spaa_tapconv_t dd = d;
     dd.ksplit = pl.ksplit;
+    // (bit 8 asked for the in-kernel fix-up but the launch declined it: the caller's workspace still begins with the counter header --
+    // the partial sums and the second pass go past it, and the counters stay zero for the next launch that takes the fix-up)
+    if (pl.ksplit > 1 && (d.reserved1 & 256) && !geo.fix) dd.splitk_ws = d.splitk_ws + SPAA_SPLITK_HDR_FLOATS;
     static bool attr_set[15][SPAA_MAX_DEVICES] = {};
     // kernel variant: bit 0 = late V (waves 4-7 transform one step ahead), bit 1 = xi groups expanded.  Default 3 / 2 (measured:
     // conv4 500 -> 462 us, conv5 461 -> 415 us against variant 0); `reserved0` bits 16-17 flip bits for A/B measurements

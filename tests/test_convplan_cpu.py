@@ -4,7 +4,7 @@ import torch
 import torch.nn.functional as F
 
 from spaa_amd import convplan as cp
-from tapconv_emu import emulate, nhwc, nchw
+from tapconv_emu import emulate, nhwc, nchw, packed_taps as cp_taps
 
 torch.manual_seed(0)
 
@@ -186,3 +186,66 @@ def test_small_linear_plan_dispatch():
     assert not plan.applies(torch.zeros(3, 1, 1, 20), y, {})                     # a wider buffer (channel window)
     assert plan.flops(3, 1, 1) == plan.conv.flops(3, 1, 1)
     assert not isinstance(cp.linear_dgrad_plan(torch.randn(10, 16), device='cpu'), cp.SmallLinearPlan)   # 10 outputs: rows not 16-byte aligned
+
+
+def _f64(t):
+    return t.detach().double()
+
+
+@pytest.mark.parametrize('kind', ['conv', 'conv_s2', 'dgrad_s2', 'dgrad_fold', 'deconv_fold', 'deconv_k3', 'deconv_dgrad', 'linear'])
+def test_emulate_fp64_packed_taps(kind):
+    """The fp64 reference of tests/test_tuned_launches_gpu.py: `emulate` in fp64 on the weights as the kernels read them (the packed
+    fp32 matrix: packed_taps) equals torch's fp64 convolution ops of the fp32-rounded weights to the last bits, for every plan kind
+    the benchmarked networks launch; the magnitude sum is the same op on |x| and |W|."""
+    torch.manual_seed(7)
+    b, h, w = 2, 9, 11
+    if kind in ('conv', 'conv_s2'):
+        s, co, ci = (1 if kind == 'conv' else 2), 40, 36
+        wt, bias = torch.randn(co, ci, 3, 3), torch.randn(co)
+        x = torch.randn(b, ci, h, w, dtype=torch.float64)
+        plan = cp.conv_fwd_plan(wt, bias, s, 1, device='cpu')
+        op = lambda x_, w_, b_: F.conv2d(x_, w_, b_, s, 1)   # noqa: E731
+        wref, bref = _f64(wt), _f64(bias)
+    elif kind in ('dgrad_s2', 'dgrad_fold'):
+        co, ci = 64, 8
+        wt = torch.randn(co, ci, 3, 3)
+        x = torch.randn(b, co, (h + 1) // 2, (w + 1) // 2, dtype=torch.float64)
+        plan = cp.conv_dgrad_plan(wt, 2, 1, device='cpu', fold=kind == 'dgrad_fold')
+        assert (plan.nfold == 4) == (kind == 'dgrad_fold')
+        op = lambda x_, w_, b_: torch.nn.grad.conv2d_input((b, ci, h, w), w_, x_, 2, 1)   # noqa: E731
+        wref, bref = _f64(wt), None
+    elif kind in ('deconv_fold', 'deconv_k3'):
+        ci, co = 32, 12
+        k, p, op_ = (2, 0, 0) if kind == 'deconv_fold' else (3, 1, 1)
+        wt, bias = torch.randn(ci, co, k, k), torch.randn(co)
+        x = torch.randn(b, ci, h, w, dtype=torch.float64)
+        plan = cp.deconv_fwd_plan(wt, bias, 2, p, device='cpu', fold=True)
+        assert plan.nfold == 4
+        op = lambda x_, w_, b_: F.conv_transpose2d(x_, w_, b_, 2, p, op_)   # noqa: E731
+        wref, bref = _f64(wt), _f64(bias)
+    elif kind == 'deconv_dgrad':
+        ci, co = 8, 12
+        wt = torch.randn(ci, co, 3, 3)
+        x = torch.randn(b, co, 2 * h, 2 * w, dtype=torch.float64)
+        plan = cp.deconv_dgrad_plan(wt, 2, 1, device='cpu')
+        op = lambda x_, w_, b_: F.conv2d(x_, w_, b_, 2, 1)   # noqa: E731
+        wref, bref = _f64(wt), None
+    else:
+        wt, bias = torch.randn(24, 40), torch.randn(24)
+        x = torch.randn(5, 40, 1, 1, dtype=torch.float64)
+        plan = cp.linear_fwd_plan(wt, bias, device='cpu')
+        plan = getattr(plan, 'conv', plan)
+        op = lambda x_, w_, b_: F.linear(x_.flatten(1), w_, b_).view(5, -1, 1, 1)   # noqa: E731
+        wref, bref = _f64(wt), _f64(bias)
+    ref = op(x, wref, bref)
+    sref = op(x.abs(), wref.abs(), None)
+    y, sm = emulate(plan, nhwc(x, plan.cin_p), ref.shape[2], ref.shape[3], dtype=torch.float64, taps=cp_taps(plan), magnitude=True)
+    assert y.dtype == torch.float64
+    scale = sref.abs().max().item()
+    assert (nchw(y) - ref).abs().max().item() <= 1e-12 * scale
+    assert (nchw(sm) - sref).abs().max().item() <= 1e-12 * scale
+    assert (nchw(emulate(plan, nhwc(x, plan.cin_p), ref.shape[2], ref.shape[3], dtype=torch.float64, taps=cp_taps(plan), bias=False))
+            - op(x, wref, None)).abs().max().item() <= 1e-12 * scale
+    # the fp16 plane: the same sums over the fp16-rounded weights
+    yh = emulate(plan, nhwc(x, plan.cin_p), ref.shape[2], ref.shape[3], dtype=torch.float64, taps=cp_taps(plan, half=True))
+    assert (nchw(yh) - op(x, wref.half().double(), bref)).abs().max().item() <= 1e-12 * scale

@@ -1426,9 +1426,13 @@ def test_perc_al_adversary_projector(hip, golden_dir, targeted, confidence):
 
 
 def test_vgg16_classifier_vs_oracle(hip):
-    """VGG-16 body (config 5 of BASELINE.json) on tapconv + generic pooling vs the oracle restatement."""
-    csd = syn.vgg16_state_dict(3, logit_gain=5.0, fc_width=512)
-    for (h, crop, insz, b) in [(64, (60, 60), (48, 48), 2), (256, (240, 240), (224, 224), 1)]:
+    """VGG-16 body (config 5 of BASELINE.json) on tapconv + generic pooling vs the oracle restatement -- with a test-sized head and
+    with torchvision's full one (25088 -> 4096 -> 4096 -> 1000: the head bench.py runs).  (The full head's input gradient is
+    compared gate-aware in test_perc_al_with_vgg16_at_full_size: here 8192 more ReLU units near 0 make the plain image-gradient
+    bound a matter of the seed -- measured 6.8e-3 relative L2 for this case, a flip in the head reaching the whole image.)"""
+    small, full = syn.vgg16_state_dict(3, logit_gain=5.0, fc_width=512), syn.vgg16_state_dict(3, logit_gain=5.0, fc_width=4096)
+    for (csd, h, crop, insz, b) in [(small, 64, (60, 60), (48, 48), 2), (small, 256, (240, 240), (224, 224), 1),
+                                    (full, 256, (240, 240), (224, 224), 2)]:
         torch.manual_seed(2)
         im = torch.rand(b, 3, h, h, requires_grad=True)
         raw, p, idx = so.OracleClassifier('vgg16', csd, input_sz=insz)(im, crop)
@@ -1439,9 +1443,11 @@ def test_vgg16_classifier_vs_oracle(hip):
         raw2, p2, idx2 = clf(im2, crop)
         (raw2 * r.to(DEV)).sum().backward()
         assert rel_inf(raw2, raw) < 1e-5
+        assert (idx2[:, 0] == idx[:, 0]).all()
+        if csd is full:
+            continue
         # 13 ReLU convs + 5 max-pools without skip connections: a gate / arg-max flip reaches the whole image
         assert rel_l2(im2.grad, im.grad) < 5e-3 and outlier_fraction(im2.grad, im.grad, 1e-3) < 5e-2
-        assert (idx2[:, 0] == idx[:, 0]).all()
 
 
 def test_inception_v3_classifier_vs_oracle(hip):
@@ -2298,8 +2304,10 @@ def test_perc_al_with_vgg16_at_full_size(hip):
     import gates
     from spaa_amd.perc_al import PerC_AL, PerCALState
     n_clean = 0
-    for h, crop, insz, fcw, b in [(64, (60, 60), (48, 48), 256, 8), (256, (240, 240), (224, 224), 256, 4)]:
-        csd = syn.vgg16_state_dict(3, logit_gain=5.0, fc_width=fcw)
+    # (the last case: bench.py's own classifier -- vgg16_state_dict(2, logit_gain=20.0), the full 4096-wide head)
+    for h, crop, insz, csd, b in [(64, (60, 60), (48, 48), syn.vgg16_state_dict(3, logit_gain=5.0, fc_width=256), 8),
+                                  (256, (240, 240), (224, 224), syn.vgg16_state_dict(3, logit_gain=5.0, fc_width=256), 4),
+                                  (256, (240, 240), (224, 224), syn.vgg16_state_dict(2, logit_gain=20.0), 4)]:
         clf = hip['clf'].Classifier('vgg16', DEV, state_dict=csd, input_sz=insz)
         oclf = so.OracleClassifier('vgg16', csd, input_sz=insz)
         # (iteration 0 starts from delta = 0: copies of ONE scene would have identical gates, so the small size uses b scenes)
@@ -3177,6 +3185,87 @@ def test_small_linear(hip, m, k, n):
         assert dplan.last_tile == 75 and rel_inf(gx.cpu().view(m, k), (g.double() @ w.double()).float()) < 2e-6
 
 
+
+@pytest.mark.parametrize('m,k,n', [(64, 4096, 1000), (65, 512, 1000), (64, 4100, 1000), (64, 4096, 1028)])
+def test_small_linear_route_boundaries(hip, m, k, n):
+    """convplan.SmallLinearPlan at the edges of its route: VGG-16's last layer at bench batch (64 x 4096 -> 1000: at the K limit 4096
+    and under the weight limit 2^22) takes the kernel; one row more, four K more or 28 outputs more (weights over 2^22: a bare
+    convolution plan) leave it.  Either way fp64 accuracy at the fp32 dot-product level, and the gated input gradient the VGG-16
+    backward runs (`gate=h`: the wrapped convolution tiles)."""
+    cp, lib = hip['cp'], hip['lib']
+    torch.manual_seed(m + k + n)
+    w, bias, x = torch.randn(n, k) / k ** 0.5, torch.randn(n), torch.randn(m, k)
+    ref = x.double() @ w.double().t() + bias.double()
+    plan = cp.linear_fwd_plan(w, bias, DEV, 'fc')
+    small = m <= 64 and k <= 4096 and n * k <= (1 << 22)
+    assert isinstance(plan, cp.SmallLinearPlan) == (n * k <= (1 << 22))
+    y = torch.full((m, 1, 1, n), float('nan'), device=DEV)
+    plan.run(x.view(m, 1, 1, k).to(DEV), y)
+    assert (plan.last_tile == 75) == small, (plan.last_tile, small)
+    assert rel_inf(y.cpu().view(m, n), ref.float()) < 2e-6
+    g, h = torch.randn(m, n), torch.randn(m, k)
+    dplan = cp.linear_dgrad_plan(w, DEV, 'fc_dgrad')
+    ref_g = g.double() @ w.double()
+    gx = torch.full((m, 1, 1, k), float('nan'), device=DEV)
+    dplan.run(g.view(m, 1, 1, n).to(DEV), gx)
+    assert (dplan.last_tile == 75) == (m <= 64 and n * k <= (1 << 22)), dplan.last_tile
+    assert rel_inf(gx.cpu().view(m, k), ref_g.float()) < 2e-6
+    gx.fill_(float('nan'))
+    dplan.run(g.view(m, 1, 1, n).to(DEV), gx, gate=h.view(m, 1, 1, k).to(DEV))
+    assert dplan.last_tile != 75
+    assert rel_inf(gx.cpu().view(m, k), (ref_g * (h > 0)).float()) < 2e-6
+
+
+def test_k_range_fixup_declined_leaves_header_alone(hip):
+    """`reserved1` bit 8 (SPAA_SPLITK_FIXUP=1): the K ranges meet inside the kernel behind a header of arrival counters -- unless the
+    launcher declines (more (region, N tile) pairs than the header holds, Cout % 4, a workspace of 2 GiB or more).  A declined launch
+    must run the two-pass form PAST the header: partial sums written over the counters would leave the next accepted launch on the
+    same workspace with garbage counters, no workgroup seeing itself arrive last, and its output never written.  One plan each of the
+    Winograd kernel and the patch-staged fp16 kernel's K-range form: a declined shape, then an accepted one, both bitwise the two-pass
+    result, the header zero after both."""
+    cp = hip['cp']
+    keep = (cp.WINO_SPLITK_FIXUP, cp.FORCE_TILE, cp.DEBUG_WINO_NOCANVAS, cp.H16P_CV)
+    try:
+        # Winograd, 64-wide N tile (tile 71), two K ranges: B x ceil(H / 16) x ceil(W / 32) regions x 2 N tiles
+        torch.manual_seed(11)
+        wt, bias = torch.randn(128, 64, 3, 3) / 24.0, torch.randn(128)
+        plan = cp.conv_fwd_plan(wt, bias, 1, 1, DEV)
+        cp.FORCE_TILE, cp.DEBUG_WINO_NOCANVAS = 71 + 100 * 2, 1
+        for b, hw, declined in ((17, 256, True), (2, 64, False)):
+            xin = torch.randn(b, hw, hw, 64, device=DEV)
+            outs = []
+            for fix in (False, True):
+                cp.WINO_SPLITK_FIXUP = fix
+                out = torch.full((b, hw, hw, 128), float('nan'), device=DEV)
+                plan.run(xin, out)
+                wp = plan.wino.last_wino_plan
+                assert wp[1] == 2 and plan.wino.last_ksplit == 2, wp
+                assert (wp[5] // wp[1] > cp.SPLITK_HDR) == declined, (b, hw, wp)
+                outs.append(out)
+            assert torch.equal(outs[0], outs[1]), ('winograd', b, hw)
+            assert int(plan.wino._ws_fix[:cp.SPLITK_HDR].view(torch.int32).abs().max()) == 0
+        # the patch-staged fp16 kernel's canvas / K-range form (chosen by the rules for small, badly filled images; 64-wide N tile and
+        # two K ranges forced): many small images give more (region, N tile) pairs than the header holds
+        cp.FORCE_TILE, cp.WINO_SPLITK_FIXUP = 0, False
+        cp.H16P_CV = (64, 2, 0)
+        wt = torch.randn(128, 64, 3, 3) / 24.0
+        plan = cp.conv_fwd_plan(wt, None, 1, 1, DEV)
+        for b, hh, ww, declined in ((3000, 17, 33, True), (4, 17, 33, False)):
+            xin = torch.randn(b, hh, ww, 64, device=DEV).half()
+            outs = []
+            for fix in (False, True):
+                cp.WINO_SPLITK_FIXUP = fix
+                out = torch.full((b, hh, ww, 128), float('nan'), device=DEV, dtype=torch.float16)
+                plan.run(xin, out)
+                wp = plan.last_h16p_plan
+                assert plan.last_tile == 68 and wp[1] == 2 and plan.last_ksplit == 2, (plan.last_tile, wp)
+                assert (wp[5] // wp[1] > cp.SPLITK_HDR) == declined, (b, hh, ww, wp)
+                outs.append(out)
+            assert torch.equal(outs[0], outs[1]), ('h16p', b, hh, ww)
+            assert int(plan._ws_fix[:cp.SPLITK_HDR].view(torch.int32).abs().max()) == 0
+    finally:
+        cp.WINO_SPLITK_FIXUP, cp.FORCE_TILE, cp.DEBUG_WINO_NOCANVAS, cp.H16P_CV = keep
+
 def test_tapconv_fp16_split_k(hip):
     """Split-K of the fp16 implicit-GEMM kernel (skinny GEMMs: a fully connected layer at batch 64, a 7 x 7 x 512 layer): raw fp32
     partial sums + a fixed-order second pass with the epilogue; against fp64 on the same fp16-rounded operands and against the
@@ -3467,7 +3556,7 @@ def test_fp16_storage_attack_loops(hip, golden_dir):
 F16_MEASURED = {'value': 0.0, 'near': 0.0, 'tie': 0.0}
 
 
-@pytest.mark.parametrize('body', ['resnet18', 'vgg16', 'inception_v3'])
+@pytest.mark.parametrize('body', ['resnet18', 'vgg16', 'inception_v3', 'vgg16_full_head'])
 def test_fp16_storage_first_iteration_gate_aware(hip, body):
     """fp16-storage mode against the fp32 oracle, decomposed like the fp32 path (tests/gates.py): every ReLU / clamp / arg-max
     gate on which the two disagree sits within fp16 rounding of its threshold (near_zero), the activations agree to fp16
@@ -3477,15 +3566,18 @@ def test_fp16_storage_first_iteration_gate_aware(hip, body):
     # measured (profiles/r03_parity.txt): value 1.86e-3, near 9.6e-4, tie 8.2e-4, camera image 1.7e-4, target logit 1.4e-2,
     # projector image with the oracle's gates 3.5e-4 (ResNet-18) / 2.1e-3 (VGG-16: thirteen fp16 layers deep) / 2.4e-3 (Inception-v3)
     tol = dict(near_zero=2.9e-3, value_tol=5.6e-3, cam=5.2e-4, logit=4.3e-2,
-               image={'resnet18': 1.1e-3, 'vgg16': 6.2e-3, 'inception_v3': 7.3e-3}[body], measured=F16_MEASURED)
+               image={'resnet18': 1.1e-3, 'vgg16': 6.2e-3, 'inception_v3': 7.3e-3, 'vgg16_full_head': 6.2e-3}[body], measured=F16_MEASURED)
     if body == 'resnet18':
         st = _first_iteration_gate_aware(hip, body, syn.resnet18_state_dict(2, logit_gain=20.0), (64, 64), (64, 64), (60, 60),
                                          [204, 291, 7], 3, storage='f16', tol=tol)
     elif body == 'inception_v3':
         st = _first_iteration_gate_aware(hip, body, syn.inception_v3_state_dict(2, logit_gain=20.0), (107, 107), (128, 128),
                                          (120, 120), [204, 291], 12, storage='f16', tol=tol)
-    else:   # (fp16-storage VGG-16: 224 x 224 input, the configs[4] geometry)
+    elif body == 'vgg16':   # (fp16-storage VGG-16: 224 x 224 input, the configs[4] geometry)
         st = _first_iteration_gate_aware(hip, body, syn.vgg16_state_dict(3, logit_gain=5.0, fc_width=256), (224, 224), (256, 256),
+                                         (240, 240), [204, 291], 11, storage='f16', tol=tol)
+    else:   # (... with bench.py's classifier: the full 25088 -> 4096 -> 4096 -> 1000 head, fp16 split-K in its first layer)
+        st = _first_iteration_gate_aware(hip, 'vgg16', syn.vgg16_state_dict(2, logit_gain=20.0), (224, 224), (256, 256),
                                          (240, 240), [204, 291], 11, storage='f16', tol=tol)
     print(f'fp16 storage, {body}: projector image rel Linf plain {st.errs["plain"].tolist()}, with the oracle\'s gates '
           f'{st.errs["oracle_gates"].tolist()}; gates differing {st.flips.tolist()}; largest so far {F16_MEASURED}')
