@@ -288,6 +288,12 @@ int spaa_warp_bwd_tiled_sumsq(const float* g_xw, const float* x, const int32_t* 
                               const int32_t* tbox, int box_cap, float* g_x, int B, int Hp, int Wp, int Hc, int Wc, int clamp01,
                               float gray, float prjl2_scale, const int32_t* state, float* partial_ss, const uint8_t* clamp_bits,
                               spaa_stream_t stream);
+/* ... with one prjl2 scale per sample: prjl2_scale float [B] on the device (0: the sample has no prjl2 term; x is read only for
+ * the samples whose scale is not 0).  Same kernel; per sample bitwise the scalar launch with that sample's scale. */
+int spaa_warp_bwd_tiled_sumsq_ps(const float* g_xw, const float* x, const int32_t* off, const int32_t* lidx, const float* w_e,
+                                 const int32_t* tbox, int box_cap, float* g_x, int B, int Hp, int Wp, int Hc, int Wc, int clamp01,
+                                 float gray, const float* prjl2_scale, const int32_t* state, float* partial_ss,
+                                 const uint8_t* clamp_bits, spaa_stream_t stream);
 /* F.grid_sample forward (models.py:184,340) from the per-attack TAP TABLE of spaa_warp_taps instead of the grid: tap_src [Hc*Wc][4]
  * projector pixel of every bilinear tap (0x7fffffff: outside, weight 0), tap_wgt [Hc*Wc][4] its weight x mask -- the table the
  * deterministic backward pass is built from, so the pair is an exact adjoint.  A workgroup owns a 32 x 8 tile of camera pixels and four
@@ -410,6 +416,9 @@ int spaa_train_loss_fwd_bwd(const float* infer, const float* target, const float
 int spaa_stealth_loss_fwd_bwd(const float* y, const float* scene, const float* scene_lab, float caml2_w,
                               float camdE_w, float gscale, float* g_y, float* de_map, float* partial, int B, int HW,
                               spaa_stream_t stream);
+/* ... with per-sample weights: caml2_w = params[b][1], camdE_w = params[b][2] of the per-sample table (see spaa_decide_ps) */
+int spaa_stealth_loss_fwd_bwd_ps(const float* y, const float* scene, const float* scene_lab, const float* params,
+                                 float gscale, float* g_y, float* de_map, float* partial, int B, int HW, spaa_stream_t stream);
 
 /* calc_img_dists (utils.py:420-491), NHWC4 images x, y of `npix` = B*H*W pixels: per-pixel terms of PSNR/RMSE (sum of
  * squared differences), mean L2 (:460-471), mean L_inf (:475-486) and mean dE2000 (differential_color_functions.py:183-190)
@@ -494,6 +503,15 @@ int spaa_decide(const float* logits, int ncls, const int32_t* target, int target
                 int HW, const float* prjl2, float prjl2_w, float caml2_w, float camdE_w, float d_thr,
                 float p_thresh, float adv_scale, int32_t* state, float* stats, float* g_logits, int B,
                 spaa_stream_t stream);
+/* Per-sample attack parameters (one batch = several attack configurations, spaa_sweep).  The _ps entry points launch the SAME
+ * kernels as their scalar forms with the scalars read per sample from a device table:
+ *   params float [B][4] = (prjl2_w, caml2_w, camdE_w, d_thr)      flags int32 [B]: bit 0 = targeted
+ * p_thresh and adv_scale stay scalars.  prjl2 may be NULL; a sample with prjl2_w == 0 reads it as 0 (stats[b][4] = 0), as the
+ * scalar launch does when its caller passes prjl2 = NULL.  With every sample's parameters equal to the scalars, the outputs are
+ * bitwise those of the scalar launch; with mixed parameters, each sample's are bitwise those of the scalar launch on that sample. */
+int spaa_decide_ps(const float* logits, int ncls, const int32_t* target, const float* partial, int nblk, int HW,
+                   const float* prjl2, const float* params, const int32_t* flags, float p_thresh, float adv_scale,
+                   int32_t* state, float* stats, float* g_logits, int B, spaa_stream_t stream);
 /* Cotangent at the PCNet output: g = best_adv_b ? g_col : g_adv (one backward pass serves both of the reference's,
  * :302,310), then the backward of clamp(relu(pre), max=1) (models.py:301): pass where 0 < ypre <= 1 (ypre NULL: none).
  * all [B,npix,4] */
@@ -505,6 +523,9 @@ int spaa_prjl2_fwd(const float* x, float gray, float* prjl2, int B, int HW, spaa
  * block partials of ||g_b||^2 -> partial [B][ceil(HW/256)] */
 int spaa_grad_sumsq(float* g, const float* x, float gray, float prjl2_scale, const int32_t* state, float* partial,
                     int B, int HW, spaa_stream_t stream);
+/* ... with prjl2_scale float [B] on the device, one per sample (0: no prjl2 term) */
+int spaa_grad_sumsq_ps(float* g, const float* x, float gray, const float* prjl2_scale, const int32_t* state, float* partial,
+                       int B, int HW, spaa_stream_t stream);
 /* x_b -= lr_b * g_b/||g_b||_2 with lr = best_adv ? col_lr : adv_lr (:307,315); then where succ: x_best_b = x_b
  * (post-step, Q4) and cam_best_b = cam_b (:323-328).   x, g, x_best: [B,HWp,4]; cam, cam_best: [B,HWc,4] */
 int spaa_step_and_track(float* x, const float* g, const float* partial, const int32_t* state, float adv_lr,

@@ -15,7 +15,8 @@ def __getattr__(name):
     if name in ('Classifier', 'ClassifierEngine', 'load_imagenet_labels'):
         from . import classifier
         return getattr(classifier, name)
-    if name in ('spaa', 'spaa_attack', 'AttackState'):
+    if name in ('spaa', 'spaa_attack', 'AttackState', 'spaa_sweep', 'run_projector_based_attack', 'get_attacker_cfg',
+                'to_attacker_cfg_str'):
         from . import projector_based_attack
         return getattr(projector_based_attack, name)
     if name in ('rgb2lab_diff', 'ciede2000_diff', 'deltaE', 'stealth_loss_with_grad'):

@@ -68,6 +68,7 @@ _SIGNATURES = {
     'spaa_warp_bwd_gather': [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p],
     'spaa_warp_bwd_tiled': [_p, _p, _p, _p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _i, _p],
     'spaa_warp_bwd_tiled_sumsq': [_p, _p, _p, _p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _i, _f, _f, _p, _p, _p, _p],
+    'spaa_warp_bwd_tiled_sumsq_ps': [_p, _p, _p, _p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _i, _f, _p, _p, _p, _p, _p],
     'spaa_warp_fwd_taps': [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p],
     'spaa_warp_bwd_grid': [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p],
     'spaa_warp_finish_grid_bwd': [_p, _p, _p, _p, _p, _i, _p],
@@ -91,6 +92,7 @@ _SIGNATURES = {
     'spaa_rgb2lab_bwd': [_p, _p, _p, _i, _p],
     'spaa_ciede2000_bwd': [_p, _p, _p, _p, _p, _i, _p],
     'spaa_stealth_loss_fwd_bwd': [_p, _p, _p, _f, _f, _f, _p, _p, _p, _i, _i, _p],
+    'spaa_stealth_loss_fwd_bwd_ps': [_p, _p, _p, _p, _f, _p, _p, _p, _i, _i, _p],
     'spaa_img_dists': [_p, _p, _p, _i, _p],
     'spaa_train_loss_fwd_bwd': [_p, _p, _p, _f, _f, _p, _p, _p, _p, _p, _i, _i, _i, _p],
     'spaa_ssim': [_p, _p, _p, _p, _i, _i, _i, _p],
@@ -121,9 +123,11 @@ _SIGNATURES = {
     'spaa_avgpool_fwd': [_p, _p, _i, _i, _i, _p],
     'spaa_avgpool_bwd': [_p, _p, _p, _i, _i, _i, _p],
     'spaa_decide': [_p, _i, _p, _i, _p, _i, _i, _p, _f, _f, _f, _f, _f, _f, _p, _p, _p, _i, _p],
+    'spaa_decide_ps': [_p, _i, _p, _p, _i, _i, _p, _p, _p, _f, _f, _p, _p, _p, _i, _p],
     'spaa_select_grad': [_p, _p, _p, _p, _p, _i, _i, _p],
     'spaa_prjl2_fwd': [_p, _f, _p, _i, _i, _p],
     'spaa_grad_sumsq': [_p, _p, _f, _f, _p, _p, _i, _i, _p],
+    'spaa_grad_sumsq_ps': [_p, _p, _f, _p, _p, _p, _i, _i, _p],
     'spaa_step_and_track': [_p, _p, _p, _p, _f, _f, _p, _p, _p, _i, _i, _i, _p],
     'spaa_step_and_track_n': [_p, _p, _p, _i, _p, _f, _f, _p, _p, _p, _i, _i, _i, _p, _p],
     'spaa_onepixel_preproc': [_p, _p, _i, _i, _i, _p, _i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_float), C.POINTER(C.c_float), _p],

@@ -22,11 +22,20 @@ __global__ __launch_bounds__(256) void decide_kernel(const float* __restrict__ l
                                                      const float* __restrict__ prjl2, float prjl2_w, float caml2_w,
                                                      float camdE_w, float d_thr, float p_thresh, float adv_scale,
                                                      int32_t* __restrict__ state, float* __restrict__ stats,
-                                                     float* __restrict__ g_logits) {
+                                                     float* __restrict__ g_logits, const float* __restrict__ params,
+                                                     const int32_t* __restrict__ flags) {
     __shared__ float red[4];
     __shared__ float s_max[4];
     __shared__ int s_arg[4];
     const int b = blockIdx.x;
+    // spaa_decide_ps: this sample's (prjl2_w, caml2_w, camdE_w, d_thr) and targeted flag replace the scalars (uniform per workgroup)
+    if (params != nullptr) {
+        prjl2_w = params[4 * b];
+        caml2_w = params[4 * b + 1];
+        camdE_w = params[4 * b + 2];
+        d_thr = params[4 * b + 3];
+        targeted = flags[b] & 1;
+    }
     const float* lg = logits + (size_t)b * ncls;
     // argmax (first maximum) and max
     float mx = -INFINITY;
@@ -82,7 +91,8 @@ __global__ __launch_bounds__(256) void decide_kernel(const float* __restrict__ l
     if (threadIdx.x == 0) {
         const float caml2 = a / (float)HW;
         const float camdE = d / (float)HW;
-        const float pl2 = (prjl2 != nullptr) ? prjl2[b] : 0.f;
+        // (per-sample mode: a sample without the prjl2 term reads 0, as the scalar launch whose caller passes prjl2 = NULL)
+        const float pl2 = (prjl2 != nullptr && (params == nullptr || prjl2_w != 0.f)) ? prjl2[b] : 0.f;
         float col = prjl2_w * pl2;
         col += caml2_w * caml2;
         col += camdE_w * camdE;
@@ -147,9 +157,11 @@ __global__ __launch_bounds__(256) void prjl2_kernel(const float4* __restrict__ x
 __global__ __launch_bounds__(256) void grad_sumsq_kernel(float4* __restrict__ g, const float4* __restrict__ x,
                                                          float gray, float prjl2_scale,
                                                          const int32_t* __restrict__ state,
-                                                         float* __restrict__ partial, int HW) {
+                                                         float* __restrict__ partial, int HW,
+                                                         const float* __restrict__ prjl2_scales) {
     __shared__ float red[4];
     const int b = blockIdx.y;
+    if (prjl2_scales != nullptr) prjl2_scale = prjl2_scales[b];   // spaa_grad_sumsq_ps: per sample (0 = no prjl2 term)
     const int pix = blockIdx.x * 256 + threadIdx.x;
     float ss = 0.f;
     if (pix < HW) {
@@ -227,15 +239,31 @@ __global__ void track_cam_kernel(const float4* __restrict__ cam, float4* __restr
 
 extern "C" {
 
-int spaa_decide(const float* logits, int ncls, const int32_t* target, int targeted, const float* partial, int nblk,
-                int HW, const float* prjl2, float prjl2_w, float caml2_w, float camdE_w, float d_thr, float p_thresh,
-                float adv_scale, int32_t* state, float* stats, float* g_logits, int B, spaa_stream_t stream) {
+static int launch_decide(const float* logits, int ncls, const int32_t* target, int targeted, const float* partial, int nblk,
+                         int HW, const float* prjl2, float prjl2_w, float caml2_w, float camdE_w, float d_thr, float p_thresh,
+                         float adv_scale, int32_t* state, float* stats, float* g_logits, int B, const float* params,
+                         const int32_t* flags, spaa_stream_t stream) {
     if (!logits || !target || !partial || !state || !stats || !g_logits || B < 1 || ncls < 1 || nblk < 1 || HW < 1)
         return hipErrorInvalidValue;
     hipLaunchKernelGGL(decide_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, logits, ncls, target, targeted,
                        partial, nblk, HW, prjl2, prjl2_w, caml2_w, camdE_w, d_thr, p_thresh, adv_scale, state, stats,
-                       g_logits);
+                       g_logits, params, flags);
     return (int)hipGetLastError();
+}
+
+int spaa_decide(const float* logits, int ncls, const int32_t* target, int targeted, const float* partial, int nblk,
+                int HW, const float* prjl2, float prjl2_w, float caml2_w, float camdE_w, float d_thr, float p_thresh,
+                float adv_scale, int32_t* state, float* stats, float* g_logits, int B, spaa_stream_t stream) {
+    return launch_decide(logits, ncls, target, targeted, partial, nblk, HW, prjl2, prjl2_w, caml2_w, camdE_w, d_thr, p_thresh,
+                         adv_scale, state, stats, g_logits, B, nullptr, nullptr, stream);
+}
+
+int spaa_decide_ps(const float* logits, int ncls, const int32_t* target, const float* partial, int nblk, int HW,
+                   const float* prjl2, const float* params, const int32_t* flags, float p_thresh, float adv_scale,
+                   int32_t* state, float* stats, float* g_logits, int B, spaa_stream_t stream) {
+    if (!params || !flags) return hipErrorInvalidValue;
+    return launch_decide(logits, ncls, target, 0, partial, nblk, HW, prjl2, 0.f, 0.f, 0.f, 0.f, p_thresh, adv_scale, state, stats,
+                         g_logits, B, params, flags, stream);
 }
 
 int spaa_select_grad(const float* g_adv, const float* g_col, const int32_t* state, const float* ypre, float* g, int B,
@@ -253,13 +281,24 @@ int spaa_prjl2_fwd(const float* x, float gray, float* prjl2, int B, int HW, spaa
     return (int)hipGetLastError();
 }
 
-int spaa_grad_sumsq(float* g, const float* x, float gray, float prjl2_scale, const int32_t* state, float* partial,
-                    int B, int HW, spaa_stream_t stream) {
+static int launch_grad_sumsq(float* g, const float* x, float gray, float prjl2_scale, const float* prjl2_scales,
+                             const int32_t* state, float* partial, int B, int HW, spaa_stream_t stream) {
     if (!g || !x || !state || !partial || B < 1 || HW < 1) return hipErrorInvalidValue;
     dim3 grid((HW + 255) / 256, B);
     hipLaunchKernelGGL(grad_sumsq_kernel, grid, dim3(256), 0, (hipStream_t)stream, (float4*)g, (const float4*)x, gray,
-                       prjl2_scale, state, partial, HW);
+                       prjl2_scale, state, partial, HW, prjl2_scales);
     return (int)hipGetLastError();
+}
+
+int spaa_grad_sumsq(float* g, const float* x, float gray, float prjl2_scale, const int32_t* state, float* partial,
+                    int B, int HW, spaa_stream_t stream) {
+    return launch_grad_sumsq(g, x, gray, prjl2_scale, nullptr, state, partial, B, HW, stream);
+}
+
+int spaa_grad_sumsq_ps(float* g, const float* x, float gray, const float* prjl2_scale, const int32_t* state, float* partial,
+                       int B, int HW, spaa_stream_t stream) {
+    if (!prjl2_scale) return hipErrorInvalidValue;
+    return launch_grad_sumsq(g, x, gray, 0.f, prjl2_scale, state, partial, B, HW, stream);
 }
 
 int spaa_step_and_track(float* x, const float* g, const float* partial, const int32_t* state, float adv_lr,

@@ -354,9 +354,13 @@ __global__ __launch_bounds__(256) void stealth_loss_kernel(const float4* __restr
                                                            const float4* __restrict__ scene_lab, float caml2_w,
                                                            float camdE_w, float gscale, float4* __restrict__ g_y,
                                                            float* __restrict__ de_map, float* __restrict__ partial,
-                                                           int HW) {
+                                                           int HW, const float* __restrict__ params) {
     __shared__ float red[4];
     const int b = blockIdx.y;
+    if (params != nullptr) {   // spaa_stealth_loss_fwd_bwd_ps: this sample's weights (params[b] = prjl2_w, caml2_w, camdE_w, d_thr)
+        caml2_w = params[4 * b + 1];
+        camdE_w = params[4 * b + 2];
+    }
     const int pix = blockIdx.x * 256 + threadIdx.x;
     float l2 = 0.f, de = 0.f;
     if (pix < HW) {
@@ -684,15 +688,27 @@ int spaa_ciede2000_bwd(const float* lab1, const float* lab2, const float* g_de, 
     return (int)hipGetLastError();
 }
 
-int spaa_stealth_loss_fwd_bwd(const float* y, const float* scene, const float* scene_lab, float caml2_w,
-                              float camdE_w, float gscale, float* g_y, float* de_map, float* partial, int B, int HW,
-                              spaa_stream_t stream) {
+static int launch_stealth_loss(const float* y, const float* scene, const float* scene_lab, float caml2_w, float camdE_w,
+                               const float* params, float gscale, float* g_y, float* de_map, float* partial, int B, int HW,
+                               spaa_stream_t stream) {
     if (!y || !scene || !scene_lab || !g_y || !partial || B < 1 || HW < 1) return hipErrorInvalidValue;
     dim3 grid((HW + 255) / 256, B);
     hipLaunchKernelGGL(stealth_loss_kernel, grid, dim3(256), 0, (hipStream_t)stream, (const float4*)y,
                        (const float4*)scene, (const float4*)scene_lab, caml2_w, camdE_w, gscale, (float4*)g_y,
-                       de_map, partial, HW);
+                       de_map, partial, HW, params);
     return (int)hipGetLastError();
+}
+
+int spaa_stealth_loss_fwd_bwd(const float* y, const float* scene, const float* scene_lab, float caml2_w,
+                              float camdE_w, float gscale, float* g_y, float* de_map, float* partial, int B, int HW,
+                              spaa_stream_t stream) {
+    return launch_stealth_loss(y, scene, scene_lab, caml2_w, camdE_w, nullptr, gscale, g_y, de_map, partial, B, HW, stream);
+}
+
+int spaa_stealth_loss_fwd_bwd_ps(const float* y, const float* scene, const float* scene_lab, const float* params,
+                                 float gscale, float* g_y, float* de_map, float* partial, int B, int HW, spaa_stream_t stream) {
+    if (!params) return hipErrorInvalidValue;
+    return launch_stealth_loss(y, scene, scene_lab, 0.f, 0.f, params, gscale, g_y, de_map, partial, B, HW, stream);
 }
 
 }  // extern "C"

@@ -311,7 +311,8 @@ __global__ __launch_bounds__(256) void warp_bwd_tiled_kernel(const float4* __res
                                                              float4* __restrict__ g_x, int B, int Hp, int Wp, int Hc, int Wc,
                                                              int ntx, int box_cap, int clamp, float* __restrict__ partial_ss,
                                                              const int32_t* __restrict__ state, float gray, float prjl2_scale,
-                                                             const uint8_t* __restrict__ clamp_bits) {
+                                                             const uint8_t* __restrict__ clamp_bits,
+                                                             const float* __restrict__ prjl2_scales) {
     extern __shared__ __attribute__((aligned(16))) float4 box[];   // [WB][box_cap]
     const int tile = blockIdx.x, b0 = blockIdx.y * WB;
     const int ty = tile / ntx, tx = tile - ty * ntx;
@@ -330,12 +331,16 @@ __global__ __launch_bounds__(256) void warp_bwd_tiled_kernel(const float4* __res
     const int e0 = live ? off[sp] : 0, e1 = live ? off[sp + 1] : 0;
     float4 xv[WB];
     // (`clamp_bits`: the gate's three comparisons as one byte per pixel from the kernel that wrote x -- spaa_step_and_track_n --: 1 byte
-    // per pixel instead of x's 16; x itself only for the prjl2 term)
-    const bool need_x = (clamp && clamp_bits == nullptr) || (partial_ss != nullptr && prjl2_scale != 0.f);
+    // per pixel instead of x's 16; x itself only for the prjl2 term -- per image: spaa_warp_bwd_tiled_sumsq_ps reads each image's
+    // prjl2 scale from `prjl2_scales`, and x only of the images whose scale is not 0)
     unsigned int cb[WB];
+    float pscale[WB];
 #pragma unroll
     for (int k = 0; k < WB; ++k) {
-        const size_t o = (size_t)(b0 + k < B ? b0 + k : B - 1) * HWp + sp;
+        const int bk = b0 + k < B ? b0 + k : B - 1;
+        const size_t o = (size_t)bk * HWp + sp;
+        pscale[k] = (prjl2_scales != nullptr) ? prjl2_scales[bk] : prjl2_scale;
+        const bool need_x = (clamp && clamp_bits == nullptr) || (partial_ss != nullptr && pscale[k] != 0.f);
         xv[k] = (need_x && live) ? x[o] : make_float4(0.f, 0.f, 0.f, 0.f);
         cb[k] = (clamp && clamp_bits != nullptr && live) ? clamp_bits[o] : 7u;
     }
@@ -411,11 +416,11 @@ __global__ __launch_bounds__(256) void warp_bwd_tiled_kernel(const float4* __res
             // spaa_grad_sumsq folded in (round 6): the prjl2 term's gradient for samples taking the colour step
             // (projector_based_attack.py:275,310: d ||gray - x|| / dx = -(gray - x) / n, zero where the norm is zero), then this
             // pixel's share of ||g_b||^2 -- the same arithmetic, one launch and one pass over g_x less per iteration
-            if (prjl2_scale != 0.f && state[4 * (b0 + k) + 1] != 0) {
+            if (pscale[k] != 0.f && state[4 * (b0 + k) + 1] != 0) {
                 const float d0 = gray - v.x, d1 = gray - v.y, d2 = gray - v.z;
                 const float n = sqrtf(d0 * d0 + d1 * d1 + d2 * d2);
                 if (n != 0.f) {
-                    const float kk = -prjl2_scale / n;
+                    const float kk = -pscale[k] / n;
                     r0 += kk * d0;
                     r1 += kk * d1;
                     r2 += kk * d2;
@@ -542,7 +547,7 @@ int spaa_warp_bwd_gather(const float* g_xw, const float* g_xs, const float* x, c
 static int launch_warp_bwd_tiled(const float* g_xw, const float* x, const int32_t* off, const int32_t* lidx, const float* w_e,
                                  const int32_t* tbox, int box_cap, float* g_x, int B, int Hp, int Wp, int Hc, int Wc, int clamp,
                                  float* partial_ss, const int32_t* state, float gray, float prjl2_scale, const uint8_t* clamp_bits,
-                                 spaa_stream_t stream) {
+                                 const float* prjl2_scales, spaa_stream_t stream) {
     if (!g_xw || !x || !off || !lidx || !w_e || !tbox || !g_x || B < 1 || Hp < 1 || Wp < 1 || Hc < 1 || Wc < 1 || box_cap < 1 ||
         (size_t)box_cap * WB * 16 > 64 * 1024)
         return hipErrorInvalidValue;
@@ -553,14 +558,15 @@ static int launch_warp_bwd_tiled(const float* g_xw, const float* x, const int32_
     if (partial_ss != nullptr && smem < 4 * WB * sizeof(float)) smem = 4 * WB * sizeof(float);
     hipLaunchKernelGGL(warp_bwd_tiled_kernel, dim3(ntx * nty, (B + WB - 1) / WB), dim3(256), smem,
                        (hipStream_t)stream, (const float4*)g_xw, (const float4*)x, off, lidx, w_e, tbox, (float4*)g_x, B, Hp, Wp,
-                       Hc, Wc, ntx, box_cap, clamp, partial_ss, state, gray, prjl2_scale, clamp_bits);
+                       Hc, Wc, ntx, box_cap, clamp, partial_ss, state, gray, prjl2_scale, clamp_bits, prjl2_scales);
     return (int)hipGetLastError();
 }
 
 int spaa_warp_bwd_tiled(const float* g_xw, const float* x, const int32_t* off, const int32_t* lidx, const float* w_e,
                         const int32_t* tbox, int box_cap, float* g_x, int B, int Hp, int Wp, int Hc, int Wc, int clamp,
                         spaa_stream_t stream) {
-    return launch_warp_bwd_tiled(g_xw, x, off, lidx, w_e, tbox, box_cap, g_x, B, Hp, Wp, Hc, Wc, clamp, nullptr, nullptr, 0.f, 0.f, nullptr, stream);
+    return launch_warp_bwd_tiled(g_xw, x, off, lidx, w_e, tbox, box_cap, g_x, B, Hp, Wp, Hc, Wc, clamp, nullptr, nullptr, 0.f, 0.f, nullptr, nullptr,
+                                 stream);
 }
 
 int spaa_warp_bwd_tiled_sumsq(const float* g_xw, const float* x, const int32_t* off, const int32_t* lidx, const float* w_e,
@@ -569,7 +575,16 @@ int spaa_warp_bwd_tiled_sumsq(const float* g_xw, const float* x, const int32_t* 
                               spaa_stream_t stream) {
     if (!partial_ss || (prjl2_scale != 0.f && !state)) return hipErrorInvalidValue;
     return launch_warp_bwd_tiled(g_xw, x, off, lidx, w_e, tbox, box_cap, g_x, B, Hp, Wp, Hc, Wc, clamp, partial_ss, state, gray, prjl2_scale,
-                                 clamp_bits, stream);
+                                 clamp_bits, nullptr, stream);
+}
+
+int spaa_warp_bwd_tiled_sumsq_ps(const float* g_xw, const float* x, const int32_t* off, const int32_t* lidx, const float* w_e,
+                                 const int32_t* tbox, int box_cap, float* g_x, int B, int Hp, int Wp, int Hc, int Wc, int clamp,
+                                 float gray, const float* prjl2_scale, const int32_t* state, float* partial_ss,
+                                 const uint8_t* clamp_bits, spaa_stream_t stream) {
+    if (!partial_ss || !prjl2_scale || !state) return hipErrorInvalidValue;
+    return launch_warp_bwd_tiled(g_xw, x, off, lidx, w_e, tbox, box_cap, g_x, B, Hp, Wp, Hc, Wc, clamp, partial_ss, state, gray, 0.f,
+                                 clamp_bits, prjl2_scale, stream);
 }
 
 int spaa_warp_fwd_taps(const float* x, const int32_t* tap_src, const float* tap_wgt, float* xw, int B, int Hp, int Wp, int Hc, int Wc,

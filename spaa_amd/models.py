@@ -881,7 +881,7 @@ class PCNetEngine:
     def warp_backward(self, g_xw, sumsq=None, clamp_bits=None):
         """Adjoint of the masked grid_sample (models.py:184,340): deterministic gather over the transposed tap lists; the
         mask is folded into the tap weights.  `sumsq` = (partial [B, sumsq_tiles()], gray, prjl2_scale, state): spaa_grad_sumsq folded
-        into the tiled kernel's epilogue (only with sumsq_tiles() > 0).  `clamp_bits` [B, Hp * Wp] uint8 (with `sumsq` only): the clamp
+        into the tiled kernel's epilogue (only with sumsq_tiles() > 0); prjl2_scale a float or a [B] device tensor (one per sample).  `clamp_bits` [B, Hp * Wp] uint8 (with `sumsq` only): the clamp
         gate's comparisons for the x of the last forward pass, as spaa_step_and_track_n wrote them (the caller answers for that)."""
         g = self.g
         if sumsq is not None:
@@ -891,6 +891,13 @@ class PCNetEngine:
             if clamp_bits is not None:
                 assert clamp_bits.shape == (self.B, self.Hp * self.Wp) and clamp_bits.dtype == torch.uint8 and clamp_bits.is_contiguous()
             lidx, w_e, tbox, cap = self.tiled
+            if isinstance(scale, torch.Tensor):   # one prjl2 scale per sample (several attack configurations in one batch)
+                assert scale.shape == (self.B,) and scale.dtype == torch.float32 and scale.is_contiguous()
+                _lib.call('spaa_warp_bwd_tiled_sumsq_ps', _lib.ptr(g_xw), _lib.ptr(self._x), C_ptr(self.tap_off), C_ptr(lidx),
+                          _lib.ptr(w_e), C_ptr(tbox), cap, _lib.ptr(g['x']), self.B, self.Hp, self.Wp, self.Hc, self.Wc, self._clamp,
+                          float(gray), _lib.ptr(scale), _lib.ptr(state), _lib.ptr(part),
+                          _lib.ptr(clamp_bits) if clamp_bits is not None else None)
+                return g['x']
             _lib.call('spaa_warp_bwd_tiled_sumsq', _lib.ptr(g_xw), _lib.ptr(self._x), C_ptr(self.tap_off), C_ptr(lidx), _lib.ptr(w_e),
                       C_ptr(tbox), cap, _lib.ptr(g['x']), self.B, self.Hp, self.Wp, self.Hc, self.Wc, self._clamp, float(gray), float(scale),
                       _lib.ptr(state), _lib.ptr(part), _lib.ptr(clamp_bits) if clamp_bits is not None else None)

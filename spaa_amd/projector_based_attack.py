@@ -30,6 +30,19 @@ GRAPH_MAX_PIXELS = int(os.environ.get('SPAA_GRAPH_MAX_PIXELS', str(16 * 256 * 25
 LAST_RUN = {}   # of the last spaa() call: executed iterations (1 eager + iters - 1 replays = iters: a capture executes nothing), graph or not
 
 
+LOSS_TERMS = ('prjl2', 'caml2', 'camdE')
+
+
+def loss_weights(stealth_loss):
+    """(prjl2_w, caml2_w, camdE_w) of a stealth-loss string (projector_based_attack.py:275-287: a term is on when its name occurs)."""
+    return (0.1 if 'prjl2' in stealth_loss else 0.0, 1.0 if 'caml2' in stealth_loss else 0.0,
+            1.0 if 'camdE' in stealth_loss else 0.0)
+
+
+def _is_scalar(v):
+    return isinstance(v, (bool, int, float)) or (isinstance(v, torch.Tensor) and v.ndim == 0) or getattr(v, 'ndim', None) == 0
+
+
 def _unwrap(m):
     return m.module if hasattr(m, 'module') and not isinstance(m, (PCNet, Classifier)) else m
 
@@ -106,12 +119,43 @@ class AttackState:
         self.g_logits = torch.zeros(B, self.clf.ncls, device=dev)
         self.prjl2 = torch.zeros(B, device=dev)
         self.target = torch.tensor([int(t) for t in target_idx], dtype=torch.int32, device=dev)
-        self.prjl2_w = 0.1 if 'prjl2' in stealth_loss else 0.0
-        self.caml2_w = 1.0 if 'caml2' in stealth_loss else 0.0
-        self.camdE_w = 1.0 if 'camdE' in stealth_loss else 0.0
+        # `stealth_loss`: one string for the batch, or one per sample (spaa_sweep).  self.prjl2_w / caml2_w / camdE_w are the batch's
+        # weights when every sample has the same ones, else None: the per-sample table of the _ps launches carries them.
+        losses = [stealth_loss] * B if isinstance(stealth_loss, str) else list(stealth_loss)
+        if len(losses) != B:
+            raise ValueError(f'stealth_loss: {len(losses)} strings for {B} samples')
+        self.loss_w = [loss_weights(s) for s in losses]
+        uniform = all(w == self.loss_w[0] for w in self.loss_w)
+        self.prjl2_w, self.caml2_w, self.camdE_w = self.loss_w[0] if uniform else (None, None, None)
+        self.any_prjl2 = any(w[0] for w in self.loss_w)
+        self._ps_key = None      # (targeted, d_thr) per sample of the uploaded table, None: scalar launches
+        self.ps_params = torch.zeros(B, 4, device=dev)
+        self.ps_flags = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.ps_prjl2_scale = torch.zeros(B, device=dev)
+
+    def _per_sample(self, targeted, d_thr):
+        """The batch's (targeted, d_thr) as scalars when every sample agrees and the loss weights are uniform (the launches of a single
+        attack, unchanged); else uploads the per-sample table (once per distinct setting: a captured graph replays the table it
+        read) and returns None."""
+        B = self.B
+        tg = [bool(targeted)] * B if _is_scalar(targeted) else [bool(t) for t in targeted]
+        dt = [float(d_thr)] * B if _is_scalar(d_thr) else [float(d) for d in d_thr]
+        if len(tg) != B or len(dt) != B:
+            raise ValueError(f'targeted / d_thr: one value or {B} values')
+        if self.caml2_w is not None and all(t == tg[0] for t in tg) and all(d == dt[0] for d in dt):
+            return tg[0], dt[0]
+        key = (tuple(tg), tuple(dt))
+        if key != self._ps_key:
+            params = torch.tensor([list(w) + [d] for w, d in zip(self.loss_w, dt)], dtype=torch.float32)
+            self.ps_params.copy_(params)
+            self.ps_flags.copy_(torch.tensor([int(t) for t in tg], dtype=torch.int32))
+            self.ps_prjl2_scale.copy_(params[:, 0] / (B * self.HWp) * self.gs_col)
+            self._ps_key = key
+        return None
 
     def iteration(self, targeted, d_thr, adv_lr, col_lr, p_thresh, adv_w=1.0):
-        """One pass of the loop body (projector_based_attack.py:264-328), ~90 kernel launches, no host sync."""
+        """One pass of the loop body (projector_based_attack.py:264-328), ~90 kernel launches, no host sync.  `targeted` and `d_thr`:
+        one value for the batch or one per sample."""
         with torch.cuda.device(self.dev):
             self._forward_decide(targeted, d_thr, p_thresh, adv_w)
             self._backward_step(adv_lr, col_lr)
@@ -129,8 +173,20 @@ class AttackState:
 
     def _forward_decide(self, targeted, d_thr, p_thresh, adv_w):
         B, p = self.B, _lib.ptr
+        uni = self._per_sample(targeted, d_thr)
         y = self.eng.forward(self.x, clamp01=True)                                   # :265
         logits = self.clf.forward(y)                                                 # :266
+        self._y, self._uniform = y, uni is not None
+        if uni is None:   # several attack configurations in one batch: the same kernels, their parameters per sample
+            if self.any_prjl2:
+                _lib.call('spaa_prjl2_fwd', p(self.x), self.gray, p(self.prjl2), B, self.HWp)
+            _lib.call('spaa_stealth_loss_fwd_bwd_ps', p(y), p(self.scene4), p(self.scene_lab), p(self.ps_params),
+                      self.gs_col / (B * self.HWc), p(self.g_col), None, p(self.partial_loss), B, self.HWc)
+            _lib.call('spaa_decide_ps', p(logits), self.clf.ncls, p(self.target), p(self.partial_loss), self.nblk_c, self.HWc,
+                      p(self.prjl2) if self.any_prjl2 else None, p(self.ps_params), p(self.ps_flags), float(p_thresh),
+                      adv_w / B * self.gs_adv, p(self.state), p(self.stats), p(self.g_logits), B)
+            return
+        targeted, d_thr = uni
         if self.prjl2_w:
             _lib.call('spaa_prjl2_fwd', p(self.x), self.gray, p(self.prjl2), B, self.HWp)    # :275
         _lib.call('spaa_stealth_loss_fwd_bwd', p(y), p(self.scene4), p(self.scene_lab), self.caml2_w, self.camdE_w,
@@ -139,12 +195,12 @@ class AttackState:
                   self.nblk_c, self.HWc, p(self.prjl2) if self.prjl2_w else None, self.prjl2_w, self.caml2_w,
                   self.camdE_w, float(d_thr), float(p_thresh), adv_w / B * self.gs_adv, p(self.state), p(self.stats),
                   p(self.g_logits), B)                                               # :269-272, :290-299, :318-320
-        self._y = y
 
     def _backward_step(self, adv_lr, col_lr):
         B, p, y = self.B, _lib.ptr, self._y
         g_adv = self.clf.backward(self.g_logits)                                     # :302 (classifier part)
-        prjl2_scale = self.prjl2_w / (B * self.HWp) * self.gs_col
+        # (mixed configurations: the prjl2 scale is a [B] device tensor, and the sums of squares take the _ps launches)
+        prjl2_scale = self.prjl2_w / (B * self.HWp) * self.gs_col if self._uniform else self.ps_prjl2_scale
         ss = (self.partial_ss, self.gray, prjl2_scale, self.state) if self.ss_tiles else None   # (||g||^2 from the adjoint's epilogue)
         bits = self.clamp_bits if (self.clamp_bits is not None and self._bits_version == self.x._version) else None
         if self.eng.can_select():   # (the per-sample choice and the clamp gate as the first phase of the fused head kernel)
@@ -153,8 +209,11 @@ class AttackState:
             _lib.call('spaa_select_grad', p(g_adv), p(self.g_col), p(self.state), p(self.eng.a['Ypre']), p(self.gP), B,
                       self.HWc)
             gx = self.eng.backward(self.gP, sumsq=ss, clamp_bits=bits)               # :302 / :310 (PCNet part)
-        if not self.ss_tiles:
+        if not self.ss_tiles and self._uniform:
             _lib.call('spaa_grad_sumsq', p(gx), p(self.x), self.gray, prjl2_scale, p(self.state), p(self.partial_ss), B, self.HWp)
+        elif not self.ss_tiles:
+            _lib.call('spaa_grad_sumsq_ps', p(gx), p(self.x), self.gray, p(prjl2_scale), p(self.state), p(self.partial_ss), B,
+                      self.HWp)
         _lib.call('spaa_step_and_track_n', p(self.x), p(gx), p(self.partial_ss), self.partial_ss.shape[1], p(self.state), float(adv_lr),
                   float(col_lr), p(self.x_best), p(y), p(self.cam_best), B, self.HWp, self.HWc,
                   p(self.clamp_bits) if self.clamp_bits is not None else None)       # :307,315,323-328
@@ -190,10 +249,27 @@ def spaa(pcnet, classifier, imagenet_labels, target_idx, targeted, cam_scene, d_
         return _spaa_foreign_classifier(pcnet, classifier, imagenet_labels, target_idx, targeted, cam_scene, d_thr,
                                         stealth_loss, device, setup_info, iters, adv_lr, col_lr, p_thresh, trace)
     st = AttackState(pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, device, storage=storage)
-    if trace is None and not verbose and iters >= 4 and st.B * st.HWc <= GRAPH_MAX_PIXELS:
+
+    def report(i):
+        if i % 30 == 0 or i == iters - 1:
+            s, f = st.state.cpu(), st.stats.cpu()
+            v = 7 if (targeted and st.B > 7) else 0
+            name = imagenet_labels[int(s[v, 3])] if imagenet_labels else ''
+            print(f'col_loss = {f[:, 3].mean():<9.4f} | prjl2 = {f[:, 4].mean() * 255:<9.4f} | caml2 = '
+                  f'{f[:, 1].mean() * 255:<9.4f} | camdE = {f[:, 2].mean():<9.4f} | p = {f[v, 0]:.4f} | y = '
+                  f'{int(s[v, 3]):3d} ({name})')
+
+    _run(st, targeted, d_thr, iters, adv_lr, col_lr, p_thresh, trace, report if verbose else None)
+    return st.results()
+
+
+def _run(st, targeted, d_thr, iters, adv_lr, col_lr, p_thresh, trace=None, report=None):
+    """The loop of spaa() (projector_based_attack.py:264-328) on an AttackState; `targeted` / `d_thr` one value or one per sample."""
+    if trace is None and report is None and iters >= 4 and st.B * st.HWc <= GRAPH_MAX_PIXELS:
         # Few pixels (the reference's own calls: B = 1 and B = 10 at 240 x 320): an iteration's ~120 launches take the GPU
         # less time than the host needs to enqueue them.  The loop body has no host-side dependence on the iteration, so it is
-        # captured ONCE as a HIP graph (after one eager iteration: kernel attributes and workspaces exist) and replayed.
+        # captured ONCE as a HIP graph (after one eager iteration: kernel attributes, workspaces and the per-sample table exist)
+        # and replayed.
         with torch.cuda.device(st.dev):
             st.iteration(targeted, d_thr, adv_lr, col_lr, p_thresh)
             done = 1
@@ -206,7 +282,7 @@ def spaa(pcnet, classifier, imagenet_labels, target_idx, targeted, cam_scene, d_
                 # the capture was refused or a launch inside it failed: the remaining iterations run kernel by kernel (same
                 # results; a real launch error shows again there, un-captured) -- said aloud, and recorded in LAST_RUN
                 warnings.warn(f'spaa(): HIP-graph capture of the iteration failed, running eagerly: {type(e).__name__}: {e}',
-                              RuntimeWarning, stacklevel=2)
+                              RuntimeWarning, stacklevel=3)
                 graph = None
             while done < iters:
                 if graph is not None:
@@ -215,20 +291,89 @@ def spaa(pcnet, classifier, imagenet_labels, target_idx, targeted, cam_scene, d_
                     st.iteration(targeted, d_thr, adv_lr, col_lr, p_thresh)
                 done += 1
         LAST_RUN.update(iterations=done, graph=graph is not None)
-        return st.results()
+        return
     LAST_RUN.update(iterations=iters, graph=False)
     for i in range(iters):
         st.iteration(targeted, d_thr, adv_lr, col_lr, p_thresh)
         if trace is not None:
             trace.append((st.state.clone(), st.stats.clone()))
-        if verbose and (i % 30 == 0 or i == iters - 1):
-            s, f = st.state.cpu(), st.stats.cpu()
-            v = 7 if (targeted and st.B > 7) else 0
-            name = imagenet_labels[int(s[v, 3])] if imagenet_labels else ''
-            print(f'col_loss = {f[:, 3].mean():<9.4f} | prjl2 = {f[:, 4].mean() * 255:<9.4f} | caml2 = '
-                  f'{f[:, 1].mean() * 255:<9.4f} | camdE = {f[:, 2].mean():<9.4f} | p = {f[v, 0]:.4f} | y = '
-                  f'{int(s[v, 3]):3d} ({name})')
-    return st.results()
+        if report is not None:
+            report(i)
+
+
+def plan_sweep(configs, max_batch=64):
+    """Host side of spaa_sweep: validates `configs` [(stealth_loss, d_thr, targeted, target_idx), ...] and flattens them, in order,
+    into samples (config index, stealth_loss, d_thr, targeted, target), cut into chunks [(start, stop), ...] of at most `max_batch`
+    samples (a chunk may hold several configs and may split one).  Errors name the config."""
+    if int(max_batch) < 1:
+        raise ValueError(f'max_batch must be >= 1, got {max_batch}')
+    samples = []
+    for i, cfg in enumerate(configs):
+        try:
+            loss, d_thr, targeted, target_idx = cfg
+        except (TypeError, ValueError):
+            raise ValueError(f'configs[{i}]: expected (stealth_loss, d_thr, targeted, target_idx), got {cfg!r}') from None
+        if not isinstance(loss, str) or not loss or any(t not in LOSS_TERMS for t in loss.split('_')):
+            raise ValueError(f'configs[{i}]: unknown stealth loss {loss!r} (terms joined by "_": {", ".join(LOSS_TERMS)})')
+        target_idx = list(target_idx)
+        if not target_idx:
+            raise ValueError(f'configs[{i}]: target_idx is empty: nothing to attack')
+        samples += [(i, loss, float(d_thr), bool(targeted), int(t)) for t in target_idx]
+    if not samples:
+        raise ValueError('configs is empty: nothing to attack')
+    mb = int(max_batch)
+    return samples, [(a, min(a + mb, len(samples))) for a in range(0, len(samples), mb)]
+
+
+def split_sweep(samples, ncfg, chunk_results):
+    """Inverse of plan_sweep's flattening: per-chunk (cam [n,...], prj [n,...]) in sample order -> one (cam, prj) per config."""
+    cams = torch.cat([c for c, _ in chunk_results])
+    prjs = torch.cat([p for _, p in chunk_results])
+    assert cams.shape[0] == len(samples)
+    out, a = [], 0
+    for i in range(ncfg):
+        b = a
+        while b < len(samples) and samples[b][0] == i:
+            b += 1
+        out.append((cams[a:b], prjs[a:b]))
+        a = b
+    return out
+
+
+def spaa_sweep(pcnet, classifier, imagenet_labels, cam_scene, setup_info, device, configs, *, iters=50, adv_lr=2, col_lr=1,
+               p_thresh=0.9, max_batch=64, storage='f32', trace=None):
+    """Several SPAA attacks on one PCNet, scene and classifier as few batched attacks (the reference's driver makes one spaa() call
+    per configuration: projector_based_attack.py:24-148).  `configs`: [(stealth_loss, d_thr, targeted, target_idx), ...]; returns one
+    (cam_infer_best, prj_adv_best) per config, in order -- what spaa(pcnet, classifier, imagenet_labels, target_idx, targeted,
+    cam_scene, d_thr, stealth_loss, device, setup_info) returns for it: samples do not interact, so only the batch differs.  The
+    samples of all configs are flattened in order and cut into chunks of at most `max_batch` (one AttackState each, the loop of
+    spaa() with its loss weights, targeted flag and d_thr per sample); `trace` receives one list per chunk, of the per-iteration
+    (state, stats) pairs spaa() records (the chunk's samples in flattened order)."""
+    samples, chunks = plan_sweep(configs, max_batch)
+    pcnet, classifier = _unwrap(pcnet), _unwrap(classifier)
+    if not isinstance(pcnet, PCNet):
+        raise TypeError('spaa_sweep needs a spaa_amd.PCNet (the HIP path has no generic PCNet fallback)')
+    if not isinstance(classifier, Classifier):
+        raise TypeError('spaa_sweep needs a spaa_amd.Classifier')
+    if torch.device(device).type != 'cuda':
+        raise RuntimeError('spaa_amd.spaa_sweep runs on the GPU only (no CPU fallback); got device=%s' % device)
+    sc = cam_scene.detach()
+    while sc.ndim < 4:
+        sc = sc[None]
+    cam_sz = tuple(pcnet.warping_net.out_size)
+    if sc.ndim != 4 or sc.shape[0] != 1 or tuple(sc.shape[1:]) != (3,) + cam_sz:
+        raise ValueError(f'cam_scene must be [3,H,W] or [1,3,H,W] with (H, W) = {cam_sz} (PCNet\'s output); got {tuple(cam_scene.shape)}')
+    results = []
+    for a, b in chunks:
+        part = samples[a:b]
+        st = AttackState(pcnet, classifier, [t for *_, t in part], sc, [s[1] for s in part], setup_info, device, storage=storage)
+        tr = [] if trace is not None else None
+        _run(st, [s[3] for s in part], [s[2] for s in part], iters, adv_lr, col_lr, p_thresh, tr)
+        if trace is not None:
+            trace.append(tr)
+        results.append(st.results())
+        del st
+    return split_sweep(samples, len(configs), results)
 
 
 class _StealthFn(torch.autograd.Function):
@@ -318,3 +463,102 @@ def _spaa_foreign_classifier(pcnet, classifier, imagenet_labels, target_idx, tar
 
 
 spaa_attack = spaa  # name used by BASELINE.json's north_star
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# The reference's attack driver (projector_based_attack.py:24-148, :169-209)
+ATTACKERS = ('SPAA', 'PerC-AL+CompenNet++', 'One-pixel_DE')
+MODEL_TRAIN_CFG = dict(loss='l1+ssim', num_train=500, batch_size=24, max_iters=2000)   # get_model_train_cfg's defaults (train_network.py)
+
+
+def get_attacker_cfg(attacker_name, data_root, setup_list, device_ids=[0], load_pretrained=False, plot_on=True):
+    """projector_based_attack.py:169-192: the default attacker configuration, as a mapping with attribute access."""
+    from .io import SetupInfo
+    cfg = SetupInfo(attacker_name=attacker_name, classifier_names=['inception_v3', 'resnet18', 'vgg16'], data_root=data_root,
+                    setup_list=setup_list, device='cuda', device_ids=device_ids, load_pretrained=load_pretrained, plot_on=plot_on)
+    if attacker_name == 'SPAA':
+        cfg.stealth_losses, cfg.d_threshes = ['caml2', 'camdE', 'camdE_caml2'], [5, 7, 9, 11]
+    elif attacker_name == 'PerC-AL+CompenNet++':
+        cfg.stealth_losses, cfg.d_threshes = ['camdE'], [11]
+    elif attacker_name == 'One-pixel_DE':
+        cfg.stealth_losses, cfg.d_threshes = ['-'], ['-']
+    return cfg
+
+
+def to_attacker_cfg_str(attacker_name):
+    """projector_based_attack.py:195-209: (attacker_cfg_str, model_cfg_str), the result folders' names."""
+    if attacker_name not in ATTACKERS:
+        raise ValueError(f'{attacker_name} not supported!')
+    m = MODEL_TRAIN_CFG
+    tail = f'{m["loss"]}_{m["num_train"]}_{m["batch_size"]}_{m["max_iters"]}'
+    if attacker_name == 'SPAA':
+        return f'SPAA_PCNet_{tail}', f'PCNet_{tail}'
+    if attacker_name == 'PerC-AL+CompenNet++':
+        return f'{attacker_name}_{tail}', f'CompenNet++_{tail}'
+    return attacker_name, None
+
+
+def run_projector_based_attack(cfg, *, models=None, classifiers=None, iters=50):
+    """projector_based_attack.py:24-148 for the deep-learning attackers: per setup and classifier, 10 targeted attacks (the first 10
+    imagenet10 classes) and 1 untargeted attack (the scene's top-1) for every stealth loss x d_thr; results under
+    <setup>/prj/adv and <setup>/cam/infer/adv / <attacker_cfg_str>/<loss>/<d_thr>/<classifier>/img_0001..0011.png (1-10 targeted,
+    11 untargeted).  For SPAA one classifier's whole sweep is ONE spaa_sweep call.
+    `models`: setup name -> trained PCNet (SPAA) / CompenNetPlusplus (PerC-AL+CompenNet++); `classifiers`: classifier name ->
+    spaa_amd.Classifier.  (The reference trains or loads the model and downloads the classifier weights here; neither is done.)"""
+    import itertools
+    import random
+    from os.path import join
+    from . import io
+    from .classifier import load_imagenet_labels
+    name = cfg.attacker_name
+    if name not in ATTACKERS:
+        raise ValueError(f'{name} not supported!')
+    if name == 'One-pixel_DE':
+        raise NotImplementedError('One-pixel_DE attacks the real scene through a projector and a camera; use '
+                                  'spaa_amd.DigitalOnePixelAttacker for the digital attack')
+    device = torch.device(cfg.device)
+    random.seed(0)   # (ut.reset_rng_seeds(0))
+    torch.manual_seed(0)
+    attacker_cfg_str = to_attacker_cfg_str(name)[0]
+    for setup_name in cfg.setup_list:
+        model = (models or {}).get(setup_name)
+        if model is None:
+            raise ValueError(f'run_projector_based_attack: pass models={{{setup_name!r}: trained '
+                             f'{"PCNet" if name == "SPAA" else "CompenNetPlusplus"}}} (models are not trained here)')
+        missing = [c for c in cfg.classifier_names if c not in (classifiers or {})]
+        if missing:
+            raise ValueError(f'run_projector_based_attack: pass classifiers={{name: spaa_amd.Classifier}} for {missing} '
+                             '(weights cannot be downloaded here)')
+        setup_path = join(cfg.data_root, 'setups', setup_name)
+        setup_info = io.load_setup_info(setup_path)
+        cp_sz = setup_info['classifier_crop_sz']
+        th, tw = tuple(setup_info['cam_im_sz'])[::-1]
+        im = io.torch_imread(join(setup_path, 'cam/raw/ref/img_0002.png'))
+        i0, j0 = int(round((im.shape[-2] - th) / 2.)), int(round((im.shape[-1] - tw) / 2.))   # (img_proc.center_crop)
+        cam_scene = im[..., i0:i0 + th, j0:j0 + tw].to(device)
+        imagenet_labels = load_imagenet_labels(join(cfg.data_root, 'imagenet1000_clsidx_to_labels.txt'))
+        target_labels = load_imagenet_labels(join(cfg.data_root, 'imagenet10_clsidx_to_labels.txt'))
+        target_idx = list(dict(itertools.islice(target_labels.items(), 10)).keys())
+        model.eval()
+        for param in model.parameters():
+            param.requires_grad = False
+        for classifier_name in cfg.classifier_names:
+            classifier = classifiers[classifier_name]
+            with torch.no_grad():
+                raw_score, _, _ = classifier(cam_scene, cp_sz)
+            true_idx = int(raw_score[0].argmax())   # (pred_idx[0, 0] of the sorted result; also for a Classifier made with sort_results=False)
+            grid = [(loss, d_thr) for loss in cfg.stealth_losses for d_thr in cfg.d_threshes]
+            if name == 'SPAA':
+                configs = [c for loss, d_thr in grid for c in ((loss, d_thr, True, target_idx), (loss, d_thr, False, [true_idx]))]
+                res = spaa_sweep(model, classifier, imagenet_labels, cam_scene, setup_info, device, configs, iters=iters)
+                res = {g: (res[2 * k], res[2 * k + 1]) for k, g in enumerate(grid)}
+            else:
+                from .perc_al import perc_al_compennet_pp
+                res = {(loss, d_thr): tuple(perc_al_compennet_pp(model, classifier, imagenet_labels, t, tg, cam_scene, d_thr, device,
+                                                                 setup_info) for t, tg in ((target_idx, True), ([true_idx], False)))
+                       for loss, d_thr in grid}
+            for (loss, d_thr), ((cam_tar, prj_tar), (cam_untar, prj_untar)) in res.items():
+                folder = join(attacker_cfg_str, loss, str(d_thr), classifier_name)
+                io.save_imgs(torch.cat((cam_tar, cam_untar), 0), join(setup_path, 'cam/infer/adv', folder))
+                io.save_imgs(torch.cat((prj_tar, prj_untar), 0), join(setup_path, 'prj/adv', folder))
+    return cfg
