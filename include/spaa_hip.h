@@ -420,16 +420,28 @@ int spaa_stealth_loss_fwd_bwd(const float* y, const float* scene, const float* s
 int spaa_stealth_loss_fwd_bwd_ps(const float* y, const float* scene, const float* scene_lab, const float* params,
                                  float gscale, float* g_y, float* de_map, float* partial, int B, int HW, spaa_stream_t stream);
 
-/* calc_img_dists (utils.py:420-491), NHWC4 images x, y of `npix` = B*H*W pixels: per-pixel terms of PSNR/RMSE (sum of
- * squared differences), mean L2 (:460-471), mean L_inf (:475-486) and mean dE2000 (differential_color_functions.py:183-190)
- * reduced per 256-pixel block in fixed order: partial[(npix+255)/256][4] = (sum d^2, sum ||d||_2, sum max|d|, sum dE). */
-int spaa_img_dists(const float* x, const float* y, float* partial, int npix, spaa_stream_t stream);
-
-/* SSIM map sum (pytorch_ssim/__init__.py:26-58: 11x11 Gaussian `window` [121] as create_window builds it, replicate
- * padding, C1 = 0.01^2, C2 = 0.03^2, per channel): partial[B][ceil(H/16)][ceil(W/16)] = sum over the tile's pixels and
- * 3 channels; the mean is the sum of all partials / (B*3*H*W). */
-int spaa_ssim(const float* x, const float* y, const float* window, float* partial, int B, int H, int W,
-              spaa_stream_t stream);
+/* calc_img_dists (utils.py:420-491) of many image pairs in one launch: for every pair, the sums over its crop
+ * rectangle of the per-pixel terms of PSNR/RMSE (d^2 over the 3 channels), SSIM (pytorch_ssim/__init__.py:26-58: the
+ * 11x11 Gaussian `window` [121] as create_window builds it, C1 = 0.01^2, C2 = 0.03^2, per channel, replicate padding
+ * clamped to the CROP rectangle, so no pixel outside it enters a window), mean L2 (:460-471, ||d||_2), mean L_inf
+ * (:475-486, max|d|) and mean dE2000 (differential_color_functions.py:183-190).
+ * x and y are read as NCHW fp32 planes: side s of a pair is the [3][s_H][s_W] image at element offset s_off of its base
+ * pointer, cropped to rows [s_y0, s_y0 + h) x columns [s_x0, s_x0 + w).  y_const != 0: the y side is the constant colour
+ * y_rgb (no memory read; `y` may then be NULL when no pair reads it).
+ * Tiles are 16x16 crop pixels; pair p owns tiles [tile0, tile0 + ceil(h/16) * ceil(w/16)), row-major over its crop;
+ * tile_pair[ntiles] maps a tile to its pair.  partial[ntiles][5] = the tile's (sum d^2, sum SSIM map, sum ||d||_2,
+ * sum max|d|, sum dE): fixed slots, no atomics; the caller adds a pair's tiles in order.  The host checks every
+ * rectangle against its image and every offset against its buffer (32-bit plane indices, 64-bit offsets). */
+typedef struct {
+    int64_t x_off, y_off;
+    int32_t xH, xW, xy0, xx0;
+    int32_t yH, yW, yy0, yx0;
+    int32_t h, w, tile0, y_const;
+    float y_rgb[3];
+    int32_t reserved;
+} spaa_img_pair_t;   /* 80 bytes */
+int spaa_img_stats(const float* x, const float* y, const spaa_img_pair_t* pairs, const int32_t* tile_pair, int ntiles,
+                   const float* window, float* partial, spaa_stream_t stream);
 
 /* ---- classifier pre/post-processing (classifier.py:55-72, img_proc.py:117-132) --------------------------- */
 /* center_crop + F.interpolate(mode='area') + Normalize, NHWC4 in -> NHWC4 out; mean3/std3 are HOST pointers */

@@ -16,7 +16,7 @@ def __getattr__(name):
         from . import classifier
         return getattr(classifier, name)
     if name in ('spaa', 'spaa_attack', 'AttackState', 'spaa_sweep', 'run_projector_based_attack', 'get_attacker_cfg',
-                'to_attacker_cfg_str'):
+                'to_attacker_cfg_str', 'summarize_single_attacker', 'summarize_all_attackers'):
         from . import projector_based_attack
         return getattr(projector_based_attack, name)
     if name in ('rgb2lab_diff', 'ciede2000_diff', 'deltaE', 'stealth_loss_with_grad'):
@@ -34,9 +34,9 @@ def __getattr__(name):
     if name in ('DigitalOnePixelAttacker', 'perturb_image'):
         from . import one_pixel_attacker
         return getattr(one_pixel_attacker, name)
-    if name == 'calc_img_dists':
+    if name in ('calc_img_dists', 'img_stats', 'dists_from_sums'):
         from . import metrics
-        return metrics.calc_img_dists
+        return getattr(metrics, name)
     if name in ('torch_imread', 'torch_imread_mt', 'save_imgs', 'load_setup_info', 'save_checkpoint'):
         from . import io
         return getattr(io, name)

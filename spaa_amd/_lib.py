@@ -46,6 +46,15 @@ class TapConv(C.Structure):
     ]
 
 
+class ImgPair(C.Structure):
+    """spaa_img_pair_t: one image pair of spaa_img_stats (include/spaa_hip.h)."""
+    _fields_ = [('x_off', C.c_int64), ('y_off', C.c_int64),
+                ('xH', C.c_int32), ('xW', C.c_int32), ('xy0', C.c_int32), ('xx0', C.c_int32),
+                ('yH', C.c_int32), ('yW', C.c_int32), ('yy0', C.c_int32), ('yx0', C.c_int32),
+                ('h', C.c_int32), ('w', C.c_int32), ('tile0', C.c_int32), ('y_const', C.c_int32),
+                ('y_rgb', C.c_float * 3), ('reserved', C.c_int32)]
+
+
 _i, _f, _p, _l, _d = C.c_int, C.c_float, C.c_void_p, C.c_int64, C.c_double
 
 # name -> argument types (all return int)
@@ -93,9 +102,8 @@ _SIGNATURES = {
     'spaa_ciede2000_bwd': [_p, _p, _p, _p, _p, _i, _p],
     'spaa_stealth_loss_fwd_bwd': [_p, _p, _p, _f, _f, _f, _p, _p, _p, _i, _i, _p],
     'spaa_stealth_loss_fwd_bwd_ps': [_p, _p, _p, _p, _f, _p, _p, _p, _i, _i, _p],
-    'spaa_img_dists': [_p, _p, _p, _i, _p],
+    'spaa_img_stats': [_p, _p, _p, _p, _i, _p, _p, _p],
     'spaa_train_loss_fwd_bwd': [_p, _p, _p, _f, _f, _p, _p, _p, _p, _p, _i, _i, _i, _p],
-    'spaa_ssim': [_p, _p, _p, _p, _i, _i, _i, _p],
     'spaa_add_nhwc4': [_p, _p, _p, _i, _p],
     'spaa_ce_grad': [_p, _i, _p, _f, _p, _i, _p],
     'spaa_masked_step': [_p, _p, _p, _p, _i, _i, _f, _i, _i, _p],

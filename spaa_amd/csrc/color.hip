@@ -414,50 +414,40 @@ __global__ __launch_bounds__(256) void stealth_loss_kernel(const float4* __restr
 // symmetric kernel below (argument order swapped inside ciede2000 is NOT equivalent, so it has its own adjoint).
 
 // ---------------------------------------------------------------------------------------------------------------
-// calc_img_dists (utils.py:420-491): per-pixel terms of MSE / mean-L2 / mean-L_inf / mean dE2000 in one pass.
-// partial[block][4] = (sum d^2 over 3 channels, sum ||d||_2, sum max|d|, sum dE); the host adds the blocks in order.
-__global__ __launch_bounds__(256) void img_dists_kernel(const float4* __restrict__ x, const float4* __restrict__ y,
-                                                        float* __restrict__ partial, int npix) {
-    __shared__ float red[4];
-    const int idx = blockIdx.x * 256 + threadIdx.x;
-    float sq = 0.f, l2 = 0.f, li = 0.f, de = 0.f;
-    if (idx < npix) {
-        const float4 a = x[idx], b = y[idx];
-        const float dx = a.x - b.x, dy = a.y - b.y, dz = a.z - b.z;
-        sq = dx * dx + dy * dy + dz * dz;
-        l2 = sqrtf(sq);
-        li = fmaxf(fabsf(dx), fmaxf(fabsf(dy), fabsf(dz)));
-        float L1, A1, B1, L2, A2, B2;
-        rgb_to_lab(a.x, a.y, a.z, L1, A1, B1);
-        rgb_to_lab(b.x, b.y, b.z, L2, A2, B2);
-        de = ciede2000<false>(L1, A1, B1, L2, A2, B2).de;
-    }
-    const float s0 = block_sum(sq, red), s1 = block_sum(l2, red), s2 = block_sum(li, red),
-                s3 = block_sum(de, red);
-    if (threadIdx.x == 0) {
-        partial[4 * blockIdx.x + 0] = s0;
-        partial[4 * blockIdx.x + 1] = s1;
-        partial[4 * blockIdx.x + 2] = s2;
-        partial[4 * blockIdx.x + 3] = s3;
-    }
-}
-
-// SSIM (pytorch_ssim/__init__.py:26-58): 11x11 Gaussian window (sigma 1.5, passed in as the reference builds it),
-// replicate padding, per channel; partial[block] = sum of the SSIM map over the block's 16x16 pixels x 3 channels.
+// calc_img_dists (utils.py:420-491) of a table of image pairs, one block per 16x16 tile of a pair's crop rectangle (the tile list of
+// all pairs is flattened: tile_pair[tile] -> pair).  x and y are NCHW fp32 planes read in place (no crop copy, no NHWC4 conversion);
+// the y side may be a constant colour.  Per tile, in the same pass over the halo: the SSIM map (pytorch_ssim/__init__.py:26-58:
+// the 11x11 Gaussian window passed in as the reference builds it, replicate padding CLAMPED TO THE CROP, the reference's
+// cc(...) then _ssim) and the per-pixel terms of MSE / mean-L2 / mean-L_inf / mean dE2000.
+// partial[tile][5] = (sum d^2 over 3 channels, sum SSIM over 3 channels, sum ||d||_2, sum max|d|, sum dE): fixed slots, no
+// atomics; the host adds a pair's tiles in order.
 constexpr int SS_T = 16, SS_R = 5, SS_P = SS_T + 2 * SS_R;
-__global__ __launch_bounds__(256) void ssim_kernel(const float4* __restrict__ x, const float4* __restrict__ y,
-                                                   const float* __restrict__ window, float* __restrict__ partial, int H,
-                                                   int W) {
+static_assert(sizeof(spaa_img_pair_t) == 80, "spaa_img_pair_t: the layout _lib.ImgPair restates");
+__global__ __launch_bounds__(256) void img_stats_kernel(const float* __restrict__ x, const float* __restrict__ y,
+                                                        const spaa_img_pair_t* __restrict__ pairs,
+                                                        const int32_t* __restrict__ tile_pair,
+                                                        const float* __restrict__ window, float* __restrict__ partial) {
     __shared__ float4 sx[SS_P * SS_P], sy[SS_P * SS_P];
     __shared__ float sw[121];
     __shared__ float red[4];
-    const int b = blockIdx.z, y0 = blockIdx.y * SS_T, x0 = blockIdx.x * SS_T;
-    const size_t base = (size_t)b * H * W;
+    const int tile = blockIdx.x;
+    const spaa_img_pair_t P = pairs[tile_pair[tile]];
+    const int ntx = (P.w + SS_T - 1) / SS_T, lt = tile - P.tile0;
+    const int ty = lt / ntx, y0 = ty * SS_T, x0 = (lt - ty * ntx) * SS_T;
+    const float* xb = x + P.x_off;
+    const int xplane = P.xH * P.xW;
     for (int i = threadIdx.x; i < SS_P * SS_P; i += 256) {
         const int py = i / SS_P, px = i - py * SS_P;
-        const int iy = min(max(y0 + py - SS_R, 0), H - 1), ix = min(max(x0 + px - SS_R, 0), W - 1);  // replicate
-        sx[i] = x[base + (size_t)iy * W + ix];
-        sy[i] = y[base + (size_t)iy * W + ix];
+        const int cy = min(max(y0 + py - SS_R, 0), P.h - 1), cx = min(max(x0 + px - SS_R, 0), P.w - 1);  // replicate, inside the crop
+        const int xi = (P.xy0 + cy) * P.xW + P.xx0 + cx;
+        sx[i] = make_float4(xb[xi], xb[xi + xplane], xb[xi + 2 * xplane], 0.f);
+        if (P.y_const) {
+            sy[i] = make_float4(P.y_rgb[0], P.y_rgb[1], P.y_rgb[2], 0.f);
+        } else {
+            const float* yb = y + P.y_off;
+            const int yplane = P.yH * P.yW, yi = (P.yy0 + cy) * P.yW + P.yx0 + cx;
+            sy[i] = make_float4(yb[yi], yb[yi + yplane], yb[yi + 2 * yplane], 0.f);
+        }
     }
     if (threadIdx.x < 121) sw[threadIdx.x] = window[threadIdx.x];
     __syncthreads();
@@ -477,8 +467,8 @@ __global__ __launch_bounds__(256) void ssim_kernel(const float4* __restrict__ x,
                 s12[ch] = fmaf(w, av[ch] * cv[ch], s12[ch]);
             }
         }
-    float v = 0.f;
-    if (y0 + ly < H && x0 + lx < W) {
+    float v = 0.f, sq = 0.f, l2 = 0.f, li = 0.f, de = 0.f;
+    if (y0 + ly < P.h && x0 + lx < P.w) {
         const float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f;
 #pragma unroll
         for (int ch = 0; ch < 3; ++ch) {
@@ -486,9 +476,26 @@ __global__ __launch_bounds__(256) void ssim_kernel(const float4* __restrict__ x,
             v += ((2.f * m12 + C1) * (2.f * (s12[ch] - m12) + C2)) /
                  ((m11 + m22 + C1) * ((s11[ch] - m11) + (s22[ch] - m22) + C2));
         }
+        const float4 a = sx[(ly + SS_R) * SS_P + lx + SS_R], b = sy[(ly + SS_R) * SS_P + lx + SS_R];
+        const float dx = a.x - b.x, dy = a.y - b.y, dz = a.z - b.z;
+        sq = dx * dx + dy * dy + dz * dz;
+        l2 = sqrtf(sq);
+        li = fmaxf(fabsf(dx), fmaxf(fabsf(dy), fabsf(dz)));
+        float L1, A1, B1, L2, A2, B2;
+        rgb_to_lab(a.x, a.y, a.z, L1, A1, B1);
+        rgb_to_lab(b.x, b.y, b.z, L2, A2, B2);
+        de = ciede2000<false>(L1, A1, B1, L2, A2, B2).de;
     }
-    const float s = block_sum(v, red);
-    if (threadIdx.x == 0) partial[((size_t)b * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = s;
+    const float s0 = block_sum(sq, red), s1 = block_sum(v, red), s2 = block_sum(l2, red), s3 = block_sum(li, red),
+                s4 = block_sum(de, red);
+    if (threadIdx.x == 0) {
+        float* o = partial + (size_t)tile * 5;
+        o[0] = s0;
+        o[1] = s1;
+        o[2] = s2;
+        o[3] = s3;
+        o[4] = s4;
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -644,18 +651,10 @@ int spaa_train_loss_fwd_bwd(const float* infer, const float* target, const float
     return (int)hipGetLastError();
 }
 
-int spaa_img_dists(const float* x, const float* y, float* partial, int npix, spaa_stream_t stream) {
-    if (!x || !y || !partial || npix < 1) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(img_dists_kernel, dim3((npix + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const float4*)x,
-                       (const float4*)y, partial, npix);
-    return (int)hipGetLastError();
-}
-
-int spaa_ssim(const float* x, const float* y, const float* window, float* partial, int B, int H, int W,
-              spaa_stream_t stream) {
-    if (!x || !y || !window || !partial || B < 1 || H < 1 || W < 1 || B > 65535) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(ssim_kernel, dim3((W + SS_T - 1) / SS_T, (H + SS_T - 1) / SS_T, B), dim3(256), 0,
-                       (hipStream_t)stream, (const float4*)x, (const float4*)y, window, partial, H, W);
+int spaa_img_stats(const float* x, const float* y, const spaa_img_pair_t* pairs, const int32_t* tile_pair, int ntiles,
+                   const float* window, float* partial, spaa_stream_t stream) {
+    if (!x || !pairs || !tile_pair || !window || !partial || ntiles < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(img_stats_kernel, dim3(ntiles), dim3(256), 0, (hipStream_t)stream, x, y, pairs, tile_pair, window, partial);
     return (int)hipGetLastError();
 }
 

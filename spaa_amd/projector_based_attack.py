@@ -14,6 +14,7 @@ with the reference values as defaults.  Differences in *mechanism*, not in resul
 """
 import warnings
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -562,3 +563,241 @@ def run_projector_based_attack(cfg, *, models=None, classifiers=None, iters=50):
                 io.save_imgs(torch.cat((cam_tar, cam_untar), 0), join(setup_path, 'cam/infer/adv', folder))
                 io.save_imgs(torch.cat((prj_tar, prj_untar), 0), join(setup_path, 'prj/adv', folder))
     return cfg
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# The summary step (projector_based_attack.py:417-614): success rates and image metrics of every attack configuration of a setup.
+SUMMARY_STEALTH_LOSSES = ['caml2', 'camdE', 'camdE_caml2', '-']
+SUMMARY_D_THRESHES = [5, 7, 9, 11, '-']
+SUMMARY_CLASSIFIERS = ['inception_v3', 'resnet18', 'vgg16']
+SUMMARY_CHUNK = 64   # images per classifier launch in the summary (the last chunk is padded: one engine geometry per image size)
+_PHASES = ['Valid', 'prj', 'infer', 'real']
+_METRICS = ['PSNR', 'RMSE', 'SSIM', 'L2', 'Linf', 'dE']
+SUMMARY_COLUMNS = (['Setup', 'Attacker', 'Stealth_loss', 'd_thr', 'Classifier', 'T.top-1_infer', 'T.top-5_infer', 'T.top-1_real',
+                    'T.top-5_real', 'U.top-1_infer', 'U.top-1_real'] + [_PHASES[0] + '_' + m for m in _METRICS] +
+                   [f'{g}.{x}_{m}' for g in ('T', 'U', 'All') for x in _PHASES[1:] for m in _METRICS])
+
+
+def attack_success(idx_infer, idx_real, idx_scene, target_idx):
+    """projector_based_attack.py:493-506: (T.top-1_infer, T.top-5_infer, T.top-1_real, T.top-5_real, U.top-1_infer, U.top-1_real)
+    from class indices sorted by descending probability ([n + 1, >= 5]: rows 0..n-1 the targeted attacks on `target_idx`, row n
+    the untargeted one) and the scene's (`idx_scene[0, 0]` is its top-1).  Targeted rates are fractions, untargeted flags 0/1."""
+    n = len(target_idx)
+    idx_infer, idx_real, idx_scene = np.asarray(idx_infer), np.asarray(idx_real), np.asarray(idx_scene)
+    t1_infer = np.count_nonzero(idx_infer[:n, 0] == target_idx) / n
+    t5_infer = np.count_nonzero([target_idx[i] in idx_infer[i, :5] for i in range(n)]) / n
+    t1_real = np.count_nonzero(idx_real[:n, 0] == target_idx) / n
+    t5_real = np.count_nonzero([target_idx[i] in idx_real[i, :5] for i in range(n)]) / n
+    true_idx = idx_scene[0, 0]
+    return (t1_infer, t5_infer, t1_real, t5_real, int(np.count_nonzero(idx_infer[n, 0] != true_idx)),
+            int(np.count_nonzero(idx_real[n, 0] != true_idx)))
+
+
+def write_stats(table, path):
+    """The reference's table files: tab-separated, 4 decimals (stats.txt, stats_all.txt)."""
+    table.to_csv(path, index=False, float_format='%.4f', sep='\t')
+
+
+def _sorted_classes(classifier, ims, crop_sz, chunk=None):
+    """Class indices sorted by descending softmax probability (classifier.py:64-72) of every image of `ims` (a list of [b,3,H,W]
+    tensors): images of one size go through the classifier in equal chunks of at most SUMMARY_CHUNK, the last one padded with
+    zeros (one engine geometry per size)."""
+    chunk = chunk or SUMMARY_CHUNK
+    out = [None] * len(ims)
+    by_shape = {}
+    for k, t in enumerate(ims):
+        by_shape.setdefault(tuple(t.shape[1:]), []).append(k)
+    for shape, ks in by_shape.items():
+        stack = torch.cat([ims[k] for k in ks])
+        b = -(-stack.shape[0] // -(-stack.shape[0] // chunk))   # (the fewest chunks of at most `chunk`, padding < their number)
+        probs = []
+        for s in range(0, stack.shape[0], b):
+            part = stack[s:s + b]
+            m = part.shape[0]
+            if m < b:
+                part = torch.cat((part, part.new_zeros(b - m, *shape)))
+            with torch.no_grad():
+                raw = classifier(part, crop_sz)[0]
+                probs.append(torch.softmax(raw.detach(), dim=1)[:m].cpu())
+        idx = torch.cat(probs).sort(descending=True)[1].numpy()
+        a = 0
+        for k in ks:
+            out[k] = idx[a:a + ims[k].shape[0]]
+            a += ims[k].shape[0]
+    return out
+
+
+def _nonempty(d):
+    import os
+    return os.path.exists(d) and len(os.listdir(d)) > 0
+
+
+def summarize_single_attacker(attacker_name, data_root, setup_list, device='cuda', device_ids=[0], *, classifiers=None):
+    """projector_based_attack.py:417-574: per setup, one row per attack configuration (stealth loss x d_thr x classifier) of
+    `attacker_name` found on disk -- targeted top-1 / top-5 and untargeted top-1 success of the inferred and the real
+    camera-captured attacks, and PSNR / RMSE / SSIM / L2 / L_inf / dE2000 of the projector images (vs the grey illumination), the
+    inferred and the captured images (centre-cropped, vs the centre-cropped scene) over the targeted (T), untargeted (U) and all
+    (All) attacks; <setup>/ret/<attacker_cfg_str>/stats.txt as the reference writes it.  Returns the last setup's DataFrame.
+
+    `classifiers`: classifier name -> spaa_amd.Classifier (the reference builds them from downloaded weights); a configuration
+    present on disk whose classifier is not given raises ValueError.  Differences from the reference:
+      * a missing or empty folder skips that configuration only (the reference leaves the classifier loop at the first one);
+      * the Valid_* columns are NaN, with a note, when the validation inferences are not on disk (this project's trainers do not
+        write */infer/test);
+      * no montages and no stats.xlsx (neither cv2 nor an Excel engine is a dependency).
+    Mechanism: all images of a setup are loaded at once, each classifier sees them in chunks of SUMMARY_CHUNK, and every image
+    metric of the setup comes from ONE metrics.img_stats launch, grouped on the host with metrics.dists_from_sums."""
+    import itertools
+    import os
+    from os.path import join
+    import pandas as pd
+    from . import io
+    from . import metrics as M
+    from .classifier import load_imagenet_labels
+    if attacker_name not in ATTACKERS:
+        raise ValueError(f'{attacker_name} not supported!')
+    device = torch.device(device)
+    attacker_cfg_str, model_cfg_str = to_attacker_cfg_str(attacker_name)
+    dl_based = attacker_name in ('SPAA', 'PerC-AL+CompenNet++')
+    n = 10   # 10 targeted attacks and 1 untargeted attack
+    target_labels = load_imagenet_labels(join(data_root, 'imagenet10_clsidx_to_labels.txt'))
+    target_idx = list(dict(itertools.islice(target_labels.items(), n)).keys())
+    table = pd.DataFrame(columns=SUMMARY_COLUMNS)
+    for setup_name in setup_list:
+        setup_path = join(data_root, 'setups', setup_name)
+        print(f'\nCalculating stats of [{attacker_name}] on [{setup_path}]')
+        setup_info = io.load_setup_info(setup_path)
+        cp_sz = tuple(setup_info['classifier_crop_sz'])
+        gray = float(setup_info['prj_brightness'])
+        cam_scene = io.torch_imread(join(setup_path, 'cam/raw/ref/img_0002.png')).to(device)
+
+        cfgs = []   # (stealth_loss, d_thr, classifier_name, prj_adv_path, cam_real_path, cam_infer_path)
+        for stealth_loss, d_thr, classifier_name in itertools.product(SUMMARY_STEALTH_LOSSES, SUMMARY_D_THRESHES, SUMMARY_CLASSIFIERS):
+            folder = join(attacker_cfg_str, stealth_loss, str(d_thr), classifier_name)
+            dirs = [join(setup_path, 'prj/adv', folder), join(setup_path, 'cam/raw/adv', folder)]
+            if dl_based:
+                dirs.append(join(setup_path, 'cam/infer/adv', folder))
+            missing = next((d for d in dirs if not _nonempty(d)), None)
+            if missing is not None:
+                print(f'No such folder/images: {missing}\n'
+                      f'Maybe [{attacker_name}] has no [{join(stealth_loss, str(d_thr), classifier_name)}] attack cfg, or you forget '
+                      'to project and capture.\n')
+                continue
+            cfgs.append((stealth_loss, d_thr, classifier_name, *dirs))
+        no_clf = sorted({c[2] for c in cfgs if c[2] not in (classifiers or {})}, key=SUMMARY_CLASSIFIERS.index)
+        if no_clf:
+            raise ValueError(f'summarize_single_attacker: [{setup_name}] has attack results for {no_clf}: pass classifiers={{name: '
+                             'spaa_amd.Classifier} for them (weights cannot be downloaded here)')
+
+        prj = [io.torch_imread_mt(c[3]).to(device) for c in cfgs]
+        real = [io.torch_imread_mt(c[4]).to(device) for c in cfgs]
+        infer = [io.torch_imread_mt(c[5]).to(device) for c in cfgs] if dl_based else real
+        for c, p, r, i in zip(cfgs, prj, real, infer):
+            if not p.shape[0] == r.shape[0] == i.shape[0] > n:
+                raise ValueError(f'{join(*map(str, c[:3]))}: expected the same number (> {n}) of prj / cam images, got '
+                                 f'{p.shape[0]} / {r.shape[0]} / {i.shape[0]}')
+
+        # classification: per classifier, the scene and every inferred / captured image of its configurations
+        idx = {}   # (config, 'scene' / 'infer' / 'real') -> sorted class indices
+        for cname in SUMMARY_CLASSIFIERS:
+            ks = [k for k, c in enumerate(cfgs) if c[2] == cname]
+            if not ks:
+                continue
+            clf = classifiers[cname]
+            ims = [cam_scene[None]] + [infer[k] for k in ks] + ([real[k] for k in ks] if dl_based else [])
+            res = _sorted_classes(clf, ims, cp_sz)
+            for j, k in enumerate(ks):
+                idx[k, 'scene'] = res[0]
+                idx[k, 'infer'] = res[1 + j]
+                idx[k, 'real'] = res[1 + len(ks) + j] if dl_based else res[1 + j]
+
+        # image metrics: one launch over every pair of the setup
+        xs, ys, pairs, spans = [], [cam_scene.reshape(-1)], [], {}
+        xoff, yoff = 0, cam_scene.numel()
+
+        def add(key, x, ps_fn):
+            nonlocal xoff
+            ps = ps_fn(xoff)
+            xs.append(x.reshape(-1))
+            xoff += x.numel()
+            spans[key] = list(range(len(pairs), len(pairs) + len(ps)))
+            pairs.extend(ps)
+
+        for k in range(len(cfgs)):
+            add((k, 'prj'), prj[k], lambda o, t=prj[k]: M.stack_pairs(t.shape[0], t.shape[-2:], x_off=o, rgb=(gray,) * 3))
+            for kind, t in (('infer', infer[k]), ('real', real[k])) if dl_based else (('real', real[k]),):
+                add((k, kind), t, lambda o, t=t: M.stack_pairs(t.shape[0], t.shape[-2:], cam_scene.shape[-2:], crop=cp_sz, x_off=o,
+                                                                  y_off=0, y_step=0))
+            if not dl_based:
+                spans[k, 'infer'] = spans[k, 'real']
+        valid = None
+        if attacker_name == 'One-pixel_DE':
+            valid = (0,) * 6
+        else:
+            if attacker_name == 'SPAA':
+                vx, vy, vcrop = join(setup_path, 'cam/infer/test', model_cfg_str), join(setup_path, 'cam/raw/test'), cp_sz
+            else:
+                vx, vy, vcrop = join(setup_path, 'prj/infer/test', model_cfg_str), join(data_root, 'prj_share/test'), None
+            if _nonempty(vx) and _nonempty(vy):
+                a, b = io.torch_imread_mt(vx).to(device), io.torch_imread_mt(vy).to(device)
+                if a.shape[0] != b.shape[0]:
+                    raise ValueError(f'{vx} and {vy} hold {a.shape[0]} and {b.shape[0]} images')
+                add('valid', a, lambda o: M.stack_pairs(a.shape[0], a.shape[-2:], b.shape[-2:], crop=vcrop, x_off=o, y_off=yoff))
+                ys.append(b.reshape(-1))
+            else:
+                print(f'No validation inferences ({vx} and {vy}): the Valid_* columns are NaN')
+                valid = (float('nan'),) * 6
+        if pairs:
+            with _lib.on_device(device):
+                sums, npix = M.img_stats(torch.cat(xs), torch.cat(ys), pairs)
+        if valid is None:
+            valid = M.dists_from_sums(sums, npix, spans['valid'])
+
+        rows = []
+        for k, (stealth_loss, d_thr, cname, *_) in enumerate(cfgs):
+            groups = [M.dists_from_sums(sums, npix, spans[k, kind][sel]) for sel in (slice(0, n), slice(n, n + 1), slice(None))
+                      for kind in ('prj', 'infer', 'real')]
+            rows.append([setup_name, attacker_cfg_str, stealth_loss, d_thr, cname,
+                         *attack_success(idx[k, 'infer'], idx[k, 'real'], idx[k, 'scene'], target_idx), *valid,
+                         *itertools.chain.from_iterable(groups)])
+        table = pd.DataFrame(rows, columns=SUMMARY_COLUMNS) if rows else pd.DataFrame(columns=SUMMARY_COLUMNS)
+
+        print(f'\n-------------------- [{attacker_name}] results on [{setup_name}] --------------------')
+        print(table.to_string(index=False, float_format='%.4f'))
+        print('-------------------------------------- End of result table ---------------------------\n')
+        ret_path = join(setup_path, 'ret', attacker_cfg_str)
+        os.makedirs(ret_path, exist_ok=True)
+        write_stats(table, join(ret_path, 'stats.txt'))
+    return table
+
+
+def summarize_all_attackers(attacker_names, data_root, setup_list, recreate_stats_and_imgs=False, *, classifiers=None):
+    """projector_based_attack.py:577-614: concatenate <setup>/ret/<attacker_cfg_str>/stats.txt of every setup and attacker
+    (recreated first by summarize_single_attacker when `recreate_stats_and_imgs`), and the pivot table of the SPAA paper's
+    Table 1 (supplementary Table 2).  Writes <data_root>/setups/stats_all.txt and pivot_table_all.txt (tab-separated, 4
+    decimals; the reference's .xlsx copies are not written: no Excel engine is a dependency).  Returns (table, pivot_table)."""
+    import warnings
+    from os.path import join
+    import pandas as pd
+    table = []
+    for setup_name in setup_list:
+        setup_path = join(data_root, 'setups', setup_name)
+        for attacker_name in attacker_names:
+            attacker_cfg_str = to_attacker_cfg_str(attacker_name)[0]
+            ret_path = join(setup_path, 'ret', attacker_cfg_str)
+            print(f'\nGathering stats of {ret_path}')
+            if recreate_stats_and_imgs:
+                summarize_single_attacker(attacker_name=attacker_name, data_root=data_root, setup_list=[setup_name],
+                                          classifiers=classifiers)
+            table.append(pd.read_csv(join(ret_path, 'stats.txt'), index_col=None, header=0, sep='\t'))
+    table = pd.concat(table, axis=0, ignore_index=True)
+    with warnings.catch_warnings():
+        warnings.simplefilter('ignore', FutureWarning)   # (pandas' note on aggfunc=np.mean: the reference's call is kept as it is)
+        pivot_table = pd.pivot_table(table, values=['T.top-1_real', 'T.top-5_real', 'U.top-1_real', 'T.real_L2', 'T.real_Linf',
+                                                    'T.real_dE', 'T.real_SSIM', 'All.real_L2', 'All.real_Linf', 'All.real_dE',
+                                                    'All.real_SSIM'],
+                                     index=['Attacker', 'd_thr', 'Stealth_loss', 'Classifier'], aggfunc=np.mean, sort=False)
+    pivot_table = pivot_table.sort_index(level=[0, 1], ascending=[False, True])   # to match SPAA Table order
+    write_stats(table, join(data_root, 'setups/stats_all.txt'))
+    pivot_table.to_csv(join(data_root, 'setups/pivot_table_all.txt'), float_format='%.4f', sep='\t', index=True)
+    return table, pivot_table
