@@ -464,6 +464,9 @@ int spaa_avgpool_bwd(const float* g_out, const float* act, float* g_in, int B, i
 
 /* Generic NHWC pooling of the VGG-16 / Inception-v3 bodies (C % 4 == 0); `*_cstride/_coff` address a channel window
  * of a concatenated buffer; backward passes are deterministic gathers with an optional ReLU gate of the input.
+ * Geometry, as torch's pooling: the input covers one padded window (Hin + 2p >= k, Win + 2p >= k), 2p <= k, and
+ * Hout = floor((Hin + 2p - k) / s) + 1 (likewise Wout); anything else is refused.  Max pooling takes k <= 11: the arg-max byte
+ * holds the window offset ky * k + kx in bits 0-6 (at most 120) and "maximum > 0" in bit 7.  avg_pool2d takes k <= 15.
  * NaN contract: the stand-alone pool propagates a NaN of its input ("NaN wins", like ATen's max_pool2d).  Every ReLU epilogue of this
  * library is fmaxf(v, 0), which maps a NaN pre-activation to 0 -- in the separate conv + ReLU launch exactly as in the fused
  * conv + ReLU + 2 x 2 pool epilogue (spaa_tapconv_h16p, bit 6) -- so the two forms of a conv -> ReLU -> pool chain agree on every input,

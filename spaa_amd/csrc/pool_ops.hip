@@ -120,9 +120,7 @@ __global__ void maxpool_bwd_quad_kernel(const T* __restrict__ g_out, const uchar
     }
 }
 
-// CK/CS/CP > 0: kernel / stride / padding known at compile time (3 / 2 / 1: the ResNet stem pool in fp16 storage -- the runtime
-// divisions of the generic form cost more than the loads)
-template <typename T, int CK = 0, int CS = 0, int CP = 0>
+template <typename T>
 __global__ void maxpool_bwd_kernel(const T* __restrict__ g_out, const uchar4* __restrict__ argmax,
                                    const int relu_gate, T* __restrict__ g_in, Geo g,
                                    int gout_c4stride, int gout_c4off) {
@@ -134,43 +132,9 @@ __global__ void maxpool_bwd_kernel(const T* __restrict__ g_out, const uchar4* __
     r /= g.Win;
     const int iy = r % g.Hin;
     const int b = r / g.Hin;
-    const int K = CK ? CK : g.k, S = CS ? CS : g.s, P = CK ? CP : g.p;
+    const int K = g.k, S = g.s, P = g.p;
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
     const unsigned char need = relu_gate ? 0x80 : 0x00;  // relu_gate: only windows whose maximum is positive pass
-    if constexpr (CK == 3 && CS == 2 && CP == 1) {
-        // branch-free (classifier_ops.hip: maxpool_bwd_kernel): the two candidate output rows / columns, four unconditional loads
-        int oyc[2], kyc[2], oxc[2], kxc[2];
-        bool yok[2], xok[2];
-        if (iy & 1) { oyc[0] = (iy + 1) >> 1; kyc[0] = 0; oyc[1] = (iy - 1) >> 1; kyc[1] = 2; yok[0] = oyc[0] < g.Hout; yok[1] = true; }
-        else        { oyc[0] = iy >> 1; kyc[0] = 1; oyc[1] = 0; kyc[1] = 0; yok[0] = oyc[0] < g.Hout; yok[1] = false; }
-        if (ix & 1) { oxc[0] = (ix + 1) >> 1; kxc[0] = 0; oxc[1] = (ix - 1) >> 1; kxc[1] = 2; xok[0] = oxc[0] < g.Wout; xok[1] = true; }
-        else        { oxc[0] = ix >> 1; kxc[0] = 1; oxc[1] = 0; kxc[1] = 0; xok[0] = oxc[0] < g.Wout; xok[1] = false; }
-        uchar4 am[4];
-        f4 gv[4];
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const size_t opix = ((size_t)b * g.Hout + (yok[i] ? oyc[i] : 0)) * g.Wout + (xok[j] ? oxc[j] : 0);
-                am[2 * i + j] = argmax[opix * g.C4 + c];
-                gv[2 * i + j] = io4<T>::ld(g_out, 4 * (opix * gout_c4stride + gout_c4off + c));
-            }
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const bool ok = yok[i] && xok[j];
-                const unsigned char kk = (unsigned char)(kyc[i] * 3 + kxc[j]);
-                const uchar4 a = am[2 * i + j];
-                const f4 go = gv[2 * i + j];
-                if (ok && (a.x & 0x7f) == kk && (a.x & need) == need) acc.x += go.x;
-                if (ok && (a.y & 0x7f) == kk && (a.y & need) == need) acc.y += go.y;
-                if (ok && (a.z & 0x7f) == kk && (a.z & need) == need) acc.z += go.z;
-                if (ok && (a.w & 0x7f) == kk && (a.w & need) == need) acc.w += go.w;
-            }
-        io4<T>::st(g_in, 4 * (size_t)idx, f4{acc.x, acc.y, acc.z, acc.w});
-        return;
-    }
     for (int ky = 0; ky < K; ++ky) {
         const int t = iy + P - ky;
         if (t < 0 || (t % S)) continue;
@@ -408,8 +372,12 @@ __global__ __launch_bounds__(256) void maxpool2x2_bwd_kernel(const T* __restrict
 
 inline int nb(int64_t n) { return (int)((n + 255) / 256); }
 
-inline bool geo_ok(int B, int Hin, int Win, int C, int Hout, int Wout, int k, int s, int p) {
-    return B > 0 && Hin > 0 && Win > 0 && C > 0 && !(C & 3) && k > 0 && k <= 15 && s > 0 && p >= 0 && 2 * p <= k &&
+// The input must cover one padded window (Hin + 2p >= k: C's division truncates toward zero, so a shorter input would pass the
+// output-size test with Hout = 1).  Max pooling takes k <= 11: the arg-max byte keeps the window offset ky * k + kx in bits 0-6,
+// and 11 * 11 - 1 = 120 is the largest that fits beside the sign flag in bit 7.
+inline bool geo_ok(int B, int Hin, int Win, int C, int Hout, int Wout, int k, int s, int p, bool maxpool) {
+    return B > 0 && Hin > 0 && Win > 0 && C > 0 && !(C & 3) && k > 0 && k <= (maxpool ? 11 : 15) && s > 0 && p >= 0 &&
+           2 * p <= k && Hin + 2 * p >= k && Win + 2 * p >= k &&
            Hout == (Hin + 2 * p - k) / s + 1 && Wout == (Win + 2 * p - k) / s + 1 &&
            (int64_t)B * Hin * Win * C < ((int64_t)1 << 31);
 }
@@ -420,7 +388,7 @@ extern "C" {
 
 int spaa_maxpool_fwd(const float* in, float* out, uint8_t* argmax, int B, int Hin, int Win, int C, int Hout, int Wout,
                      int k, int s, int p, int out_cstride, int out_coff, spaa_stream_t stream) {
-    if (!in || !out || !argmax || !geo_ok(B, Hin, Win, C, Hout, Wout, k, s, p) || (out_cstride & 3) || (out_coff & 3) ||
+    if (!in || !out || !argmax || !geo_ok(B, Hin, Win, C, Hout, Wout, k, s, p, true) || (out_cstride & 3) || (out_coff & 3) ||
         out_coff + C > out_cstride)
         return hipErrorInvalidValue;
     Geo g{B, Hin, Win, C / 4, Hout, Wout, k, s, p};
@@ -437,7 +405,7 @@ int spaa_maxpool_fwd(const float* in, float* out, uint8_t* argmax, int B, int Hi
 
 int spaa_maxpool_fwd_f16(const void* in, void* out, uint8_t* argmax, int B, int Hin, int Win, int C, int Hout, int Wout,
                          int k, int s, int p, int out_cstride, int out_coff, spaa_stream_t stream) {
-    if (!in || !out || !argmax || !geo_ok(B, Hin, Win, C, Hout, Wout, k, s, p) || (out_cstride & 3) || (out_coff & 3) ||
+    if (!in || !out || !argmax || !geo_ok(B, Hin, Win, C, Hout, Wout, k, s, p, true) || (out_cstride & 3) || (out_coff & 3) ||
         out_coff + C > out_cstride)
         return hipErrorInvalidValue;
     Geo g{B, Hin, Win, C / 4, Hout, Wout, k, s, p};
@@ -456,7 +424,7 @@ int spaa_maxpool_fwd_f16(const void* in, void* out, uint8_t* argmax, int B, int 
 int spaa_maxpool_bwd(const float* g_out, const uint8_t* argmax, int relu_gate, float* g_in, int B, int Hin,
                      int Win, int C, int Hout, int Wout, int k, int s, int p, int gout_cstride, int gout_coff,
                      spaa_stream_t stream) {
-    if (!g_out || !argmax || !g_in || !geo_ok(B, Hin, Win, C, Hout, Wout, k, s, p) || (gout_cstride & 3) ||
+    if (!g_out || !argmax || !g_in || !geo_ok(B, Hin, Win, C, Hout, Wout, k, s, p, true) || (gout_cstride & 3) ||
         (gout_coff & 3) || gout_coff + C > gout_cstride)
         return hipErrorInvalidValue;
     Geo g{B, Hin, Win, C / 4, Hout, Wout, k, s, p};
@@ -474,7 +442,7 @@ int spaa_maxpool_bwd(const float* g_out, const uint8_t* argmax, int relu_gate, f
 int spaa_maxpool_bwd_f16(const void* g_out, const uint8_t* argmax, int relu_gate, void* g_in, int B, int Hin, int Win,
                          int C, int Hout, int Wout, int k, int s, int p, int gout_cstride, int gout_coff,
                          spaa_stream_t stream) {
-    if (!g_out || !argmax || !g_in || !geo_ok(B, Hin, Win, C, Hout, Wout, k, s, p) || (gout_cstride & 3) ||
+    if (!g_out || !argmax || !g_in || !geo_ok(B, Hin, Win, C, Hout, Wout, k, s, p, true) || (gout_cstride & 3) ||
         (gout_coff & 3) || gout_coff + C > gout_cstride)
         return hipErrorInvalidValue;
     Geo g{B, Hin, Win, C / 4, Hout, Wout, k, s, p};
@@ -498,7 +466,7 @@ int spaa_maxpool_bwd_f16(const void* g_out, const uint8_t* argmax, int relu_gate
 
 int spaa_avgpool2d_fwd(const float* in, float* out, int B, int Hin, int Win, int C, int Hout, int Wout, int k, int s,
                        int p, int out_cstride, int out_coff, spaa_stream_t stream) {
-    if (!in || !out || !geo_ok(B, Hin, Win, C, Hout, Wout, k, s, p) || (out_cstride & 3) || (out_coff & 3) ||
+    if (!in || !out || !geo_ok(B, Hin, Win, C, Hout, Wout, k, s, p, false) || (out_cstride & 3) || (out_coff & 3) ||
         out_coff + C > out_cstride)
         return hipErrorInvalidValue;
     Geo g{B, Hin, Win, C / 4, Hout, Wout, k, s, p};
@@ -509,7 +477,7 @@ int spaa_avgpool2d_fwd(const float* in, float* out, int B, int Hin, int Win, int
 
 int spaa_avgpool2d_fwd_f16(const void* in, void* out, int B, int Hin, int Win, int C, int Hout, int Wout, int k, int s,
                            int p, int out_cstride, int out_coff, spaa_stream_t stream) {
-    if (!in || !out || !geo_ok(B, Hin, Win, C, Hout, Wout, k, s, p) || (out_cstride & 3) || (out_coff & 3) ||
+    if (!in || !out || !geo_ok(B, Hin, Win, C, Hout, Wout, k, s, p, false) || (out_cstride & 3) || (out_coff & 3) ||
         out_coff + C > out_cstride)
         return hipErrorInvalidValue;
     Geo g{B, Hin, Win, C / 4, Hout, Wout, k, s, p};
@@ -520,7 +488,7 @@ int spaa_avgpool2d_fwd_f16(const void* in, void* out, int B, int Hin, int Win, i
 
 int spaa_avgpool2d_bwd(const float* g_out, float* g_in, int B, int Hin, int Win, int C, int Hout, int Wout, int k,
                        int s, int p, int gout_cstride, int gout_coff, spaa_stream_t stream) {
-    if (!g_out || !g_in || !geo_ok(B, Hin, Win, C, Hout, Wout, k, s, p) || (gout_cstride & 3) || (gout_coff & 3) ||
+    if (!g_out || !g_in || !geo_ok(B, Hin, Win, C, Hout, Wout, k, s, p, false) || (gout_cstride & 3) || (gout_coff & 3) ||
         gout_coff + C > gout_cstride)
         return hipErrorInvalidValue;
     Geo g{B, Hin, Win, C / 4, Hout, Wout, k, s, p};
@@ -531,7 +499,7 @@ int spaa_avgpool2d_bwd(const float* g_out, float* g_in, int B, int Hin, int Win,
 
 int spaa_avgpool2d_bwd_f16(const void* g_out, void* g_in, int B, int Hin, int Win, int C, int Hout, int Wout, int k,
                            int s, int p, int gout_cstride, int gout_coff, spaa_stream_t stream) {
-    if (!g_out || !g_in || !geo_ok(B, Hin, Win, C, Hout, Wout, k, s, p) || (gout_cstride & 3) || (gout_coff & 3) ||
+    if (!g_out || !g_in || !geo_ok(B, Hin, Win, C, Hout, Wout, k, s, p, false) || (gout_cstride & 3) || (gout_coff & 3) ||
         gout_coff + C > gout_cstride)
         return hipErrorInvalidValue;
     Geo g{B, Hin, Win, C / 4, Hout, Wout, k, s, p};
