@@ -11,6 +11,10 @@ timed step's outputs as DIR/<name>.npy (the inputs are synthetic and seeded: the
 N > 1: every rank attacks its own 64 samples (weak scaling, no data-path collective); the only exchange is the final
 result gather, timed separately (`gather_ms`).  `--gpus N` without a torchrun environment starts the N ranks itself
 (before anything touches the GPU).  Prints ONE JSON line on rank 0.
+A plain run measures the headline only (set-up, warm-up, the K timed steps, the dump, the result line).  `--full` adds everything
+else, after the timed region: the per-kernel roofline and the kernel-choice report (rank 0), the CPU baseline, and for the default
+configuration the other configurations of BASELINE.json, `spaa()` end to end and the sustained runs (`--no-cpu-baseline`,
+`--no-modes` leave parts of it out).  The timed region and the state it starts from are the same with and without `--full`.
 """
 import argparse
 import json
@@ -522,10 +526,15 @@ def main():
                          '(BASELINE.json configs[4]; an extra data point, never the headline)')
     ap.add_argument('--attack', default='spaa', choices=['spaa', 'perc_al'],
                     help='spaa (the bench line) or perc_al = PerC_AL.adversary_projector loop body (configs[4], with --classifier vgg16)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline, also measure and check everything else: per-kernel roofline, kernel-choice report, CPU '
+                         'baseline, and (default configuration) the other configurations of BASELINE.json, spaa() end to end and '
+                         'the sustained runs')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
     ap.add_argument('--no-modes', action='store_true',
-                    help='skip the extra configurations timed after the headline (f16 storage, Inception-v3, VGG-16 + PerC-AL)')
-    ap.add_argument('--profile-out', default=None, help='write the per-layer tapconv timing table (JSON) here')
+                    help='with --full: skip the extra configurations timed after the headline (f16 storage, Inception-v3, '
+                         'VGG-16 + PerC-AL, spaa() end to end, sustained runs)')
+    ap.add_argument('--profile-out', default=None, help='with --full: write the per-layer tapconv timing table (JSON) here')
     ap.add_argument('--dump-outputs', default=None, metavar='DIR',
                     help="after the timed steps, write what rank 0's last timed step computed as DIR/<name>.npy (float32, at most "
                          '64 MB in all: a fixed, seeded sample of the batch when it is larger), for output-for-output comparisons')
@@ -534,6 +543,8 @@ def main():
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error('--steps must be >= 1 and --warmup >= 0')
+    if args.profile_out and not args.full:
+        ap.error('--profile-out needs --full (the per-layer table comes from the instrumented passes)')
 
     world_env = os.environ.get('WORLD_SIZE')
     if args.gpus > 1 and world_env is None:
@@ -572,7 +583,9 @@ def main():
     torch.cuda.synchronize()
     # which conv kernel dominates?  One instrumented step (outside the timed region) tells; its launches then carry HIP events
     # INSIDE the timed region (a dozen launches per step: nothing measurable on the step time), so that the roofline's launch
-    # duration is that of the back-to-back loop the rocprofv3 summary of the same command sees
+    # duration is that of the back-to-back loop the rocprofv3 summary of the same command sees.  A plain run (no --full) reads none
+    # of it and still runs it: these two steps advance the attack state, and the events are part of the timed steps, so the timed
+    # region, its inputs and the dumped outputs are those of a --full run
     from spaa_amd import convplan
     dom_ids, timed_events = None, []
     if rank == 0:
@@ -611,10 +624,9 @@ def main():
     # the last timed step's outputs, before the instrumented passes below run further steps on the same state
     dumped = dump_outputs(step_outputs(st, args.attack), args.dump_outputs) if args.dump_outputs and rank == 0 else None
 
-    # instrumented passes: HIP events around every launch (same stream) -> per-kernel rooflines
-    from spaa_amd import convplan
+    # --full: instrumented passes, HIP events around every launch (same stream) -> per-kernel rooflines
     roof, table = None, {}
-    if rank == 0:
+    if rank == 0 and args.full:
         n_prof = 3
         per_tile, per_layer, other, t_roof_x6, t_roof_f32 = instrumented_pass(st, args, n_prof)
         tot_ms = sum(v[1] for v in per_tile.values())
@@ -734,15 +746,17 @@ def main():
         out['ranks_seen'] = {'world_size': dist.get_world_size() if dist is not None else 1,
                              'backend': dist.get_backend() if dist is not None else None,
                              'device_count': torch.cuda.device_count(), 'local_rank': local_rank}
-        try:   # kernel choices of the timed configuration that were not measured table entries (spaa_amd/tapconv_tune.json)
-            from spaa_amd import convplan as _cp
-            _tr = _cp.tune_report()
-            out['tune'] = {'borrowed_from_nearest_pixel_count': len(_tr['borrowed']), 'rule_chosen': len(_tr['untuned']),
-                           'shapes': (_tr['borrowed'] + _tr['untuned'])[:12],
-                           'note': 'layer-shape keys Cin_Cout_taps_sin_sout_M of this process, once-per-attack set-up launches included'}
-        except Exception:   # noqa: BLE001
-            pass
-        if world == 1 and not args.no_cpu_baseline and args.classifier == 'resnet18' and args.dtype == 'f32' and args.attack == 'spaa':
+        if args.full:
+            try:   # kernel choices of the timed configuration that were not measured table entries (spaa_amd/tapconv_tune.json)
+                from spaa_amd import convplan as _cp
+                _tr = _cp.tune_report()
+                out['tune'] = {'borrowed_from_nearest_pixel_count': len(_tr['borrowed']), 'rule_chosen': len(_tr['untuned']),
+                               'shapes': (_tr['borrowed'] + _tr['untuned'])[:12],
+                               'note': 'layer-shape keys Cin_Cout_taps_sin_sout_M of this process, once-per-attack set-up launches included'}
+            except Exception:   # noqa: BLE001
+                pass
+        if (args.full and world == 1 and not args.no_cpu_baseline and args.classifier == 'resnet18' and args.dtype == 'f32'
+                and args.attack == 'spaa'):
             log(f'cpu baseline on {usable_cores()} cores')
             try:
                 out['cpu_baseline'] = cpu_baseline(sd, csd, setup, scenes)
@@ -752,7 +766,7 @@ def main():
         else:
             out['cpu_baseline'] = None
         default_run = world == 1 and args.classifier == 'resnet18' and args.dtype == 'f32' and args.attack == 'spaa'
-        if default_run and not args.no_modes:
+        if default_run and args.full and not args.no_modes:
             # the other configurations of BASELINE.json, each timed like the headline after it (never part of `value`)
             log('extra modes: f16 storage, Inception-v3 (f32, f16 storage), VGG-16 + PerC-AL in f16 storage')
             del st

@@ -1,4 +1,4 @@
-"""CPU: the bench line committed under profiles/ (produced by `python bench.py` on the GPU box, tools/collect_profiles.sh)
+"""CPU: the bench line committed under profiles/ (produced by `python bench.py --full` on the GPU box, tools/collect_profiles.sh)
 carries every field of the measurement contract, and its numbers are mutually consistent."""
 import glob
 import json
@@ -97,6 +97,17 @@ def test_dump_outputs_writes_a_fixed_sample_within_budget(tmp_path):
     s3 = bench.dump_outputs(outs, str(tmp_path / 'd3'))
     assert s3['rows'] == 'all' and np.array_equal(np.load(tmp_path / 'd3' / 'a.npy'), outs['a'].numpy())
     assert bench.DUMP_BUDGET_BYTES <= 64 * 10 ** 6
+
+
+def test_profile_out_needs_full(tmp_path):
+    """The per-layer table comes from the instrumented passes, which only `--full` runs: asking a plain run for it is an error
+    (before anything touches the GPU), not a missing file."""
+    import subprocess
+    import sys
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--profile-out', str(tmp_path / 'layers.json')],
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and '--profile-out needs --full' in r.stderr and not r.stdout.strip()
+    assert not (tmp_path / 'layers.json').exists()
 
 
 def test_gpus_flag_launches_that_many_ranks():

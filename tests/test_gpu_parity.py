@@ -3829,3 +3829,29 @@ def test_bench_dump_outputs(tmp_path):
     for name in ('cam_infer', 'cam_infer_best', 'prj_adv_best'):
         a = np.load(out / f'{name}.npy')
         assert a.min() >= 0.0 and a.max() <= 1.0, name
+
+
+def test_bench_plain_run_and_full(tmp_path):
+    """A plain `bench.py` run reports the headline only; `--full` adds the per-kernel roofline, the kernel-choice report and the
+    per-layer table (fresh child processes; the CPU baseline and the extra configurations are left out here for time)."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--steps', '2', '--warmup', '1'],
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-4000:]
+    plain = json.loads(r.stdout.strip().splitlines()[-1])
+    assert plain['steps'] == 2 and plain['value'] > 0 and abs(plain['value'] - 1e3 / plain['ms_per_step']) < 0.01 * plain['value']
+    assert plain['roofline'] is None and plain['cpu_baseline'] is None
+    assert not {'tune', 'modes', 'sustained', 'configs0_gpu'} & set(plain)
+    table = tmp_path / 'layers.json'
+    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--full', '--steps', '2', '--warmup', '1', '--no-cpu-baseline',
+                        '--no-modes', '--profile-out', str(table)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-4000:]
+    full = json.loads(r.stdout.strip().splitlines()[-1])
+    assert full['steps'] == 2 and full['value'] > 0 and full['cpu_baseline'] is None and 'tune' in full
+    roof = full['roofline']
+    assert roof['bound'] == 'mfma' and 0.0 < roof['frac'] < 1.0 and roof['step']['ms_per_step'] > 0
+    with open(table) as fh:
+        assert json.load(fh)['per_layer']

@@ -8,10 +8,10 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/${TAG}_vgg_train
 mkdir -p $O
 cd $R
-python3 bench.py --classifier vgg16 --attack perc_al --dtype f16s --steps 10 --no-cpu-baseline --no-modes --profile-out $O/vgg16_percal_f16s_tapconv_layers.json > $O/vgg16_percal_f16s_bench.json 2> $O/vgg.log
+python3 bench.py --full --classifier vgg16 --attack perc_al --dtype f16s --steps 10 --no-cpu-baseline --no-modes --profile-out $O/vgg16_percal_f16s_tapconv_layers.json > $O/vgg16_percal_f16s_bench.json 2> $O/vgg.log
 echo "vgg table done"
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats -d $O/stats_vgg -o kt --output-format csv -- python3 $R/bench.py --classifier vgg16 --attack perc_al --dtype f16s --steps 10 --warmup 2 --no-cpu-baseline --no-modes > $O/vgg_under_rocprof.log 2>&1
+rocprofv3 --kernel-trace --stats -d $O/stats_vgg -o kt --output-format csv -- python3 $R/bench.py --full --classifier vgg16 --attack perc_al --dtype f16s --steps 10 --warmup 2 --no-cpu-baseline --no-modes > $O/vgg_under_rocprof.log 2>&1
 find $O/stats_vgg -name "*kernel_stats.csv" -exec cp {} $O/vgg16_percal_f16s_kernel_stats.csv \;
 echo "vgg rocprof done"
 cd $R

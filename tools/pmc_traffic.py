@@ -53,7 +53,7 @@ def main():
         out[name] = e
     with open(a.out, 'w') as fh:
         json.dump({'note': 'FETCH_SIZE x2 (gfx950 correction) + WRITE_SIZE, KiB -> bytes, averaged per launch; '
-                           'separate --pmc passes over `bench.py --steps 3 --warmup 1 --no-cpu-baseline`',
+                           'separate --pmc passes over `bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-modes`',
                    'kernels': out}, fh, indent=1)
     for k, e in sorted(out.items(), key=lambda kv: -kv[1]['hbm_bytes_per_launch'] * kv[1]['launches'])[:12]:
         print(f"{k[:60]:60s} n={e['launches']:5d} fetch={e.get('fetch_bytes_per_launch', 0) / 1e6:9.2f} MB "
