@@ -192,7 +192,7 @@ def pcnet_forward(sd, x, s, per_batch_grid=False, use_rough=True):
 def rgb2xyz(rgb):
     mt = torch.tensor([[0.4124, 0.3576, 0.1805],
                        [0.2126, 0.7152, 0.0722],
-                       [0.0193, 0.1192, 0.9504]])
+                       [0.0193, 0.1192, 0.9504]], dtype=rgb.dtype)   # (fp64 input: the whole map in fp64)
     mask1 = (rgb > 0.0405).float()
     mask1_no = 1 - mask1
     t = mask1 * (((rgb + 0.055) / 1.055) ** 2.4)

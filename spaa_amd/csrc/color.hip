@@ -210,7 +210,10 @@ __device__ __forceinline__ DE ciede2000(float L1, float A1, float B1, float L2, 
     {
         const float den = aCP7 + k25_7;
         const float aCP6 = fdiv(aCP7, aCP);
-        aCP_b += rC_b * (fdiv(0.5f, rC)) * (fdiv(k25_7, (den * den))) * 7.f * aCP6;
+        // d sqrt(f) / d f = 0.5 / sqrt(f) with f = aCP^7 / (aCP^7 + 25^7) underflowed to 0 (aCP below ~1e-5): 0.5 / 0 would
+        // give inf (or NaN against aCP6 == 0); the true derivative there is ~3.5 aCP^2.5 / 25^3.5 < 1e-16, taken as 0
+        const float r_rC = rC > 0.f ? fdiv(0.5f, rC) : 0.f;
+        aCP_b += rC_b * r_rC * (fdiv(k25_7, (den * den))) * 7.f * aCP6;
     }
     float aHP_b = dRO_b * dRO * (-2.f * (e * (1.f / 25.f)));
     aHP_b += T_b * kRad * (0.17f * fsin(t1) - 0.48f * fsin(t2) - 0.96f * fsin(t3) + 0.8f * fsin(t4));
@@ -249,7 +252,8 @@ __device__ __forceinline__ DE ciede2000(float L1, float A1, float B1, float L2, 
     if (G_b != 0.f) {
         const float den = aC7 + k25_7;
         const float aC6 = fdiv(aC7, aC);
-        aC_b = G_b * (-fdiv(0.25f, sfG)) * (fdiv(k25_7, (den * den))) * 7.f * aC6;
+        const float r_sfG = sfG > 0.f ? -fdiv(0.25f, sfG) : 0.f;   // (likewise: fG underflowed for aC below ~1e-5)
+        aC_b = G_b * r_sfG * (fdiv(k25_7, (den * den))) * 7.f * aC6;
     }
     const float C1_b = aC_b * 0.5f;
     A1_b += C1_b * (fdiv(A1, C1));
