@@ -314,6 +314,12 @@ int spaa_warp_finish_grid_bwd(const float* g_fine, const float* coarse, const fl
  * partial: ceil(Hout*Wout/256) * (6 + 2 (T+2)) floats of scratch (block sums, added in order) */
 int spaa_warp_coarse_grid_bwd(const float* g_coarse, const float* affine6, const float* theta, const float* ctrl, int T, int Hin,
                               int Win, int Hout, int Wout, float* partial, float* g_params, spaa_stream_t stream);
+/* out = gate ? sum_b g[b] + add : 0 over the first C channels of NHWC fp32 tensors with channel stride `cstride`: g [B,H,W,cstride],
+ * add / out [1,H,W,cstride] (add NULL: nothing added); gate_bits [1,H,W,cstride/4] one byte per 4 channels in the mask_out / gate_bits
+ * format above (NULL: no gate); C % 4 == 0, cstride % 4 == 0, C <= cstride.  b runs 0 .. B-1 in order, then add, then the gate (no
+ * atomics).  The gradient of a scene-only layer run once at batch 1 from the batch-B cotangents it feeds (PCNet training). */
+int spaa_batch_sum_gate_bits(const float* g, const float* add, const uint8_t* gate_bits, float* out, int B, int H, int W, int C,
+                             int cstride, spaa_stream_t stream);
 /* ---- CompenNet++ training step (train_network.py:130-232), csrc/compennet_train.hip ----------------------------
  * out[0] = (act[0] > 0) * sum_b g[b] over the first C channels of NHWC tensors with channel stride `cstride`: g [B,H,W,cstride],
  * act / out [1,H,W,cstride] (act NULL: no gate); C % 4 == 0, cstride % 4 == 0, C <= cstride.  The sum runs b = 0 .. B-1 in

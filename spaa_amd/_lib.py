@@ -83,6 +83,7 @@ _SIGNATURES = {
     'spaa_warp_finish_grid_bwd': [_p, _p, _p, _p, _p, _i, _p],
     'spaa_warp_coarse_grid_bwd': [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p],
     'spaa_batch_sum_gate': [_p, _p, _p, _i, _i, _i, _i, _i, _p],
+    'spaa_batch_sum_gate_bits': [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p],
     'spaa_warp_bwd_grid2': [_p, _p, _i, _p, _p, _i, _p, _p, _i, _i, _i, _i, _p],
     'spaa_shading_tail_fwd': [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p],
     'spaa_shading_head_bwd': [_p, _p, _p, _p, _p, _p, _i, _i, _i, _p],

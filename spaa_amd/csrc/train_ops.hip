@@ -158,6 +158,42 @@ __global__ void relu_gate_kernel(const float4* __restrict__ g, const float4* __r
     out[i] = make_float4(a.x > 0.f ? v.x : 0.f, a.y > 0.f ? v.y : 0.f, a.z > 0.f ? v.z : 0.f, a.w > 0.f ? v.w : 0.f);
 }
 
+// out[p][c] = gate[p][c] ? (sum_b g[b][p][c]) + add[p][c] : 0 for c < C: the gradient of a layer that runs once, at batch 1, on
+// an input shared by the whole batch (the scene), from the batch-B cotangents it feeds.  One thread per 4 channels of one pixel;
+// b runs 0 .. B-1 in order, `add` (a batch-1 tensor, may be NULL) joins last, then the gate: bitwise reproducible.  gate_bits
+// (may be NULL) holds one byte per 4 channels of the layout [npix][cs4] (mask_out / gate_bits of include/spaa_hip.h: bit e set
+// = channel 4 q + e passes).  g [B][npix][cstride], add / out [npix][cstride]; channels C .. cstride-1 of out are not written.
+__global__ __launch_bounds__(256) void batch_sum_gate_bits_kernel(const float4* __restrict__ g, const float4* __restrict__ add,
+                                                                  const uint8_t* __restrict__ gate_bits, float4* __restrict__ out,
+                                                                  int B, int64_t npix, int cq, int cs4) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= npix * cq) return;
+    const int64_t pix = i / cq;
+    const int64_t o = pix * cs4 + (i - pix * cq);
+    const int64_t img = npix * cs4;
+    float4 s = g[o];
+#pragma unroll 4
+    for (int b = 1; b < B; ++b) {
+        const float4 v = g[(int64_t)b * img + o];
+        s.x += v.x;
+        s.y += v.y;
+        s.z += v.z;
+        s.w += v.w;
+    }
+    if (add != nullptr) {
+        const float4 a = add[o];
+        s.x += a.x;
+        s.y += a.y;
+        s.z += a.z;
+        s.w += a.w;
+    }
+    if (gate_bits != nullptr) {
+        const unsigned m = gate_bits[o];
+        s = make_float4((m & 1u) ? s.x : 0.f, (m & 2u) ? s.y : 0.f, (m & 4u) ? s.z : 0.f, (m & 8u) ? s.w : 0.f);
+    }
+    out[o] = s;
+}
+
 __global__ void sum_rows_kernel(const float* __restrict__ partial, float* __restrict__ out, int nrows, int ncols) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= ncols) return;
@@ -218,6 +254,15 @@ int spaa_relu_gate(const float* g, const float* act, float* out, int64_t n, spaa
     if (!g || !act || !out || n < 4 || (n & 3)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(relu_gate_kernel, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const float4*)g,
                        (const float4*)act, (float4*)out, n / 4);
+    return (int)hipGetLastError();
+}
+
+int spaa_batch_sum_gate_bits(const float* g, const float* add, const uint8_t* gate_bits, float* out, int B, int H, int W, int C,
+                             int cstride, spaa_stream_t stream) {
+    if (!g || !out || B < 1 || H < 1 || W < 1 || C < 4 || (C & 3) || (cstride & 3) || C > cstride) return hipErrorInvalidValue;
+    const int64_t npix = (int64_t)H * W, n = npix * (C / 4);
+    hipLaunchKernelGGL(batch_sum_gate_bits_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       (const float4*)g, (const float4*)add, gate_bits, (float4*)out, B, npix, C / 4, cstride / 4);
     return (int)hipGetLastError();
 }
 

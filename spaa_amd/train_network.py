@@ -40,9 +40,20 @@ def _window(window_size=11, sigma=1.5):
 
 class PCNetTrainer:
     """State of one PCNet training run: engine, per-parameter Adam moments, schedules.  `step(prj_batch, cam_batch)` is one
-    iteration of the reference's loop body (train_network.py:293-357)."""
+    iteration of the reference's loop body (train_network.py:293-357).
 
-    def __init__(self, pcnet, cam_scene, batch_size, l2_reg=1e-4, lr_drop_ratio=0.2, device='cuda'):
+    Every model `train_eval_pcnet` builds by name (:476-595) trains: `use_mask` (no mask: the warped image is not masked),
+    `use_rough` (False: ShadingNetSPAA(use_rough=False), the surface branch sees the scene alone), WarpingNet `with_refine`
+    (False: no grid-refine net, its Adam group is empty) and `fix_shading_net` (the ShadingNet's parameters have
+    requires_grad=False: no weight gradients, no Adam step, their values stay as they are).
+
+    `collapse`: the layers that see only the scene (skipConv1 and, with use_rough=False, conv1_s .. conv4_s) run once, at batch 1
+    -- the scene is one image expanded to the batch (:245) -- their outputs are broadcast into the batch-B residual inputs, and
+    their gradients start from the batch sum of the cotangents they feed (spaa_batch_sum_gate_bits).  The default (None) is on for
+    every variant and off for the SPAA configuration (mask, rough input, refine net, trainable ShadingNet), whose step stays the
+    batch-B one."""
+
+    def __init__(self, pcnet, cam_scene, batch_size, l2_reg=1e-4, lr_drop_ratio=0.2, device='cuda', collapse=None):
         if not isinstance(pcnet, PCNet):
             raise TypeError('PCNetTrainer needs a spaa_amd.PCNet')
         dev = torch.device(device)
@@ -51,14 +62,17 @@ class PCNetTrainer:
         self.dev, self.pc, self.B = dev, pcnet, batch_size
         self.l2_reg, self.gamma = float(l2_reg), float(lr_drop_ratio)
         wn, sn = pcnet.warping_net, pcnet.shading_net
-        if not wn.with_refine:
-            raise NotImplementedError('training covers the SPAA configuration (WarpingNet with the grid-refine net)')
-        if not pcnet.use_rough:
-            raise NotImplementedError('training covers the SPAA configuration (use_rough=True)')
+        if wn.theta.shape[1] != wn.nctrl + 2:
+            raise NotImplementedError('training covers the reduced TPS form (T + 2 parameters) the reference uses')
+        self.refine, self.rough, self.use_mask = bool(wn.with_refine), bool(pcnet.use_rough), bool(pcnet.use_mask)
+        self.fix_shading = not any(prm.requires_grad for prm in sn.parameters())     # PCNet(fix_shading_net=True)
+        spaa_cfg = self.refine and self.rough and self.use_mask and not self.fix_shading
+        self.collapse = (not spaa_cfg) if collapse is None else bool(collapse)
         with _lib.on_device(dev):
             s = cam_scene.detach().float().to(dev)
             while s.ndim < 4:
                 s = s[None]
+            self.scene1 = to_nhwc4(s[:1].contiguous())
             self.scene4 = to_nhwc4(s.expand(batch_size, -1, -1, -1).contiguous())
             self.Hc, self.Wc = wn.out_size
             self.window = _window().to(dev)
@@ -69,14 +83,16 @@ class PCNetTrainer:
     def _build(self, wn, sn):
         dev, B = self.dev, self.B
         self.eng = None   # created at the first step (needs the projector size)
-        # parameter groups of train_network.py:247-256
+        # parameter groups of train_network.py:247-256 (a frozen ShadingNet: torch.optim.Adam skips parameters without a gradient)
         self.params = dict(self.pc.named_parameters())
         self.groups = {
             'w1': dict(names=['warping_net.affine_mat', 'warping_net.theta'], lr=1e-2, wd=0.0, milestone=100),
             'w2': dict(names=[n for n in self.params if 'warping_net.grid_refine_net' in n], lr=5e-3, wd=0.0, milestone=1200),
-            's': dict(names=[n for n in self.params if 'warping_net' not in n], lr=1e-3, wd=self.l2_reg, milestone=1800)}
-        self.m = {n: torch.zeros_like(p, device=dev) for n, p in self.params.items()}
-        self.v = {n: torch.zeros_like(p, device=dev) for n, p in self.params.items()}
+            's': dict(names=[] if self.fix_shading else [n for n in self.params if 'warping_net' not in n], lr=1e-3, wd=self.l2_reg,
+                      milestone=1800)}
+        trained = [n for g in self.groups.values() for n in g['names']]
+        self.m = {n: torch.zeros_like(self.params[n], device=dev) for n in trained}
+        self.v = {n: torch.zeros_like(self.params[n], device=dev) for n in trained}
         self.grads = {}
 
     def _make_engine(self, prj_size):
@@ -91,66 +107,89 @@ class PCNetTrainer:
             cp.attach_maps(plan, builder, mod.weight.detach().cpu())
             self.maps.append((plan, mod.weight, mod.bias if with_bias else None))
 
-        for nm, (st, pad) in _SHADING.items():
-            mod = getattr(sn, nm)
-            reg(eng.f[nm], lambda w, st=st, pad=pad: cp.conv_fwd_plan(w, None, st, pad, 'cpu'), mod, True)
-            in_ch = (3, 6) if nm == 'conv1_s' else None
-            reg(eng.d[nm], lambda w, st=st, pad=pad, in_ch=in_ch: cp.conv_dgrad_plan(w, st, pad, 'cpu', in_ch=in_ch), mod, False)
-        for nm, pad in (('transConv1', 1), ('transConv2', 0)):
-            mod = getattr(sn, nm)
-            reg(eng.f[nm], lambda w, pad=pad: cp.deconv_fwd_plan(w, None, 2, pad, 'cpu'), mod, True)
-            reg(eng.d[nm], lambda w, pad=pad: cp.deconv_dgrad_plan(w, 2, pad, 'cpu'), mod, False)
-        for key, i, pad in (('skip1a', 0, 0), ('skip1b', 2, 1), ('skip1c', 4, 1)):
-            reg(eng.f[key], lambda w, pad=pad: cp.conv_fwd_plan(w, None, 1, pad, 'cpu'), sn.skipConv1[i], True)
-        # weight-gradient plans: only the geometry matters (taps / classes / packing layout), built once; transposed
-        # convolutions unfolded (one weight matrix per output-parity class)
-        self.wg = {}
-        for nm, (st, pad) in _SHADING.items():
-            self.wg[nm] = self._wg_plan(getattr(sn, nm), lambda w, st=st, pad=pad: cp.conv_fwd_plan(w, None, st, pad, 'cpu'))
-        for nm, pad in (('transConv1', 1), ('transConv2', 0)):
-            self.wg[nm] = self._wg_plan(getattr(sn, nm), lambda w, pad=pad: cp.deconv_fwd_plan(w, None, 2, pad, 'cpu', fold=False))
-        for key, i, pad in (('skip1a', 0, 0), ('skip1b', 2, 1), ('skip1c', 4, 1)):
-            self.wg[key] = self._wg_plan(sn.skipConv1[i], lambda w, pad=pad: cp.conv_fwd_plan(w, None, 1, pad, 'cpu'))
-        # input-gradient plans of the two inner skipConv1 layers (the attack never needs them: skipConv1 sees the scene only)
-        self.skip_d = {}
-        for key, i in (('skip1b', 2), ('skip1c', 4)):
-            mod = sn.skipConv1[i]
-            pl = cp.conv_dgrad_plan(mod.weight, 1, 1, dev, key + '_dgrad')
-            reg(pl, lambda w: cp.conv_dgrad_plan(w, 1, 1, 'cpu'), mod, False)
-            self.skip_d[key] = pl
+        self.wg, self.skip_d, self.sd = {}, {}, {}
+        if not self.fix_shading:   # (a frozen ShadingNet keeps the packed weights the engine was built with)
+            for nm, (st, pad) in _SHADING.items():
+                mod = getattr(sn, nm)
+                reg(eng.f[nm], lambda w, st=st, pad=pad: cp.conv_fwd_plan(w, None, st, pad, 'cpu'), mod, True)
+                if nm in eng.d:
+                    in_ch = (3, 6) if nm == 'conv1_s' else None
+                    reg(eng.d[nm], lambda w, st=st, pad=pad, in_ch=in_ch: cp.conv_dgrad_plan(w, st, pad, 'cpu', in_ch=in_ch), mod, False)
+            for nm, pad in (('transConv1', 1), ('transConv2', 0)):
+                mod = getattr(sn, nm)
+                reg(eng.f[nm], lambda w, pad=pad: cp.deconv_fwd_plan(w, None, 2, pad, 'cpu'), mod, True)
+                reg(eng.d[nm], lambda w, pad=pad: cp.deconv_dgrad_plan(w, 2, pad, 'cpu'), mod, False)
+            for key, i, pad in (('skip1a', 0, 0), ('skip1b', 2, 1), ('skip1c', 4, 1)):
+                reg(eng.f[key], lambda w, pad=pad: cp.conv_fwd_plan(w, None, 1, pad, 'cpu'), sn.skipConv1[i], True)
+            # weight-gradient plans: only the geometry matters (taps / classes / packing layout), built once; transposed
+            # convolutions unfolded (one weight matrix per output-parity class)
+            for nm, (st, pad) in _SHADING.items():
+                self.wg[nm] = self._wg_plan(getattr(sn, nm), lambda w, st=st, pad=pad: cp.conv_fwd_plan(w, None, st, pad, 'cpu'))
+            for nm, pad in (('transConv1', 1), ('transConv2', 0)):
+                self.wg[nm] = self._wg_plan(getattr(sn, nm), lambda w, pad=pad: cp.deconv_fwd_plan(w, None, 2, pad, 'cpu', fold=False))
+            for key, i, pad in (('skip1a', 0, 0), ('skip1b', 2, 1), ('skip1c', 4, 1)):
+                self.wg[key] = self._wg_plan(sn.skipConv1[i], lambda w, pad=pad: cp.conv_fwd_plan(w, None, 1, pad, 'cpu'))
+            # input-gradient plans of the two inner skipConv1 layers (the attack never needs them: skipConv1 sees the scene only)
+            for key, i in (('skip1b', 2), ('skip1c', 4)):
+                mod = sn.skipConv1[i]
+                pl = cp.conv_dgrad_plan(mod.weight, 1, 1, dev, key + '_dgrad')
+                reg(pl, lambda w: cp.conv_dgrad_plan(w, 1, 1, 'cpu'), mod, False)
+                self.skip_d[key] = pl
+            # use_rough=False: the surface branch's input gradients (the engine has none: for the attack the branch is a constant)
+            if not self.rough:
+                for nm in ('conv2_s', 'conv3_s', 'conv4_s'):
+                    st, pad = _SHADING[nm]
+                    mod = getattr(sn, nm)
+                    pl = cp.conv_dgrad_plan(mod.weight, st, pad, dev, 'train.' + nm + '_dgrad')
+                    reg(pl, lambda w, st=st, pad=pad: cp.conv_dgrad_plan(w, st, pad, 'cpu'), mod, False)
+                    self.sd[nm] = pl
         # grid-refine net (models.py:123-134): forward, input-gradient and weight-gradient plans
-        g = wn.grid_refine_net
         self.rf, self.rd, self.rwg = {}, {}, {}
-        for i, kind in ((0, 'conv'), (2, 'conv'), (4, 'deconv'), (6, 'deconv')):
-            mod = g[i]
-            if kind == 'conv':
-                fb = lambda w: cp.conv_fwd_plan(w, None, 2, 1, 'cpu')
-                db = lambda w: cp.conv_dgrad_plan(w, 2, 1, 'cpu')
-                self.rf[i] = cp.conv_fwd_plan(mod.weight, mod.bias, 2, 1, dev, f'refine{i}')
-                self.rd[i] = cp.conv_dgrad_plan(mod.weight, 2, 1, dev, f'refine{i}_dgrad')
-                wb = fb
-            else:
-                fb = lambda w: cp.deconv_fwd_plan(w, None, 2, 0, 'cpu')
-                db = lambda w: cp.deconv_dgrad_plan(w, 2, 0, 'cpu')
-                self.rf[i] = cp.deconv_fwd_plan(mod.weight, mod.bias, 2, 0, dev, f'refine{i}')
-                self.rd[i] = cp.deconv_dgrad_plan(mod.weight, 2, 0, dev, f'refine{i}_dgrad')
-                wb = lambda w: cp.deconv_fwd_plan(w, None, 2, 0, 'cpu', fold=False)
-            reg(self.rf[i], fb, mod, True)
-            reg(self.rd[i], db, mod, False)
-            self.rwg[i] = self._wg_plan(mod, wb)
+        if self.refine:
+            g = wn.grid_refine_net
+            for i, kind in ((0, 'conv'), (2, 'conv'), (4, 'deconv'), (6, 'deconv')):
+                mod = g[i]
+                if kind == 'conv':
+                    fb = lambda w: cp.conv_fwd_plan(w, None, 2, 1, 'cpu')
+                    db = lambda w: cp.conv_dgrad_plan(w, 2, 1, 'cpu')
+                    self.rf[i] = cp.conv_fwd_plan(mod.weight, mod.bias, 2, 1, dev, f'refine{i}')
+                    self.rd[i] = cp.conv_dgrad_plan(mod.weight, 2, 1, dev, f'refine{i}_dgrad')
+                    wb = fb
+                else:
+                    fb = lambda w: cp.deconv_fwd_plan(w, None, 2, 0, 'cpu')
+                    db = lambda w: cp.deconv_dgrad_plan(w, 2, 0, 'cpu')
+                    self.rf[i] = cp.deconv_fwd_plan(mod.weight, mod.bias, 2, 0, dev, f'refine{i}')
+                    self.rd[i] = cp.deconv_dgrad_plan(mod.weight, 2, 0, dev, f'refine{i}_dgrad')
+                    wb = lambda w: cp.deconv_fwd_plan(w, None, 2, 0, 'cpu', fold=False)
+                reg(self.rf[i], fb, mod, True)
+                reg(self.rd[i], db, mod, False)
+                self.rwg[i] = self._wg_plan(mod, wb)
         H, W = self.Hc, self.Wc
 
         def z(*shape):
             return torch.zeros(*shape, device=dev)
 
-        self.grid_ws = dict(coarse=z(1, H, W, 4), r0=z(1, H // 2, W // 2, 32), r2=z(1, H // 4, W // 4, 64),
-                            r4=z(1, H // 2, W // 2, 32), refine=z(1, H, W, 4), fine=z(H, W, 4),
-                            g_fine=z(H, W, 4), g_sum=z(1, H, W, 4), g_r6=z(1, H, W, 4), g_r4=z(1, H // 2, W // 2, 32),
-                            g_r2=z(1, H // 4, W // 4, 64), g_r0=z(1, H // 2, W // 2, 32), g_c0=z(1, H, W, 4),
+        self.grid_ws = dict(coarse=z(1, H, W, 4), fine=z(H, W, 4), g_fine=z(H, W, 4), g_sum=z(1, H, W, 4),
                             partial=z(((H * W + 255) // 256) * (6 + 2 * (wn.nctrl + 2))), g_params=z(6 + 2 * (wn.nctrl + 2)))
+        if self.refine:
+            self.grid_ws.update(r0=z(1, H // 2, W // 2, 32), r2=z(1, H // 4, W // 4, 64), r4=z(1, H // 2, W // 2, 32), refine=z(1, H, W, 4),
+                                g_r6=z(1, H, W, 4), g_r4=z(1, H // 2, W // 2, 32), g_r2=z(1, H // 4, W // 4, 64),
+                                g_r0=z(1, H // 2, W // 2, 32), g_c0=z(1, H, W, 4))
         B = self.B
-        self.t0, self.t1 = z(B, H, W, 4), z(B, H, W, 4)              # skipConv1 intermediates (kept for its gradients)
-        self.g_r1, self.g_t1, self.g_t0 = z(B, H, W, 4), z(B, H, W, 4), z(B, H, W, 4)
+        nb = 1 if self.collapse else B                               # skipConv1 runs at batch 1 when collapsed
+        self.t0, self.t1 = z(nb, H, W, 4), z(nb, H, W, 4)            # skipConv1 intermediates (kept for its gradients)
+        self.g_r1, self.g_t1, self.g_t0 = z(nb, H, W, 4), z(nb, H, W, 4), z(nb, H, W, 4)
+        if self.collapse:
+            self.r1, self.sum_r1 = z(1, H, W, 4), z(1, H, W, 4)
+        if self.collapse and not self.rough:
+            # the surface branch at batch 1: activations, their ReLU-gate bytes, gradients (w.r.t. the pre-activations) and the
+            # input gradients that join the batch sums
+            H2, W2, H4, W4 = H // 2, W // 2, H // 4, W // 4
+            shp = {'S1': (H2, W2, 32), 'S2': (H4, W4, 64), 'S3': (H4, W4, 128), 'S4': (H4, W4, 256)}
+            self.s1a = {k: z(1, *v) for k, v in shp.items()}
+            self.s1m = {k: torch.zeros(1, v[0], v[1], v[2] // 4, dtype=torch.uint8, device=dev) for k, v in shp.items()}
+            self.s1g = {k: z(1, *v) for k, v in shp.items()}
+            self.s1t = {k: z(1, *shp[k]) for k in ('S1', 'S2', 'S3')}
         nblk = ((H + 15) // 16) * ((W + 15) // 16)
         self.loss_ws = dict(mmu=z(B, H, W, 4), m11=z(B, H, W, 4), m12=z(B, H, W, 4), partial=z(B * nblk, 3), gY=z(B, H, W, 4),
                             gP=z(B, H, W, 4))
@@ -180,26 +219,49 @@ class PCNetTrainer:
         self._ctrl = wn.ctrl_pts.detach().float().contiguous().view(-1)
         _lib.call('spaa_warp_coarse_grid', _lib.ptr(self._aff), _lib.ptr(self._theta), _lib.ptr(self._ctrl), wn.nctrl, hi, wi,
                   H, W, _lib.ptr(ws['coarse']))
-        R, L = _lib.ACT_RELU, _lib.ACT_LEAKY01
-        self.rf[0].run(ws['coarse'], ws['r0'], act=R)
-        self.rf[2].run(ws['r0'], ws['r2'], act=R)
-        self.rf[4].run(ws['r2'], ws['r4'], act=R)
-        self.rf[6].run(ws['r4'], ws['refine'], act=L)
-        _lib.call('spaa_warp_finish_grid', _lib.ptr(ws['coarse']), _lib.ptr(ws['refine']), _lib.ptr(ws['fine']), H * W)
+        if self.refine:
+            R, L = _lib.ACT_RELU, _lib.ACT_LEAKY01
+            self.rf[0].run(ws['coarse'], ws['r0'], act=R)
+            self.rf[2].run(ws['r0'], ws['r2'], act=R)
+            self.rf[4].run(ws['r2'], ws['r4'], act=R)
+            self.rf[6].run(ws['r4'], ws['refine'], act=L)
+        _lib.call('spaa_warp_finish_grid', _lib.ptr(ws['coarse']), _lib.ptr(ws.get('refine')), _lib.ptr(ws['fine']), H * W)
         eng = self.eng
         eng.grid = ws['fine']
         eng.tap_off, eng.tap_order, eng.tap_wm, eng.tap_src = transposed_taps(eng.grid, prj_size, (H, W), eng.mask, want_table=True)
         eng.tiled = None   # (the grid changes every step: the per-tile boxes of the LDS-staged gather are not rebuilt)
 
     def _set_scene(self):
-        """PCNetEngine.set_scene, keeping the skipConv1 intermediates."""
+        """PCNetEngine.set_scene, keeping the skipConv1 intermediates; with `collapse` the scene-only layers at batch 1, broadcast."""
         eng = self.eng
         eng.version += 1
         eng.scene = self.scene4
         R = _lib.ACT_RELU
-        eng.f['skip1a'].run(self.scene4, self.t0, act=R)
+        if not self.collapse:
+            eng.f['skip1a'].run(self.scene4, self.t0, act=R)
+            eng.f['skip1b'].run(self.t0, self.t1, act=R)
+            eng.f['skip1c'].run(self.t1, eng.a['R1'], act=R)
+            if not self.rough:
+                eng._surface_branch(self.scene4)
+            return
+        eng.f['skip1a'].run(self.scene1, self.t0, act=R)
         eng.f['skip1b'].run(self.t0, self.t1, act=R)
-        eng.f['skip1c'].run(self.t1, eng.a['R1'], act=R)
+        eng.f['skip1c'].run(self.t1, self.r1, act=R)
+        eng.a['R1'].copy_(self.r1.expand_as(eng.a['R1']))
+        if not self.rough:
+            a, m, f = self.s1a, self.s1m, eng.f
+            f['conv1_s'].run(self.scene1, a['S1'], act=R, mask_out=m['S1'])
+            f['conv2_s'].run(a['S1'], a['S2'], act=R, mask_out=m['S2'])
+            f['conv3_s'].run(a['S2'], a['S3'], act=R, mask_out=m['S3'])
+            f['conv4_s'].run(a['S3'], a['S4'], act=R, mask_out=m['S4'])
+            for k in ('S1', 'S2', 'S3', 'S4'):
+                dict.__getitem__(eng.a, k).copy_(a[k].expand_as(eng.a[k]))
+
+    def _batch_sum(self, g, add, gate_bits, out, B):
+        """out = gate(sum_b g[b] + add) (spaa_batch_sum_gate_bits) over NHWC [B,H,W,C] -> [1,H,W,C]."""
+        _, h, w, c = out.shape
+        _lib.call('spaa_batch_sum_gate_bits', _lib.ptr(g), _lib.ptr(add), C_ptr(gate_bits) if gate_bits is not None else None,
+                  _lib.ptr(out), B, h, w, c, c)
 
     # ------------------------------------------------------------------------------------------------------------
     def step(self, prj_batch, cam_batch, loss=None):
@@ -237,6 +299,32 @@ class PCNetTrainer:
         _lib.call('spaa_select_grad', p(lw['gY']), p(lw['gY']), p(self.ones_state), p(eng.a['Ypre']), p(lw['gP']), B, H * W)
         # ---- backward: input gradients (fills every layer's pre-activation gradient), then weight gradients
         eng.backward(lw['gP'], input_grad=False)   # (no gradient w.r.t. the projector image: it is data here)
+        if not self.fix_shading:
+            self._shading_wgrads()
+        # ---- WarpingNet: grid gradient (summed over the batch), refine net, TPS / affine parameters
+        self._warping_grads(x4)
+        # ---- optimiser steps (:318-320) and schedulers (:354-356)
+        gr = self.grads
+        self.iters += 1
+        for gname, grp in self.groups.items():
+            lr = grp['lr'] * (self.gamma if (self.iters - 1) >= grp['milestone'] else 1.0)
+            for n in grp['names']:
+                prm = self.params[n]
+                gt = gr[n].contiguous()
+                assert gt.numel() == prm.numel(), n
+                _lib.call('spaa_adam_step', p(prm.data.view(-1)), p(gt.view(-1)), p(self.m[n].view(-1)), p(self.v[n].view(-1)),
+                          prm.numel(), lr, 0.9, 0.999, 1e-8, grp['wd'], self.iters)
+        self.pc.invalidate()
+        part = lw['partial'].sum(dim=0).cpu()
+        n_el = 3.0 * B * H * W
+        l1, l2 = float(part[1]) / n_el, float(part[2]) / n_el
+        total = l1_w * l1 + ssim_w * (1.0 - float(part[0]) / n_el)
+        return total, l2
+
+    def _shading_wgrads(self):
+        """Weight and bias gradients of every ShadingNet layer from the pre-activation gradients eng.backward left."""
+        p = _lib.ptr
+        eng, lw = self.eng, self.loss_ws
         a, g = eng.a, eng.g
         gr = self.grads
         wplan = self.wg
@@ -257,58 +345,84 @@ class PCNetTrainer:
         wgrad('conv1', sp + 'conv1', a['xw'], g['P1'])
         wgrad('skipConv3', sp + 'skipConv3', a['X2'], g['P5'])
         wgrad('skipConv2', sp + 'skipConv2', a['X1'], g['P6'])
-        wgrad('conv4_s', sp + 'conv4_s', a['S3'], g['S4'])
-        wgrad('conv3_s', sp + 'conv3_s', a['S2'], g['S3'])
-        wgrad('conv2_s', sp + 'conv2_s', a['S1'], g['S2'])
-        wgrad('conv1_s', sp + 'conv1_s', a['cat8'], g['S1'])
+        if self.rough:
+            wgrad('conv4_s', sp + 'conv4_s', a['S3'], g['S4'])
+            wgrad('conv3_s', sp + 'conv3_s', a['S2'], g['S3'])
+            wgrad('conv2_s', sp + 'conv2_s', a['S1'], g['S2'])
+            wgrad('conv1_s', sp + 'conv1_s', a['cat8'], g['S1'])
+        elif self.collapse:
+            # the surface branch ran once (batch 1): res_k_s = relu(conv_k_s(.)) enters relu(conv_k(x) + res_k_s) of every sample,
+            # so d/d res_k_s = sum_b P_k[b]; gS_k = gate(S_k) . (conv_{k+1}_s^T(gS_{k+1}) + sum_b P_k[b])
+            sa, sm, sg, st = self.s1a, self.s1m, self.s1g, self.s1t
+            self._batch_sum(g['P4'], None, sm['S4'], sg['S4'], self.B)
+            wgrad('conv4_s', sp + 'conv4_s', sa['S3'], sg['S4'])
+            self.sd['conv4_s'].run(sg['S4'], st['S3'])
+            self._batch_sum(g['P3'], st['S3'], sm['S3'], sg['S3'], self.B)
+            wgrad('conv3_s', sp + 'conv3_s', sa['S2'], sg['S3'])
+            self.sd['conv3_s'].run(sg['S3'], st['S2'])
+            self._batch_sum(g['P2'], st['S2'], sm['S2'], sg['S2'], self.B)
+            wgrad('conv2_s', sp + 'conv2_s', sa['S1'], sg['S2'])
+            self.sd['conv2_s'].run(sg['S2'], st['S1'])
+            self._batch_sum(g['P1'], st['S1'], sm['S1'], sg['S1'], self.B)
+            wgrad('conv1_s', sp + 'conv1_s', self.scene1, sg['S1'])
+        else:
+            # the same chain at batch B (the B samples' branches are identical; the weight gradients sum over them).  The first gate
+            # is the batch-1 kernel over the B images laid end to end as one [1, B H/4, W/4, 256] tensor
+            m = eng.m
+            s4 = g['S4']
+            self._batch_sum(g['P4'], None, m['S4'], s4.view(1, -1, *s4.shape[2:]), 1)
+            wgrad('conv4_s', sp + 'conv4_s', a['S3'], g['S4'])
+            self.sd['conv4_s'].run(g['S4'], g['S3'], add=g['P3'], gate_bits=m['S3'])
+            wgrad('conv3_s', sp + 'conv3_s', a['S2'], g['S3'])
+            self.sd['conv3_s'].run(g['S3'], g['S2'], add=g['P2'], gate_bits=m['S2'])
+            wgrad('conv2_s', sp + 'conv2_s', a['S1'], g['S2'])
+            self.sd['conv2_s'].run(g['S2'], g['S1'], add=g['P1'], gate_bits=m['S1'])
+            wgrad('conv1_s', sp + 'conv1_s', self.scene4, g['S1'])
         # skipConv1 (on the scene; its output is added to conv6's pre-activation, models.py:291,301)
-        _lib.call('spaa_relu_gate', p(lw['gP']), p(a['R1']), p(self.g_r1), lw['gP'].numel())     # ReLU after skipConv1.4
+        if self.collapse:   # (batch 1: the ReLU gate of R1 is the same for every sample, so the batch sum comes first)
+            self._batch_sum(lw['gP'], None, None, self.sum_r1, self.B)
+            _lib.call('spaa_relu_gate', p(self.sum_r1), p(self.r1), p(self.g_r1), self.g_r1.numel())
+            skip_in = self.scene1
+        else:
+            _lib.call('spaa_relu_gate', p(lw['gP']), p(a['R1']), p(self.g_r1), lw['gP'].numel())     # ReLU after skipConv1.4
+            skip_in = self.scene4
         wgrad('skip1c', sp + 'skipConv1.4', self.t1, self.g_r1)
         self.skip_d['skip1c'].run(self.g_r1, self.g_t1, gate=self.t1)
         wgrad('skip1b', sp + 'skipConv1.2', self.t0, self.g_t1)
         self.skip_d['skip1b'].run(self.g_t1, self.g_t0, gate=self.t0)
-        wgrad('skip1a', sp + 'skipConv1.0', self.scene4, self.g_t0)
-        # ---- WarpingNet: grid gradient (summed over the batch), refine net, TPS / affine parameters
-        ws = self.grid_ws
-        _lib.call('spaa_warp_bwd_grid', p(g['xw']), p(x4), p(eng.grid), p(eng.mask), p(ws['g_fine']), B, eng.Hp, eng.Wp, H, W)
-        _lib.call('spaa_warp_finish_grid_bwd', p(ws['g_fine']), p(ws['coarse']), p(ws['refine']), p(ws['g_sum']), p(ws['g_r6']),
-                  H * W)
-        wp = 'warping_net.grid_refine_net.'
+        wgrad('skip1a', sp + 'skipConv1.0', skip_in, self.g_t0)
 
-        def rwgrad(i, inp, gout):
-            dw, db = self.rwg[i].wgrad(inp, gout)
-            gr[wp + f'{i}.weight'] = self.rwg[i].unpack_grad(dw)
-            gr[wp + f'{i}.bias'] = db
+    def _warping_grads(self, x4):
+        """Gradients of the WarpingNet parameters: grid (summed over the batch), refine net, TPS / affine."""
+        p = _lib.ptr
+        eng, ws, gr = self.eng, self.grid_ws, self.grads
+        B, H, W = self.B, self.Hc, self.Wc
+        _lib.call('spaa_warp_bwd_grid', p(eng.g['xw']), p(x4), p(eng.grid), p(eng.mask), p(ws['g_fine']), B, eng.Hp, eng.Wp, H, W)
+        _lib.call('spaa_warp_finish_grid_bwd', p(ws['g_fine']), p(ws['coarse']), p(ws.get('refine')), p(ws['g_sum']),
+                  p(ws.get('g_r6')), H * W)
+        g_coarse = ws['g_sum']   # (without the refine net the coarse grid is the fine grid before the clamp)
+        if self.refine:
+            wp = 'warping_net.grid_refine_net.'
 
-        rwgrad(6, ws['r4'], ws['g_r6'])
-        self.rd[6].run(ws['g_r6'], ws['g_r4'], gate=ws['r4'])
-        rwgrad(4, ws['r2'], ws['g_r4'])
-        self.rd[4].run(ws['g_r4'], ws['g_r2'], gate=ws['r2'])
-        rwgrad(2, ws['r0'], ws['g_r2'])
-        self.rd[2].run(ws['g_r2'], ws['g_r0'], gate=ws['r0'])
-        rwgrad(0, ws['coarse'], ws['g_r0'])
-        self.rd[0].run(ws['g_r0'], ws['g_c0'], add=ws['g_sum'])               # + the skip connection (models.py:176)
+            def rwgrad(i, inp, gout):
+                dw, db = self.rwg[i].wgrad(inp, gout)
+                gr[wp + f'{i}.weight'] = self.rwg[i].unpack_grad(dw)
+                gr[wp + f'{i}.bias'] = db
+
+            rwgrad(6, ws['r4'], ws['g_r6'])
+            self.rd[6].run(ws['g_r6'], ws['g_r4'], gate=ws['r4'])
+            rwgrad(4, ws['r2'], ws['g_r4'])
+            self.rd[4].run(ws['g_r4'], ws['g_r2'], gate=ws['r2'])
+            rwgrad(2, ws['r0'], ws['g_r2'])
+            self.rd[2].run(ws['g_r2'], ws['g_r0'], gate=ws['r0'])
+            rwgrad(0, ws['coarse'], ws['g_r0'])
+            self.rd[0].run(ws['g_r0'], ws['g_c0'], add=ws['g_sum'])               # + the skip connection (models.py:176)
+            g_coarse = ws['g_c0']
         wn = self.pc.warping_net
-        _lib.call('spaa_warp_coarse_grid_bwd', p(ws['g_c0']), p(self._aff), p(self._theta), p(self._ctrl), wn.nctrl, eng.Hp,
+        _lib.call('spaa_warp_coarse_grid_bwd', p(g_coarse), p(self._aff), p(self._theta), p(self._ctrl), wn.nctrl, eng.Hp,
                   eng.Wp, H, W, p(ws['partial']), p(ws['g_params']))
         gr['warping_net.affine_mat'] = ws['g_params'][:6].view(1, 2, 3)
         gr['warping_net.theta'] = ws['g_params'][6:].view(1, wn.nctrl + 2, 2)
-        # ---- optimiser steps (:318-320) and schedulers (:354-356)
-        self.iters += 1
-        for gname, grp in self.groups.items():
-            lr = grp['lr'] * (self.gamma if (self.iters - 1) >= grp['milestone'] else 1.0)
-            for n in grp['names']:
-                prm = self.params[n]
-                gt = gr[n].contiguous()
-                assert gt.numel() == prm.numel(), n
-                _lib.call('spaa_adam_step', p(prm.data.view(-1)), p(gt.view(-1)), p(self.m[n].view(-1)), p(self.v[n].view(-1)),
-                          prm.numel(), lr, 0.9, 0.999, 1e-8, grp['wd'], self.iters)
-        self.pc.invalidate()
-        part = lw['partial'].sum(dim=0).cpu()
-        n_el = 3.0 * B * H * W
-        l1, l2 = float(part[1]) / n_el, float(part[2]) / n_el
-        total = l1_w * l1 + ssim_w * (1.0 - float(part[0]) / n_el)
-        return total, l2
 
 
 def compute_loss(prj_infer, prj_train, loss_option):
