@@ -595,6 +595,26 @@ int spaa_onepixel_preproc(const float* base, const int32_t* cand, int P, int npi
 int spaa_onepixel_score(const float* logits, int ncls, int target, int targeted, float* energy, int32_t* argmax, float* pmax,
                         int P, spaa_stream_t stream);
 
+/* ---- direct-light mask of a camera view (train_network.py:68-80 load_data, img_proc.py:13-65 threshold_im) ---- */
+/* Nayar's separation of N >= 2 shifted-checkerboard captures cb [N][3][H][W] (planar fp32, projector backlight b in [0, 1)):
+ * per pixel and channel l1 = max_n, l2 = min_n, direct = (l1 - l2) / (float)(1 - b), indirect = 2 (l2 - (float)b l1) /
+ * (float)(1 - b b); then clip(direct, 0, 1), g = (0.299f R + 0.587f G) + 0.114f B, gray_u8 [H][W] = (uint8)(g 255f) truncated.
+ * Each step is one correctly rounded fp32 operation in that order (numpy float32 gives the same bytes).  direct (before the clip)
+ * and indirect: optional [3][H][W] outputs, may be NULL.  N == 1: cb is the direct image itself (no separation, no indirect).
+ * H, W >= 2. */
+int spaa_cb_direct_gray(const float* cb, int N, int H, int W, double b, uint8_t* gray_u8, float* direct, float* indirect,
+                        spaa_stream_t stream);
+/* smooth_u8 = the 3 x 3 Gaussian (sigma 1.5, BORDER_REFLECT_101) of gray_u8 in integer arithmetic: weights round(256 g) =
+ * (79, 98, 79), rows then columns without intermediate rounding, (v + 32768) >> 16.  hist [256] uint32: the histogram of smooth_u8
+ * is ADDED to it (zero it first: spaa_zero); integer atomics, exact in any order.  Not in place. */
+int spaa_mask_blur_hist(const uint8_t* gray_u8, int H, int W, uint8_t* smooth_u8, uint32_t* hist, spaa_stream_t stream);
+/* Two-class Otsu over the present value range [vmin, vmax] of hist: candidate k splits [vmin..k] | [k+1..vmax], between-class
+ * variance w0 w1 (mu0 - mu1)^2 from exact integer sums in double, first maximum; t = the smallest present value above that k.
+ * mask [H][W] bytes = smooth_u8 >= t; out6 int32 = {t, xmin, ymin, xmax, ymax, count} of the mask (integer atomics; written in
+ * full, no initialisation needed).  Fewer than two distinct values: out6[0] = -1, the mask empty. */
+int spaa_otsu_mask_bbox(const uint8_t* smooth_u8, const uint32_t* hist, int H, int W, uint8_t* mask, int32_t* out6,
+                        spaa_stream_t stream);
+
 /* misc */
 int spaa_zero(void* p, int64_t bytes, spaa_stream_t stream);
 const char* spaa_version(void);

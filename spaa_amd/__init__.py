@@ -28,7 +28,8 @@ def __getattr__(name):
     if name in ('PerC_AL', 'perc_al_compennet_pp'):
         from . import perc_al
         return getattr(perc_al, name)
-    if name in ('PCNetTrainer', 'train_pcnet', 'CompenNetTrainer', 'train_compennet_pp', 'init_compennet', 'evaluate_model'):
+    if name in ('PCNetTrainer', 'train_pcnet', 'CompenNetTrainer', 'train_compennet_pp', 'init_compennet', 'evaluate_model', 'load_data',
+                'get_model_train_cfg', 'train_eval_pcnet', 'train_eval_compennet_pp'):
         from . import train_network
         return getattr(train_network, name)
     if name in ('DigitalOnePixelAttacker', 'perturb_image'):
@@ -37,6 +38,9 @@ def __getattr__(name):
     if name in ('calc_img_dists', 'img_stats', 'dists_from_sums'):
         from . import metrics
         return getattr(metrics, name)
+    if name in ('threshold_im', 'get_affine_transform', 'center_crop', 'expand_4d', 'resize'):
+        from . import img_proc
+        return getattr(img_proc, name)
     if name in ('torch_imread', 'torch_imread_mt', 'save_imgs', 'load_setup_info', 'save_checkpoint'):
         from . import io
         return getattr(io, name)

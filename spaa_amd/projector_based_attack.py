@@ -499,13 +499,17 @@ def to_attacker_cfg_str(attacker_name):
     return attacker_name, None
 
 
-def run_projector_based_attack(cfg, *, models=None, classifiers=None, iters=50):
+def run_projector_based_attack(cfg, *, models=None, classifiers=None, iters=50, train=False, model_cfg=None):
     """projector_based_attack.py:24-148 for the deep-learning attackers: per setup and classifier, 10 targeted attacks (the first 10
     imagenet10 classes) and 1 untargeted attack (the scene's top-1) for every stealth loss x d_thr; results under
     <setup>/prj/adv and <setup>/cam/infer/adv / <attacker_cfg_str>/<loss>/<d_thr>/<classifier>/img_0001..0011.png (1-10 targeted,
     11 untargeted).  For SPAA one classifier's whole sweep is ONE spaa_sweep call.
     `models`: setup name -> trained PCNet (SPAA) / CompenNetPlusplus (PerC-AL+CompenNet++); `classifiers`: classifier name ->
-    spaa_amd.Classifier.  (The reference trains or loads the model and downloads the classifier weights here; neither is done.)"""
+    spaa_amd.Classifier (the reference downloads the classifier weights here; that is not done).
+    `train=True`: a setup without an entry in `models` is trained, or with cfg.load_pretrained loaded from its checkpoint, as the
+    reference does (:50-60): train_network.train_eval_pcnet (SPAA) / train_eval_compennet_pp (PerC-AL+CompenNet++) on
+    get_model_train_cfg's defaults, with the fields of `model_cfg` (a mapping, e.g. dict(max_iters=100)) laid over them; the last
+    configuration is left in cfg.model_cfg.  The default, train=False, raises for such a setup."""
     import itertools
     import random
     from os.path import join
@@ -523,6 +527,14 @@ def run_projector_based_attack(cfg, *, models=None, classifiers=None, iters=50):
     attacker_cfg_str = to_attacker_cfg_str(name)[0]
     for setup_name in cfg.setup_list:
         model = (models or {}).get(setup_name)
+        if model is None and train:
+            from . import train_network as tn
+            mcfg = tn.get_model_train_cfg(model_list=['PCNet' if name == 'SPAA' else 'CompenNet++'], data_root=cfg.data_root,
+                                          setup_list=[setup_name], device_ids=cfg.device_ids, load_pretrained=cfg.load_pretrained,
+                                          plot_on=cfg.plot_on)
+            mcfg.device = cfg.device
+            mcfg.update(model_cfg or {})
+            model, _, cfg.model_cfg = (tn.train_eval_pcnet if name == 'SPAA' else tn.train_eval_compennet_pp)(mcfg)
         if model is None:
             raise ValueError(f'run_projector_based_attack: pass models={{{setup_name!r}: trained '
                              f'{"PCNet" if name == "SPAA" else "CompenNetPlusplus"}}} (models are not trained here)')

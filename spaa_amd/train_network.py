@@ -1,5 +1,6 @@
 """PCNet and CompenNet++ training steps on HIP.  CompenNet++: `CompenNetTrainer`,
-`train_compennet_pp`, `init_compennet`, `evaluate_model` at the end of this file (train_network.py:98-232, :395-441).
+`train_compennet_pp`, `init_compennet`, `evaluate_model` further down (train_network.py:98-232, :395-441); the drivers in front of
+the attack -- `load_data`, `get_model_train_cfg`, `train_eval_pcnet`, `train_eval_compennet_pp` (:39-82, :444-733) -- at the end.
 
 Mirrors `train_pcnet` of /root/reference/src/python/train_network.py:235-363 and `compute_loss` :367-392: one iteration =
 forward of PCNet (WarpingNet with its CURRENT parameters: the sampling grid is rebuilt every step, models.py:163-185) ->
@@ -942,3 +943,247 @@ def init_compennet(compennet, data_root, cfg, *, max_iters=500, batch_size=48, n
     init_data = dict(cam_scene=cam_scene, cam_train=torch.abs(prj_train - 0.3 * cam_scene.expand_as(prj_train)), prj_train=prj_train)
     compennet, _, _, _ = train_compennet_pp(compennet, init_data, None, init_cfg)
     return compennet
+
+
+# ================================================================================================================
+# The reference's drivers in front of the attack: load_data, get_model_train_cfg, train_eval_pcnet, train_eval_compennet_pp
+# (train_network.py:39-82, :444-733).  No DataParallel, no visdom (`plot_on` is accepted and ignored), no .xlsx log.
+# ================================================================================================================
+LOG_COLUMNS = ['Setup', 'Model', 'Loss', 'Num train', 'Batch', 'Iters', 'PSNR', 'RMSE', 'SSIM', 'L2', 'L-inf', 'dE']   # utils.py:683
+PCNET_MODELS = ('PCNet', 'PCNet_no_mask', 'PCNet_no_rough', 'PCNet_no_mask_no_rough', 'PCNet_w/o_refine')
+
+
+def load_data(data_root, setup_name, input_size=None, compensation=False, *, device='cuda'):
+    """train_network.py:39-82: reads `<data_root>/setups/<setup_name>/cam/raw/{ref,train,test,cb}` and `<data_root>/prj_share/
+    {train,test}` and returns (cam_scene [1,3,H,W] = ref/img_0002, cam_train, cam_valid, prj_train, prj_valid (as many as cam_valid),
+    im_mask bool [H,W], mask_corners, setup_info), all on the host like the reference's.  The direct-light mask of the checkerboard
+    captures (Nayar's separation with backlight 0.9, then img_proc.threshold_im's chain) is three launches of csrc/direct_mask.hip on
+    `device`; there is no CPU fallback.  `compensation=True` (unused by the reference) is not implemented."""
+    from os.path import join
+    from . import io, img_proc
+    if compensation:
+        raise NotImplementedError('load_data: only compensation=False (the branch the reference uses) is implemented')
+    dev = img_proc._require_gpu(device)
+    setup_path = join(data_root, 'setups', setup_name)
+    print(f"Loading data from '{setup_path}'")
+    setup_info = io.load_setup_info(setup_path)
+    cam_ref = io.torch_imread_mt(join(setup_path, 'cam/raw/ref'), size=input_size)
+    gray_idx = 1                                   # ref/img_0002: the surface lit by prj_brightness
+    cam_scene = cam_ref[gray_idx].unsqueeze(0)
+    cam_train = io.torch_imread_mt(join(setup_path, 'cam/raw/train'), size=input_size)
+    prj_train = io.torch_imread_mt(join(data_root, 'prj_share/train'))
+    cam_valid = io.torch_imread_mt(join(setup_path, 'cam/raw/test'), size=input_size)
+    prj_valid = io.torch_imread_mt(join(data_root, 'prj_share/test'), index=list(range(cam_valid.shape[0])))
+    im_cb = io.torch_imread_mt(join(setup_path, 'cam/raw/cb'), size=input_size)
+    if im_cb.shape[0] < 2:
+        raise ValueError(f'load_data: the direct-light separation needs at least two checkerboard captures, found {im_cb.shape[0]}')
+    im_mask, _, mask_corners = img_proc._finish(img_proc.direct_mask(im_cb, img_proc.BACKLIGHT, device=dev))
+    return cam_scene, cam_train, cam_valid, prj_train, prj_valid, torch.from_numpy(im_mask), mask_corners, setup_info
+
+
+def get_model_train_cfg(model_list, data_root=None, setup_list=None, device_ids=[0], center_crop=False, load_pretrained=False,
+                        plot_on=True, single=False):
+    """train_network.py:444-473: the default training configuration (a mapping with attribute access)."""
+    from .io import SetupInfo
+    cfg = SetupInfo(data_root=data_root, setup_list=setup_list, device='cuda', device_ids=device_ids, load_pretrained=load_pretrained,
+                    max_iters=2000, batch_size=24, lr=1e-3, lr_drop_ratio=0.2, lr_drop_rate=800, l2_reg=1e-4, train_plot_rate=50,
+                    valid_rate=200, plot_on=plot_on, center_crop=center_crop)
+    if single:
+        cfg.update(model_name=model_list[0], num_train=500, loss='l1+ssim')
+    else:
+        cfg.update(model_list=model_list, num_train_list=[500], loss_list=['l1+ssim'])
+    return cfg
+
+
+def _reset_rng_seeds(seed):
+    """utils.py:70-76."""
+    import numpy as np
+    np.random.seed(seed)
+    random.seed(seed)
+    torch.manual_seed(seed)
+    torch.cuda.manual_seed_all(seed)
+
+
+def _init_log(log_dir):
+    """utils.py:678-684 without the .xlsx twin: (rows, `<log_dir>/<datetime>.txt`)."""
+    import time
+    os.makedirs(log_dir, exist_ok=True)
+    return [], os.path.join(log_dir, time.strftime('%Y-%m-%d_%H_%M_%S', time.localtime()) + '.txt')
+
+
+def _write_log(rows, filename):
+    """utils.py:687-694: the table as CSV with 4 decimals (rewritten after every row, so an interrupted run keeps its rows)."""
+    import pandas as pd
+    ret = pd.DataFrame(rows, columns=LOG_COLUMNS)
+    ret.to_csv(filename, mode='w', index=False, float_format='%.4f')
+    print(f'Log file saved to {filename}')
+    return ret
+
+
+def _mean_rows(rows, model_list, n_setups):
+    """train_network.py:583-586: per model, the mean of the numeric columns over its rows."""
+    import numpy as np
+    out = []
+    for model_name in model_list:
+        sel = [r for r in rows if r[1] == model_name]
+        out.append([f'[mean]_{n_setups}_setups', model_name, float('nan')] + [float(np.mean([r[k] for r in sel])) for k in range(3, 12)])
+    return out
+
+
+def _affine_from_corners(mask_corners):
+    """The WarpingNet's initial affine (train_network.py:542-546): grid_sample warps inversely, so the matrix maps the output
+    square's corners to the mask's box."""
+    from .img_proc import get_affine_transform
+    src_pts = [[-1, -1], [1, -1], [1, 1]]
+    return torch.from_numpy(get_affine_transform(mask_corners[0:3], src_pts)).float().flatten()
+
+
+def _build_pcnet(model_name, cam_mask, mask_corners, out_size, device):
+    """A fresh PCNet by name (train_network.py:532-552): seed 123, ShadingNetSPAA / WarpingNet variants from the name, the affine
+    from the mask corners."""
+    from .models import ShadingNetSPAA, WarpingNet
+    _reset_rng_seeds(123)
+    use_rough, use_mask = 'no_rough' not in model_name, 'no_mask' not in model_name
+    shading_net = ShadingNetSPAA(use_rough=use_rough)
+    warping_net = WarpingNet(out_size=tuple(out_size), with_refine='w/o_refine' not in model_name)   # warps prj to the camera view
+    warping_net.set_affine(_affine_from_corners(mask_corners))
+    return PCNet(cam_mask.float(), warping_net, shading_net, fix_shading_net=False, use_mask=use_mask, use_rough=use_rough).to(device)
+
+
+def _build_compennet_pp(model_name, compen_net, mask_corners, prj_size, device):
+    """A fresh CompenNet++ (train_network.py:653-668): seed 0, a WarpingNet with the affine from the mask corners, a copy of the
+    initialised CompenNet."""
+    from .models import CompenNetPlusplus, WarpingNet
+    _reset_rng_seeds(0)
+    warping_net = WarpingNet(out_size=tuple(prj_size), with_refine='w/o_refine' not in model_name)   # warps the camera view to prj
+    warping_net.set_affine(_affine_from_corners(mask_corners))
+    return CompenNetPlusplus(warping_net, compen_net).to(device)
+
+
+def _setup_data(cfg_default, setup_name, device, crop):
+    """Loads one setup (train_network.py:488-509, :615-630): host training tensors, validation data on the device."""
+    from .img_proc import center_crop as cc
+    cam_scene, cam_train, cam_valid, prj_train, prj_valid, cam_mask, mask_corners, setup_info = load_data(
+        cfg_default.data_root, setup_name, device=device)
+    cfg_default.setup_info = setup_info
+    if crop:
+        cp_sz = tuple(setup_info['classifier_crop_sz'])
+        cam_scene, cam_train, cam_valid, cam_mask = (cc(t, cp_sz) for t in (cam_scene, cam_train, cam_valid, cam_mask))
+    cam_scene = cam_scene.to(device)
+    cam_valid, prj_valid = cam_valid.to(device), prj_valid.to(device)
+    valid_data = dict(cam_scene=cam_scene.expand(cam_valid.shape[0], -1, -1, -1), cam_valid=cam_valid, prj_valid=prj_valid)
+    return cam_scene, cam_train, prj_train, cam_mask, mask_corners, valid_data
+
+
+def _configurations(cfg_default, setup_name):
+    """The num_train x model x loss loops (train_network.py:511-530): yields (cfg, model_name, loss, num_train, model_version)."""
+    from .io import SetupInfo
+    for num_train in cfg_default.num_train_list:
+        cfg = SetupInfo({k: v for k, v in cfg_default.items() if k not in ('num_train_list', 'model_list', 'loss_list', 'setup_list')})
+        cfg.num_train = num_train
+        for model_name in cfg_default.model_list:
+            cfg.model_name = model_name.replace('/', '_')
+            for loss in cfg_default.loss_list:
+                cfg.setup_name = setup_name.replace('/', '_')
+                cfg.loss = loss
+                yield cfg, model_name, loss, num_train, f'{cfg.model_name}_{loss}_{num_train}_{cfg.batch_size}_{cfg.max_iters}'
+
+
+def _print_options(cfg):
+    print('-------------------------------------- Training Options -----------------------------------')
+    print('\n'.join(f'{k}: {v}' for k, v in cfg.items()))
+
+
+def train_eval_pcnet(cfg_default):
+    """train_network.py:476-594: for every setup x num_train x model x loss of `cfg_default` (get_model_train_cfg), train a PCNet
+    (`train_pcnet`) or, with load_pretrained, load `<data_root>/../checkpoint/<io.opt_to_string(cfg)>.pth`; evaluate it on the
+    validation pairs; write the inferred camera images to `<setup>/cam/infer/test/<model_version>`; log one row per configuration
+    and the per-model `[mean]_N_setups` rows to `<data_root>/../log/<datetime>.txt`.  The checkpoint is saved here after training
+    (the reference's train_pcnet does it, :361).  Models by name: PCNet, PCNet_no_mask, PCNet_no_rough, PCNet_no_mask_no_rough,
+    PCNet_w/o_refine.  Returns (the last model, the log as a DataFrame, the last configuration)."""
+    from os.path import join
+    from . import io, metrics
+    data_root = cfg_default.data_root
+    device = torch.device(cfg_default.device)
+    rows, log_file = _init_log(join(data_root, '../log'))
+    pcnet = cfg = None
+    for setup_name in cfg_default.setup_list:
+        cam_scene, cam_train, prj_train, cam_mask, mask_corners, valid_data = _setup_data(cfg_default, setup_name, device,
+                                                                                         cfg_default.center_crop)
+        for cfg, model_name, loss, num_train, model_version in _configurations(cfg_default, setup_name):
+            if not model_name.startswith('PCNet'):
+                raise ValueError(f'train_eval_pcnet: unknown model {model_name!r} (one of {PCNET_MODELS})')
+            train_data = dict(cam_scene=cam_scene, cam_train=cam_train[:num_train], prj_train=prj_train[:num_train], mask=cam_mask)
+            pcnet = _build_pcnet(model_name, cam_mask, mask_corners, tuple(cam_train.shape[-2:]), device)
+            _print_options(cfg)
+            ckpt_dir = join(data_root, '../checkpoint')
+            if not cfg.load_pretrained:
+                print(f'------------------------------------ Start training {model_name:s} ---------------------------')
+                pcnet, _, _, _ = train_pcnet(pcnet, train_data, valid_data, cfg)
+                print('Checkpoint saved to ' + io.save_checkpoint(ckpt_dir, pcnet, io.opt_to_string(cfg)))
+            else:
+                print(f'------------------------------------ Loading pretrained {model_name:s} ---------------------------')
+                pcnet.load_state_dict(torch.load(join(ckpt_dir, io.opt_to_string(cfg) + '.pth'), map_location=device))
+            cam_valid_infer = evaluate_model(pcnet, valid_data)[-1]
+            rows.append([setup_name, model_name, loss, num_train, cfg.batch_size, cfg.max_iters,
+                         *metrics.calc_img_dists(cam_valid_infer, valid_data['cam_valid'])])
+            _write_log(rows, log_file)
+            infer_path = join(data_root, 'setups', setup_name, 'cam/infer/test', model_version)
+            io.save_imgs(cam_valid_infer, infer_path)
+            print('Inferred camera-captured (relit) images saved to ' + infer_path)
+    rows += _mean_rows(rows, cfg_default.model_list, len(cfg_default.setup_list))
+    ret = _write_log(rows, log_file)
+    print(ret.to_string(justify='center', float_format='%.4f'))
+    return pcnet, ret, cfg
+
+
+def train_eval_compennet_pp(cfg_default):
+    """train_network.py:597-733, like `train_eval_pcnet` for CompenNet++: a CompenNet initialised once by `init_compennet` (its
+    checkpoint is loaded when present), then per configuration a WarpingNet with the affine from the mask corners + a copy of that
+    CompenNet, trained by `train_compennet_pp` (seed 0; it saves the checkpoint itself) or loaded; the inferred projector images go to
+    `<setup>/prj/infer/test/<model_version>`, and when `<setup>/cam/desire/test` exists its compensations to `<setup>/prj/cmp/test/
+    <model_version>`.  An optional `cfg_default['init_compennet']` = dict(max_iters=, batch_size=, num_train=) shrinks the
+    initialisation run (its defaults are the reference's)."""
+    import warnings
+    from os.path import join
+    from . import io, metrics
+    from .models import CompenNet
+    data_root = cfg_default.data_root
+    device = torch.device(cfg_default.device)
+    rows, log_file = _init_log(join(data_root, '../log'))
+    compen_net = init_compennet(CompenNet().to(device), data_root, cfg_default, **(cfg_default.get('init_compennet') or {}))
+    model = cfg = None
+    for setup_name in cfg_default.setup_list:
+        setup_path = join(data_root, 'setups', setup_name)
+        cam_scene, cam_train, prj_train, cam_mask, mask_corners, valid_data = _setup_data(cfg_default, setup_name, device, False)
+        prj_size = tuple(prj_train.shape[2:4])
+        for cfg, model_name, loss, num_train, model_version in _configurations(cfg_default, setup_name):
+            train_data = dict(cam_scene=cam_scene, cam_train=cam_train[:num_train], prj_train=prj_train[:num_train], mask=cam_mask)
+            model = _build_compennet_pp(model_name, compen_net, mask_corners, prj_size, device)
+            _print_options(cfg)
+            if not cfg.load_pretrained:
+                print(f'------------------------------------ Start training {model_name:s} ---------------------------')
+                model, _, _, _ = train_compennet_pp(model, train_data, valid_data, cfg)
+            else:
+                print(f'------------------------------------ Loading pretrained {model_name:s} ---------------------------')
+                model.load_state_dict(torch.load(join(data_root, '../checkpoint', io.opt_to_string(cfg) + '.pth'), map_location=device))
+            prj_valid_infer = evaluate_model(model, valid_data)[-1]
+            rows.append([setup_name, model_name, loss, num_train, cfg.batch_size, cfg.max_iters,
+                         *metrics.calc_img_dists(prj_valid_infer, valid_data['prj_valid'])])
+            _write_log(rows, log_file)
+            infer_path = join(setup_path, 'prj/infer/test', model_version)
+            io.save_imgs(prj_valid_infer, infer_path)
+            print('Inferred projector input validation images saved to ' + infer_path)
+            desire_path = join(setup_path, 'cam/desire/test')
+            if os.path.isdir(desire_path):
+                desire = io.torch_imread_mt(desire_path)
+                with torch.no_grad():
+                    cmp = torch.cat([model(d.to(device), cam_scene.expand(d.shape[0], -1, -1, -1)).cpu() for d in desire.split(16)])
+                io.save_imgs(cmp, join(setup_path, 'prj/cmp/test', model_version))
+                print('Compensation images saved to ' + join(setup_path, 'prj/cmp/test', model_version))
+            else:
+                warnings.warn(f'images and folder {desire_path:s} does not exist, no compensation images saved!')
+    rows += _mean_rows(rows, cfg_default.model_list, len(cfg_default.setup_list))
+    ret = _write_log(rows, log_file)
+    print(ret.to_string(justify='center', float_format='%.4f'))
+    return model, ret, cfg
