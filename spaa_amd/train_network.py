@@ -1,19 +1,23 @@
-"""PCNet and CompenNet++ training steps on HIP.  CompenNet++: `CompenNetTrainer`,
-`train_compennet_pp`, `init_compennet`, `evaluate_model` further down (train_network.py:98-232, :395-441); the drivers in front of
-the attack -- `load_data`, `get_model_train_cfg`, `train_eval_pcnet`, `train_eval_compennet_pp` (:39-82, :444-733) -- at the end.
+"""PCNet and CompenNet++ training on HIP.  First what the two trainers share (`_TrainedPlans`, `_GridTrainer`,
+`_LossHead`, `_adam`), then PCNet (`PCNetTrainer`, `compute_loss`, `train_pcnet`: train_network.py:235-392), CompenNet++
+(`CompenNetTrainer`, `evaluate_model`, `train_compennet_pp`, `init_compennet`: :98-232, :395-441) and the drivers in front of the
+attack (`load_data`, `get_model_train_cfg`, `train_eval_pcnet`, `train_eval_compennet_pp`: :39-82, :444-733).
 
-Mirrors `train_pcnet` of /root/reference/src/python/train_network.py:235-363 and `compute_loss` :367-392: one iteration =
+`PCNetTrainer` mirrors `train_pcnet` of the reference's train_network.py:235-363 and `compute_loss` :367-392: one iteration =
 forward of PCNet (WarpingNet with its CURRENT parameters: the sampling grid is rebuilt every step, models.py:163-185) ->
 l1 [+ (1 - SSIM)] loss -> gradients of all 44 parameter tensors -> three Adam optimisers (affine/TPS lr 1e-2, grid-refine
 net lr 5e-3, ShadingNet lr 1e-3 with L2 weight decay `l2_reg`) with MultiStepLR(milestones 100 / 1200 / 1800, gamma
-`lr_drop_ratio`) -> `l1` only for the first 400 iterations, then `l1+ssim` (:300-303).
+`lr_drop_ratio`) -> `l1` only for the first 400 iterations, then `l1+ssim` (:300-303).  `CompenNetTrainer`: see its docstring.
 
 Everything arithmetic runs in libspaa_hip.so:
-  forward / input gradients      PCNetEngine (tapconv kernels; the packed weights are refreshed on the device each step)
-  weight / bias gradients        spaa_tapconv_wgrad          (csrc/tapconv_wgrad.hip)
-  loss + its gradient            spaa_train_loss_fwd_bwd     (csrc/color.hip)
-  grid / affine / TPS gradients  spaa_warp_bwd_grid, spaa_warp_finish_grid_bwd, spaa_warp_coarse_grid_bwd (csrc/train_ops.hip)
-  optimiser                      spaa_adam_step
+  PCNet forward / input gradients  PCNetEngine (tapconv kernels; the packed weights are refreshed on the device each step)
+  CompenNet forward / backward     tapconv plans (_CompenNetEngine), spaa_batch_sum_gate, spaa_relu_gate; the warps: spaa_warp_fwd
+  weight / bias gradients          spaa_tapconv_wgrad          (csrc/tapconv_wgrad.hip)
+  loss + its gradient              spaa_train_loss_fwd_bwd     (csrc/color.hip), spaa_select_grad (clamp gate)
+  grid (current parameters)        spaa_warp_coarse_grid, refine-net tapconv plans, spaa_warp_finish_grid
+  grid / affine / TPS gradients    spaa_warp_bwd_grid (PCNet) or spaa_warp_bwd_grid2 (CompenNet++), spaa_warp_finish_grid_bwd,
+                                   spaa_warp_coarse_grid_bwd   (csrc/train_ops.hip)
+  optimiser                        spaa_adam_step
 PyTorch supplies device memory and index plumbing (re-packing a changed parameter into the kernels' layout through
 precomputed index maps).  No CPU fallback.
 """
@@ -27,10 +31,14 @@ from . import _lib
 from . import convplan as cp
 from .models import PCNet, PCNetEngine, to_nhwc4, to_nchw, C_ptr, transposed_taps
 
-# (parameter module name, forward builder, input-gradient builder) exactly as PCNetEngine builds them (models.py)
+# ShadingNet's convolutions, module name -> (stride, padding), as PCNetEngine builds them (models.py); transConv1 / 2 and skipConv1 apart
 _SHADING = {
     'conv1': (2, 1), 'conv2': (2, 1), 'conv3': (1, 1), 'conv4': (1, 1), 'conv5': (1, 1), 'conv1_s': (2, 1),
     'conv2_s': (2, 1), 'conv3_s': (1, 1), 'conv4_s': (1, 1), 'conv6': (1, 1), 'skipConv3': (1, 1), 'skipConv2': (1, 0)}
+
+
+def _zeros(dev):
+    return lambda *shape: torch.zeros(*shape, device=dev)
 
 
 def _window(window_size=11, sigma=1.5):
@@ -39,6 +47,166 @@ def _window(window_size=11, sigma=1.5):
     return g.mm(g.t()).float().reshape(-1).contiguous()
 
 
+# ================================================================================================================
+# What the two trainers share: trained plans, the WarpingNet's grid, the loss head, Adam
+# ================================================================================================================
+class _TrainedPlans:
+    """The plans whose packed weights follow the parameters: `refresh()` re-packs each on the device from its parameter."""
+
+    def __init__(self, dev):
+        self.dev, self.maps = dev, []   # maps: (plan, weight parameter, bias parameter or None)
+
+    def reg(self, plan, builder, mod, with_bias):
+        cp.attach_maps(plan, builder, mod.weight.detach().cpu())
+        self.maps.append((plan, mod.weight, mod.bias if with_bias else None))
+        return plan
+
+    def wg_plan(self, mod, builder):
+        """A plan used for its geometry only (taps, classes, packing layout): tap list on the device, unpack map attached."""
+        w = mod.weight.detach().cpu()
+        pl = builder(w)
+        pl.weights, pl.taps, pl.w_split = pl.weights.to(self.dev), pl.taps.to(self.dev), None
+        cp.attach_maps(pl, builder, w)
+        return pl
+
+    def dgrad(self, mod, deconv, st, pad, name):
+        """The registered input-gradient plan of one trained convolution (`deconv`: a transposed one)."""
+        bwd = cp.deconv_dgrad_plan if deconv else cp.conv_dgrad_plan
+        return self.reg(bwd(mod.weight, st, pad, self.dev, name), lambda w: bwd(w, st, pad, 'cpu'), mod, False)
+
+    def layer(self, mod, deconv, st, pad, names, dgrad=True):
+        """(forward, input-gradient, weight-gradient) plans of one trained convolution, the first two registered and named `names`.
+        A transposed convolution's weight-gradient plan is unfolded (one weight matrix per output-parity class); without `dgrad`
+        there is no input-gradient plan (None)."""
+        fwd, unfold = (cp.deconv_fwd_plan, dict(fold=False)) if deconv else (cp.conv_fwd_plan, {})
+        f = self.reg(fwd(mod.weight, mod.bias, st, pad, self.dev, names[0]), lambda w: fwd(w, None, st, pad, 'cpu'), mod, True)
+        wg = self.wg_plan(mod, lambda w: fwd(w, None, st, pad, 'cpu', **unfold))
+        return f, self.dgrad(mod, deconv, st, pad, names[1]) if dgrad else None, wg
+
+    def refresh(self):
+        for plan, w, b in self.maps:
+            plan.refresh(w, b)
+
+
+class _GridTrainer:
+    """The WarpingNet's sampling grid under training: `forward()` builds it from the CURRENT parameters (models.py:168-178) and keeps
+    every intermediate; `backward(grads)` turns the gradient w.r.t. the fine grid (`ws['g_fine']`, filled by the caller's own warp
+    kernel) into the gradients of the grid-refine net, `affine_mat` and `theta`.  `src_size`: the size of the images the grid samples
+    (PCNet: the projector's; CompenNet++: the camera's).  Without the grid-refine net (`with_refine=False`) there are no refine plans."""
+
+    def __init__(self, wn, src_size, plans, dev):
+        self.wn, self.src_size = wn, tuple(src_size)
+        H, W = self.out_size = wn.out_size
+        z = _zeros(dev)
+        ncol = 6 + 2 * (wn.nctrl + 2)
+        self.ws = dict(coarse=z(1, H, W, 4), fine=z(H, W, 4), g_fine=z(H, W, 4), g_sum=z(1, H, W, 4),
+                       partial=z(((H * W + 255) // 256) * ncol), g_params=z(ncol))
+        self.rf, self.rd, self.rwg = {}, {}, {}
+        if not wn.with_refine:
+            return
+        # grid-refine net (models.py:123-134): two convolutions, two transposed convolutions
+        for i, deconv, pad in ((0, False, 1), (2, False, 1), (4, True, 0), (6, True, 0)):
+            self.rf[i], self.rd[i], self.rwg[i] = plans.layer(wn.grid_refine_net[i], deconv, 2, pad, (f'refine{i}', f'refine{i}_dgrad'))
+        self.ws.update(r0=z(1, H // 2, W // 2, 32), r2=z(1, H // 4, W // 4, 64), r4=z(1, H // 2, W // 2, 32), refine=z(1, H, W, 4),
+                       g_r6=z(1, H, W, 4), g_r4=z(1, H // 2, W // 2, 32), g_r2=z(1, H // 4, W // 4, 64),
+                       g_r0=z(1, H // 2, W // 2, 32), g_c0=z(1, H, W, 4))
+
+    def forward(self):
+        """The fine grid [H,W,4] (models.py:168-178 with the current parameters)."""
+        p, wn, ws = _lib.ptr, self.wn, self.ws
+        (hi, wi), (H, W) = self.src_size, self.out_size
+        self._aff = wn.affine_mat.detach().float().contiguous().view(-1)
+        self._theta = wn.theta.detach().float().contiguous().view(-1)
+        self._ctrl = wn.ctrl_pts.detach().float().contiguous().view(-1)
+        _lib.call('spaa_warp_coarse_grid', p(self._aff), p(self._theta), p(self._ctrl), wn.nctrl, hi, wi, H, W, p(ws['coarse']))
+        if self.rf:
+            R, L = _lib.ACT_RELU, _lib.ACT_LEAKY01
+            self.rf[0].run(ws['coarse'], ws['r0'], act=R)
+            self.rf[2].run(ws['r0'], ws['r2'], act=R)
+            self.rf[4].run(ws['r2'], ws['r4'], act=R)
+            self.rf[6].run(ws['r4'], ws['refine'], act=L)
+        _lib.call('spaa_warp_finish_grid', p(ws['coarse']), p(ws.get('refine')), p(ws['fine']), H * W)
+        return ws['fine']
+
+    def backward(self, grads):
+        p, wn, ws = _lib.ptr, self.wn, self.ws
+        (hi, wi), (H, W) = self.src_size, self.out_size
+        _lib.call('spaa_warp_finish_grid_bwd', p(ws['g_fine']), p(ws['coarse']), p(ws.get('refine')), p(ws['g_sum']),
+                  p(ws.get('g_r6')), H * W)
+        g_coarse = ws['g_sum']   # (without the refine net the coarse grid is the fine grid before the clamp)
+        if self.rf:
+            wp = 'warping_net.grid_refine_net.'
+
+            def rwgrad(i, inp, gout):
+                dw, db = self.rwg[i].wgrad(inp, gout)
+                grads[wp + f'{i}.weight'] = self.rwg[i].unpack_grad(dw)
+                grads[wp + f'{i}.bias'] = db
+
+            rwgrad(6, ws['r4'], ws['g_r6'])
+            self.rd[6].run(ws['g_r6'], ws['g_r4'], gate=ws['r4'])
+            rwgrad(4, ws['r2'], ws['g_r4'])
+            self.rd[4].run(ws['g_r4'], ws['g_r2'], gate=ws['r2'])
+            rwgrad(2, ws['r0'], ws['g_r2'])
+            self.rd[2].run(ws['g_r2'], ws['g_r0'], gate=ws['r0'])
+            rwgrad(0, ws['coarse'], ws['g_r0'])
+            self.rd[0].run(ws['g_r0'], ws['g_c0'], add=ws['g_sum'])               # + the skip connection (models.py:176)
+            g_coarse = ws['g_c0']
+        _lib.call('spaa_warp_coarse_grid_bwd', p(g_coarse), p(self._aff), p(self._theta), p(self._ctrl), wn.nctrl, hi, wi, H, W,
+                  p(ws['partial']), p(ws['g_params']))
+        grads['warping_net.affine_mat'] = ws['g_params'][:6].view(1, 2, 3)
+        grads['warping_net.theta'] = ws['g_params'][6:].view(1, wn.nctrl + 2, 2)
+
+
+class _LossHead:
+    """compute_loss (train_network.py:367-392) and its gradient as one launch of spaa_train_loss_fwd_bwd, workspaces kept across steps.
+    `gate`: also the workspace of the output layer's clamp / ReLU gate (the trainers; `compute_loss` takes the values alone)."""
+
+    def __init__(self, B, H, W, dev, gate=True):
+        z = _zeros(dev)
+        self.B, self.H, self.W = B, H, W
+        self.window = _window().to(dev)
+        nblk = ((H + 15) // 16) * ((W + 15) // 16)
+        self.ws = dict(mmu=z(B, H, W, 4), m11=z(B, H, W, 4), m12=z(B, H, W, 4), partial=z(B * nblk, 3), gY=z(B, H, W, 4))
+        if gate:
+            self.ws['gP'] = z(B, H, W, 4)
+            self.ones_state = torch.ones(B, 4, dtype=torch.int32, device=dev)
+
+    def launch(self, y4, t4, l1_w, ssim_w):
+        p, ws = _lib.ptr, self.ws
+        _lib.call('spaa_train_loss_fwd_bwd', p(y4), p(t4), p(self.window), l1_w, ssim_w, p(ws['mmu']), p(ws['m11']), p(ws['m12']),
+                  p(ws['partial']), p(ws['gY']), self.B, self.H, self.W)
+
+    def grad(self, y4, t4, ypre, loss):
+        """The loss `loss` of the inferred image y4 against t4; returns its gradient w.r.t. the output layer's pre-activation
+        (`ypre`: relu of it, the clamp / ReLU gate)."""
+        p, ws = _lib.ptr, self.ws
+        self.launch(y4, t4, 1.0 if 'l1' in loss else 0.0, 1.0 if 'ssim' in loss else 0.0)
+        _lib.call('spaa_select_grad', p(ws['gY']), p(ws['gY']), p(self.ones_state), p(ypre), p(ws['gP']), self.B, self.H * self.W)
+        return ws['gP']
+
+    def value(self, loss):
+        """(loss value, l2 (MSE) value) of the last `grad` as Python floats: the one host sync of a step."""
+        part = self.ws['partial'].sum(dim=0).cpu()
+        n_el = 3.0 * self.B * self.H * self.W
+        l1_w, ssim_w = (1.0 if 'l1' in loss else 0.0), (1.0 if 'ssim' in loss else 0.0)
+        l1, l2 = float(part[1]) / n_el, float(part[2]) / n_el
+        return l1_w * l1 + ssim_w * (1.0 - float(part[0]) / n_el), l2
+
+
+def _adam(params, grads, m, v, names, lr, wd, t):
+    """Step `t` of torch.optim.Adam (betas 0.9 / 0.999, eps 1e-8, L2 weight decay `wd`) on the parameters `names`."""
+    p = _lib.ptr
+    for n in names:
+        prm = params[n]
+        gt = grads[n].contiguous()
+        assert gt.numel() == prm.numel(), n
+        _lib.call('spaa_adam_step', p(prm.data.view(-1)), p(gt.view(-1)), p(m[n].view(-1)), p(v[n].view(-1)), prm.numel(), lr, 0.9,
+                  0.999, 1e-8, wd, t)
+
+
+# ================================================================================================================
+# PCNet training (train_network.py:235-363)
+# ================================================================================================================
 class PCNetTrainer:
     """State of one PCNet training run: engine, per-parameter Adam moments, schedules.  `step(prj_batch, cam_batch)` is one
     iteration of the reference's loop body (train_network.py:293-357).
@@ -76,107 +244,61 @@ class PCNetTrainer:
             self.scene1 = to_nhwc4(s[:1].contiguous())
             self.scene4 = to_nhwc4(s.expand(batch_size, -1, -1, -1).contiguous())
             self.Hc, self.Wc = wn.out_size
-            self.window = _window().to(dev)
-            self._build(wn, sn)
+            self.loss = _LossHead(batch_size, self.Hc, self.Wc, dev)
+            # parameter groups of train_network.py:247-256 (a frozen ShadingNet: torch.optim.Adam skips parameters without a gradient)
+            self.params = dict(pcnet.named_parameters())
+            self.groups = {
+                'w1': dict(names=['warping_net.affine_mat', 'warping_net.theta'], lr=1e-2, wd=0.0, milestone=100),
+                'w2': dict(names=[n for n in self.params if 'warping_net.grid_refine_net' in n], lr=5e-3, wd=0.0, milestone=1200),
+                's': dict(names=[] if self.fix_shading else [n for n in self.params if 'warping_net' not in n], lr=1e-3,
+                          wd=self.l2_reg, milestone=1800)}
+            trained = [n for g in self.groups.values() for n in g['names']]
+            self.m = {n: torch.zeros_like(self.params[n], device=dev) for n in trained}
+            self.v = {n: torch.zeros_like(self.params[n], device=dev) for n in trained}
+        self.grads = {}
+        self.eng = None   # created at the first step (needs the projector size)
         self.iters = 0
 
     # ------------------------------------------------------------------------------------------------------------
-    def _build(self, wn, sn):
-        dev, B = self.dev, self.B
-        self.eng = None   # created at the first step (needs the projector size)
-        # parameter groups of train_network.py:247-256 (a frozen ShadingNet: torch.optim.Adam skips parameters without a gradient)
-        self.params = dict(self.pc.named_parameters())
-        self.groups = {
-            'w1': dict(names=['warping_net.affine_mat', 'warping_net.theta'], lr=1e-2, wd=0.0, milestone=100),
-            'w2': dict(names=[n for n in self.params if 'warping_net.grid_refine_net' in n], lr=5e-3, wd=0.0, milestone=1200),
-            's': dict(names=[] if self.fix_shading else [n for n in self.params if 'warping_net' not in n], lr=1e-3, wd=self.l2_reg,
-                      milestone=1800)}
-        trained = [n for g in self.groups.values() for n in g['names']]
-        self.m = {n: torch.zeros_like(self.params[n], device=dev) for n in trained}
-        self.v = {n: torch.zeros_like(self.params[n], device=dev) for n in trained}
-        self.grads = {}
-
     def _make_engine(self, prj_size):
-        """PCNetEngine + index maps to refresh its packed weights, wgrad plans (unfolded geometry), refine-net plans."""
-        wn, sn = self.pc.warping_net, self.pc.shading_net
-        dev = self.dev
+        """PCNetEngine + index maps to refresh its packed weights, wgrad plans (unfolded geometry), the WarpingNet's grid."""
+        sn, dev = self.pc.shading_net, self.dev
         eng = PCNetEngine(self.pc, self.B, prj_size, fuse_skip2=False)
         eng.fuse_tail = False   # the weight gradients of conv6 / transConv2 read X7 and its gradient
-        self.maps = []   # (plan, parameter, bias parameter or None)
+        plans = self.plans = _TrainedPlans(dev)
 
-        def reg(plan, builder, mod, with_bias):
-            cp.attach_maps(plan, builder, mod.weight.detach().cpu())
-            self.maps.append((plan, mod.weight, mod.bias if with_bias else None))
+        def layers():
+            """(plan name, module, forward builder, input-gradient builder of eng.d's plan or None, weight-gradient builder: its plan matters
+            for its geometry only, a transposed convolution's is unfolded) of every ShadingNet layer as PCNetEngine builds it (models.py)."""
+            for nm, (st, pad) in _SHADING.items():
+                fb = (lambda w, st=st, pad=pad: cp.conv_fwd_plan(w, None, st, pad, 'cpu'))
+                in_ch = (3, 6) if nm == 'conv1_s' else None
+                db = (lambda w, st=st, pad=pad, in_ch=in_ch: cp.conv_dgrad_plan(w, st, pad, 'cpu', in_ch=in_ch))
+                yield nm, getattr(sn, nm), fb, db if nm in eng.d else None, fb
+            for nm, pad in (('transConv1', 1), ('transConv2', 0)):
+                yield (nm, getattr(sn, nm), lambda w, pad=pad: cp.deconv_fwd_plan(w, None, 2, pad, 'cpu'),
+                       lambda w, pad=pad: cp.deconv_dgrad_plan(w, 2, pad, 'cpu'),
+                       lambda w, pad=pad: cp.deconv_fwd_plan(w, None, 2, pad, 'cpu', fold=False))
+            for nm, i, pad in (('skip1a', 0, 0), ('skip1b', 2, 1), ('skip1c', 4, 1)):
+                fb = (lambda w, pad=pad: cp.conv_fwd_plan(w, None, 1, pad, 'cpu'))
+                yield nm, sn.skipConv1[i], fb, None, fb
 
         self.wg, self.skip_d, self.sd = {}, {}, {}
         if not self.fix_shading:   # (a frozen ShadingNet keeps the packed weights the engine was built with)
-            for nm, (st, pad) in _SHADING.items():
-                mod = getattr(sn, nm)
-                reg(eng.f[nm], lambda w, st=st, pad=pad: cp.conv_fwd_plan(w, None, st, pad, 'cpu'), mod, True)
-                if nm in eng.d:
-                    in_ch = (3, 6) if nm == 'conv1_s' else None
-                    reg(eng.d[nm], lambda w, st=st, pad=pad, in_ch=in_ch: cp.conv_dgrad_plan(w, st, pad, 'cpu', in_ch=in_ch), mod, False)
-            for nm, pad in (('transConv1', 1), ('transConv2', 0)):
-                mod = getattr(sn, nm)
-                reg(eng.f[nm], lambda w, pad=pad: cp.deconv_fwd_plan(w, None, 2, pad, 'cpu'), mod, True)
-                reg(eng.d[nm], lambda w, pad=pad: cp.deconv_dgrad_plan(w, 2, pad, 'cpu'), mod, False)
-            for key, i, pad in (('skip1a', 0, 0), ('skip1b', 2, 1), ('skip1c', 4, 1)):
-                reg(eng.f[key], lambda w, pad=pad: cp.conv_fwd_plan(w, None, 1, pad, 'cpu'), sn.skipConv1[i], True)
-            # weight-gradient plans: only the geometry matters (taps / classes / packing layout), built once; transposed
-            # convolutions unfolded (one weight matrix per output-parity class)
-            for nm, (st, pad) in _SHADING.items():
-                self.wg[nm] = self._wg_plan(getattr(sn, nm), lambda w, st=st, pad=pad: cp.conv_fwd_plan(w, None, st, pad, 'cpu'))
-            for nm, pad in (('transConv1', 1), ('transConv2', 0)):
-                self.wg[nm] = self._wg_plan(getattr(sn, nm), lambda w, pad=pad: cp.deconv_fwd_plan(w, None, 2, pad, 'cpu', fold=False))
-            for key, i, pad in (('skip1a', 0, 0), ('skip1b', 2, 1), ('skip1c', 4, 1)):
-                self.wg[key] = self._wg_plan(sn.skipConv1[i], lambda w, pad=pad: cp.conv_fwd_plan(w, None, 1, pad, 'cpu'))
+            for nm, mod, fb, db, wb in layers():
+                plans.reg(eng.f[nm], fb, mod, True)
+                if db is not None:
+                    plans.reg(eng.d[nm], db, mod, False)
+                self.wg[nm] = plans.wg_plan(mod, wb)
             # input-gradient plans of the two inner skipConv1 layers (the attack never needs them: skipConv1 sees the scene only)
             for key, i in (('skip1b', 2), ('skip1c', 4)):
-                mod = sn.skipConv1[i]
-                pl = cp.conv_dgrad_plan(mod.weight, 1, 1, dev, key + '_dgrad')
-                reg(pl, lambda w: cp.conv_dgrad_plan(w, 1, 1, 'cpu'), mod, False)
-                self.skip_d[key] = pl
+                self.skip_d[key] = plans.dgrad(sn.skipConv1[i], False, 1, 1, key + '_dgrad')
             # use_rough=False: the surface branch's input gradients (the engine has none: for the attack the branch is a constant)
-            if not self.rough:
-                for nm in ('conv2_s', 'conv3_s', 'conv4_s'):
-                    st, pad = _SHADING[nm]
-                    mod = getattr(sn, nm)
-                    pl = cp.conv_dgrad_plan(mod.weight, st, pad, dev, 'train.' + nm + '_dgrad')
-                    reg(pl, lambda w, st=st, pad=pad: cp.conv_dgrad_plan(w, st, pad, 'cpu'), mod, False)
-                    self.sd[nm] = pl
-        # grid-refine net (models.py:123-134): forward, input-gradient and weight-gradient plans
-        self.rf, self.rd, self.rwg = {}, {}, {}
-        if self.refine:
-            g = wn.grid_refine_net
-            for i, kind in ((0, 'conv'), (2, 'conv'), (4, 'deconv'), (6, 'deconv')):
-                mod = g[i]
-                if kind == 'conv':
-                    fb = lambda w: cp.conv_fwd_plan(w, None, 2, 1, 'cpu')
-                    db = lambda w: cp.conv_dgrad_plan(w, 2, 1, 'cpu')
-                    self.rf[i] = cp.conv_fwd_plan(mod.weight, mod.bias, 2, 1, dev, f'refine{i}')
-                    self.rd[i] = cp.conv_dgrad_plan(mod.weight, 2, 1, dev, f'refine{i}_dgrad')
-                    wb = fb
-                else:
-                    fb = lambda w: cp.deconv_fwd_plan(w, None, 2, 0, 'cpu')
-                    db = lambda w: cp.deconv_dgrad_plan(w, 2, 0, 'cpu')
-                    self.rf[i] = cp.deconv_fwd_plan(mod.weight, mod.bias, 2, 0, dev, f'refine{i}')
-                    self.rd[i] = cp.deconv_dgrad_plan(mod.weight, 2, 0, dev, f'refine{i}_dgrad')
-                    wb = lambda w: cp.deconv_fwd_plan(w, None, 2, 0, 'cpu', fold=False)
-                reg(self.rf[i], fb, mod, True)
-                reg(self.rd[i], db, mod, False)
-                self.rwg[i] = self._wg_plan(mod, wb)
-        H, W = self.Hc, self.Wc
-
-        def z(*shape):
-            return torch.zeros(*shape, device=dev)
-
-        self.grid_ws = dict(coarse=z(1, H, W, 4), fine=z(H, W, 4), g_fine=z(H, W, 4), g_sum=z(1, H, W, 4),
-                            partial=z(((H * W + 255) // 256) * (6 + 2 * (wn.nctrl + 2))), g_params=z(6 + 2 * (wn.nctrl + 2)))
-        if self.refine:
-            self.grid_ws.update(r0=z(1, H // 2, W // 2, 32), r2=z(1, H // 4, W // 4, 64), r4=z(1, H // 2, W // 2, 32), refine=z(1, H, W, 4),
-                                g_r6=z(1, H, W, 4), g_r4=z(1, H // 2, W // 2, 32), g_r2=z(1, H // 4, W // 4, 64),
-                                g_r0=z(1, H // 2, W // 2, 32), g_c0=z(1, H, W, 4))
-        B = self.B
+            for nm in ('conv2_s', 'conv3_s', 'conv4_s') if not self.rough else ():
+                self.sd[nm] = plans.dgrad(getattr(sn, nm), False, *_SHADING[nm], 'train.' + nm + '_dgrad')
+        self.warp = _GridTrainer(self.pc.warping_net, prj_size, plans, dev)   # (the grid samples the projector image)
+        B, H, W = self.B, self.Hc, self.Wc
+        z = _zeros(dev)
         nb = 1 if self.collapse else B                               # skipConv1 runs at batch 1 when collapsed
         self.t0, self.t1 = z(nb, H, W, 4), z(nb, H, W, 4)            # skipConv1 intermediates (kept for its gradients)
         self.g_r1, self.g_t1, self.g_t0 = z(nb, H, W, 4), z(nb, H, W, 4), z(nb, H, W, 4)
@@ -191,45 +313,14 @@ class PCNetTrainer:
             self.s1m = {k: torch.zeros(1, v[0], v[1], v[2] // 4, dtype=torch.uint8, device=dev) for k, v in shp.items()}
             self.s1g = {k: z(1, *v) for k, v in shp.items()}
             self.s1t = {k: z(1, *shp[k]) for k in ('S1', 'S2', 'S3')}
-        nblk = ((H + 15) // 16) * ((W + 15) // 16)
-        self.loss_ws = dict(mmu=z(B, H, W, 4), m11=z(B, H, W, 4), m12=z(B, H, W, 4), partial=z(B * nblk, 3), gY=z(B, H, W, 4),
-                            gP=z(B, H, W, 4))
-        self.ones_state = torch.ones(B, 4, dtype=torch.int32, device=dev)
         self.eng = eng
 
-    def _wg_plan(self, mod, builder):
-        """A plan used for its geometry only (taps, classes, packing layout): tap list on the device, unpack map attached."""
-        w = mod.weight.detach().cpu()
-        pl = builder(w)
-        pl.weights, pl.taps, pl.w_split = pl.weights.to(self.dev), pl.taps.to(self.dev), None
-        cp.attach_maps(pl, builder, w)
-        return pl
-
-    # ------------------------------------------------------------------------------------------------------------
-    def _refresh_weights(self):
-        for plan, w, b in self.maps:
-            plan.refresh(w, b)
-
-    def _build_grid(self, prj_size):
-        """models.py:168-178 with the current parameters, keeping every intermediate for the backward pass."""
-        wn, ws = self.pc.warping_net, self.grid_ws
-        hi, wi = prj_size
-        H, W = self.Hc, self.Wc
-        self._aff = wn.affine_mat.detach().float().contiguous().view(-1)
-        self._theta = wn.theta.detach().float().contiguous().view(-1)
-        self._ctrl = wn.ctrl_pts.detach().float().contiguous().view(-1)
-        _lib.call('spaa_warp_coarse_grid', _lib.ptr(self._aff), _lib.ptr(self._theta), _lib.ptr(self._ctrl), wn.nctrl, hi, wi,
-                  H, W, _lib.ptr(ws['coarse']))
-        if self.refine:
-            R, L = _lib.ACT_RELU, _lib.ACT_LEAKY01
-            self.rf[0].run(ws['coarse'], ws['r0'], act=R)
-            self.rf[2].run(ws['r0'], ws['r2'], act=R)
-            self.rf[4].run(ws['r2'], ws['r4'], act=R)
-            self.rf[6].run(ws['r4'], ws['refine'], act=L)
-        _lib.call('spaa_warp_finish_grid', _lib.ptr(ws['coarse']), _lib.ptr(ws.get('refine')), _lib.ptr(ws['fine']), H * W)
+    def _build_grid(self):
+        """The engine's grid and taps from the WarpingNet's current parameters."""
         eng = self.eng
-        eng.grid = ws['fine']
-        eng.tap_off, eng.tap_order, eng.tap_wm, eng.tap_src = transposed_taps(eng.grid, prj_size, (H, W), eng.mask, want_table=True)
+        eng.grid = self.warp.forward()
+        eng.tap_off, eng.tap_order, eng.tap_wm, eng.tap_src = transposed_taps(eng.grid, (eng.Hp, eng.Wp), (self.Hc, self.Wc), eng.mask,
+                                                                              want_table=True)
         eng.tiled = None   # (the grid changes every step: the per-tile boxes of the LDS-staged gather are not rebuilt)
 
     def _set_scene(self):
@@ -238,16 +329,14 @@ class PCNetTrainer:
         eng.version += 1
         eng.scene = self.scene4
         R = _lib.ACT_RELU
+        scene, r1 = (self.scene1, self.r1) if self.collapse else (self.scene4, eng.a['R1'])
+        eng.f['skip1a'].run(scene, self.t0, act=R)
+        eng.f['skip1b'].run(self.t0, self.t1, act=R)
+        eng.f['skip1c'].run(self.t1, r1, act=R)
         if not self.collapse:
-            eng.f['skip1a'].run(self.scene4, self.t0, act=R)
-            eng.f['skip1b'].run(self.t0, self.t1, act=R)
-            eng.f['skip1c'].run(self.t1, eng.a['R1'], act=R)
             if not self.rough:
                 eng._surface_branch(self.scene4)
             return
-        eng.f['skip1a'].run(self.scene1, self.t0, act=R)
-        eng.f['skip1b'].run(self.t0, self.t1, act=R)
-        eng.f['skip1c'].run(self.t1, self.r1, act=R)
         eng.a['R1'].copy_(self.r1.expand_as(eng.a['R1']))
         if not self.rough:
             a, m, f = self.s1a, self.s1m, eng.f
@@ -285,47 +374,34 @@ class PCNetTrainer:
         if self.eng is None:
             self._make_engine(tuple(prj_batch.shape[-2:]))
         eng = self.eng
-        prj_size = (eng.Hp, eng.Wp)
         # ---- forward with the current parameters
-        self._refresh_weights()
-        self._build_grid(prj_size)
+        self.plans.refresh()
+        self._build_grid()
         self._set_scene()
         y4 = eng.forward(x4, clamp01=False)                                      # model(prj, scene) :306
-        # ---- loss and its gradient w.r.t. the inferred image (compute_loss :367-392)
-        lw = self.loss_ws
-        l1_w, ssim_w = (1.0 if 'l1' in loss else 0.0), (1.0 if 'ssim' in loss else 0.0)
-        _lib.call('spaa_train_loss_fwd_bwd', p(y4), p(t4), p(self.window), l1_w, ssim_w, p(lw['mmu']), p(lw['m11']), p(lw['m12']),
-                  p(lw['partial']), p(lw['gY']), B, H, W)
-        # clamp / ReLU gate of the output layer: gradient w.r.t. conv6's pre-activation
-        _lib.call('spaa_select_grad', p(lw['gY']), p(lw['gY']), p(self.ones_state), p(eng.a['Ypre']), p(lw['gP']), B, H * W)
+        # ---- loss and its gradient w.r.t. conv6's pre-activation (compute_loss :367-392, then the output layer's clamp / ReLU gate)
+        gP = self.loss.grad(y4, t4, eng.a['Ypre'], loss)
         # ---- backward: input gradients (fills every layer's pre-activation gradient), then weight gradients
-        eng.backward(lw['gP'], input_grad=False)   # (no gradient w.r.t. the projector image: it is data here)
+        eng.backward(gP, input_grad=False)   # (no gradient w.r.t. the projector image: it is data here)
         if not self.fix_shading:
-            self._shading_wgrads()
-        # ---- WarpingNet: grid gradient (summed over the batch), refine net, TPS / affine parameters
-        self._warping_grads(x4)
+            self._shading_wgrads(gP)
+        # ---- WarpingNet: grid gradient (summed over the batch), then refine net, TPS / affine parameters
+        _lib.call('spaa_warp_bwd_grid', p(eng.g['xw']), p(x4), p(eng.grid), p(eng.mask), p(self.warp.ws['g_fine']), B, eng.Hp, eng.Wp,
+                  H, W)
+        self.warp.backward(self.grads)
         # ---- optimiser steps (:318-320) and schedulers (:354-356)
-        gr = self.grads
         self.iters += 1
-        for gname, grp in self.groups.items():
+        for grp in self.groups.values():
             lr = grp['lr'] * (self.gamma if (self.iters - 1) >= grp['milestone'] else 1.0)
-            for n in grp['names']:
-                prm = self.params[n]
-                gt = gr[n].contiguous()
-                assert gt.numel() == prm.numel(), n
-                _lib.call('spaa_adam_step', p(prm.data.view(-1)), p(gt.view(-1)), p(self.m[n].view(-1)), p(self.v[n].view(-1)),
-                          prm.numel(), lr, 0.9, 0.999, 1e-8, grp['wd'], self.iters)
+            _adam(self.params, self.grads, self.m, self.v, grp['names'], lr, grp['wd'], self.iters)
         self.pc.invalidate()
-        part = lw['partial'].sum(dim=0).cpu()
-        n_el = 3.0 * B * H * W
-        l1, l2 = float(part[1]) / n_el, float(part[2]) / n_el
-        total = l1_w * l1 + ssim_w * (1.0 - float(part[0]) / n_el)
-        return total, l2
+        return self.loss.value(loss)
 
-    def _shading_wgrads(self):
-        """Weight and bias gradients of every ShadingNet layer from the pre-activation gradients eng.backward left."""
+    def _shading_wgrads(self, gP):
+        """Weight and bias gradients of every ShadingNet layer from `gP` (w.r.t. conv6's pre-activation) and the pre-activation
+        gradients eng.backward left."""
         p = _lib.ptr
-        eng, lw = self.eng, self.loss_ws
+        eng = self.eng
         a, g = eng.a, eng.g
         gr = self.grads
         wplan = self.wg
@@ -336,7 +412,7 @@ class PCNetTrainer:
             gr[pname + '.bias'] = db
 
         sp = 'shading_net.'
-        wgrad('conv6', sp + 'conv6', a['X7'], lw['gP'])
+        wgrad('conv6', sp + 'conv6', a['X7'], gP)
         wgrad('transConv2', sp + 'transConv2', a['X6'], g['P7'])
         wgrad('transConv1', sp + 'transConv1', a['X5'], g['P6'])
         wgrad('conv5', sp + 'conv5', a['X4'], g['P5'])
@@ -381,49 +457,17 @@ class PCNetTrainer:
             wgrad('conv1_s', sp + 'conv1_s', self.scene4, g['S1'])
         # skipConv1 (on the scene; its output is added to conv6's pre-activation, models.py:291,301)
         if self.collapse:   # (batch 1: the ReLU gate of R1 is the same for every sample, so the batch sum comes first)
-            self._batch_sum(lw['gP'], None, None, self.sum_r1, self.B)
+            self._batch_sum(gP, None, None, self.sum_r1, self.B)
             _lib.call('spaa_relu_gate', p(self.sum_r1), p(self.r1), p(self.g_r1), self.g_r1.numel())
             skip_in = self.scene1
         else:
-            _lib.call('spaa_relu_gate', p(lw['gP']), p(a['R1']), p(self.g_r1), lw['gP'].numel())     # ReLU after skipConv1.4
+            _lib.call('spaa_relu_gate', p(gP), p(a['R1']), p(self.g_r1), gP.numel())                 # ReLU after skipConv1.4
             skip_in = self.scene4
         wgrad('skip1c', sp + 'skipConv1.4', self.t1, self.g_r1)
         self.skip_d['skip1c'].run(self.g_r1, self.g_t1, gate=self.t1)
         wgrad('skip1b', sp + 'skipConv1.2', self.t0, self.g_t1)
         self.skip_d['skip1b'].run(self.g_t1, self.g_t0, gate=self.t0)
         wgrad('skip1a', sp + 'skipConv1.0', skip_in, self.g_t0)
-
-    def _warping_grads(self, x4):
-        """Gradients of the WarpingNet parameters: grid (summed over the batch), refine net, TPS / affine."""
-        p = _lib.ptr
-        eng, ws, gr = self.eng, self.grid_ws, self.grads
-        B, H, W = self.B, self.Hc, self.Wc
-        _lib.call('spaa_warp_bwd_grid', p(eng.g['xw']), p(x4), p(eng.grid), p(eng.mask), p(ws['g_fine']), B, eng.Hp, eng.Wp, H, W)
-        _lib.call('spaa_warp_finish_grid_bwd', p(ws['g_fine']), p(ws['coarse']), p(ws.get('refine')), p(ws['g_sum']),
-                  p(ws.get('g_r6')), H * W)
-        g_coarse = ws['g_sum']   # (without the refine net the coarse grid is the fine grid before the clamp)
-        if self.refine:
-            wp = 'warping_net.grid_refine_net.'
-
-            def rwgrad(i, inp, gout):
-                dw, db = self.rwg[i].wgrad(inp, gout)
-                gr[wp + f'{i}.weight'] = self.rwg[i].unpack_grad(dw)
-                gr[wp + f'{i}.bias'] = db
-
-            rwgrad(6, ws['r4'], ws['g_r6'])
-            self.rd[6].run(ws['g_r6'], ws['g_r4'], gate=ws['r4'])
-            rwgrad(4, ws['r2'], ws['g_r4'])
-            self.rd[4].run(ws['g_r4'], ws['g_r2'], gate=ws['r2'])
-            rwgrad(2, ws['r0'], ws['g_r2'])
-            self.rd[2].run(ws['g_r2'], ws['g_r0'], gate=ws['r0'])
-            rwgrad(0, ws['coarse'], ws['g_r0'])
-            self.rd[0].run(ws['g_r0'], ws['g_c0'], add=ws['g_sum'])               # + the skip connection (models.py:176)
-            g_coarse = ws['g_c0']
-        wn = self.pc.warping_net
-        _lib.call('spaa_warp_coarse_grid_bwd', p(g_coarse), p(self._aff), p(self._theta), p(self._ctrl), wn.nctrl, eng.Hp,
-                  eng.Wp, H, W, p(ws['partial']), p(ws['g_params']))
-        gr['warping_net.affine_mat'] = ws['g_params'][:6].view(1, 2, 3)
-        gr['warping_net.theta'] = ws['g_params'][6:].view(1, wn.nctrl + 2, 2)
 
 
 def compute_loss(prj_infer, prj_train, loss_option):
@@ -435,12 +479,9 @@ def compute_loss(prj_infer, prj_train, loss_option):
     with _lib.on_device(dev):
         y4, t4 = to_nhwc4(prj_infer), to_nhwc4(prj_train.to(dev))
         b, h, w, _ = y4.shape
-        nblk = ((h + 15) // 16) * ((w + 15) // 16)
-        ws = [torch.zeros_like(y4) for _ in range(4)]
-        part = torch.zeros(b * nblk, 3, device=dev)
-        _lib.call('spaa_train_loss_fwd_bwd', _lib.ptr(y4), _lib.ptr(t4), _lib.ptr(_window().to(dev)), 1.0, 1.0, _lib.ptr(ws[0]),
-                  _lib.ptr(ws[1]), _lib.ptr(ws[2]), _lib.ptr(part), _lib.ptr(ws[3]), b, h, w)
-        s = part.sum(dim=0) / (3.0 * b * h * w)
+        head = _LossHead(b, h, w, dev, gate=False)
+        head.launch(y4, t4, 1.0, 1.0)   # (both terms always; the option picks from them below)
+        s = head.ws['partial'].sum(dim=0) / (3.0 * b * h * w)
         loss = torch.zeros((), device=dev)
         if 'l1' in loss_option:
             loss = loss + s[1]
@@ -455,7 +496,7 @@ def train_pcnet(model, train_data, valid_data, cfg):
     """train_network.py:235-363 (without the visdom plots): `train_data` = dict(cam_scene [1,3,H,W], cam_train, prj_train),
     `cfg` with max_iters, batch_size, num_train, l2_reg, lr_drop_ratio, device.  Returns (model, valid_psnr, valid_rmse,
     valid_ssim) like the reference."""
-    get = (lambda k, d=None: cfg[k] if k in cfg else d) if isinstance(cfg, dict) else (lambda k, d=None: getattr(cfg, k, d))
+    get = _cfg_getter(cfg)
     dev = torch.device(get('device', 'cuda'))
     tr = PCNetTrainer(model, train_data['cam_scene'], get('batch_size'), get('l2_reg', 1e-4), get('lr_drop_ratio', 0.2), dev)
     cam_train, prj_train = train_data['cam_train'], train_data['prj_train']
@@ -491,37 +532,20 @@ class _CompenNetEngine:
     The backbone runs at batch B.  The surface branch (conv1_s .. conv4_s) runs once, at batch 1: the scene is one image
     expanded to the batch (train_network.py:139), so every sample's branch is the same.  Its outputs are broadcast into the
     backbone's residual inputs; its gradient is the batch sum of the backbone pre-activation gradients it feeds
-    (spaa_batch_sum_gate), the same gradient as the reference's up to summation order.  Packed weights are refreshed on the
-    device each step (attach_maps / ConvPlan.refresh).  `input_grad`: also produce the gradients w.r.t. both inputs (the
-    warped camera image and the warped scene: CompenNet++ needs them for the grid)."""
+    (spaa_batch_sum_gate), the same gradient as the reference's up to summation order.  Every plan is registered with `plans`
+    (_TrainedPlans), which refreshes the packed weights on the device each step.  `input_grad`: also produce the gradients
+    w.r.t. both inputs (the warped camera image and the warped scene: CompenNet++ needs them for the grid)."""
 
-    def __init__(self, cn, B, H, W, dev, input_grad):
+    def __init__(self, cn, B, H, W, dev, plans, input_grad):
         self.cn, self.B, self.H, self.W, self.dev, self.input_grad = cn, B, H, W, dev, input_grad
-        self.maps = []   # (plan, weight parameter, bias parameter or None) of every plan whose packed weights must follow training
         self.f, self.d, self.wg = {}, {}, {}
-        need_d = set(_COMPEN_CONV) | set(_COMPEN_DECONV)
-        if not input_grad:
-            need_d -= {'conv1', 'conv1_s', 'skipConv1.0'}
-        for nm, (st, pad) in _COMPEN_CONV.items():
-            mod = cn.get_submodule(nm)
-            fb = (lambda w, st=st, pad=pad: cp.conv_fwd_plan(w, None, st, pad, 'cpu'))
-            self.f[nm] = self._reg(cp.conv_fwd_plan(mod.weight, mod.bias, st, pad, dev, 'train.' + nm), fb, mod, True)
-            self.wg[nm] = self._wg_plan(mod, fb)
-            if nm in need_d:
-                db = (lambda w, st=st, pad=pad: cp.conv_dgrad_plan(w, st, pad, 'cpu'))
-                self.d[nm] = self._reg(cp.conv_dgrad_plan(mod.weight, st, pad, dev, 'train.' + nm + '_dgrad'), db, mod, False)
-        for nm in _COMPEN_DECONV:
-            mod = cn.get_submodule(nm)
-            fb = (lambda w: cp.deconv_fwd_plan(w, None, 2, 0, 'cpu'))
-            self.f[nm] = self._reg(cp.deconv_fwd_plan(mod.weight, mod.bias, 2, 0, dev, 'train.' + nm), fb, mod, True)
-            self.wg[nm] = self._wg_plan(mod, lambda w: cp.deconv_fwd_plan(w, None, 2, 0, 'cpu', fold=False))
-            db = (lambda w: cp.deconv_dgrad_plan(w, 2, 0, 'cpu'))
-            self.d[nm] = self._reg(cp.deconv_dgrad_plan(mod.weight, 2, 0, dev, 'train.' + nm + '_dgrad'), db, mod, False)
+        no_d = () if input_grad else ('conv1', 'conv1_s', 'skipConv1.0')   # (the layers that read the inputs: self.d[.] is None)
+        layers = [(nm, False, sp) for nm, sp in _COMPEN_CONV.items()] + [(nm, True, (2, 0)) for nm in _COMPEN_DECONV]
+        for nm, deconv, (st, pad) in layers:
+            self.f[nm], self.d[nm], self.wg[nm] = plans.layer(cn.get_submodule(nm), deconv, st, pad,
+                                                              ('train.' + nm, 'train.' + nm + '_dgrad'), nm not in no_d)
         H2, W2, H4, W4 = H // 2, W // 2, H // 4, W // 4
-
-        def z(*shape):
-            return torch.zeros(*shape, device=dev)
-
+        z = _zeros(dev)
         shp = {'S1': (H2, W2, 32), 'S2': (H4, W4, 64), 'S3': (H4, W4, 128), 'S4': (H4, W4, 256)}
         self.a = {k: z(1, *v) for k, v in shp.items()}                                   # surface branch, batch 1
         self.a.update({'b' + k: z(B, *v) for k, v in shp.items()})                       # ... broadcast to the batch
@@ -533,23 +557,6 @@ class _CompenNetEngine:
                       t1=z(B, H, W, 4), t0=z(B, H, W, 4), xs=z(B, H, W, 4), xw=z(B, H, W, 4),
                       S4=z(1, H4, W4, 256), sum3=z(1, H4, W4, 128), S3=z(1, H4, W4, 128), sum2=z(1, H4, W4, 64), S2=z(1, H4, W4, 64),
                       sum1=z(1, H2, W2, 32), S1=z(1, H2, W2, 32), sw=z(1, H, W, 4))
-
-    def _reg(self, plan, builder, mod, with_bias):
-        cp.attach_maps(plan, builder, mod.weight.detach().cpu())
-        self.maps.append((plan, mod.weight, mod.bias if with_bias else None))
-        return plan
-
-    def _wg_plan(self, mod, builder):
-        """A plan used for its geometry only (taps, classes, packing layout): tap list on the device, unpack map attached."""
-        w = mod.weight.detach().cpu()
-        pl = builder(w)
-        pl.weights, pl.taps, pl.w_split = pl.weights.to(self.dev), pl.taps.to(self.dev), None
-        cp.attach_maps(pl, builder, w)
-        return pl
-
-    def refresh(self):
-        for plan, w, b in self.maps:
-            plan.refresh(w, b)
 
     def forward(self, xw, sw):
         """models.py:74-94: xw [B,H,W,4] the (warped) image, sw [1,H,W,4] the (warped) scene.  Returns (Y, Ypre) [B,H,W,4]:
@@ -642,14 +649,7 @@ class CompenNetTrainer:
     """State of one CompenNet++ (or bare CompenNet) training run: engine, Adam moments, learning rate.  `step(cam_batch,
     prj_batch)` is one iteration of the reference's loop body (train_network.py:180-192) plus its scheduler step (:226):
     one torch.optim.Adam over ALL parameters (WarpingNet included) with L2 weight decay `l2_reg`, StepLR(lr_drop_rate,
-    lr_drop_ratio).  Everything arithmetic runs in libspaa_hip.so:
-      grid (current parameters)      spaa_warp_coarse_grid, refine-net tapconv plans, spaa_warp_finish_grid
-      warps (image and scene)        spaa_warp_fwd
-      CompenNet forward / backward   tapconv plans (_CompenNetEngine), spaa_tapconv_wgrad, spaa_batch_sum_gate, spaa_relu_gate
-      loss + its gradient            spaa_train_loss_fwd_bwd, spaa_select_grad (clamp gate)
-      grid / affine / TPS gradients  spaa_warp_bwd_grid2, spaa_warp_finish_grid_bwd, spaa_warp_coarse_grid_bwd
-      optimiser                      spaa_adam_step
-    PyTorch supplies device memory and index plumbing.  No CPU fallback."""
+    lr_drop_ratio).  The kernels: the module docstring."""
 
     def __init__(self, model, cam_scene, batch_size, lr=1e-3, l2_reg=1e-4, lr_drop_rate=800, lr_drop_ratio=0.2, device='cuda'):
         from .models import CompenNet, CompenNetPlusplus
@@ -685,104 +685,16 @@ class CompenNetTrainer:
         self.params = dict(model.named_parameters())
         with _lib.on_device(dev):
             self.scene4 = to_nhwc4(s.to(dev))
-            self.window = _window().to(dev)
             self.m = {n: torch.zeros_like(p) for n, p in self.params.items()}
             self.v = {n: torch.zeros_like(p) for n, p in self.params.items()}
-            self.eng = _CompenNetEngine(cn, self.B, self.H, self.W, dev, input_grad=self.pp)
+            self.plans = _TrainedPlans(dev)
+            self.eng = _CompenNetEngine(cn, self.B, self.H, self.W, dev, self.plans, input_grad=self.pp)
             if self.pp:
-                self._build_warp()
-
-            def z(*shape):
-                return torch.zeros(*shape, device=dev)
-
-            B, H, W = self.B, self.H, self.W
-            nblk = ((H + 15) // 16) * ((W + 15) // 16)
-            self.loss_ws = dict(mmu=z(B, H, W, 4), m11=z(B, H, W, 4), m12=z(B, H, W, 4), partial=z(B * nblk, 3), gY=z(B, H, W, 4),
-                                gP=z(B, H, W, 4))
-            self.ones_state = torch.ones(B, 4, dtype=torch.int32, device=dev)
+                self.warp = _GridTrainer(wn, (self.Hs, self.Ws), self.plans, dev)   # (the grid samples the camera images)
+                self.xw, self.sw = (torch.zeros(n, self.H, self.W, 4, device=dev) for n in (self.B, 1))   # the warped images, scene
+            self.loss = _LossHead(self.B, self.H, self.W, dev)
         self.grads = {}
         self.iters = 0
-
-    # ------------------------------------------------------------------------------------------------------------
-    def _build_warp(self):
-        """Plans of the grid-refine net (models.py:123-134): forward, input-gradient, weight-gradient; grid workspaces."""
-        wn, dev, eng = self.wn, self.dev, self.eng
-        g = wn.grid_refine_net
-        self.rf, self.rd, self.rwg = {}, {}, {}
-        for i, kind in ((0, 'conv'), (2, 'conv'), (4, 'deconv'), (6, 'deconv')):
-            mod = g[i]
-            if kind == 'conv':
-                fb = (lambda w: cp.conv_fwd_plan(w, None, 2, 1, 'cpu'))
-                db = (lambda w: cp.conv_dgrad_plan(w, 2, 1, 'cpu'))
-                self.rf[i] = cp.conv_fwd_plan(mod.weight, mod.bias, 2, 1, dev, f'refine{i}')
-                self.rd[i] = cp.conv_dgrad_plan(mod.weight, 2, 1, dev, f'refine{i}_dgrad')
-                wb = fb
-            else:
-                fb = (lambda w: cp.deconv_fwd_plan(w, None, 2, 0, 'cpu'))
-                db = (lambda w: cp.deconv_dgrad_plan(w, 2, 0, 'cpu'))
-                self.rf[i] = cp.deconv_fwd_plan(mod.weight, mod.bias, 2, 0, dev, f'refine{i}')
-                self.rd[i] = cp.deconv_dgrad_plan(mod.weight, 2, 0, dev, f'refine{i}_dgrad')
-                wb = (lambda w: cp.deconv_fwd_plan(w, None, 2, 0, 'cpu', fold=False))
-            eng._reg(self.rf[i], fb, mod, True)
-            eng._reg(self.rd[i], db, mod, False)
-            self.rwg[i] = eng._wg_plan(mod, wb)
-        H, W, B = self.H, self.W, self.B
-
-        def z(*shape):
-            return torch.zeros(*shape, device=dev)
-
-        ncol = 6 + 2 * (wn.nctrl + 2)
-        self.grid_ws = dict(coarse=z(1, H, W, 4), r0=z(1, H // 2, W // 2, 32), r2=z(1, H // 4, W // 4, 64),
-                            r4=z(1, H // 2, W // 2, 32), refine=z(1, H, W, 4), fine=z(H, W, 4),
-                            g_fine=z(H, W, 4), g_sum=z(1, H, W, 4), g_r6=z(1, H, W, 4), g_r4=z(1, H // 2, W // 2, 32),
-                            g_r2=z(1, H // 4, W // 4, 64), g_r0=z(1, H // 2, W // 2, 32), g_c0=z(1, H, W, 4),
-                            partial=z(((H * W + 255) // 256) * ncol), g_params=z(ncol))
-        self.xw, self.sw = z(B, H, W, 4), z(1, H, W, 4)
-
-    def _grid_forward(self):
-        """models.py:168-178 with the current parameters, keeping every intermediate for the backward pass."""
-        wn, ws = self.wn, self.grid_ws
-        H, W = self.H, self.W
-        self._aff = wn.affine_mat.detach().float().contiguous().view(-1)
-        self._theta = wn.theta.detach().float().contiguous().view(-1)
-        self._ctrl = wn.ctrl_pts.detach().float().contiguous().view(-1)
-        _lib.call('spaa_warp_coarse_grid', _lib.ptr(self._aff), _lib.ptr(self._theta), _lib.ptr(self._ctrl), wn.nctrl, self.Hs,
-                  self.Ws, H, W, _lib.ptr(ws['coarse']))
-        R, L = _lib.ACT_RELU, _lib.ACT_LEAKY01
-        self.rf[0].run(ws['coarse'], ws['r0'], act=R)
-        self.rf[2].run(ws['r0'], ws['r2'], act=R)
-        self.rf[4].run(ws['r2'], ws['r4'], act=R)
-        self.rf[6].run(ws['r4'], ws['refine'], act=L)
-        _lib.call('spaa_warp_finish_grid', _lib.ptr(ws['coarse']), _lib.ptr(ws['refine']), _lib.ptr(ws['fine']), H * W)
-        return ws['fine']
-
-    def _grid_backward(self, g_xw, cam4, g_sw):
-        """Gradient of the loss w.r.t. the WarpingNet parameters from the gradients w.r.t. BOTH warped images (models.py:208-209)."""
-        p, ws, wn, gr = _lib.ptr, self.grid_ws, self.wn, self.grads
-        H, W = self.H, self.W
-        _lib.call('spaa_warp_bwd_grid2', p(g_xw), p(cam4), self.B, p(g_sw), p(self.scene4), 1, p(ws['fine']), p(ws['g_fine']),
-                  self.Hs, self.Ws, H, W)
-        _lib.call('spaa_warp_finish_grid_bwd', p(ws['g_fine']), p(ws['coarse']), p(ws['refine']), p(ws['g_sum']), p(ws['g_r6']),
-                  H * W)
-        wp = 'warping_net.grid_refine_net.'
-
-        def rwgrad(i, inp, gout):
-            dw, db = self.rwg[i].wgrad(inp, gout)
-            gr[wp + f'{i}.weight'] = self.rwg[i].unpack_grad(dw)
-            gr[wp + f'{i}.bias'] = db
-
-        rwgrad(6, ws['r4'], ws['g_r6'])
-        self.rd[6].run(ws['g_r6'], ws['g_r4'], gate=ws['r4'])
-        rwgrad(4, ws['r2'], ws['g_r4'])
-        self.rd[4].run(ws['g_r4'], ws['g_r2'], gate=ws['r2'])
-        rwgrad(2, ws['r0'], ws['g_r2'])
-        self.rd[2].run(ws['g_r2'], ws['g_r0'], gate=ws['r0'])
-        rwgrad(0, ws['coarse'], ws['g_r0'])
-        self.rd[0].run(ws['g_r0'], ws['g_c0'], add=ws['g_sum'])               # + the skip connection (models.py:176)
-        _lib.call('spaa_warp_coarse_grid_bwd', p(ws['g_c0']), p(self._aff), p(self._theta), p(self._ctrl), wn.nctrl, self.Hs,
-                  self.Ws, H, W, p(ws['partial']), p(ws['g_params']))
-        gr['warping_net.affine_mat'] = ws['g_params'][:6].view(1, 2, 3)
-        gr['warping_net.theta'] = ws['g_params'][6:].view(1, wn.nctrl + 2, 2)
 
     # ------------------------------------------------------------------------------------------------------------
     def step(self, cam_batch, prj_batch, loss='l1+ssim'):
@@ -807,39 +719,30 @@ class CompenNetTrainer:
         cam4 = to_nhwc4(cam_batch.to(self.dev))
         t4 = to_nhwc4(prj_batch.to(self.dev))
         # ---- forward with the current parameters (model(cam, scene) :185)
-        eng.refresh()
+        self.plans.refresh()
         if self.pp:
-            fine = self._grid_forward()
+            fine = self.warp.forward()
             _lib.call('spaa_warp_fwd', p(cam4), p(fine), None, None, p(self.xw), None, B, self.Hs, self.Ws, H, W, 0)
             _lib.call('spaa_warp_fwd', p(self.scene4), p(fine), None, None, p(self.sw), None, 1, self.Hs, self.Ws, H, W, 0)
             xw, sw = self.xw, self.sw
         else:
             xw, sw = cam4, self.scene4
         y4, ypre = eng.forward(xw, sw)
-        # ---- loss and its gradient w.r.t. the output (compute_loss :367-392), then the clamp / ReLU gate of conv6
-        lw = self.loss_ws
-        l1_w, ssim_w = (1.0 if 'l1' in loss else 0.0), (1.0 if 'ssim' in loss else 0.0)
-        _lib.call('spaa_train_loss_fwd_bwd', p(y4), p(t4), p(self.window), l1_w, ssim_w, p(lw['mmu']), p(lw['m11']), p(lw['m12']),
-                  p(lw['partial']), p(lw['gY']), B, H, W)
-        _lib.call('spaa_select_grad', p(lw['gY']), p(lw['gY']), p(self.ones_state), p(ypre), p(lw['gP']), B, H * W)
-        # ---- backward
-        gin = eng.backward(lw['gP'], xw, sw, self.grads, self.prefix)
+        # ---- loss and its gradient w.r.t. conv6's pre-activation (compute_loss :367-392, then the clamp / ReLU gate of conv6)
+        gP = self.loss.grad(y4, t4, ypre, loss)
+        # ---- backward; the WarpingNet's from the gradients w.r.t. BOTH warped images (models.py:208-209)
+        gin = eng.backward(gP, xw, sw, self.grads, self.prefix)
         if self.pp:
-            self._grid_backward(gin[0], cam4, gin[1])
+            _lib.call('spaa_warp_bwd_grid2', p(gin[0]), p(cam4), B, p(gin[1]), p(self.scene4), 1, p(fine), p(self.warp.ws['g_fine']),
+                      self.Hs, self.Ws, H, W)
+            self.warp.backward(self.grads)
         # ---- Adam over all parameters (:190-192), then StepLR (:226)
         self.iters += 1
-        for n, prm in self.params.items():
-            gt = self.grads[n].contiguous()
-            assert gt.numel() == prm.numel(), n
-            _lib.call('spaa_adam_step', p(prm.data.view(-1)), p(gt.view(-1)), p(self.m[n].view(-1)), p(self.v[n].view(-1)),
-                      prm.numel(), self.lr, 0.9, 0.999, 1e-8, self.l2_reg, self.iters)
+        _adam(self.params, self.grads, self.m, self.v, self.params, self.lr, self.l2_reg, self.iters)
         if self.iters % self.lr_drop_rate == 0:
             self.lr *= self.gamma
         self.model.invalidate()
-        part = lw['partial'].sum(dim=0).cpu()
-        n_el = 3.0 * B * H * W
-        l1, l2 = float(part[1]) / n_el, float(part[2]) / n_el
-        return l1_w * l1 + ssim_w * (1.0 - float(part[0]) / n_el), l2
+        return self.loss.value(loss)
 
 
 def _cfg_getter(cfg):
@@ -1094,6 +997,63 @@ def _print_options(cfg):
     print('\n'.join(f'{k}: {v}' for k, v in cfg.items()))
 
 
+def _save_compensations(model, cam_scene, setup_path, model_version):
+    """train_network.py:696-719: the compensations of `<setup>/cam/desire/test` to `<setup>/prj/cmp/test/<model_version>`."""
+    import warnings
+    from os.path import join
+    from . import io
+    desire_path = join(setup_path, 'cam/desire/test')
+    if os.path.isdir(desire_path):
+        desire = io.torch_imread_mt(desire_path)
+        with torch.no_grad():
+            cmp = torch.cat([model(d.to(cam_scene.device), cam_scene.expand(d.shape[0], -1, -1, -1)).cpu() for d in desire.split(16)])
+        io.save_imgs(cmp, join(setup_path, 'prj/cmp/test', model_version))
+        print('Compensation images saved to ' + join(setup_path, 'prj/cmp/test', model_version))
+    else:
+        warnings.warn(f'images and folder {desire_path:s} does not exist, no compensation images saved!')
+
+
+def _train_eval(cfg_default, log, crop, build, train, save_ckpt, gt_key, infer_dir, infer_what, after=None):
+    """The loop of both drivers (train_network.py:476-594, :597-733).  Per model family: `build(model_name, cam_mask, mask_corners,
+    cam_train, prj_train, device)` makes a fresh model; `train` is its train_* function, `save_ckpt` says that the checkpoint is saved
+    here and not by `train`; the model infers `valid_data[gt_key]`, written to `<setup>/<infer_dir>/<model_version>`; `after(model,
+    cam_scene, setup_path, model_version)` is an extra step per configuration.  `log`: `_init_log`'s pair."""
+    from os.path import join
+    from . import io, metrics
+    data_root = cfg_default.data_root
+    device = torch.device(cfg_default.device)
+    rows, log_file = log
+    model = cfg = None
+    for setup_name in cfg_default.setup_list:
+        setup_path = join(data_root, 'setups', setup_name)
+        cam_scene, cam_train, prj_train, cam_mask, mask_corners, valid_data = _setup_data(cfg_default, setup_name, device, crop)
+        for cfg, model_name, loss, num_train, model_version in _configurations(cfg_default, setup_name):
+            model = build(model_name, cam_mask, mask_corners, cam_train, prj_train, device)
+            train_data = dict(cam_scene=cam_scene, cam_train=cam_train[:num_train], prj_train=prj_train[:num_train], mask=cam_mask)
+            _print_options(cfg)
+            if not cfg.load_pretrained:
+                print(f'------------------------------------ Start training {model_name:s} ---------------------------')
+                model = train(model, train_data, valid_data, cfg)[0]
+                if save_ckpt:
+                    print('Checkpoint saved to ' + io.save_checkpoint(join(data_root, '../checkpoint'), model, io.opt_to_string(cfg)))
+            else:
+                print(f'------------------------------------ Loading pretrained {model_name:s} ---------------------------')
+                model.load_state_dict(torch.load(join(data_root, '../checkpoint', io.opt_to_string(cfg) + '.pth'), map_location=device))
+            infer = evaluate_model(model, valid_data)[-1]
+            rows.append([setup_name, model_name, loss, num_train, cfg.batch_size, cfg.max_iters,
+                         *metrics.calc_img_dists(infer, valid_data[gt_key])])
+            _write_log(rows, log_file)
+            infer_path = join(setup_path, infer_dir, model_version)
+            io.save_imgs(infer, infer_path)
+            print(f'Inferred {infer_what} images saved to ' + infer_path)
+            if after is not None:
+                after(model, cam_scene, setup_path, model_version)
+    rows += _mean_rows(rows, cfg_default.model_list, len(cfg_default.setup_list))
+    ret = _write_log(rows, log_file)
+    print(ret.to_string(justify='center', float_format='%.4f'))
+    return model, ret, cfg
+
+
 def train_eval_pcnet(cfg_default):
     """train_network.py:476-594: for every setup x num_train x model x loss of `cfg_default` (get_model_train_cfg), train a PCNet
     (`train_pcnet`) or, with load_pretrained, load `<data_root>/../checkpoint/<io.opt_to_string(cfg)>.pth`; evaluate it on the
@@ -1101,40 +1061,13 @@ def train_eval_pcnet(cfg_default):
     and the per-model `[mean]_N_setups` rows to `<data_root>/../log/<datetime>.txt`.  The checkpoint is saved here after training
     (the reference's train_pcnet does it, :361).  Models by name: PCNet, PCNet_no_mask, PCNet_no_rough, PCNet_no_mask_no_rough,
     PCNet_w/o_refine.  Returns (the last model, the log as a DataFrame, the last configuration)."""
-    from os.path import join
-    from . import io, metrics
-    data_root = cfg_default.data_root
-    device = torch.device(cfg_default.device)
-    rows, log_file = _init_log(join(data_root, '../log'))
-    pcnet = cfg = None
-    for setup_name in cfg_default.setup_list:
-        cam_scene, cam_train, prj_train, cam_mask, mask_corners, valid_data = _setup_data(cfg_default, setup_name, device,
-                                                                                         cfg_default.center_crop)
-        for cfg, model_name, loss, num_train, model_version in _configurations(cfg_default, setup_name):
-            if not model_name.startswith('PCNet'):
-                raise ValueError(f'train_eval_pcnet: unknown model {model_name!r} (one of {PCNET_MODELS})')
-            train_data = dict(cam_scene=cam_scene, cam_train=cam_train[:num_train], prj_train=prj_train[:num_train], mask=cam_mask)
-            pcnet = _build_pcnet(model_name, cam_mask, mask_corners, tuple(cam_train.shape[-2:]), device)
-            _print_options(cfg)
-            ckpt_dir = join(data_root, '../checkpoint')
-            if not cfg.load_pretrained:
-                print(f'------------------------------------ Start training {model_name:s} ---------------------------')
-                pcnet, _, _, _ = train_pcnet(pcnet, train_data, valid_data, cfg)
-                print('Checkpoint saved to ' + io.save_checkpoint(ckpt_dir, pcnet, io.opt_to_string(cfg)))
-            else:
-                print(f'------------------------------------ Loading pretrained {model_name:s} ---------------------------')
-                pcnet.load_state_dict(torch.load(join(ckpt_dir, io.opt_to_string(cfg) + '.pth'), map_location=device))
-            cam_valid_infer = evaluate_model(pcnet, valid_data)[-1]
-            rows.append([setup_name, model_name, loss, num_train, cfg.batch_size, cfg.max_iters,
-                         *metrics.calc_img_dists(cam_valid_infer, valid_data['cam_valid'])])
-            _write_log(rows, log_file)
-            infer_path = join(data_root, 'setups', setup_name, 'cam/infer/test', model_version)
-            io.save_imgs(cam_valid_infer, infer_path)
-            print('Inferred camera-captured (relit) images saved to ' + infer_path)
-    rows += _mean_rows(rows, cfg_default.model_list, len(cfg_default.setup_list))
-    ret = _write_log(rows, log_file)
-    print(ret.to_string(justify='center', float_format='%.4f'))
-    return pcnet, ret, cfg
+    def build(model_name, cam_mask, mask_corners, cam_train, prj_train, device):
+        if not model_name.startswith('PCNet'):
+            raise ValueError(f'train_eval_pcnet: unknown model {model_name!r} (one of {PCNET_MODELS})')
+        return _build_pcnet(model_name, cam_mask, mask_corners, tuple(cam_train.shape[-2:]), device)
+
+    return _train_eval(cfg_default, _init_log(os.path.join(cfg_default.data_root, '../log')), cfg_default.center_crop, build, train_pcnet,
+                       True, 'cam_valid', 'cam/infer/test', 'camera-captured (relit)')
 
 
 def train_eval_compennet_pp(cfg_default):
@@ -1144,46 +1077,13 @@ def train_eval_compennet_pp(cfg_default):
     `<setup>/prj/infer/test/<model_version>`, and when `<setup>/cam/desire/test` exists its compensations to `<setup>/prj/cmp/test/
     <model_version>`.  An optional `cfg_default['init_compennet']` = dict(max_iters=, batch_size=, num_train=) shrinks the
     initialisation run (its defaults are the reference's)."""
-    import warnings
-    from os.path import join
-    from . import io, metrics
     from .models import CompenNet
-    data_root = cfg_default.data_root
-    device = torch.device(cfg_default.device)
-    rows, log_file = _init_log(join(data_root, '../log'))
-    compen_net = init_compennet(CompenNet().to(device), data_root, cfg_default, **(cfg_default.get('init_compennet') or {}))
-    model = cfg = None
-    for setup_name in cfg_default.setup_list:
-        setup_path = join(data_root, 'setups', setup_name)
-        cam_scene, cam_train, prj_train, cam_mask, mask_corners, valid_data = _setup_data(cfg_default, setup_name, device, False)
-        prj_size = tuple(prj_train.shape[2:4])
-        for cfg, model_name, loss, num_train, model_version in _configurations(cfg_default, setup_name):
-            train_data = dict(cam_scene=cam_scene, cam_train=cam_train[:num_train], prj_train=prj_train[:num_train], mask=cam_mask)
-            model = _build_compennet_pp(model_name, compen_net, mask_corners, prj_size, device)
-            _print_options(cfg)
-            if not cfg.load_pretrained:
-                print(f'------------------------------------ Start training {model_name:s} ---------------------------')
-                model, _, _, _ = train_compennet_pp(model, train_data, valid_data, cfg)
-            else:
-                print(f'------------------------------------ Loading pretrained {model_name:s} ---------------------------')
-                model.load_state_dict(torch.load(join(data_root, '../checkpoint', io.opt_to_string(cfg) + '.pth'), map_location=device))
-            prj_valid_infer = evaluate_model(model, valid_data)[-1]
-            rows.append([setup_name, model_name, loss, num_train, cfg.batch_size, cfg.max_iters,
-                         *metrics.calc_img_dists(prj_valid_infer, valid_data['prj_valid'])])
-            _write_log(rows, log_file)
-            infer_path = join(setup_path, 'prj/infer/test', model_version)
-            io.save_imgs(prj_valid_infer, infer_path)
-            print('Inferred projector input validation images saved to ' + infer_path)
-            desire_path = join(setup_path, 'cam/desire/test')
-            if os.path.isdir(desire_path):
-                desire = io.torch_imread_mt(desire_path)
-                with torch.no_grad():
-                    cmp = torch.cat([model(d.to(device), cam_scene.expand(d.shape[0], -1, -1, -1)).cpu() for d in desire.split(16)])
-                io.save_imgs(cmp, join(setup_path, 'prj/cmp/test', model_version))
-                print('Compensation images saved to ' + join(setup_path, 'prj/cmp/test', model_version))
-            else:
-                warnings.warn(f'images and folder {desire_path:s} does not exist, no compensation images saved!')
-    rows += _mean_rows(rows, cfg_default.model_list, len(cfg_default.setup_list))
-    ret = _write_log(rows, log_file)
-    print(ret.to_string(justify='center', float_format='%.4f'))
-    return model, ret, cfg
+    log = _init_log(os.path.join(cfg_default.data_root, '../log'))
+    compen_net = init_compennet(CompenNet().to(torch.device(cfg_default.device)), cfg_default.data_root, cfg_default,
+                                **(cfg_default.get('init_compennet') or {}))
+
+    def build(model_name, cam_mask, mask_corners, cam_train, prj_train, device):
+        return _build_compennet_pp(model_name, compen_net, mask_corners, tuple(prj_train.shape[2:4]), device)
+
+    return _train_eval(cfg_default, log, False, build, train_compennet_pp, False, 'prj_valid', 'prj/infer/test',
+                       'projector input validation', _save_compensations)
