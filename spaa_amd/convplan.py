@@ -10,6 +10,7 @@ so one MFMA kernel serves all of them.  The weights are frozen during an attack
 
 This module only rearranges weights (layout plumbing, on the host); the arithmetic happens in the HIP kernel.
 """
+import collections
 import ctypes as C
 import os
 
@@ -63,13 +64,7 @@ H16P_LEAN_WIDE = int(os.environ.get('SPAA_H16P_LEAN_WIDE', '2'))   # 64-wide two
 DEBUG_H16_2STAGE = int(os.environ.get('SPAA_H16_2STAGE', '0'))      # 1: the fp16 implicit-GEMM kernel never takes its four-stage form (A/B measurements)
 FOLD_K3S2 = os.environ.get('SPAA_FOLD_K3S2', '1') != '0'   # 3x3 / s2 input gradients with few output channels: classes folded
 FOLD_K3S2_MAX_COUT = 32
-FOLD_DECONV = True  # k2/s2 transposed convs: parity classes folded into GEMM rows (one read of the input)
-ENABLE_X6 = True  # build the split-bf16 weight planes (needed by tiles 12-14)
 WINOGRAD = os.environ.get('SPAA_WINOGRAD', '1') != '0'  # 3x3/s1 layers: allow the Winograd F(2x2,3x3) kernel (tile 70)
-
-
-def masked_any(*m):
-    return any(x is not None for x in m)
 
 
 def _load_tune():
@@ -132,6 +127,21 @@ def _ceil(a, b):
     return (a + b - 1) // b * b
 
 
+def _bf16_planes(w, dim=0):
+    """fp32 tensor -> int16 tensor with three planes stacked at `dim`: bf16 h, m, l with w == h + m + l exactly (the operands of
+    the bf16x6 kernels: tapconv_x6.hip)."""
+    planes, rest = [], w
+    for _ in range(3):     # h, then m from what h leaves, then l from what h + m leave
+        planes.append(rest.to(torch.bfloat16))
+        rest = rest - planes[-1].float()
+    return torch.stack(planes, dim).view(torch.int16)
+
+
+# what `ConvPlan.run` passes from step to step: the shape facts of a launch (`_check`) and its kernel (`_choose`)
+_Shape = collections.namedtuple('_Shape', 'b hin win cs_in hout wout cs_out hm wm in_f16 out_f16 cin2k key nepi nmask')
+_Choice = collections.namedtuple('_Choice', 'tile ksplit h16p_cv wino')
+
+
 class TapClassSpec:
     """One output-parity class: output offset and a list of (dy, dx, W[n, c]) taps."""
 
@@ -172,18 +182,10 @@ class ConvPlan:
             w_chunks.append(wp.reshape(-1))
             w_off += npad * kpad
         self.classes_host = classes
+        self._cls_c = (_lib.TapClass * _lib.MAX_CLASSES)(*[_lib.TapClass(**c) for c in self.cls])   # (`cls` as a descriptor holds it, built once: `cls` is not edited after this)
         self.weights = torch.cat(w_chunks).to(device) if w_off > 0 else torch.zeros(4, device=device)
         # the same weights as three bf16 planes with w == h + m + l exactly (tapconv_x6.hip)
-        self.w_split = None
-        if ENABLE_X6 and w_off > 0:
-            parts = []
-            for wp in w_chunks:
-                h = wp.to(torch.bfloat16)
-                r1 = wp - h.float()
-                m = r1.to(torch.bfloat16)
-                lo = (r1 - m.float()).to(torch.bfloat16)
-                parts.append(torch.stack([h, m, lo]).view(torch.int16).reshape(-1))
-            self.w_split = torch.cat(parts).to(device)
+        self.w_split = torch.cat([_bf16_planes(wp).reshape(-1) for wp in w_chunks]).to(device) if w_off > 0 else None
         tl = tap_list if tap_list else [(0, 0)]
         self.tap_range = (min(t[0] for t in tl), max(t[0] for t in tl), min(t[1] for t in tl), max(t[1] for t in tl))
         taps = torch.tensor(tl, dtype=torch.int32).reshape(-1)
@@ -239,31 +241,34 @@ class ConvPlan:
         """Fuse a 1 x 1 convolution of a tensor at OUTPUT resolution into this stride-2 layer (tile 74): `weight2` [Cout, Cin2] (Cin2 =
         32 or 64).  `run(..., inp2=...)` then adds it before bias / residual / activation; the bias becomes the sum of both."""
         assert self.x6p_ok()
-        w2 = weight2.detach().float().reshape(weight2.shape[0], -1).cpu()
-        assert w2.shape[0] == self.cout and w2.shape[1] in (32, 64)
+        w2 = self._second_source(weight2, bias2)
         wp = torch.zeros(self._npad, w2.shape[1])
         wp[:self.cout] = w2
         self.w2_split = split_planes(wp).reshape(-1).to(self._dev)
-        self.cin2 = w2.shape[1]
-        b = self.bias.clone() if self.bias is not None else torch.zeros(self.cout, device=self._dev)
-        if bias2 is not None:
-            b = b + bias2.detach().float().to(b.device)
-        self.bias2 = b          # bias of the fused launch
         return self
 
     def attach_second_source_h16(self, weight2, bias2=None):
         """fp16 storage: the same fusion for a FOLDED stride-2 transposed layer on the patch-staged fp16 kernel (tile 68, nfold = 4):
         `weight2` [Cout, Cin2] rounded to fp16 (as `w_half`).  `run(..., inp2=...)` (fp16 tensors) then adds the 1 x 1 convolution."""
         assert self.nfold == 4 and len(self.cls) == 1 and self.cout % 16 == 0
+        self.w2_half = self._second_source(weight2, bias2).half().contiguous().to(self._dev)
+        return self
+
+    def _second_source(self, weight2, bias2):
+        """What both second-source forms share: `weight2` as an fp32 [Cout, Cin2] host matrix (checked), `cin2`, and `bias2` = the bias
+        of the fused launch (this layer's + the second source's)."""
         w2 = weight2.detach().float().reshape(weight2.shape[0], -1).cpu()
         assert w2.shape[0] == self.cout and w2.shape[1] in (32, 64)
-        self.w2_half = w2.half().contiguous().to(self._dev)
         self.cin2 = w2.shape[1]
         b = self.bias.clone() if self.bias is not None else torch.zeros(self.cout, device=self._dev)
         if bias2 is not None:
             b = b + bias2.detach().float().to(b.device)
         self.bias2 = b
-        return self
+        return w2
+
+    def _wmat(self, c):
+        """The packed fp32 matrix [Npad][Kpad] of class `c` (an entry of `self.cls`): a view of `self.weights`."""
+        return self.weights[c['w_off']:c['w_off'] + self._npad * c['Kpad']].view(self._npad, c['Kpad'])
 
     def c3_ok(self):
         """First layer of a network for csrc/tapconv_c3.hip (tile 76): a convolution over a 3-channel image (NHWC4, zero lane), one
@@ -275,31 +280,21 @@ class ConvPlan:
         """The weights as tile 76 stages them: K = (tap, channel of 3) products only, [NK][3 bf16 planes: w == h + m + l][BN rows][32],
         16-byte chunk c of row n stored at chunk c ^ ((n >> 3 & 1) << 1) (conflict-free fragment reads); packed on first use.
         `half` (fp16-storage mode): ONE plane of the weights rounded to fp16, same rows and swizzle."""
-        if half:
-            if getattr(self, '_c3h', None) is None:
-                nt, c = self.ntaps_total, self.cls[0]
-                nk, bn = (1 if 3 * nt <= 32 else 5), (32 if self.cout <= 32 else 64)
-                w = self.weights[c['w_off']:c['w_off'] + self._npad * c['Kpad']].view(self._npad, c['Kpad'])[:bn, :4 * nt]
-                w = w.reshape(bn, nt, 4)[:, :, :3].reshape(bn, 3 * nt)
-                w = torch.nn.functional.pad(w, (0, 32 * nk - 3 * nt)).float().cpu().half().view(torch.int16)
-                pl = w.view(bn, nk, 4, 8).permute(1, 0, 2, 3).contiguous()                              # [nk][row][chunk][8]
-                n = torch.arange(bn)
-                idx = (torch.arange(4)[None, :] ^ (((n >> 3) & 1) << 1)[:, None])
-                pl = torch.gather(pl, 2, idx[None, :, :, None].expand(nk, bn, 4, 8))
-                self._c3h = pl.contiguous().reshape(-1).to(self._dev)
-            return self._c3h
-        if getattr(self, '_c3', None) is None:
-            nt, c = self.ntaps_total, self.cls[0]
+        attr = '_c3h' if half else '_c3'
+        if getattr(self, attr, None) is None:
+            nt = self.ntaps_total
             nk, bn = (1 if 3 * nt <= 32 else 5), (32 if self.cout <= 32 else 64)
-            w = self.weights[c['w_off']:c['w_off'] + self._npad * c['Kpad']].view(self._npad, c['Kpad'])[:bn, :4 * nt]
+            w = self._wmat(self.cls[0])[:bn, :4 * nt]
             w = w.reshape(bn, nt, 4)[:, :, :3].reshape(bn, 3 * nt)
             w = torch.nn.functional.pad(w, (0, 32 * nk - 3 * nt)).float().cpu()
-            pl = split_planes(w).view(3, bn, nk, 4, 8).permute(2, 0, 1, 3, 4).contiguous()        # [nk][plane][row][chunk][8]
+            pl = w.half().view(torch.int16)[None] if half else split_planes(w)                      # [plane][row][32 nk]
+            npl = pl.shape[0]
+            pl = pl.view(npl, bn, nk, 4, 8).permute(2, 0, 1, 3, 4).contiguous()                     # [nk][plane][row][chunk][8]
             n = torch.arange(bn)
             idx = (torch.arange(4)[None, :] ^ (((n >> 3) & 1) << 1)[:, None])                       # logical chunk held by each slot
-            pl = torch.gather(pl, 3, idx[None, None, :, :, None].expand(nk, 3, bn, 4, 8))
-            self._c3 = pl.contiguous().reshape(-1).to(self._dev)
-        return self._c3
+            pl = torch.gather(pl, 3, idx[None, None, :, :, None].expand(nk, npl, bn, 4, 8))
+            setattr(self, attr, pl.contiguous().reshape(-1).to(self._dev))
+        return getattr(self, attr)
 
     def thin_fold(self, half):
         """The weights in the folded layout of the thin-output matrix-core kernel: GEMM rows = class * 4 + channel (16 rows; rows of
@@ -313,7 +308,7 @@ class ConvPlan:
             tbh, tbw, nkb = max(dy1 - dy0 + 1, 2), dx1 - dx0 + 1, self.cin_p // 32
             wf = torch.zeros(16, tbh, tbw, self.cin_p, device=dev)
             for i, (c, spec) in enumerate(zip(self.cls, self.classes_host)):
-                wp = self.weights[c['w_off']:c['w_off'] + self._npad * c['Kpad']].view(self._npad, c['Kpad'])
+                wp = self._wmat(c)
                 for t, (dy, dx, _w) in enumerate(spec.taps):
                     wf[4 * i:4 * i + self.cout, dy - dy0, dx - dx0] = wp[:self.cout, t * self.cin_p:(t + 1) * self.cin_p]
             w = wf.view(16, tbh, tbw, nkb, 4, 8).permute(3, 2, 1, 0, 4, 5).contiguous()   # [kb][dxi][dyi][row][chunk][8]
@@ -321,14 +316,7 @@ class ConvPlan:
             sw[..., 8:, 0, :], sw[..., 8:, 2, :] = w[..., 8:, 2, :], w[..., 8:, 0, :]
             sw[..., 8:, 1, :], sw[..., 8:, 3, :] = w[..., 8:, 3, :], w[..., 8:, 1, :]
             sw = sw.reshape(nkb, tbw, tbh, 16, 32)
-            if half:
-                planes = sw.half().unsqueeze(2).view(torch.int16)
-            else:
-                h = sw.to(torch.bfloat16)
-                r1 = sw - h.float()
-                m = r1.to(torch.bfloat16)
-                lo = (r1 - m.float()).to(torch.bfloat16)
-                planes = torch.stack([h, m, lo], dim=2).view(torch.int16)               # [kb][dxi][plane][dyi][16][32]
+            planes = sw.half().unsqueeze(2).view(torch.int16) if half else _bf16_planes(sw, 2)   # [kb][dxi][plane][dyi][16][32]
             self._thin[key] = planes.contiguous().reshape(-1)
         return self._thin[key]
 
@@ -339,7 +327,7 @@ class ConvPlan:
             parts = []
             for c in self.cls:
                 k64 = _ceil(c['K'], 64)
-                wp = self.weights[c['w_off']:c['w_off'] + self._npad * c['Kpad']].view(self._npad, c['Kpad'])
+                wp = self._wmat(c)
                 wh = torch.zeros(self._npad, k64, dtype=torch.float16, device=self.weights.device)
                 wh[:, :c['K']] = wp[:, :c['K']].to(torch.float16)
                 parts.append(wh.reshape(-1))
@@ -363,7 +351,27 @@ class ConvPlan:
         `unpool` = (arg-max bytes uint8 [B,Hin/2,Win/2,C], full-size gradient buffer [B,Hin,Win,Cs]): `inp` is the gradient w.r.t. the OUTPUT of
         the 2 x 2 / stride-2 max-pool that followed this layer's input (an input-gradient plan of torchvision VGG-16): where the
         two-workgroup form of the patch-staged fp16 kernel serves the layer the pool's adjoint (with its ReLU gate) runs as the patch
-        prologue and the full-size gradient is never written; anywhere else spaa_maxpool_bwd fills the buffer first."""
+        prologue and the full-size gradient is never written; anywhere else spaa_maxpool_bwd fills the buffer first.
+        Four steps: `_check` (operands -> shape facts), `_choose` (the kernel: tile, K split), `_describe` (the TapConv descriptor),
+        `_launch` (launcher plan, workspace, launch, profile record)."""
+        s = self._check(inp, out, add, gate, aux_out, gate2, mask_out, gate_bits, gate2_bits, inp2, in_coff, in2_coff, out_coff,
+                        pool_adjoint, unpool)
+        ch = self._choose(s, gate is not None and gate_mode == _lib.GATE_MUL, inp2 is not None, pool_adjoint is not None, _wino)
+        if ch.wino:   # (tile and K ranges travel as arguments: the shared Winograd plan keeps no per-call state)
+            return self.wino.run(inp, out, add, gate, gate_mode, act, aux_out, gate2, in_coff, out_coff, add_coff, gate_coff,
+                                 mask_out, gate_bits, gate2_bits, inp2, in2_coff, _wino=(ch.tile, ch.ksplit))
+        d = self._describe(s, ch, inp, out, add, gate, gate_mode, act, aux_out, gate2, in_coff, out_coff, add_coff, gate_coff,
+                           mask_out, gate_bits, gate2_bits, inp2, in2_coff, pool_adjoint)
+        self._launch(d, s, ch, inp, out, inp2, _wino, pool, unpool)
+        return out
+
+    def _class_grid(self, hout, wout):
+        """Pixels of one output-parity class (the GEMM's rows per image): the output's own at stride 1."""
+        return (hout + self.s_out - 1) // self.s_out, (wout + self.s_out - 1) // self.s_out
+
+    def _check(self, inp, out, add, gate, aux_out, gate2, mask_out, gate_bits, gate2_bits, inp2, in_coff, in2_coff, out_coff,
+               pool_adjoint, unpool):
+        """Step 1 of `run`: the operands' devices, storage types and shapes; returns the shape facts the later steps need."""
         _lib.check_dev(inp, out, add, gate, aux_out, gate2, inp2, half_ok=True)
         _lib.check_mask(mask_out, gate_bits, gate2_bits)
         in_f16, out_f16 = inp.dtype == torch.float16, out.dtype == torch.float16
@@ -376,7 +384,7 @@ class ConvPlan:
             assert unpool[1].shape == (b, 2 * hin, 2 * win, cs_in) and unpool[1].dtype == inp.dtype
             hin, win = 2 * hin, 2 * win       # (the layer's input grid; `inp` is at the pooled resolution)
         if pool_adjoint is not None:
-            parg, (hin, win), pgate = pool_adjoint
+            parg, (hin, win), _pgate = pool_adjoint
             if (in_f16 or out_f16 or inp2 is not None or parg.dtype != torch.uint8 or tuple(parg.shape) != tuple(inp.shape) or cs_in != self.cin_p
                     or in_coff or inp.shape[1:3] != ((hin - 1) // 2 + 1, (win - 1) // 2 + 1)):
                 raise ValueError(f'{self.name}: pool_adjoint needs fp32 tensors, arg-max bytes of the pooled gradient\'s shape and a 3/2/1 pool geometry')
@@ -386,47 +394,16 @@ class ConvPlan:
             raise ValueError(f'{self.name}: a two-source plan needs `inp2` [B, H, W, >= {cin2k} channels] of the storage type of `inp`')
         assert b == b2 and cs_in % 4 == 0 and in_coff % 4 == 0 and in_coff + self.cin_p - cin2k <= cs_in
         assert out_coff + self.cout <= cs_out
-        d = _lib.TapConv()
-        d.inp, d.Hin, d.Win, d.Cin, d.in_cstride, d.in_coff = inp.data_ptr(), hin, win, self.cin_p, cs_in, in_coff
-        d.out, d.Hout, d.Wout, d.Cout, d.out_cstride, d.out_coff = out.data_ptr(), hout, wout, self.cout, cs_out, out_coff
-        d.B = b
-        if self.s_out == 1:
-            d.Hm, d.Wm = hout, wout
-        else:
-            d.Hm, d.Wm = (hout + self.s_out - 1) // self.s_out, (wout + self.s_out - 1) // self.s_out
-        d.s_in, d.s_out = self.s_in, self.s_out
-        d.weights, d.taps = self.weights.data_ptr(), self.taps.data_ptr()
-        d.io_dtype = (_lib.IO_IN_F16 if in_f16 else 0) | (_lib.IO_OUT_F16 if out_f16 else 0)
-        if in_f16:
-            if self.cin_p % 32 or any(c['Kpad'] != c['K'] for c in self.cls):
-                raise ValueError(f'{self.name}: fp16-storage input needs Cin % 32 == 0 (got {self.cin_p})')
-            d.w_half = self.half_plane().data_ptr()
-        d.w_split = self.w_split.data_ptr() if self.w_split is not None else None
-        d.bias = self.bias.data_ptr() if self.bias is not None else None
-        if add is not None:
-            assert add.shape[:3] == out.shape[:3] and add_coff + self.cout <= add.shape[3]
-            d.add, d.add_cstride, d.add_coff = add.data_ptr(), add.shape[3], add_coff
-        if gate is not None:
-            assert gate.shape[:3] == out.shape[:3] and gate_coff + self.cout <= gate.shape[3]
-            d.gate, d.gate_cstride, d.gate_coff, d.gate_mode = gate.data_ptr(), gate.shape[3], gate_coff, gate_mode
-        d.act = act
-        if aux_out is not None:
-            assert aux_out.shape == out.shape
-            d.aux_out = aux_out.data_ptr()
-        if gate2 is not None:
-            assert aux_out is not None and gate2.shape[:3] == out.shape[:3] and self.cout <= gate2.shape[3]
-            d.gate2, d.gate2_cstride, d.gate2_coff = gate2.data_ptr(), gate2.shape[3], 0
-        masked = mask_out is not None or gate_bits is not None or gate2_bits is not None
-        if mask_out is not None:
-            assert mask_out.shape == out.shape[:3] + (cs_out // 4,), (mask_out.shape, out.shape)
-            d.mask_out = mask_out.data_ptr()
-        if gate_bits is not None:
-            assert gate is None and gate_bits.shape[:3] == out.shape[:3] and gate_coff + self.cout <= 4 * gate_bits.shape[3]
-            d.gate_bits, d.gate_cstride, d.gate_coff = gate_bits.data_ptr(), 4 * gate_bits.shape[3], gate_coff
-        if gate2_bits is not None:
-            assert gate2 is None and aux_out is not None and gate2_bits.shape[:3] == out.shape[:3] and self.cout <= 4 * gate2_bits.shape[3]
-            d.gate2_bits, d.gate2_cstride, d.gate2_coff = gate2_bits.data_ptr(), 4 * gate2_bits.shape[3], 0
-        key = f'{self.cin_p}_{self.cout}_{self.alg_taps}_{self.s_in}_{self.s_out}_{b * d.Hm * d.Wm}' + ('_fold' if self.nfold > 1 else '')
+        if in_f16 and (self.cin_p % 32 or any(c['Kpad'] != c['K'] for c in self.cls)):
+            raise ValueError(f'{self.name}: fp16-storage input needs Cin % 32 == 0 (got {self.cin_p})')
+        nmask = (mask_out is not None) + (gate_bits is not None) + (gate2_bits is not None)
+        nepi = (add is not None) + (gate is not None) + (aux_out is not None) + (gate2 is not None)
+        hm, wm = self._class_grid(hout, wout)
+        key = f'{self.cin_p}_{self.cout}_{self.alg_taps}_{self.s_in}_{self.s_out}_{b * hm * wm}' + ('_fold' if self.nfold > 1 else '')
+        return _Shape(b, hin, win, cs_in, hout, wout, cs_out, hm, wm, in_f16, out_f16, cin2k, key, nepi, nmask)
+
+    def _forced_tile(self, in_f16):
+        """FORCE_TILE (tools/autotune.py, A/B runs) where this layer is a shape the forced kernel serves, else 0 (the usual choice)."""
         forced = FORCE_TILE
         if forced == 9 and self.cout > 4:
             forced = 0
@@ -445,11 +422,22 @@ class ConvPlan:
             forced = 0
         if (forced in H16_TILES or forced == 68) and not in_f16:   # fp16 kernels forced (A/B runs) on a layer with fp32 input
             forced = 0
-        tile = forced if forced else tuned_tile(key)
+        return forced
+
+    def _choose(self, s, gate_mul, has_inp2, has_pool_adjoint, _wino):
+        """Step 2 of `run`: the kernel of this launch, from the plan, the shape facts `s`, which optional operands are present and
+        the module switches -- no operand, no descriptor.  Returns `_Choice(tile, ksplit, h16p_cv, wino)`: `ksplit` 0 = none,
+        k > 1 = that many K ranges in the plan's workspace, -1 = stream-K; `wino`: the launch goes to `self.wino` with (tile, ksplit)
+        = the tune value's (tile, K ranges)."""
+        in_f16, out_f16, masked, cin2k, hin, win = s.in_f16, s.out_f16, s.nmask > 0, s.cin2k, s.hin, s.win
+        b, hm, wm = s.b, s.hm, s.wm
+        m_all = b * hm * wm
+        forced = self._forced_tile(in_f16)
+        tile = forced if forced else tuned_tile(s.key)
         if tile == 76 and not forced and (not self.c3_ok() or in_f16 or 'c3' in DEFAULT_DISABLE):   # (the key of a first layer, but not a 3-channel image: the rules decide)
             tile = -1
         if tile < 0:
-            tile = self._default_tile(b * d.Hm * d.Wm)
+            tile = self._default_tile(m_all)
         if out_f16 and not in_f16 and not forced and self.c3_ok() and not ({'c3', 'c3h'} & DEFAULT_DISABLE):
             # fp16-storage mode: a first layer over the 3-channel image multiplies fp16 operands (image rounded in registers, one fp16
             # weight plane) "like every other layer of the mode" -- at EVERY batch size: until round 6 only the pixel counts with a tune
@@ -468,15 +456,13 @@ class ConvPlan:
                 tile = 72   # thin output: the parity classes folded into the N dimension of a matrix-core tile (csrc/tapconv_thinmf.hip)
         if tile % 100 in (70, 71, 73):   # Winograd form of a 3x3 / stride-1 layer (csrc/tapconv_wino.hip): fp32 storage, same-size output
             # (tune values: 70 = the launcher's choice of N tile and K ranges, 71 = 64-wide N tile, 73 = 64-wide, four-wave workgroups; + 100 k = k K ranges, k = 1: none)
-            if self.wino is not None and WINOGRAD and not (in_f16 or out_f16) and (hout, wout) == (hin + 2 * self.wino_pad - 2, win + 2 * self.wino_pad - 2):
-                # (tile and K ranges travel as arguments: the shared Winograd plan keeps no per-call state)
-                return self.wino.run(inp, out, add, gate, gate_mode, act, aux_out, gate2, in_coff, out_coff, add_coff, gate_coff,
-                                     mask_out, gate_bits, gate2_bits, inp2, in2_coff, _wino=(tile % 100, tile // 100))
-            tile = 0 if forced else self._default_tile(b * d.Hm * d.Wm, winograd=False)
+            if self.wino is not None and WINOGRAD and not (in_f16 or out_f16) and (s.hout, s.wout) == (hin + 2 * self.wino_pad - 2, win + 2 * self.wino_pad - 2):
+                return _Choice(tile % 100, tile // 100, False, True)
+            tile = 0 if forced else self._default_tile(m_all, winograd=False)
         h16p_cv = False
         if in_f16:    # fp16 activations: the h16 kernels, N tile by the GEMM's width
             ngemm = self.cout * self.nfold
-            same_ok = ((hin, win) == (d.Hm, d.Wm) and self.tap_range[0] >= -1 and self.tap_range[1] <= 1 and self.tap_range[2] >= -1
+            same_ok = ((hin, win) == (hm, wm) and self.tap_range[0] >= -1 and self.tap_range[1] <= 1 and self.tap_range[2] >= -1
                        and self.tap_range[3] <= 1)
             # (unfolded stride-1 layers: any 3 x 3 tap window -- the unpadded 3 x 3 layers of Inception-v3's stem and their input gradients)
             span_ok = (self.nfold == 1 and self.s_out == 1 and self.tap_range[1] - self.tap_range[0] <= 2 and self.tap_range[3] - self.tap_range[2] <= 2
@@ -485,31 +471,30 @@ class ConvPlan:
                         and ((self.nfold == 1 and self.s_out == 1) or (self.nfold == 4 and self.s_out == 2)))
             # the forward form of a 3 x 3 / stride-2 convolution on the same kernel (S = 2: 8 x 32-pixel tiles, one patch buffer)
             patch2_ok = (len(self.cls) == 1 and 4 <= self.ntaps_total <= 9 and self.s_in == 2 and self.s_out == 1 and self.nfold == 1
-                         and not cin2k and inp2 is None and self.tap_range[1] - self.tap_range[0] <= 2 and self.tap_range[3] - self.tap_range[2] <= 2)
+                         and not cin2k and not has_inp2 and self.tap_range[1] - self.tap_range[0] <= 2 and self.tap_range[3] - self.tap_range[2] <= 2)
             if forced in H16_TILES or (forced == 68 and (patch_ok or patch2_ok)):
                 tile = forced
             elif thin_mf:
                 tile = 72
-            elif (not out_f16 and self.cout <= 4 and self.nfold == 1 and self.s_in == 1 and self.cin_p % 32 == 0 and not masked_any(mask_out, gate_bits, gate2_bits)
+            elif (not out_f16 and self.cout <= 4 and self.nfold == 1 and self.s_in == 1 and self.cin_p % 32 == 0 and not masked
                   and forced in (0, 29) and 'thin' not in DEFAULT_DISABLE):
                 tile = 29   # thin fp32 output from an fp16 activation (image-side input gradients): the patch-staged VALU kernel
             else:
                 tile = 60 if ngemm > 64 else 61 if ngemm > 32 else 62 if ngemm > 16 else 63
-                m_all = b * d.Hm * d.Wm
                 # (32 GEMM columns leave half of the 64-wide tile empty and still win: Inception-v3 Conv2d_2a 138 -> 125 us, its input gradient 148 -> 128,
                 # Conv2d_2b's 203 -> 170; `h16p64` in SPAA_DEFAULT_DISABLE: the round-4 threshold)
                 if (patch_ok and ngemm >= (64 if 'h16p64' in DEFAULT_DISABLE else 32) and 'h16p' not in DEFAULT_DISABLE and forced == 0
-                        and b * ((d.Hm + 15) // 16) * ((d.Wm + 31) // 32) * ((ngemm + 127) // 128) >= 256
-                        and d.Hm * d.Wm >= 0.6 * ((d.Hm + 15) // 16 * 16) * ((d.Wm + 31) // 32 * 32)):   # (16 x 32-pixel tiles)
+                        and b * ((hm + 15) // 16) * ((wm + 31) // 32) * ((ngemm + 127) // 128) >= 256
+                        and hm * wm >= 0.6 * ((hm + 15) // 16 * 16) * ((wm + 31) // 32 * 32)):   # (16 x 32-pixel tiles)
                     tile = 68   # 3x3 / stride 1 (or a folded stride-2 transposed layer): the input patch staged once for all taps (csrc/tapconv_h16p.hip)
                 elif (patch2_ok and ngemm >= 64 and 'h16p2' not in DEFAULT_DISABLE and forced == 0
-                      and b * ((d.Hm + 7) // 8) * ((d.Wm + 31) // 32) * ((ngemm + 127) // 128) >= 192
-                      and d.Hm * d.Wm >= 0.6 * ((d.Hm + 7) // 8 * 8) * ((d.Wm + 31) // 32 * 32)):
+                      and b * ((hm + 7) // 8) * ((wm + 31) // 32) * ((ngemm + 127) // 128) >= 192
+                      and hm * wm >= 0.6 * ((hm + 7) // 8 * 8) * ((wm + 31) // 32 * 32)):
                     tile = 68   # 3x3 / stride 2 forward: conv2 / conv2_s, transConv1's input gradient, the classifiers' stride-2 layers
-                elif (patch_ok and same_ok and self.nfold == 1 and not cin2k and inp2 is None and ngemm >= 64 and self.cin_p >= 64 and forced == 0
-                      and 'h16pcv' not in DEFAULT_DISABLE and m_all < (1 << 24) and max(d.Hm, d.Wm) <= 254):
+                elif (patch_ok and same_ok and self.nfold == 1 and not cin2k and not has_inp2 and ngemm >= 64 and self.cin_p >= 64 and forced == 0
+                      and 'h16pcv' not in DEFAULT_DISABLE and m_all < (1 << 24) and max(hm, wm) <= 254):
                     # small images / few regions with long K (ResNet-18 layer3 / layer4, VGG-16's 14 x 14 block at batch 64): the
-                    # patch-staged kernel's canvas / K-range form (the launcher's plan, asked for below: it needs the workspace)
+                    # patch-staged kernel's canvas / K-range form (the launcher's plan, asked for in `_launch`: it needs the workspace)
                     tile, h16p_cv = 68, True
                 elif tile == 60 and 'h16n64' not in DEFAULT_DISABLE and (
                         (m_all + 127) // 128 * ((ngemm + 127) // 128) < 256 or
@@ -530,17 +515,16 @@ class ConvPlan:
                 tile = 38 if (sc_ok and self.cout <= 32) else (18 if self.cout > 32 else 16)
         # tune values >= 100 encode split-K: tile + 100 * ksplit (x6d tiles, one class, enough K-steps per split)
         ksplit, tile = (tile // 100, tile % 100) if tile >= 100 else (1, tile)
+        dks = 0     # (what the descriptor gets)
         if self.nfold > 1:  # only the DMA-staged kernels know the folded epilogue
             ksplit = 1
             if not (tile in X6D_TILES or tile in H16_TILES or tile == 68):
                 tile = 34
-            d.nfold = self.nfold
         if ksplit == 9:  # stream-K (persistent x6d tiles, one class): workspace shared by all plans (one stream)
             if len(self.cls) != 1 or self.nfold > 1 or tile not in X6D_PERSISTENT or self.cin_p % 32:
                 ksplit, tile = 1, (0 if forced else tile)
             else:
-                d.splitk_ws, d.ksplit = _streamk_workspace(inp.device).data_ptr(), -1
-                ksplit = 1
+                ksplit, dks = 1, -1
         if in_f16 or out_f16:
             ksplit = 1
             if (in_f16 and tile in (60, 61, 62, 63) and len(self.cls) == 1 and self.nfold == 1 and 'h16splitk' not in DEFAULT_DISABLE
@@ -548,7 +532,7 @@ class ConvPlan:
                 # skinny GEMMs of the fp16 path (VGG-16's fully connected layers at batch 64: ONE row tile, K = 25088; ResNet layer4):
                 # split K until the grid covers the chip about twice, at least eight 64-deep steps per split
                 bn = {60: 128, 61: 64, 62: 32, 63: 16}[tile]
-                wgs = (b * d.Hm * d.Wm + 127) // 128 * ((self.cout + bn - 1) // bn)
+                wgs = (m_all + 127) // 128 * ((self.cout + bn - 1) // bn)
                 nk = (self.cls[0]['K'] + 63) // 64
                 ksplit = FORCE_KSPLIT if FORCE_KSPLIT else max(1, min(16, 512 // max(wgs, 1), nk // 8))
         if ksplit > 1:
@@ -556,26 +540,95 @@ class ConvPlan:
             if len(self.cls) != 1 or nk < 2 * ksplit or (tile not in X6D_TILES and not (in_f16 and tile in (60, 61, 62, 63))) or self.cin_p % 32:
                 ksplit, tile = 1, (0 if forced else tile)
         if ksplit > 1:
-            need = ksplit * b * d.Hm * d.Wm * ((self.cout + 127) // 128 * 128)
-            if self._ws is None or self._ws.numel() < need:
-                self._ws = torch.empty(need, device=inp.device, dtype=torch.float32)
-            d.splitk_ws, d.ksplit = self._ws.data_ptr(), ksplit
-        if gate is not None and gate_mode == _lib.GATE_MUL and tile < 25:  # multiplicative gate: newer epilogues only
-            tile = self._default_tile(b * d.Hm * d.Wm, winograd=False) % 100
-            d.ksplit, d.splitk_ws = 0, None
+            dks = ksplit
+            # (sized here, the step's one side effect: a split that a reroute below drops again, or a launch that they refuse, has
+            # grown the plan's workspace all the same -- as it always did)
+            self._kws(ksplit * m_all * ((self.cout + 127) // 128 * 128), False)
+        if gate_mul and tile < 25:  # multiplicative gate: newer epilogues only
+            tile, dks = self._default_tile(m_all, winograd=False) % 100, 0
             if tile < 25:
                 raise ValueError('GATE_MUL needs a layer shape served by the DMA-staged kernels')
         if masked and tile not in STORE4_TILES:
             # byte masks live in the shared 4-channel epilogue (epilogue.hpp): thin / fp32-MFMA kernels do not have it
-            tile = self._default_tile(b * d.Hm * d.Wm, winograd=False) % 100
-            d.ksplit, d.splitk_ws = 0, None
+            tile, dks = self._default_tile(m_all, winograd=False) % 100, 0
             if tile not in STORE4_TILES:
                 raise ValueError(f'{self.name}: gate masks need a layer shape served by the bf16x6 / smallcin kernels')
         if self.fixed_tile:
-            tile, d.ksplit, d.splitk_ws = (_wino[0] if _wino else self.fixed_tile), 0, None
+            tile, dks = (_wino[0] if _wino else self.fixed_tile), 0
+        if tile == 76 and (not self.c3_ok() or in_f16):
+            raise ValueError(f'{self.name}: tile 76 serves 3-channel-image convolutions only')
+        if cin2k:
+            if in_f16 and self.nfold == 1:
+                tile, dks = 68, 0      # (fp16 storage: the patch-staged fp16 kernel's two-source form)
+            elif tile not in (70, 71, 73):
+                raise ValueError(f'{self.name}: a two-source plan runs on the Winograd kernel (fp32 storage, same-size output) or the patch-staged fp16 kernel')
+        elif has_inp2 and in_f16:
+            # second source of a folded fp16 layer (attach_second_source_h16): the patch-staged fp16 kernel only
+            if getattr(self, 'w2_half', None) is None or not out_f16 or self.nfold != 4:
+                raise ValueError(f'{self.name}: an fp16 second source needs attach_second_source_h16() on a folded stride-2 layer')
+            tile, dks = 68, 0
+        elif has_inp2:
+            # second source (attach_second_source): the patch-staged stride-2 kernel only, fp32 storage
+            if getattr(self, 'w2_split', None) is None or in_f16 or out_f16 or not self.x6p_ok():
+                raise ValueError(f'{self.name}: a second source needs attach_second_source() on an fp32 stride-2 layer')
+            tile, dks = 74, 0
+        if has_pool_adjoint and tile != 72:
+            raise ValueError(f'{self.name}: pool_adjoint is served by the thin-output matrix-core kernel only (tile 72; got {tile})')
+        if tile == 74 and not (self.x6p_ok() and not (in_f16 or out_f16)):
+            tile = 0 if forced else self._default_tile(m_all, winograd=False) % 100
+        return _Choice(tile, dks, h16p_cv, False)
+
+    def _geometry(self, inp, b, hin, win, cs_in, in_coff, hout, wout, cs_out, out_coff):
+        """A descriptor with the part `run` and `wgrad` share: the input window, the output's shape, the class grid, taps and classes."""
+        d = _lib.TapConv()
+        d.inp, d.Hin, d.Win, d.Cin, d.in_cstride, d.in_coff = inp.data_ptr(), hin, win, self.cin_p, cs_in, in_coff
+        d.Hout, d.Wout, d.Cout, d.out_cstride, d.out_coff = hout, wout, self.cout, cs_out, out_coff
+        d.B = b
+        d.Hm, d.Wm = self._class_grid(hout, wout)
+        d.s_in, d.s_out = self.s_in, self.s_out
+        d.taps = self.taps.data_ptr()
+        d.nclass, d.cls = len(self.cls), self._cls_c
+        return d
+
+    def _describe(self, s, ch, inp, out, add, gate, gate_mode, act, aux_out, gate2, in_coff, out_coff, add_coff, gate_coff,
+                  mask_out, gate_bits, gate2_bits, inp2, in2_coff, pool_adjoint):
+        """Step 3 of `run`: the TapConv descriptor of the chosen kernel (everything but the launcher plan and the workspaces)."""
+        tile, in_f16, out_f16 = ch.tile, s.in_f16, s.out_f16
+        d = self._geometry(inp, s.b, s.hin, s.win, s.cs_in, in_coff, s.hout, s.wout, s.cs_out, out_coff)
+        d.out, d.weights = out.data_ptr(), self.weights.data_ptr()
+        d.tap_range[:] = self.tap_range
+        d.io_dtype = (_lib.IO_IN_F16 if in_f16 else 0) | (_lib.IO_OUT_F16 if out_f16 else 0)
+        if in_f16:
+            d.w_half = self.half_plane().data_ptr()
+        d.w_split = self.w_split.data_ptr() if self.w_split is not None else None
+        d.bias = self.bias.data_ptr() if self.bias is not None else None
+        if add is not None:
+            assert add.shape[:3] == out.shape[:3] and add_coff + self.cout <= add.shape[3]
+            d.add, d.add_cstride, d.add_coff = add.data_ptr(), add.shape[3], add_coff
+        if gate is not None:
+            assert gate.shape[:3] == out.shape[:3] and gate_coff + self.cout <= gate.shape[3]
+            d.gate, d.gate_cstride, d.gate_coff, d.gate_mode = gate.data_ptr(), gate.shape[3], gate_coff, gate_mode
+        d.act = act
+        if aux_out is not None:
+            assert aux_out.shape == out.shape
+            d.aux_out = aux_out.data_ptr()
+        if gate2 is not None:
+            assert aux_out is not None and gate2.shape[:3] == out.shape[:3] and self.cout <= gate2.shape[3]
+            d.gate2, d.gate2_cstride, d.gate2_coff = gate2.data_ptr(), gate2.shape[3], 0
+        if mask_out is not None:
+            assert mask_out.shape == out.shape[:3] + (s.cs_out // 4,), (mask_out.shape, out.shape)
+            d.mask_out = mask_out.data_ptr()
+        if gate_bits is not None:
+            assert gate is None and gate_bits.shape[:3] == out.shape[:3] and gate_coff + self.cout <= 4 * gate_bits.shape[3]
+            d.gate_bits, d.gate_cstride, d.gate_coff = gate_bits.data_ptr(), 4 * gate_bits.shape[3], gate_coff
+        if gate2_bits is not None:
+            assert gate2 is None and aux_out is not None and gate2_bits.shape[:3] == out.shape[:3] and self.cout <= 4 * gate2_bits.shape[3]
+            d.gate2_bits, d.gate2_cstride, d.gate2_coff = gate2_bits.data_ptr(), 4 * gate2_bits.shape[3], 0
+        if self.nfold > 1:
+            d.nfold = self.nfold
+        if ch.ksplit == -1:
+            d.splitk_ws, d.ksplit = _streamk_workspace(inp.device).data_ptr(), -1
         if tile == 76:
-            if not self.c3_ok() or in_f16:
-                raise ValueError(f'{self.name}: tile 76 serves 3-channel-image convolutions only')
             if out_f16 and 'c3h' not in DEFAULT_DISABLE:
                 # fp16-storage mode: fp16 operands like every other layer of the mode (the image rounded in registers, one fp16 weight plane)
                 d.w_split = self.c3_pack(True).data_ptr()
@@ -587,104 +640,77 @@ class ConvPlan:
                 d.w_half = self.thin_fold(True).data_ptr()
             else:
                 d.w_split = self.thin_fold(False).data_ptr()
-        if cin2k:
-            if in_f16 and self.nfold == 1:
-                tile, d.ksplit, d.splitk_ws = 68, 0, None      # (fp16 storage: the patch-staged fp16 kernel's two-source form)
-            elif tile not in (70, 71, 73):
-                raise ValueError(f'{self.name}: a two-source plan runs on the Winograd kernel (fp32 storage, same-size output) or the patch-staged fp16 kernel')
-            d.in2, d.in2_cstride, d.in2_coff, d.Cin2 = inp2.data_ptr(), inp2.shape[3], in2_coff, cin2k
-        elif inp2 is not None and in_f16:
-            # second source of a folded fp16 layer (attach_second_source_h16): the patch-staged fp16 kernel only
-            if getattr(self, 'w2_half', None) is None or not out_f16 or self.nfold != 4:
-                raise ValueError(f'{self.name}: an fp16 second source needs attach_second_source_h16() on a folded stride-2 layer')
-            assert inp2.dtype == torch.float16 and inp2.shape[:3] == out.shape[:3] and in2_coff + self.cin2 <= inp2.shape[3]
-            tile, d.ksplit, d.splitk_ws = 68, 0, None
+        if s.cin2k:
+            d.in2, d.in2_cstride, d.in2_coff, d.Cin2 = inp2.data_ptr(), inp2.shape[3], in2_coff, s.cin2k
+        elif inp2 is not None:   # second source at output resolution (attach_second_source_h16: fp16 planes; attach_second_source: bf16 planes)
+            assert inp2.dtype == inp.dtype and inp2.shape[:3] == out.shape[:3] and in2_coff + self.cin2 <= inp2.shape[3]
             d.in2, d.in2_cstride, d.in2_coff, d.Cin2 = inp2.data_ptr(), inp2.shape[3], in2_coff, self.cin2
-            d.w2_split = self.w2_half.data_ptr()
-            d.bias = self.bias2.data_ptr()
-        elif inp2 is not None:
-            # second source (attach_second_source): the patch-staged stride-2 kernel only, fp32 storage
-            if getattr(self, 'w2_split', None) is None or in_f16 or out_f16 or not self.x6p_ok():
-                raise ValueError(f'{self.name}: a second source needs attach_second_source() on an fp32 stride-2 layer')
-            assert inp2.dtype == torch.float32 and inp2.shape[:3] == out.shape[:3] and in2_coff + self.cin2 <= inp2.shape[3]
-            tile, d.ksplit, d.splitk_ws = 74, 0, None
-            d.in2, d.in2_cstride, d.in2_coff, d.Cin2 = inp2.data_ptr(), inp2.shape[3], in2_coff, self.cin2
-            d.w2_split = self.w2_split.data_ptr()
+            d.w2_split = (self.w2_half if in_f16 else self.w2_split).data_ptr()
             d.bias = self.bias2.data_ptr()
         if pool_adjoint is not None:
-            if tile != 72:
-                raise ValueError(f'{self.name}: pool_adjoint is served by the thin-output matrix-core kernel only (tile 72; got {tile})')
-            d.in2, d.in2_cstride, d.in2_coff, d.Cin2 = parg.data_ptr(), inp.shape[1], inp.shape[2], int(bool(pgate))
-        if tile == 74 and not (self.x6p_ok() and not (in_f16 or out_f16)):
-            tile = 0 if forced else self._default_tile(b * d.Hm * d.Wm, winograd=False) % 100
+            d.in2, d.in2_cstride, d.in2_coff, d.Cin2 = pool_adjoint[0].data_ptr(), inp.shape[1], inp.shape[2], int(bool(pool_adjoint[2]))
         if tile == 74 and X6P_STD and self.x6p_canonical():
             d.reserved2 = 1      # (the kernel's compile-time schedule: x6p_canonical)
-        d.tile = self.last_tile = tile     # (last_tile: for tests and reports)
+        d.tile = tile
         d.reserved0 = (DEBUG_TAPMAJOR | (DEBUG_PERSIST_CAP << 8) | (DEBUG_WINO << 16) | (DEBUG_H16_2STAGE << 25) | (DEBUG_SMALLCIN_NOSLAB << 26)
                        | (((DEBUG_THINMF & 7) << 27) if tile == 72 else 0)
                        | (((DEBUG_WINO_NOCANVAS & 1) << 30 | (DEBUG_WINO_NOCANVAS >> 1 & 1) << 29 | {1: 0, 0: 1, 2: 2}[getattr(self, 'wino_pad', 1)] << 27) if tile in (70, 71, 73) else 0))  # measurement / test switches; bits 27-28 of a Winograd launch: its zero padding (1 / 0 / 2)
-        d.nclass = len(self.cls)
-        d.tap_range[:] = self.tap_range
-        for i, c in enumerate(self.cls):
-            for k, v in c.items():
-                setattr(d.cls[i], k, v)
+        return d
+
+    def _kws(self, need, fixup):
+        """The plan's K-range workspace of at least `need` floats, grown on demand: its pointer.  `fixup`: the K ranges meet inside the
+        kernel (the last-arriving workgroup of a tile adds them in fixed order) -- the workspace that starts with a header of arrival
+        counters, zero before and after every launch (include/spaa_hip.h)."""
+        if fixup:
+            if self._ws_fix is None or self._ws_fix.numel() < need + SPLITK_HDR:
+                self._ws_fix = torch.zeros(need + SPLITK_HDR, device=self.weights.device, dtype=torch.float32)
+            return self._ws_fix.data_ptr()
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty(need, device=self.weights.device, dtype=torch.float32)
+        return self._ws.data_ptr()
+
+    def _launcher_plan(self, query, pkey, d):
+        """The launcher's own plan of a Winograd / tile-68 canvas launch (host-side query of the library: N tile, K ranges, canvas
+        layout).  It depends on the shape, the tile, the K ranges asked for, a second source and the switches in the descriptor -- not
+        on pointers: asked once per such key `pkey`, the launcher's own canvas search is the only one left per launch."""
+        wp = self._wino_plans.get(pkey)
+        if wp is None:
+            wpc = (C.c_int32 * 8)()
+            rc = getattr(_lib.load(), query)(C.byref(d), wpc)
+            if rc != 0:
+                raise RuntimeError(f'{self.name}: {query} failed with HIP error {rc}')
+            wp = self._wino_plans[pkey] = tuple(wpc)
+        return wp
+
+    def _launch(self, d, s, ch, inp, out, inp2, _wino, pool, unpool):
+        """Step 4 of `run`: the launcher's plan and the K-range workspace where the kernel has them, the pool fusions, the launch (with
+        the pool launches around it where they are not fused) and, in bench.py's instrumented pass, the profile record."""
+        tile, h16p_cv, b, hin, win, hout, wout = ch.tile, ch.h16p_cv, s.b, s.hin, s.win, s.hout, s.wout
+        self.last_tile = tile     # (last_tile: for tests and reports)
+        if ch.ksplit > 1:
+            d.splitk_ws, d.ksplit = self._ws.data_ptr(), ch.ksplit     # (the workspace `_choose` has sized)
         wino_bn = 0
         if tile in (70, 71, 73):
             # the launcher's plan (csrc/tapconv_wino.hip: N tile, canvas layout for small images, K ranges for few workgroups with
             # long K) -- asked for here because the K ranges need a workspace; its K-range count is then passed back explicitly
             want = _wino[1] if _wino else getattr(self, 'wino_ksplit', 0)
             d.ksplit = want if WINO_SPLITK else 1
-            # (the plan depends on the shape, the tile, the K ranges asked for, a second source and the switches in reserved0 -- not
-            # on pointers: asked once per such key, the launcher's own canvas search is the only one left per launch)
-            pkey = (b, hin, win, hout, wout, cs_in, tile, d.ksplit, inp2 is not None, d.reserved0)
-            wp = self._wino_plans.get(pkey)
-            if wp is None:
-                wpc = (C.c_int32 * 8)()
-                rc = _lib.load().spaa_tapconv_wino_plan(C.byref(d), wpc)
-                if rc != 0:
-                    raise RuntimeError(f'{self.name}: spaa_tapconv_wino_plan failed with HIP error {rc}')
-                wp = self._wino_plans[pkey] = tuple(wpc)
+            wp = self._launcher_plan('spaa_tapconv_wino_plan', (b, hin, win, hout, wout, s.cs_in, tile, d.ksplit, inp2 is not None, d.reserved0), d)
             wino_bn, d.ksplit = wp[0], wp[1]
             self.last_wino_plan = wp
-            if d.ksplit > 1:
-                need = d.ksplit * b * hout * wout * ((self.cout + 127) // 128 * 128)
-                if WINO_SPLITK_FIXUP:
-                    # round 6: the K ranges meet inside the kernel (the last-arriving workgroup of a tile adds them in fixed order): the
-                    # workspace starts with a header of arrival counters, zero before and after every launch (include/spaa_hip.h)
-                    if self._ws_fix is None or self._ws_fix.numel() < need + SPLITK_HDR:
-                        self._ws_fix = torch.zeros(need + SPLITK_HDR, device=inp.device, dtype=torch.float32)
-                    d.splitk_ws = self._ws_fix.data_ptr()
-                    d.reserved1 |= 256
-                else:
-                    if self._ws is None or self._ws.numel() < need:
-                        self._ws = torch.empty(need, device=inp.device, dtype=torch.float32)
-                    d.splitk_ws = self._ws.data_ptr()
         if tile == 68 and h16p_cv:
             # the launcher's plan of the canvas / K-range form (csrc/tapconv_h16p.hip), cached per launch shape like the Winograd plans
             d.reserved1 = 4 | {0: 0, 64: 1, 128: 2}[H16P_CV[0]] | (8 if len(H16P_CV) > 2 and H16P_CV[2] else 0)
             d.ksplit, d.splitk_ws = H16P_CV[1], None
-            pkey = ('h16p', b, hin, win, cs_in, d.reserved1, d.ksplit)
-            wp = self._wino_plans.get(pkey)
-            if wp is None:
-                wpc = (C.c_int32 * 8)()
-                rc = _lib.load().spaa_tapconv_h16p_plan(C.byref(d), wpc)
-                if rc != 0:
-                    raise RuntimeError(f'{self.name}: spaa_tapconv_h16p_plan failed with HIP error {rc}')
-                wp = self._wino_plans[pkey] = tuple(wpc)
+            wp = self._launcher_plan('spaa_tapconv_h16p_plan', ('h16p', b, hin, win, s.cs_in, d.reserved1, d.ksplit), d)
             d.ksplit = wp[1]
             d.reserved1 = (d.reserved1 & 8) | 4 | {64: 1, 128: 2}[wp[0]]
             self.last_h16p_plan = wp
-            if d.ksplit > 1:
-                need = d.ksplit * b * hout * wout * ((self.cout + 127) // 128 * 128)
-                if WINO_SPLITK_FIXUP:   # (the K ranges meet inside the kernel: workspace with the arrival-counter header, as the Winograd form)
-                    if self._ws_fix is None or self._ws_fix.numel() < need + SPLITK_HDR:
-                        self._ws_fix = torch.zeros(need + SPLITK_HDR, device=inp.device, dtype=torch.float32)
-                    d.splitk_ws = self._ws_fix.data_ptr()
-                    d.reserved1 |= 256
-                else:
-                    if self._ws is None or self._ws.numel() < need:
-                        self._ws = torch.empty(need, device=inp.device, dtype=torch.float32)
-                    d.splitk_ws = self._ws.data_ptr()
+        if (tile in (70, 71, 73) or (tile == 68 and h16p_cv)) and d.ksplit > 1:
+            # (round 6, WINO_SPLITK_FIXUP: the K ranges meet inside the kernel -- the workspace with the arrival-counter header)
+            d.splitk_ws = self._kws(d.ksplit * b * hout * wout * ((self.cout + 127) // 128 * 128), WINO_SPLITK_FIXUP)
+            if WINO_SPLITK_FIXUP:
+                d.reserved1 |= 256
         if tile == 68 and 'h16plean' in DEFAULT_DISABLE:
             d.reserved1 |= 16    # (A/B runs: the 64-wide stride-1 form as one workgroup per compute unit)
         if tile == 68 and not h16p_cv and self.s_in == 1 and self.cout * self.nfold > 64 and self.h16p_lean_wide(b, d.Hm, d.Wm):
@@ -700,17 +726,16 @@ class ConvPlan:
                 unpool_fused = True
             else:
                 _lib.call('spaa_maxpool_bwd_f16', _lib.hptr(inp), _lib.ptr(parg), 1, _lib.hptr(gfull), b, hin, win, self.cin_p, hin // 2, win // 2,
-                          2, 2, 0, cs_in, 0)
+                          2, 2, 0, s.cs_in, 0)
                 d.inp, d.in_cstride = gfull.data_ptr(), gfull.shape[3]
         self.last_unpool_fused = unpool_fused
         pool_fused = False
         if pool is not None:
-            assert (act == _lib.ACT_RELU and add is None and gate is None and gate2 is None and aux_out is None and mask_out is None
-                    and gate_bits is None and gate2_bits is None and out_coff == 0)
             pooled, parg, want_arg = pool
-            assert pooled.shape == (b, hout // 2, wout // 2, cs_out) and pooled.dtype == out.dtype and parg.shape == (b, hout // 2, wout // 2, self.cout)
+            assert d.act == _lib.ACT_RELU and s.nepi == 0 and s.nmask == 0 and d.out_coff == 0
+            assert pooled.shape == (b, hout // 2, wout // 2, s.cs_out) and pooled.dtype == out.dtype and parg.shape == (b, hout // 2, wout // 2, self.cout)
             if (tile == 68 and not h16p_cv and self.s_in == 1 and self.nfold == 1 and hout % 2 == 0 and wout % 2 == 0 and self.cout % 4 == 0
-                    and cs_out == self.cout and 'h16ppool' not in DEFAULT_DISABLE):
+                    and s.cs_out == self.cout and 'h16ppool' not in DEFAULT_DISABLE):
                 d.out, d.mask_out = pooled.data_ptr(), (parg.data_ptr() if want_arg else None)
                 d.reserved1 |= 64
                 pool_fused = True
@@ -718,15 +743,7 @@ class ConvPlan:
         # (for tests and reports, next to last_tile: the K split this launch runs with -- 1 none, k > 1 that many K ranges (x6d split-K,
         # fp16 split-K, the Winograd / tile-68 K-range forms), -1 stream-K)
         self.last_ksplit = d.ksplit if d.ksplit else 1
-        tid = 0
-        if PROFILE is not None:
-            tid = d.tile + 100 * (d.ksplit if d.ksplit > 1 else (9 if d.ksplit == -1 else 0))
-            if d.tile == 68 and h16p_cv:
-                tid += 1000
-            if d.tile == 70 and wino_bn == 64:   # the launcher's choice of the N tile: a kernel of its own for rocprofv3
-                tid += 1
-            if d.tile in (70, 71, 73):           # ... and so are the canvas / K-range form (+ 1000) and the two-source form (+ 2000)
-                tid += 2000 if cin2k else (1000 if (self.last_wino_plan[2] or d.ksplit > 1) else 0)
+        tid = self._profile_tid(d, h16p_cv, wino_bn, s.cin2k) if PROFILE is not None else 0
         if PROFILE is None or (PROFILE_ONLY is not None and tid not in PROFILE_ONLY):
             _lib.call('spaa_tapconv_f32', C.byref(d))
         else:  # bench.py's instrumented pass: HIP events on the launch stream around this one kernel
@@ -734,27 +751,40 @@ class ConvPlan:
             e0.record()
             _lib.call('spaa_tapconv_f32', C.byref(d))
             e1.record()
-            # algorithmic bytes: every operand read / result written once (logical channels, fp32)
-            npx = b * hout * wout
-            bi, bo = (2 if in_f16 else 4), (2 if out_f16 else 4)   # bytes per element: fp16 storage or fp32
-            nbytes = (bi * b * hin * win * self.cin_p + bo * npx * self.cout * (1 + (add is not None) + (gate is not None)
-                                                                               + (aux_out is not None) + (gate2 is not None))
-                      + bi * self.alg_taps * self.cin_p * self.cout)
-            nbytes += npx * self.cout // 4 * ((mask_out is not None) + (gate_bits is not None) + (gate2_bits is not None))
-            fl = self.flops(b, hout, wout)
-            if inp2 is not None and not cin2k:   # (second source of the stride-2 kernel; a two-source plan's channels are in cin_p)
-                nbytes += 4 * npx * self.cin2
-                fl += 2 * npx * self.cin2 * self.cout
-            if unpool_fused:   # (the pooled gradient and the arg-max bytes instead of the full-size gradient)
-                nbytes -= bi * b * hin * win * self.cin_p - (bi + 1) * b * (hin // 2) * (win // 2) * self.cin_p
-            if pool_fused:   # (the pooled tensor and its arg-max bytes instead of the full-size activation)
-                nbytes -= bo * npx * self.cout - (bo + 1) * (npx // 4) * self.cout
-            PROFILE.append((self.name, key, fl, e0, e1, tid, nbytes))
+            fl, nbytes = self._profile_work(s, inp2 is not None, unpool_fused, pool_fused)
+            PROFILE.append((self.name, s.key, fl, e0, e1, tid, nbytes))
         if pool is not None and not pool_fused:
-            pooled, parg, _want = pool
-            _lib.call('spaa_maxpool_fwd_f16' if out_f16 else 'spaa_maxpool_fwd', _lib.hptr(out), _lib.hptr(pooled), _lib.ptr(parg), b, hout, wout,
+            _lib.call('spaa_maxpool_fwd_f16' if s.out_f16 else 'spaa_maxpool_fwd', _lib.hptr(out), _lib.hptr(pooled), _lib.ptr(parg), b, hout, wout,
                       self.cout, hout // 2, wout // 2, 2, 2, 0, pooled.shape[3], 0)
-        return out
+
+    def _profile_tid(self, d, h16p_cv, wino_bn, cin2k):
+        """The kernel id bench.py reports: tile + 100 x K ranges (9: stream-K), + 1 / 1000 / 2000 for forms that are kernels of their own."""
+        tid = d.tile + 100 * (d.ksplit if d.ksplit > 1 else (9 if d.ksplit == -1 else 0))
+        if d.tile == 68 and h16p_cv:
+            tid += 1000
+        if d.tile == 70 and wino_bn == 64:   # the launcher's choice of the N tile: a kernel of its own for rocprofv3
+            tid += 1
+        if d.tile in (70, 71, 73):           # ... and so are the canvas / K-range form (+ 1000) and the two-source form (+ 2000)
+            tid += 2000 if cin2k else (1000 if (self.last_wino_plan[2] or d.ksplit > 1) else 0)
+        return tid
+
+    def _profile_work(self, s, has_inp2, unpool_fused, pool_fused):
+        """(algorithmic FLOPs, algorithmic bytes) of a launch: every operand read / result written once (logical channels)."""
+        b, hin, win = s.b, s.hin, s.win
+        npx = b * s.hout * s.wout
+        bi, bo = (2 if s.in_f16 else 4), (2 if s.out_f16 else 4)   # bytes per element: fp16 storage or fp32
+        nbytes = (bi * b * hin * win * self.cin_p + bo * npx * self.cout * (1 + s.nepi)
+                  + bi * self.alg_taps * self.cin_p * self.cout)
+        nbytes += npx * self.cout // 4 * s.nmask
+        fl = self.flops(b, s.hout, s.wout)
+        if has_inp2 and not s.cin2k:   # (second source of the stride-2 kernel; a two-source plan's channels are in cin_p)
+            nbytes += 4 * npx * self.cin2
+            fl += 2 * npx * self.cin2 * self.cout
+        if unpool_fused:   # (the pooled gradient and the arg-max bytes instead of the full-size gradient)
+            nbytes -= bi * b * hin * win * self.cin_p - (bi + 1) * b * (hin // 2) * (win // 2) * self.cin_p
+        if pool_fused:   # (the pooled tensor and its arg-max bytes instead of the full-size activation)
+            nbytes -= bo * npx * self.cout - (bo + 1) * (npx // 4) * self.cout
+        return fl, nbytes
 
     def h16p_lean_wide(self, b, hm, wm):
         """Patch-staged fp16 kernel, stride-1 form, more than 64 GEMM columns: 64-wide N tiles with two workgroups per compute unit
@@ -776,28 +806,13 @@ class ConvPlan:
         b, hin, win, cs_in = inp.shape
         b2, hout, wout, cs_out = gout.shape
         assert b == b2 and in_coff + self.cin_p <= cs_in and out_coff + self.cout <= cs_out
-        d = _lib.TapConv()
-        d.inp, d.Hin, d.Win, d.Cin, d.in_cstride, d.in_coff = inp.data_ptr(), hin, win, self.cin_p, cs_in, in_coff
-        d.Hout, d.Wout, d.Cout, d.out_cstride, d.out_coff = hout, wout, self.cout, cs_out, out_coff
-        d.B = b
-        if self.s_out == 1:
-            d.Hm, d.Wm = hout, wout
-        else:
-            d.Hm, d.Wm = (hout + self.s_out - 1) // self.s_out, (wout + self.s_out - 1) // self.s_out
-        d.s_in, d.s_out = self.s_in, self.s_out
-        d.taps = self.taps.data_ptr()
-        d.nclass = len(self.cls)
-        for i, c in enumerate(self.cls):
-            for k, v in c.items():
-                setattr(d.cls[i], k, v)
+        d = self._geometry(inp, b, hin, win, cs_in, in_coff, hout, wout, cs_out, out_coff)
         m = b * d.Hm * d.Wm
         if nchunk is None:   # enough waves to fill the chip: (taps x n tiles x c groups) x chunks ~ 4096
             blocks = self.ntaps_total * ((self.cout + 31) // 32) * ((self.cin_p + 127) // 128)
             nchunk = max(1, min(1024, (4096 + blocks - 1) // blocks, max(1, m // 64)))
         wtotal = self.weights.numel()
-        need = nchunk * max(wtotal, self.cout)
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(need, device=inp.device, dtype=torch.float32)
+        self._kws(nchunk * max(wtotal, self.cout), False)
         dw = torch.empty(wtotal, device=inp.device)
         db = torch.empty(self.cout, device=inp.device) if dbias else None
         _lib.call('spaa_tapconv_wgrad', C.byref(d), _lib.ptr(gout), _lib.ptr(dw), _lib.ptr(db), _lib.ptr(self._ws), int(nchunk))
@@ -814,15 +829,7 @@ class ConvPlan:
         w = weight.detach().float().reshape(-1)
         self.weights[self.repack_pos] = w[self.repack_src]
         if self.w_split is not None:
-            parts = []
-            for c in self.cls:
-                wp = self.weights[c['w_off']:c['w_off'] + self._npad * c['Kpad']]
-                h = wp.to(torch.bfloat16)
-                r1 = wp - h.float()
-                m = r1.to(torch.bfloat16)
-                lo = (r1 - m.float()).to(torch.bfloat16)
-                parts.append(torch.stack([h, m, lo]).view(torch.int16).reshape(-1))
-            self.w_split.copy_(torch.cat(parts))
+            self.w_split.copy_(torch.cat([_bf16_planes(self._wmat(c)).reshape(-1) for c in self.cls]))
         self.w_half = None
         self._thin = {}
         self._c3 = self._c3h = None
@@ -872,16 +879,12 @@ def _winograd_weights(plan, wino):
     """U = G g G^T of every (output, input) channel pair of `plan` (fp64 on the device, rounded once to fp32) into `wino`'s
     packed 16-'tap' matrix W[n][pos * Cin + c] and its three bf16 planes."""
     c = plan.cls[0]
-    g = plan.weights[:plan._npad * c['Kpad']].view(plan._npad, c['Kpad'])[:, :9 * plan.cin_p]
+    g = plan._wmat(c)[:, :9 * plan.cin_p]
     g = g.reshape(plan._npad, 9, plan.cin_p).double()
     u = torch.einsum('pt,ntc->npc', wino._wino_t.to(g.device), g).float().reshape(plan._npad, -1)
     u = torch.nn.functional.pad(u, (0, wino.cls[0]['Kpad'] - u.shape[1])).reshape(-1)
     wino.weights.copy_(u)
-    h = u.to(torch.bfloat16)
-    r1 = u - h.float()
-    m = r1.to(torch.bfloat16)
-    lo = (r1 - m.float()).to(torch.bfloat16)
-    wino.w_split.copy_(torch.stack([h, m, lo]).view(torch.int16).reshape(-1))
+    wino.w_split.copy_(_bf16_planes(u).reshape(-1))
 
 
 def attach_winograd(plan):
@@ -947,12 +950,7 @@ def conv_dgrad_plan_2src(weight_a, weight_b, device='cuda', name=''):
 
 def split_planes(w):
     """fp32 matrix -> int16 tensor [3, *w.shape]: the bf16 planes h, m, l with w == h + m + l exactly."""
-    w = w.detach().float().contiguous()
-    h = w.to(torch.bfloat16)
-    r1 = w - h.float()
-    m = r1.to(torch.bfloat16)
-    lo = (r1 - m.float()).to(torch.bfloat16)
-    return torch.stack([h, m, lo]).view(torch.int16).contiguous()
+    return _bf16_planes(w.detach().float().contiguous()).contiguous()
 
 
 def _w2(w):
@@ -1029,7 +1027,7 @@ def conv_dgrad_plan(weight, stride, pad, device='cuda', name='', in_ch=None, fol
         return attach_winograd(ConvPlan([c], co, hi - lo, 1, 1, None, device, name))
     assert stride == 2
     classes = _fractional_classes(wsel, kh, kw, pad)
-    if (FOLD_K3S2 if fold is None else fold) and kh == 3 and kw == 3 and co % 32 == 0 and (hi - lo) % 4 == 0 and ENABLE_X6 and (fold or hi - lo <= FOLD_K3S2_MAX_COUT):
+    if (FOLD_K3S2 if fold is None else fold) and kh == 3 and kw == 3 and co % 32 == 0 and (hi - lo) % 4 == 0 and (fold or hi - lo <= FOLD_K3S2_MAX_COUT):
         return ConvPlan([_fold_classes(classes, hi - lo, co)], co, hi - lo, 1, 2, None, device, name, nfold=4)
     return ConvPlan(classes, co, hi - lo, 1, 2, None, device, name)
 
@@ -1044,13 +1042,13 @@ def deconv_fwd_plan(weight, bias, stride, pad, device='cuda', name='', fold=None
     def wsel(ky, kx):
         return w[:, :, ky, kx].t().contiguous()
 
-    if (FOLD_DECONV if fold is None else fold) and kh == 2 and kw == 2 and pad == 0 and ci % 32 == 0 and co % 4 == 0 and ENABLE_X6:
+    if (fold is None or fold) and kh == 2 and kw == 2 and pad == 0 and ci % 32 == 0 and co % 4 == 0:
         # the four output-parity classes share the tap (0, 0): fold them into the GEMM rows (row c*co + n, c = 2 dy + dx)
         c = TapClassSpec(0, 0)
         c.add(0, 0, torch.cat([wsel(dy, dx) for dy in (0, 1) for dx in (0, 1)], 0))
         return ConvPlan([c], ci, co, 1, 2, bias, device, name, nfold=4)
     classes = _fractional_classes(wsel, kh, kw, pad)
-    if fold and kh == 3 and kw == 3 and ci % 32 == 0 and co % 4 == 0 and ENABLE_X6:   # (measured slower for transConv1: opt-in)
+    if fold and kh == 3 and kw == 3 and ci % 32 == 0 and co % 4 == 0:   # (measured slower for transConv1: opt-in)
         return ConvPlan([_fold_classes(classes, co, ci)], ci, co, 1, 2, bias, device, name, nfold=4)
     return ConvPlan(classes, ci, co, 1, 2, bias, device, name)
 

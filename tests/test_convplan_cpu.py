@@ -249,3 +249,41 @@ def test_emulate_fp64_packed_taps(kind):
     # the fp16 plane: the same sums over the fp16-rounded weights
     yh = emulate(plan, nhwc(x, plan.cin_p), ref.shape[2], ref.shape[3], dtype=torch.float64, taps=cp_taps(plan, half=True))
     assert (nchw(yh) - op(x, wref.half().double(), bref)).abs().max().item() <= 1e-12 * scale
+
+
+def test_bf16_planes_one_split_everywhere():
+    """The three bf16 planes (w == h + m + l exactly) as `split_planes`, the constructor, `thin_fold(False)`, `c3_pack()` and
+    `_winograd_weights` make them: each sums back to its fp32 matrix bit for bit and equals `split_planes` of that matrix; the
+    planes of one small seeded weight are those kept in tests/golden/convplan_launches.json."""
+    import json
+    import os
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'convplan_launches.json')) as fh:
+        want = json.load(fh)['planes']
+    w = torch.randn(*want['shape'], generator=torch.Generator().manual_seed(want['seed']))
+
+    def check(planes, fp32=None):
+        pl = planes.view(torch.int16).reshape(3, -1)
+        s = pl.view(torch.bfloat16).float()
+        total = s[0] + s[1] + s[2]                      # (8 + 8 + 8 mantissa bits: exact in fp32)
+        assert torch.equal(cp.split_planes(total).reshape(3, -1), pl)
+        if fp32 is not None:
+            assert torch.equal(total, fp32.reshape(-1))
+        return total
+
+    assert cp.split_planes(w).tolist() == want['int16']
+    check(cp.split_planes(w), w)
+    plan = cp.linear_dgrad_plan(w, device='cpu')            # [32 outputs, 4 inputs]: the constructor's planes, per class [3][Npad][Kpad]
+    plan = getattr(plan, 'conv', plan)
+    check(plan.w_split, plan.weights)
+    assert torch.equal(plan.w_split.view(3, plan._npad, -1)[:, :32, :4], cp.split_planes(w.t().contiguous()))
+    thin = cp.conv_dgrad_plan(torch.randn(32, 3, 3, 3), 2, 1, device='cpu')
+    assert thin.thin_ok()
+    t = thin.thin_fold(False)
+    nkb, tbw = thin.cin_p // 32, thin.tap_range[3] - thin.tap_range[2] + 1
+    check(t.view(nkb, tbw, 3, -1).permute(2, 0, 1, 3).contiguous())
+    c3 = cp.conv_fwd_plan(torch.randn(64, 3, 3, 3), None, 1, 1, device='cpu')
+    assert c3.c3_ok()
+    tot = check(c3.c3_pack().view(1, 3, -1).permute(1, 0, 2).contiguous())
+    assert sorted(tot[tot != 0].tolist()) == sorted(c3.weights[c3.weights != 0].tolist())
+    wino = cp.conv_fwd_plan(torch.randn(64, 32, 3, 3), None, 1, 1, device='cpu').wino
+    check(wino.w_split, wino.weights)
