@@ -594,6 +594,18 @@ int spaa_onepixel_preproc(const float* base, const int32_t* cand, int P, int npi
  * argmax = first index of the largest p (numpy.argmax, :68-72); pmax = that p */
 int spaa_onepixel_score(const float* logits, int ncls, int target, int targeted, float* energy, int32_t* argmax, float* pmax,
                         int P, spaa_stream_t stream);
+/* Projector variant (ProjectorOnePixelAttacker, :161-176) with a PCNet as the project-and-capture step.  base [Hp][Wp][4] and cand as
+ * above (the squares are painted into the PROJECTOR image); tap_src / tap_wgt [Hc*Wc][4]: the engine's tap table (spaa_warp_taps,
+ * weights x mask).  xw [P][Hc][Wc][4] = bitwise spaa_warp_fwd_taps of the P painted images: a tap reads the last square that covers
+ * its projector pixel, else base; taps outside the image (0x7fffffff) read 0.  cat8 (may be NULL) [P][Hc][Wc][8] =
+ * (s.rgb, xw.r*s.r, xw.g*s.g, xw.b*s.b, 0, 0) with scene s [Hc][Wc][4] shared by all candidates, as spaa_warp_fwd writes it */
+int spaa_onepixel_warp(const float* base, const int32_t* cand, int P, int npix, int pixel_size, const int32_t* tap_src,
+                       const float* tap_wgt, const float* scene, float* xw, float* cat8, int Hp, int Wp, int Hc, int Wc,
+                       spaa_stream_t stream);
+/* y [B][H][W][4] in [0, 1] (PCNet's output) -> the classifier input out [B][oh][ow][4]: bitwise spaa_preproc_fwd of
+ * (float)(uint8)(y * 255) / 255 (quantize != 0: the camera's 8-bit step, capture() :153-159) or of y itself (quantize == 0) */
+int spaa_capture_preproc(const float* y, float* out, int B, int H, int W, int cy0, int cx0, int ch, int cw, int oh, int ow,
+                         const float* mean3, const float* std3, int quantize, spaa_stream_t stream);
 
 /* ---- direct-light mask of a camera view (train_network.py:68-80 load_data, img_proc.py:13-65 threshold_im) ---- */
 /* Nayar's separation of N >= 2 shifted-checkerboard captures cb [N][3][H][W] (planar fp32, projector backlight b in [0, 1)):

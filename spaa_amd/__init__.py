@@ -32,7 +32,7 @@ def __getattr__(name):
                 'get_model_train_cfg', 'train_eval_pcnet', 'train_eval_compennet_pp'):
         from . import train_network
         return getattr(train_network, name)
-    if name in ('DigitalOnePixelAttacker', 'perturb_image'):
+    if name in ('DigitalOnePixelAttacker', 'ProjectorOnePixelAttacker', 'SimulatedCapture', 'perturb_image'):
         from . import one_pixel_attacker
         return getattr(one_pixel_attacker, name)
     if name in ('calc_img_dists', 'img_stats', 'dists_from_sums'):

@@ -670,10 +670,29 @@ class PCNetEngine:
         """PCNet.forward on NHWC4 input [B,Hp,Wp,4]; returns cam_infer [B,Hc,Wc,4] (a workspace view)."""
         if self.scene is None:
             raise RuntimeError('call set_scene() first')
-        a, f = self.a, self.f
-        R, N = _lib.ACT_RELU, _lib.ACT_NONE
         self.version += 1
         self.warp(x4, clamp01)
+        return self._shade()
+
+    @property
+    def needs_cat8(self):
+        """True when the shading pass reads the 8-channel concatenation a['cat8'] (use_rough without the fused conv1 pair)."""
+        return self.rough and self.pair1 is None
+
+    def forward_from_xw(self):
+        """The forward pass from a warped projector image the caller has already written into a['xw'] (and, where `needs_cat8`,
+        cat([s, xw * s]) into a['cat8']): the One-pixel attacker's spaa_onepixel_warp paints and warps its candidates there.
+        Forward only: no projector image is kept for backward()."""
+        if self.scene is None:
+            raise RuntimeError('call set_scene() first')
+        self.version += 1
+        self._x = None
+        return self._shade()
+
+    def _shade(self):
+        """ShadingNet on a['xw'] (/ a['cat8']) and the scene: everything of forward() after the warp."""
+        a, f = self.a, self.f
+        R, N = _lib.ACT_RELU, _lib.ACT_NONE
         m = self.m if (USE_GATE_MASKS or self.storage == 'f16') else {k: None for k in self.m}
         if self.pair1 is not None:
             wp, b1, bs = self.pair1

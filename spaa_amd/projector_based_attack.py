@@ -499,7 +499,7 @@ def to_attacker_cfg_str(attacker_name):
     return attacker_name, None
 
 
-def run_projector_based_attack(cfg, *, models=None, classifiers=None, iters=50, train=False, model_cfg=None):
+def run_projector_based_attack(cfg, *, models=None, classifiers=None, iters=50, train=False, model_cfg=None, capture=None):
     """projector_based_attack.py:24-148 for the deep-learning attackers: per setup and classifier, 10 targeted attacks (the first 10
     imagenet10 classes) and 1 untargeted attack (the scene's top-1) for every stealth loss x d_thr; results under
     <setup>/prj/adv and <setup>/cam/infer/adv / <attacker_cfg_str>/<loss>/<d_thr>/<classifier>/img_0001..0011.png (1-10 targeted,
@@ -509,7 +509,10 @@ def run_projector_based_attack(cfg, *, models=None, classifiers=None, iters=50, 
     `train=True`: a setup without an entry in `models` is trained, or with cfg.load_pretrained loaded from its checkpoint, as the
     reference does (:50-60): train_network.train_eval_pcnet (SPAA) / train_eval_compennet_pp (PerC-AL+CompenNet++) on
     get_model_train_cfg's defaults, with the fields of `model_cfg` (a mapping, e.g. dict(max_iters=100)) laid over them; the last
-    configuration is left in cfg.model_cfg.  The default, train=False, raises for such a setup."""
+    configuration is left in cfg.model_cfg.  The default, train=False, raises for such a setup.
+    `capture` (One-pixel_DE only, :69-73,110-142): 'model' = models[setup] is a trained PCNet that stands in for the projector and the
+    camera (SimulatedCapture; captures go under cam/infer/adv), or a function setup_info -> capture callable for a real ProCams pair
+    (captures go under cam/raw/adv): see _run_one_pixel_de."""
     import itertools
     import random
     from os.path import join
@@ -519,8 +522,11 @@ def run_projector_based_attack(cfg, *, models=None, classifiers=None, iters=50, 
     if name not in ATTACKERS:
         raise ValueError(f'{name} not supported!')
     if name == 'One-pixel_DE':
-        raise NotImplementedError('One-pixel_DE attacks the real scene through a projector and a camera; use '
-                                  'spaa_amd.DigitalOnePixelAttacker for the digital attack')
+        if capture is None:
+            raise NotImplementedError('One-pixel_DE attacks the real scene through a projector and a camera; use '
+                                      'spaa_amd.DigitalOnePixelAttacker for the digital attack, or pass capture=\'model\' (a trained '
+                                      'PCNet in `models` simulates the capture) or capture=<function setup_info -> capture callable>')
+        return _run_one_pixel_de(cfg, models, classifiers, capture)
     device = torch.device(cfg.device)
     random.seed(0)   # (ut.reset_rng_seeds(0))
     torch.manual_seed(0)
@@ -574,6 +580,91 @@ def run_projector_based_attack(cfg, *, models=None, classifiers=None, iters=50, 
                 folder = join(attacker_cfg_str, loss, str(d_thr), classifier_name)
                 io.save_imgs(torch.cat((cam_tar, cam_untar), 0), join(setup_path, 'cam/infer/adv', folder))
                 io.save_imgs(torch.cat((prj_tar, prj_untar), 0), join(setup_path, 'prj/adv', folder))
+    return cfg
+
+
+def _run_one_pixel_de(cfg, models, classifiers, capture):
+    """projector_based_attack.py:69-73,110-142: Nichols & Jasper's projector-based One-pixel DE attacker on one setup.  Per classifier
+    one untargeted attack on the scene's top-1 (popsize 50) and ten targeted ones (popsize 10), pixel_size 41, 4 generations, one after
+    another on numpy's global RNG stream as in the reference (the untargeted attack first; it is saved last, as img_0011).  Projector
+    images go under prj/adv/One-pixel_DE/-/-/<classifier>/; captures of a real `capture` under cam/raw/adv/..., those of
+    capture='model' under cam/infer/adv/... (they are inferred: the real ones are still made by projecting prj/adv).
+    An optional cfg.maxiter replaces the reference's hard-coded 4 generations."""
+    import itertools
+    import random
+    from os.path import join
+    from . import io
+    from .classifier import load_imagenet_labels
+    from .img_proc import center_crop, expand_4d
+    from .models import PCNet
+    from .one_pixel_attacker import ProjectorOnePixelAttacker, SimulatedCapture
+    if len(cfg.setup_list) != 1:
+        raise ValueError('One-pixel_DE: cfg.setup_list must hold exactly one setup (the projector and the camera see one scene), got '
+                         f'{list(cfg.setup_list)}')
+    if capture != 'model' and not callable(capture):
+        raise ValueError("capture must be 'model' or a function setup_info -> capture callable")
+    setup_name = cfg.setup_list[0]
+    missing = [c for c in cfg.classifier_names if c not in (classifiers or {})]
+    if missing:
+        raise ValueError(f'run_projector_based_attack: pass classifiers={{name: spaa_amd.Classifier}} for {missing} '
+                         '(weights cannot be downloaded here)')
+    np.random.seed(0)   # (ut.reset_rng_seeds(0); DE draws from numpy's global state)
+    random.seed(0)
+    torch.manual_seed(0)
+    if torch.cuda.is_available():
+        torch.cuda.manual_seed_all(0)
+    setup_path = join(cfg.data_root, 'setups', setup_name)
+    setup_info = io.load_setup_info(setup_path)
+    cp_sz = setup_info['classifier_crop_sz']
+    cam_scene = center_crop(io.torch_imread(join(setup_path, 'cam/raw/ref/img_0002.png')), tuple(setup_info['cam_im_sz'])[::-1])
+    if isinstance(capture, str):
+        model = (models or {}).get(setup_name)
+        if not isinstance(model, PCNet):
+            raise ValueError(f"run_projector_based_attack: capture='model' needs models={{{setup_name!r}: trained PCNet}}, got "
+                             f'{type(model).__name__}')
+        model.eval()
+        for param in model.parameters():
+            param.requires_grad = False
+        cap, cam_kind = SimulatedCapture(model, cam_scene), 'cam/infer/adv'
+    else:
+        cap, cam_kind = capture(setup_info), 'cam/raw/adv'
+    imagenet_labels = load_imagenet_labels(join(cfg.data_root, 'imagenet1000_clsidx_to_labels.txt'))
+    target_labels = load_imagenet_labels(join(cfg.data_root, 'imagenet10_clsidx_to_labels.txt'))
+    n = 10
+    target_idx = list(dict(itertools.islice(target_labels.items(), n)).keys())
+    one_pixel_de = ProjectorOnePixelAttacker(imagenet_labels, setup_info, capture=cap)
+    im_prj_org = setup_info['prj_brightness'] * torch.ones(3, *setup_info['prj_im_sz'])
+    one_pixel_de.im_prj_org, one_pixel_de.im_cam_org = im_prj_org, cam_scene
+    attacker_cfg_str = to_attacker_cfg_str('One-pixel_DE')[0]
+    for stealth_loss in cfg.stealth_losses:
+        for d_thr in cfg.d_threshes:
+            for classifier_name in cfg.classifier_names:
+                folder = join(attacker_cfg_str, stealth_loss, str(d_thr), classifier_name)
+                cam_path, prj_path = join(setup_path, cam_kind, folder), join(setup_path, 'prj/adv', folder)
+                classifier = classifiers[classifier_name]
+                with torch.no_grad():
+                    raw_score, p, _ = classifier(cam_scene, cp_sz)
+                true_idx = int(raw_score[0].argmax())   # (p.argmax() of the unsorted result; also for a sorting classifier)
+                true_label = imagenet_labels[true_idx]
+                print(f'\n-------------------- [One-pixel_DE] attacking [{classifier_name}], original prediction: ({true_label}, '
+                      f'p={p.max():.2f}), Loss: [{stealth_loss}], d_thr: [{d_thr}] --------')
+                print(f'[Untargeted] attacking [{classifier_name}]...')
+                _, prj_untar, cam_untar = one_pixel_de(im_prj_org, classifier, False, target_idx=true_idx, pixel_count=1, pixel_size=41,
+                                                       maxiter=cfg.get('maxiter', 4), popsize=50, verbose=True, true_label=true_label)
+                for i in range(n):
+                    print(f'\n[ Targeted ] attacking [{classifier_name}], target: ({imagenet_labels[target_idx[i]]})...')
+                    _, prj_tar, cam_tar = one_pixel_de(im_prj_org, classifier, True, target_idx=target_idx[i], pixel_count=1,
+                                                       pixel_size=41, maxiter=cfg.get('maxiter', 4), popsize=10, verbose=True,
+                                                       true_label=true_label)
+                    io.save_imgs(expand_4d(cam_tar), cam_path, idx=i)
+                    io.save_imgs(expand_4d(prj_tar), prj_path, idx=i)
+                io.save_imgs(expand_4d(cam_untar), cam_path, idx=n)
+                io.save_imgs(expand_4d(prj_untar), prj_path, idx=n)
+    if cam_kind == 'cam/raw/adv':
+        print(f'\nThe next step is to inspect the camera-captured adversarial projections in {join(setup_path, cam_kind, attacker_cfg_str)}')
+    else:
+        print(f'\nThe next step is to project and capture [One-pixel_DE] generated adversarial projections in '
+              f'{join(setup_path, "prj/adv", attacker_cfg_str)}')
     return cfg
 
 
