@@ -627,6 +627,29 @@ int spaa_mask_blur_hist(const uint8_t* gray_u8, int H, int W, uint8_t* smooth_u8
 int spaa_otsu_mask_bbox(const uint8_t* smooth_u8, const uint32_t* hist, int H, int W, uint8_t* mask, int32_t* out6,
                         spaa_stream_t stream);
 
+/* ---- result montages of the summary step (projector_based_attack.py:362-414 attack_results, img_proc.py:174-197 resize,
+ * torchvision make_grid(nrow=5, padding=5, pad_value=1), cv.applyColorMap) ---------------------------------------------------- */
+/* rz(x) = the ch x cw window of x at (y0, x0) (img_proc.center_crop: the caller computes the origin), then
+ * F.interpolate(mode='area') to Hp x Wp: output row o covers window rows floor(o ch / Hp) .. ceil((o + 1) ch / Hp) - 1, columns
+ * likewise; the window's values are added from 0 in row-major order and the sum is divided by the window's height, then by its
+ * width (two correctly rounded fp32 divisions, as ATen's adaptive average pooling).  cam_scene [3][Hs][Ws], cam_real
+ * [N][3][Hr][Wr], planar fp32.  minmax [N][2] = min and max over the 3 Hp Wp values |rz(real_n) - rz(scene)|; written in full
+ * (no initialisation needed), integer atomics on the bit patterns of the non-negative floats: bitwise the same on every run.
+ * Two kernels whatever N.  N <= 65535, image sides <= 32768. */
+int spaa_montage_diff_range(const float* cam_scene, int Hs, int Ws, int sy0, int sx0, const float* cam_real, int Hr, int Wr, int ry0,
+                            int rx0, int N, int ch, int cw, int Hp, int Wp, float* minmax, spaa_stream_t stream);
+/* out [N][3][Hm][Wm] bytes, Hm = 26 + Hp + 10, Wm = 5 (Wp + 5) + 5: background 255; tile k at (y = 31, x = 5 + k (Wp + 5)) =
+ * rz(scene), prj_adv[n] ([N][3][Hp][Wp]), rz(cam_infer[n]), rz(cam_real[n]) as (uint8)floor(v 255f) for v in [0, 1], and the
+ * difference tile lut[index], lut [256][3] bytes, index = (uint8)floor(m 255f), m = ((q_0 + q_1) + q_2) / 3f,
+ * q_c = (|rz(real)_c - rz(scene)_c| - mn) / (mx - mn) with (mn, mx) = minmax[n] of spaa_montage_diff_range; mx == mn: index 0.
+ * No operation is contracted or reassociated.  Then the text: glyph_recs [nrec][4] int32 = (item, x, y, glyph), font
+ * [95][font_h] row bytes (bit x = column x, font_w <= 8), glyph = character code - 32; a set bit inside the montage becomes
+ * (0, 0, 0), the rest of a glyph is clipped, a record that names no item or no glyph is skipped.  Two kernels whatever N. */
+int spaa_montage_compose(const float* cam_scene, int Hs, int Ws, int sy0, int sx0, const float* prj_adv, const float* cam_infer, int Hi,
+                         int Wi, int iy0, int ix0, const float* cam_real, int Hr, int Wr, int ry0, int rx0, int N, int ch, int cw, int Hp,
+                         int Wp, const float* minmax, const uint8_t* lut, const int32_t* glyph_recs, int nrec, const uint8_t* font,
+                         int font_w, int font_h, uint8_t* out, spaa_stream_t stream);
+
 /* misc */
 int spaa_zero(void* p, int64_t bytes, spaa_stream_t stream);
 const char* spaa_version(void);

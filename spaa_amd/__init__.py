@@ -16,7 +16,8 @@ def __getattr__(name):
         from . import classifier
         return getattr(classifier, name)
     if name in ('spaa', 'spaa_attack', 'AttackState', 'spaa_sweep', 'run_projector_based_attack', 'get_attacker_cfg',
-                'to_attacker_cfg_str', 'summarize_single_attacker', 'summarize_all_attackers'):
+                'to_attacker_cfg_str', 'summarize_single_attacker', 'summarize_all_attackers', 'project_capture_real_attack',
+                'attack_results'):
         from . import projector_based_attack
         return getattr(projector_based_attack, name)
     if name in ('rgb2lab_diff', 'ciede2000_diff', 'deltaE', 'stealth_loss_with_grad'):
@@ -41,6 +42,9 @@ def __getattr__(name):
     if name in ('threshold_im', 'get_affine_transform', 'center_crop', 'expand_4d', 'resize'):
         from . import img_proc
         return getattr(img_proc, name)
+    if name in ('attack_montages', 'layout_labels', 'attack_texts', 'JET'):
+        from . import montage
+        return getattr(montage, name)
     if name in ('torch_imread', 'torch_imread_mt', 'save_imgs', 'load_setup_info', 'save_checkpoint'):
         from . import io
         return getattr(io, name)

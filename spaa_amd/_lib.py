@@ -146,6 +146,8 @@ _SIGNATURES = {
     'spaa_cb_direct_gray': [_p, _i, _i, _i, _d, _p, _p, _p, _p],
     'spaa_mask_blur_hist': [_p, _i, _i, _p, _p, _p],
     'spaa_otsu_mask_bbox': [_p, _p, _i, _i, _p, _p, _p],
+    'spaa_montage_diff_range': [_p, _i, _i, _i, _i, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p],
+    'spaa_montage_compose': [_p, _i, _i, _i, _i, _p, _p, _i, _i, _i, _i, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _i, _p, _i, _i, _p, _p],
     'spaa_zero': [_p, _l, _p],
 }
 

@@ -668,6 +668,82 @@ def _run_one_pixel_de(cfg, models, classifiers, capture):
     return cfg
 
 
+def project_capture_real_attack(cfg, *, capture, models=None):
+    """projector_based_attack.py:151-166 (steps 5.2 / 6.2 of the reference's main.py): project every adversarial image of
+    <setup>/prj/adv/<attacker_cfg_str>/<loss>/<d_thr>/<classifier> and write its capture to the same folder under cam/raw/adv, as
+    img_%04d.png counted in the sorted order of the projector images.  SPAA and PerC-AL+CompenNet++ only, and exactly one setup
+    (ValueError otherwise; the reference asserts).  `capture` follows _run_one_pixel_de's convention: a function setup_info ->
+    (im_prj uint8 [3,Hp,Wp] -> im_cam float [3,Hc,Wc]) for a real ProCams pair, or 'model': models[setup] (a trained PCNet) stands in
+    for the projector and the camera through SimulatedCapture with the camera's 8-bit step.  A configured folder without projector
+    images raises ValueError."""
+    import os
+    from os.path import join
+    from . import io
+    from .img_proc import center_crop, expand_4d
+    name = cfg.attacker_name
+    if name not in ('SPAA', 'PerC-AL+CompenNet++'):
+        raise ValueError(f'{name} not supported, One-pixel_DE does not use this function!')
+    if len(cfg.setup_list) != 1:
+        raise ValueError(f'cfg.setup_list must hold exactly one setup (the projector and the camera see one scene), got '
+                         f'{list(cfg.setup_list)}')
+    if capture != 'model' and not callable(capture):
+        raise ValueError("capture must be 'model' or a function setup_info -> capture callable")
+    setup_name = cfg.setup_list[0]
+    setup_path = join(cfg.data_root, 'setups', setup_name)
+    setup_info = io.load_setup_info(setup_path)
+    attacker_cfg_str = to_attacker_cfg_str(name)[0]
+    folders = [join(attacker_cfg_str, loss, str(d_thr), c) for loss in cfg.stealth_losses for d_thr in cfg.d_threshes
+               for c in cfg.classifier_names]
+    for folder in folders:
+        if not _nonempty(join(setup_path, 'prj/adv', folder)):
+            raise ValueError(f'project_capture_real_attack: no projector images in {join(setup_path, "prj/adv", folder)}')
+    if isinstance(capture, str):
+        from .models import PCNet
+        from .one_pixel_attacker import SimulatedCapture
+        model = (models or {}).get(setup_name)
+        if not isinstance(model, PCNet):
+            raise ValueError(f"project_capture_real_attack: capture='model' needs models={{{setup_name!r}: trained PCNet}}, got "
+                             f'{type(model).__name__}')
+        model.eval()
+        for param in model.parameters():
+            param.requires_grad = False
+        cam_scene = center_crop(io.torch_imread(join(setup_path, 'cam/raw/ref/img_0002.png')), tuple(setup_info['cam_im_sz'])[::-1])
+        cap = SimulatedCapture(model, cam_scene, quantize=True)
+    else:
+        cap = capture(setup_info)
+    for folder in folders:
+        prj_path, cam_path = join(setup_path, 'prj/adv', folder), join(setup_path, 'cam/raw/adv', folder)
+        for i, fn in enumerate(sorted(os.listdir(prj_path))):
+            im_prj = torch.from_numpy(io._imread_rgb(join(prj_path, fn)).transpose(2, 0, 1).copy())
+            io.save_imgs(expand_4d(cap(im_prj).detach().float()), cam_path, idx=i)
+    print(f'\nThe camera-captured adversarial projections are in {join(setup_path, "cam/raw/adv", attacker_cfg_str)}')
+    return cfg
+
+
+def attack_results(ret, t, imgnet_labels, im_gray, prj_adv, cam_scene, cam_infer, cam_real, prj_im_sz, cp_sz):
+    """projector_based_attack.py:362-414: the result montage of attack `t` as a float [3,Hm,Wm] image (spaa_amd.montage's bytes
+    divided by 255).  ret['scene' / 'infer' / 'real'] = the classifier tuples (raw, p_sorted, idx_sorted); the L2 values come from
+    metrics.l2_norm.  The tiles have prj_adv's own size (Hp, Wp): the reference passes prj_im_sz, which is (w, h), as (h, w), and so
+    works for square projectors only; `prj_im_sz` is not used.  GPU only."""
+    from . import metrics as M
+    from .img_proc import center_crop
+    from .montage import attack_montages, attack_texts
+    for name, x in (('prj_adv', prj_adv), ('cam_scene', cam_scene), ('cam_infer', cam_infer), ('cam_real', cam_real)):
+        if not x.is_cuda:
+            raise RuntimeError(f'attack_results builds the montage on the GPU only (no CPU fallback): {name} is on {x.device}')
+    scene = cam_scene.reshape(-1, *cam_scene.shape[-3:])[0]
+    gray = im_gray.reshape(-1, *im_gray.shape[-3:])[0]
+    scene_cp = center_crop(scene, cp_sz)
+    l2 = (M.l2_norm(prj_adv[t], gray.to(prj_adv.device).expand_as(prj_adv[t])), M.l2_norm(center_crop(cam_infer[t], cp_sz), scene_cp),
+          M.l2_norm(center_crop(cam_real[t], cp_sz), scene_cp))
+
+    def top1(key, row):
+        return imgnet_labels[int(ret[key][2][row, 0])], float(ret[key][1][row, 0])
+    texts = attack_texts(t, top1('scene', 0), top1('infer', t), top1('real', t), l2)
+    im = attack_montages(scene, prj_adv[t:t + 1], cam_infer[t:t + 1], cam_real[t:t + 1], cp_sz, [texts])[0]
+    return im.float() / torch.full((), 255.0, device=im.device)     # (a true division: `/ 255` multiplies by 1 / 255 on the GPU)
+
+
 # ---------------------------------------------------------------------------------------------------------------------------------
 # The summary step (projector_based_attack.py:417-614): success rates and image metrics of every attack configuration of a setup.
 SUMMARY_STEALTH_LOSSES = ['caml2', 'camdE', 'camdE_caml2', '-']
@@ -701,10 +777,11 @@ def write_stats(table, path):
     table.to_csv(path, index=False, float_format='%.4f', sep='\t')
 
 
-def _sorted_classes(classifier, ims, crop_sz, chunk=None):
+def _sorted_classes(classifier, ims, crop_sz, chunk=None, top1=None):
     """Class indices sorted by descending softmax probability (classifier.py:64-72) of every image of `ims` (a list of [b,3,H,W]
     tensors): images of one size go through the classifier in equal chunks of at most SUMMARY_CHUNK, the last one padded with
-    zeros (one engine geometry per size)."""
+    zeros (one engine geometry per size).  `top1`: a list of len(ims) slots that receives each image's largest probability
+    (float32 arrays, from the same softmax)."""
     chunk = chunk or SUMMARY_CHUNK
     out = [None] * len(ims)
     by_shape = {}
@@ -722,10 +799,13 @@ def _sorted_classes(classifier, ims, crop_sz, chunk=None):
             with torch.no_grad():
                 raw = classifier(part, crop_sz)[0]
                 probs.append(torch.softmax(raw.detach(), dim=1)[:m].cpu())
-        idx = torch.cat(probs).sort(descending=True)[1].numpy()
+        p_sorted, idx = torch.cat(probs).sort(descending=True)
+        p_sorted, idx = p_sorted.numpy(), idx.numpy()
         a = 0
         for k in ks:
             out[k] = idx[a:a + ims[k].shape[0]]
+            if top1 is not None:
+                top1[k] = p_sorted[a:a + ims[k].shape[0], 0]
             a += ims[k].shape[0]
     return out
 
@@ -735,7 +815,10 @@ def _nonempty(d):
     return os.path.exists(d) and len(os.listdir(d)) > 0
 
 
-def summarize_single_attacker(attacker_name, data_root, setup_list, device='cuda', device_ids=[0], *, classifiers=None):
+MONTAGE_CHUNK = 264   # montages per attack_montages call in the summary (24 configurations; bounds the output buffer, ~300 MB at 256^2 tiles)
+
+
+def summarize_single_attacker(attacker_name, data_root, setup_list, device='cuda', device_ids=[0], *, classifiers=None, montages=False):
     """projector_based_attack.py:417-574: per setup, one row per attack configuration (stealth loss x d_thr x classifier) of
     `attacker_name` found on disk -- targeted top-1 / top-5 and untargeted top-1 success of the inferred and the real
     camera-captured attacks, and PSNR / RMSE / SSIM / L2 / L_inf / dE2000 of the projector images (vs the grey illumination), the
@@ -747,7 +830,12 @@ def summarize_single_attacker(attacker_name, data_root, setup_list, device='cuda
       * a missing or empty folder skips that configuration only (the reference leaves the classifier loop at the first one);
       * the Valid_* columns are NaN, with a note, when the validation inferences are not on disk (this project's trainers do not
         write */infer/test);
-      * no montages and no stats.xlsx (neither cv2 nor an Excel engine is a dependency).
+      * no stats.xlsx (no Excel engine is a dependency);
+      * the result montages (attack_results, <setup>/ret/<attacker_cfg_str>/<loss>/<d_thr>/<classifier>/img_0001..0011.png) are
+        written with `montages=True` only.  They come from spaa_amd.montage: all montages of a setup from ONE attack_montages call
+        (split only every MONTAGE_CHUNK montages to bound memory), with the labels' top-1 probabilities from the softmax computed
+        for the success rates and the L2 values from the img_stats sums.  Their text is a bitmap font at the tiles' edges and the
+        colour map a restatement of Jet (spaa_amd/montage.py); the tiles have the projector images' own size.
     Mechanism: all images of a setup are loaded at once, each classifier sees them in chunks of SUMMARY_CHUNK, and every image
     metric of the setup comes from ONE metrics.img_stats launch, grouped on the host with metrics.dists_from_sums."""
     import itertools
@@ -801,18 +889,20 @@ def summarize_single_attacker(attacker_name, data_root, setup_list, device='cuda
                                  f'{p.shape[0]} / {r.shape[0]} / {i.shape[0]}')
 
         # classification: per classifier, the scene and every inferred / captured image of its configurations
-        idx = {}   # (config, 'scene' / 'infer' / 'real') -> sorted class indices
+        idx, top1 = {}, {}   # (config, 'scene' / 'infer' / 'real') -> sorted class indices, top-1 probabilities
         for cname in SUMMARY_CLASSIFIERS:
             ks = [k for k, c in enumerate(cfgs) if c[2] == cname]
             if not ks:
                 continue
             clf = classifiers[cname]
             ims = [cam_scene[None]] + [infer[k] for k in ks] + ([real[k] for k in ks] if dl_based else [])
-            res = _sorted_classes(clf, ims, cp_sz)
+            top = [None] * len(ims)
+            res = _sorted_classes(clf, ims, cp_sz, top1=top)
             for j, k in enumerate(ks):
-                idx[k, 'scene'] = res[0]
-                idx[k, 'infer'] = res[1 + j]
-                idx[k, 'real'] = res[1 + len(ks) + j] if dl_based else res[1 + j]
+                idx[k, 'scene'], top1[k, 'scene'] = res[0], top[0]
+                idx[k, 'infer'], top1[k, 'infer'] = res[1 + j], top[1 + j]
+                jr = 1 + len(ks) + j if dl_based else 1 + j
+                idx[k, 'real'], top1[k, 'real'] = res[jr], top[jr]
 
         # image metrics: one launch over every pair of the setup
         xs, ys, pairs, spans = [], [cam_scene.reshape(-1)], [], {}
@@ -871,14 +961,42 @@ def summarize_single_attacker(attacker_name, data_root, setup_list, device='cuda
         ret_path = join(setup_path, 'ret', attacker_cfg_str)
         os.makedirs(ret_path, exist_ok=True)
         write_stats(table, join(ret_path, 'stats.txt'))
+
+        if montages and cfgs:
+            from .montage import attack_montages, attack_texts
+            if len({tuple(t.shape[1:]) for t in prj}) != 1 or len({tuple(t.shape[1:]) for t in infer}) != 1 or \
+                    len({tuple(t.shape[1:]) for t in real}) != 1:
+                raise ValueError(f'summarize_single_attacker: the montages of [{setup_name}] need images of one size per kind')
+            imagenet_labels = load_imagenet_labels(join(data_root, 'imagenet1000_clsidx_to_labels.txt'))
+            m = n + 1
+
+            def label(k, kind, row):
+                return imagenet_labels[int(idx[k, kind][row, 0])], float(top1[k, kind][row])
+
+            def l2(k, kind, t):
+                j = spans[k, kind][t]
+                return sums[j, 2] / npix[j] * 255
+            texts = [attack_texts(t, label(k, 'scene', 0), label(k, 'infer', t), label(k, 'real', t),
+                                  (l2(k, 'prj', t), l2(k, 'infer', t), l2(k, 'real', t)))
+                     for k in range(len(cfgs)) for t in range(m)]
+            per = max(1, MONTAGE_CHUNK // m)           # whole configurations per call
+            for a in range(0, len(cfgs), per):
+                ks = range(a, min(a + per, len(cfgs)))
+                with _lib.on_device(device):
+                    ims = attack_montages(cam_scene, torch.cat([prj[k][:m] for k in ks]), torch.cat([infer[k][:m] for k in ks]),
+                                          torch.cat([real[k][:m] for k in ks]), cp_sz, texts[a * m:(a + len(ks)) * m])
+                ims = ims.permute(0, 2, 3, 1).cpu().numpy()
+                for j, k in enumerate(ks):
+                    io.save_imgs(ims[j * m:(j + 1) * m], join(setup_path, 'ret', attacker_cfg_str, cfgs[k][0], str(cfgs[k][1]), cfgs[k][2]))
     return table
 
 
-def summarize_all_attackers(attacker_names, data_root, setup_list, recreate_stats_and_imgs=False, *, classifiers=None):
+def summarize_all_attackers(attacker_names, data_root, setup_list, recreate_stats_and_imgs=False, *, classifiers=None, montages=False):
     """projector_based_attack.py:577-614: concatenate <setup>/ret/<attacker_cfg_str>/stats.txt of every setup and attacker
     (recreated first by summarize_single_attacker when `recreate_stats_and_imgs`), and the pivot table of the SPAA paper's
     Table 1 (supplementary Table 2).  Writes <data_root>/setups/stats_all.txt and pivot_table_all.txt (tab-separated, 4
-    decimals; the reference's .xlsx copies are not written: no Excel engine is a dependency).  Returns (table, pivot_table)."""
+    decimals; the reference's .xlsx copies are not written: no Excel engine is a dependency).  `montages=True` is handed to
+    summarize_single_attacker when the stats are recreated (the result montages).  Returns (table, pivot_table)."""
     import warnings
     from os.path import join
     import pandas as pd
@@ -891,7 +1009,7 @@ def summarize_all_attackers(attacker_names, data_root, setup_list, recreate_stat
             print(f'\nGathering stats of {ret_path}')
             if recreate_stats_and_imgs:
                 summarize_single_attacker(attacker_name=attacker_name, data_root=data_root, setup_list=[setup_name],
-                                          classifiers=classifiers)
+                                          classifiers=classifiers, montages=montages)
             table.append(pd.read_csv(join(ret_path, 'stats.txt'), index_col=None, header=0, sep='\t'))
     table = pd.concat(table, axis=0, ignore_index=True)
     with warnings.catch_warnings():
