@@ -650,6 +650,28 @@ int spaa_montage_compose(const float* cam_scene, int Hs, int Ws, int sy0, int sx
                          int Wp, const float* minmax, const uint8_t* lut, const int32_t* glyph_recs, int nrec, const uint8_t* font,
                          int font_w, int font_h, uint8_t* out, spaa_stream_t stream);
 
+/* ---- PNG encoding of device-resident images (spaa_amd/png.py holds the host half: Huffman tables, chunk CRCs, files) ---------
+ * images: N images [N][3][H][W], planar fp32 (is_f32 != 0) or planar bytes.  An fp32 value becomes the low 8 bits of
+ * (int32)(x * 255f): one fp32 multiply, truncation toward zero, i.e. np.uint8(x * 255) for x in [0, 1]; NaN / inf unspecified.
+ * streams [N][H][1 + 3 W]: the PNG scanlines, RGB interleaved, each row led by its filter type.  Filters 0..4 (None, Sub, Up,
+ * Average, Paeth with tie order left, up, upper-left) are all computed from the UNFILTERED neighbours, bytes left of the row and
+ * above row 0 counting as 0; a candidate byte v costs min(v, 256 - v) and the filter with the lowest row sum wins, ties to the
+ * lowest number.  hist [N][257] uint32: the histogram of the image's stream bytes, bin 256 (end of block) = 1; written in full.
+ * adler [N][H][2] uint32: per row (sum of its 1 + 3 W bytes, sum of byte j times (1 + 3 W - j)), both mod 65521.  Integer atomics
+ * only: bitwise the same on every run.  N <= 65535, 3 W <= 30000.  Two kernels whatever N. */
+int spaa_png_filter_hist(const void* images, int is_f32, int N, int H, int W, uint8_t* streams, uint32_t* hist, uint32_t* adler,
+                         spaa_stream_t stream);
+/* The deflate stream of every image as ONE dynamic-Huffman block of literals: the header bits, the code of every stream byte in
+ * order, the code of symbol 256, the last byte zero-padded.  streams [N][stream_bytes]; tables [N][257] uint32 = code | length
+ * << 16, the code bit-reversed (deflate packs Huffman codes from their most significant bit into a stream filled from the least
+ * significant bit), length <= 15; hdr [N][64] uint32 little-endian header bits, hdr_bits [N] their count (<= 2048); offsets [N]
+ * int64: the byte offset of image n's stream in out.  out [out_bytes]: ZEROED by the caller, 4-byte aligned, out_bytes a multiple
+ * of 4 (bits are ORed in, so neighbouring images may share a word); nothing is written past out_bytes.  chunk_bits: scratch,
+ * uint32 [N][stream_bytes / 4096 + 1].  Bit positions are 64-bit.  The bytes do not depend on the order of execution. */
+int spaa_png_pack(const uint8_t* streams, int64_t stream_bytes, int N, const uint32_t* tables, const uint32_t* hdr,
+                  const int32_t* hdr_bits, const int64_t* offsets, uint32_t* chunk_bits, uint8_t* out, int64_t out_bytes,
+                  spaa_stream_t stream);
+
 /* misc */
 int spaa_zero(void* p, int64_t bytes, spaa_stream_t stream);
 const char* spaa_version(void);

@@ -148,6 +148,8 @@ _SIGNATURES = {
     'spaa_otsu_mask_bbox': [_p, _p, _i, _i, _p, _p, _p],
     'spaa_montage_diff_range': [_p, _i, _i, _i, _i, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p],
     'spaa_montage_compose': [_p, _i, _i, _i, _i, _p, _p, _i, _i, _i, _i, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _i, _p, _i, _i, _p, _p],
+    'spaa_png_filter_hist': [_p, _i, _i, _i, _i, _p, _p, _p, _p],
+    'spaa_png_pack': [_p, _l, _i, _p, _p, _p, _p, _p, _p, _l, _p],
     'spaa_zero': [_p, _l, _p],
 }
 

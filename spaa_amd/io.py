@@ -1,4 +1,5 @@
-"""On-disk formats either side of the attack path, with the reference's conventions (host side, no GPU work).
+"""On-disk formats either side of the attack path, with the reference's conventions (host side; PNG encoding of device tensors aside,
+no GPU work).
 
 Mirrors /root/reference/src/python:
   utils.py:84-167     SimpleDataset / torch_imread / torch_imread_mt / save_imgs  (PNG via OpenCV there: BGR on disk order
@@ -7,7 +8,8 @@ Mirrors /root/reference/src/python:
   train_network.py:85-95, utils.py:674-675   load_setup_info / save of setup_info.yml (OmegaConf/yaml mapping)
   utils.py:679-680, :717-721                 opt_to_string / save_checkpoint (state_dict in `<dir>/<title>.pth`)
 so that a setup directory captured and trained by the reference can be consumed, and results land where its
-`summarize_*` functions expect them.  Pillow replaces OpenCV as the codec (OpenCV is not a dependency of this package).
+`summarize_*` functions expect them.  Pillow replaces OpenCV as the codec (OpenCV is not a dependency of this package); images that
+are already on the GPU are encoded there (spaa_amd/png.py).
 """
 import os
 import warnings
@@ -18,6 +20,8 @@ import torch
 import torch.nn.functional as F
 import yaml
 from PIL import Image
+
+from . import png
 
 
 def _imread_rgb(filename):
@@ -55,8 +59,17 @@ def torch_imread_mt(img_dir, size=None, index=None, gray_scale=False, normalize=
 
 def save_imgs(im_4d, path, idx=0):
     """utils.py:146-167: [N,3,H,W] tensor or [N,H,W,3] array -> path/img_%04d.png numbered from idx + 1; float images are
-    scaled by 255 and truncated to uint8 exactly as `np.uint8(x * 255)` does."""
+    scaled by 255 and truncated to uint8 exactly as `np.uint8(x * 255)` does.
+    A float32 or uint8 CUDA tensor [N,3,H,W] is encoded on its device (spaa_amd.png.encode_png: same names, same decoded pixels;
+    float values outside [0,1] keep the low 8 bits of the truncated product); anything else -- host arrays, CPU tensors, other
+    dtypes -- is written through Pillow."""
     os.makedirs(path, exist_ok=True)
+    if isinstance(im_4d, torch.Tensor) and im_4d.is_cuda and im_4d.ndim == 4 and im_4d.shape[1] == 3 and im_4d.numel() > 0 and \
+            im_4d.dtype in (torch.float32, torch.uint8) and 3 * im_4d.shape[3] <= png.MAX_ROW_BYTES:
+        for i, data in enumerate(png.encode_png(im_4d)):
+            with open(join(path, 'img_{:04d}.png'.format(i + 1 + idx)), 'wb') as fh:
+                fh.write(data)
+        return
     if isinstance(im_4d, torch.Tensor):
         imgs = im_4d.detach().cpu().numpy().transpose(0, 2, 3, 1)
     else:

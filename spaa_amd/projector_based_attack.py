@@ -985,7 +985,6 @@ def summarize_single_attacker(attacker_name, data_root, setup_list, device='cuda
                 with _lib.on_device(device):
                     ims = attack_montages(cam_scene, torch.cat([prj[k][:m] for k in ks]), torch.cat([infer[k][:m] for k in ks]),
                                           torch.cat([real[k][:m] for k in ks]), cp_sz, texts[a * m:(a + len(ks)) * m])
-                ims = ims.permute(0, 2, 3, 1).cpu().numpy()
                 for j, k in enumerate(ks):
                     io.save_imgs(ims[j * m:(j + 1) * m], join(setup_path, 'ret', attacker_cfg_str, cfgs[k][0], str(cfgs[k][1]), cfgs[k][2]))
     return table
