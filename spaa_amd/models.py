@@ -10,7 +10,9 @@ passes).  Parameters are treated as frozen, as the attack does (projector_based_
 gradients are produced.
 """
 import copy
+import functools
 import os
+import types
 import weakref
 
 import torch
@@ -424,17 +426,170 @@ class _Activations(dict):
         return dict.__getitem__(self, k)
 
 
+def describe_routes(r):
+    """One string per route family of pcnet_routes()'s record or of a live PCNetEngine, as ConvPlan.describe gives for one layer."""
+    two_src = 'h16p' if r.storage == 'f16' else 'x6p'
+    on = {True: 'fused', False: 'separate'}
+    return {'skip2': 'fs2' if r.fs2 is not None else two_src if r.fuse_skip2 and 'transConv1x' in r.f else 'separate',
+            's2f': 'h16' if r.fs2 is not None and 'f2' in r.fs2 else 'x6' if r.s2fx is not None else 'plan',
+            'skip3': on[bool(r.fuse_skip3)], 'conv1_pair': on[r.pair1 is not None], 'conv1_pair_bwd': on[r.pair1_bwd is not None],
+            'tail': on[bool(r.fuse_tail)], 'clamp_gate': 'byte' if r.fuse_tail and r.want_gate_y else 'ypre'}
+
+
+def pcnet_routes(sn, use_rough, batch, cam_size, storage='f32', fuse_skip2=None, fuse_tail=None, device='cpu'):
+    """Which kernel serves which layer of the ShadingNetSPAA `sn`, decided here once per engine: a record of PCNetEngine's attributes
+    f, d, fs2, s2fx, pair1, pair1_bwd (None: route not taken), tail, fuse_skip2, fuse_skip3, fuse_tail, want_gate_y and _packed_from.
+    `fuse_skip2` / `fuse_tail`: None = where it applies, False = never; fuse_skip2=False also keeps off every other route whose weights
+    are packed here only (the training step refreshes the separate layers' plans).  No workspace, no GPU needed (device='cpu')."""
+    if storage not in ('f32', 'f16'):
+        raise ValueError("storage must be 'f32' or 'f16'")
+    rough, dev, f16 = bool(use_rough), device, storage == 'f16'
+    if sn.conv1_s.weight.shape[1] != (6 if rough else 3):
+        raise ValueError(f'shading_net.conv1_s takes {sn.conv1_s.weight.shape[1]} channels: use_rough={rough} needs {6 if rough else 3}')
+    Hc, Wc = cam_size
+    if Hc % 4 or Wc % 4:
+        raise ValueError('camera size must be divisible by 4')
+    frozen = fuse_skip2 is not False
+    byte_gates = USE_GATE_MASKS or f16                     # (SPAA_GATE_MASKS=0, fp32: the A/B backward reads the activations themselves)
+    small = batch * Hc * Wc * 32 < 2 ** 31                 # (the persistent stride-2 kernels address every tensor with 32-bit byte offsets; the largest -- X6 in fp16, X1 in fp32 -- holds 32 bytes per camera pixel)
+
+    def fbias(nm):
+        return getattr(sn, nm).bias.detach().float().contiguous().to(dev)
+
+    def s2f_images(pack):   # conv2 / conv2_s for s2f()
+        return {k: (pack(getattr(sn, nm).weight.permute(2, 3, 0, 1)).to(dev), fbias(nm)) for k, nm in (('f2', 'conv2'), ('f2s', 'conv2_s'))}
+
+    f, d = {}, {}
+    for nm, st in (('conv1', 2), ('conv2', 2), ('conv3', 1), ('conv4', 1), ('conv5', 1), ('conv1_s', 2),
+                   ('conv2_s', 2), ('conv3_s', 1), ('conv4_s', 1), ('conv6', 1), ('skipConv3', 1)):
+        m = getattr(sn, nm)
+        f[nm] = cp.conv_fwd_plan(m.weight, m.bias, st, 1, dev, nm)
+        if nm.endswith('_s') and not rough:
+            continue   # (no gradient through a branch that does not depend on the projector image)
+        d[nm] = cp.conv_dgrad_plan(m.weight, st, 1, dev, nm + '_dgrad', in_ch=(3, 6) if nm == 'conv1_s' else None)
+    f['skipConv2'] = cp.conv_fwd_plan(sn.skipConv2.weight, sn.skipConv2.bias, 1, 0, dev, 'skipConv2')
+    d['skipConv2'] = cp.conv_dgrad_plan(sn.skipConv2.weight, 1, 0, dev, 'skipConv2_dgrad')
+    # (fp16 storage: the four parity classes folded into the GEMM columns -- the patch-staged fp16 kernel reads the input once;
+    # in fp32 the folded form is slower than the four classes: 16 instead of 9 (class, tap) products)
+    f['transConv1'] = cp.deconv_fwd_plan(sn.transConv1.weight, sn.transConv1.bias, 2, 1, dev, 'transConv1', fold=True if f16 else None)
+    d['transConv1'] = cp.deconv_dgrad_plan(sn.transConv1.weight, 2, 1, dev, 'transConv1_dgrad')
+    f['transConv2'] = cp.deconv_fwd_plan(sn.transConv2.weight, sn.transConv2.bias, 2, 0, dev, 'transConv2')
+    d['transConv2'] = cp.deconv_dgrad_plan(sn.transConv2.weight, 2, 0, dev, 'transConv2_dgrad')
+    for key, i, pad in (('skip1a', 0, 0), ('skip1b', 2, 1), ('skip1c', 4, 1)):
+        f[key] = cp.conv_fwd_plan(sn.skipConv1[i].weight, sn.skipConv1[i].bias, 1, pad, dev, f'skipConv1.{i}')
+    r = types.SimpleNamespace(storage=storage, f=f, d=d, fs2=None, s2fx=None, pair1=None, pair1_bwd=None, fuse_skip2=False,
+                              fuse_skip3=False, fuse_tail=False, want_gate_y=False, _packed_from={})
+
+    def packed(*names):   # layer -> ((parameter, its _version now), ...): set_scene() compares
+        r._packed_from.update((nm, tuple((p, p._version) for p in getattr(sn, nm).parameters())) for nm in names)
+
+    # skip2: `transConv1(x5) + skipConv2(x1)` (models.py:293,299) and its mirror image `conv2^T(g2) + skipConv2^T(g6)` as ONE launch each,
+    # the 1 x 1 convolution as the second source of csrc/tapconv_x6p.hip (fp32; conv2_s^T on the same kernel) / csrc/tapconv_h16p.hip's folded form
+    if FUSE_SKIP2 and frozen and byte_gates and batch * (Hc // 4) * (Wc // 4) >= FUSE_SKIP2_MIN_PIXELS:
+        tc = cp.deconv_fwd_plan(sn.transConv1.weight, sn.transConv1.bias, 2, 1, dev, 'transConv1+skipConv2', fold=f16)
+        c2 = cp.conv_dgrad_plan(sn.conv2.weight, 2, 1, dev, 'conv2_dgrad+skipConv2_dgrad', fold=f16)
+        fits = (tc.nfold == 4 and c2.nfold == 4) if f16 else (tc.x6p_ok() and c2.x6p_ok())
+        if fits and tuple(sn.skipConv2.weight.shape) == (tc.cout, c2.cout, 1, 1) and c2.cout in (32, 64) and tc.cout in (32, 64):
+            attach = 'attach_second_source_h16' if f16 else 'attach_second_source'
+            getattr(tc, attach)(sn.skipConv2.weight, sn.skipConv2.bias)
+            getattr(c2, attach)(sn.skipConv2.weight.detach()[:, :, 0, 0].t().contiguous(), None)
+            if FUSE_SKIP2 & 1:
+                f['transConv1x'] = tc
+            if FUSE_SKIP2 & 2:
+                d['conv2x'] = c2
+            if not f16 and rough and FUSE_SKIP2 & 4:
+                d['conv2_s'] = cp.conv_dgrad_plan(sn.conv2_s.weight, 2, 1, dev, 'conv2_s_dgrad', fold=False)
+                d['conv2_s'].fixed_tile = 74
+            r.fuse_skip2 = True
+    # fs2 (needs skip2 in both directions), fp16 storage: those two and conv2_s^T on the persistent per-input-pixel kernel (csrc/fs2_h16.hip)
+    if (FS2_H16 and small and f16 and r.fuse_skip2 and 'transConv1x' in f and 'conv2x' in d and rough and tuple(sn.transConv1.weight.shape) == (128, 64, 3, 3)
+            and tuple(sn.conv2.weight.shape) == tuple(sn.conv2_s.weight.shape) == (64, 32, 3, 3) and tuple(sn.skipConv2.weight.shape) == (64, 32, 1, 1)):
+        s2 = sn.skipConv2.weight.detach()[:, :, 0, 0]
+        t_img, t_img2 = pack_fs2(sn.transConv1.weight.permute(2, 3, 1, 0), s2)
+        c_img, c_img2 = pack_fs2(sn.conv2.weight.permute(2, 3, 1, 0), s2.t())
+        s_img, _ = pack_fs2(sn.conv2_s.weight.permute(2, 3, 1, 0))
+        r.fs2 = dict(tc=(t_img.to(dev), t_img2.to(dev), (fbias('transConv1') + fbias('skipConv2')).contiguous()), c2=(c_img.to(dev), c_img2.to(dev)), c2s=(s_img.to(dev),))
+        # ... and (needs fs2) the three stride-2 FORWARD forms (conv2, conv2_s, transConv1's input gradient) on its sibling (csrc/s2f_h16.hip)
+        if S2F_H16:
+            r.fs2.update(s2f_images(pack_s2f), tcd=(pack_s2f(sn.transConv1.weight.permute(2, 3, 0, 1)).to(dev),))
+        packed('transConv1', 'skipConv2', 'conv2', 'conv2_s')
+    # s2f, fp32: conv2 / conv2_s (32 -> 64, stride 2) on the persistent weights-in-LDS bf16x6 kernel (csrc/s2f_x6.hip)
+    if S2F_X6 and small and frozen and not f16 and tuple(sn.conv2.weight.shape) == tuple(sn.conv2_s.weight.shape) == (64, 32, 3, 3):
+        r.s2fx = s2f_images(pack_s2f_x6)
+        packed('conv2', 'conv2_s')
+    # skip3 (needs skip2): `conv5(x4) + skipConv3(x2)` (models.py:294,298) and `conv3^T(g3) + skipConv3^T(g5)` as one two-source Winograd launch each
+    if FUSE_SKIP2 & 8 and frozen and byte_gates and cp.WINOGRAD and r.fuse_skip2:
+        c5 = cp.conv_fwd_plan_2src(sn.conv5.weight, sn.skipConv3.weight, sn.conv5.bias.detach() + sn.skipConv3.bias.detach(), dev, 'conv5+skipConv3')
+        c3 = cp.conv_dgrad_plan_2src(sn.conv3.weight, sn.skipConv3.weight, dev, 'conv3_dgrad+skipConv3_dgrad')
+        if c5 is not None and c3 is not None:
+            f['conv5x'], d['conv3x'] = c5, c3
+            r.fuse_skip3 = True
+    # conv1 pair, use_rough: `relu(conv1_s(cat[s, xw * s]))` and `relu(conv1(xw) + res1_s)` (models.py:284-285,295) as ONE launch
+    # (csrc/conv1pair.hip); the warp kernel then no longer writes the 8-channel concatenation
+    if FUSE_SKIP2 & 16 and frozen and rough and byte_gates and tuple(sn.conv1.weight.shape) == (32, 3, 3, 3) and tuple(sn.conv1_s.weight.shape) == (32, 6, 3, 3):
+        w1, ws = sn.conv1.weight.detach().float(), sn.conv1_s.weight.detach().float()
+        wp = torch.zeros(3, 32, 9, 4, device=dev)
+        for gi, wsrc in enumerate((w1, ws[:, 0:3], ws[:, 3:6])):
+            wp[gi, :, :, :3] = wsrc.permute(0, 2, 3, 1).reshape(32, 9, 3)
+        r.pair1 = (wp.contiguous(), fbias('conv1'), fbias('conv1_s'))
+        packed('conv1', 'conv1_s')
+        # its ADJOINT (needs the pair), fp16 storage: conv1^T(g_x1) + s * conv1_s^T(g_s1)[rough] as one launch
+        if FUSE_C1BWD and f16:
+            r.pair1_bwd = pack_pair1_bwd(sn.conv1.weight, sn.conv1_s.weight).to(dev)
+    # tail / head (csrc/shading_tail.hip): transConv2 + conv6 and their adjoints as one launch each, X7 and its gradient never reach
+    # HBM.  Needs the byte gate masks; the training step (weight gradients read X7 and P7) passes fuse_tail=False
+    wt, w6 = sn.transConv2.weight.detach().float().cpu(), sn.conv6.weight.detach().float().cpu()
+    assert wt.shape == (64, 32, 2, 2) and w6.shape == (3, 32, 3, 3)
+    mat = (lambda w: w.half().contiguous()) if f16 else cp.split_planes   # fp16 storage: rounded to fp16 (one MFMA per product, as every layer of the mode)
+    w6p = w6.permute(0, 2, 3, 1).reshape(3, 9, 32).contiguous()
+    r.tail = dict(w2=mat(wt.permute(2, 3, 1, 0).reshape(128, 64)).to(dev),      # ([3])[32 (2 py + px) + c][k]
+                  w2t=mat(wt.permute(0, 2, 3, 1).reshape(64, 128)).to(dev),     # ([3])[n][32 (2 py + px) + c]
+                  w6=(w6p.half() if f16 else w6p).to(dev),              # [o][3 ky + kx][c]
+                  w6t=w6.flip(2, 3).permute(2, 3, 0, 1).reshape(27, 32).contiguous().to(dev),  # [3 t + o][c], taps mirrored
+                  b2=fbias('transConv2'), b6=fbias('conv6'))
+    if FUSE_TAIL and fuse_tail is not False and byte_gates:
+        packed('transConv2', 'conv6')
+        r.fuse_tail = True
+        # (needs the fused tail) the output's clamp gate (0 < pre <= 1 per channel) as one byte per pixel, written by the tail and read by
+        # the select head; the pre-clamp tensor a['Ypre'] is then produced on demand only (_materialize_ypre)
+        r.want_gate_y = GATE_BYTE_Y
+    return r
+
+
+def s2f(inp, w_img, out, bias=None, add=None, gate_bits=None, relu=False, mask_out=None):
+    """3 x 3 / stride-2 forward form [B,Hi,Wi,Cin] -> [B,Hi/2,Wi/2,Cout]: fp16 on csrc/s2f_h16.hip (pack_s2f), fp32 on csrc/s2f_x6.hip (pack_s2f_x6)."""
+    b, hi, wi, cin = inp.shape
+    h16 = inp.dtype == torch.float16
+    p = _lib.hptr if h16 else _lib.ptr
+    _lib.call('spaa_s2f_h16' if h16 else 'spaa_s2f_x6', p(inp), cin, cin, p(w_img), _lib.ptr(bias), p(add), _lib.ptr(gate_bits), int(relu),
+              p(out), _lib.ptr(mask_out), out.shape[3], b, hi, wi)
+
+
+def fs2(inp, w_img, out, inp2=None, w2_img=None, bias=None, add=None, gate_bits=None, relu=False, mask_out=None):
+    """Fractional-stride 3 x 3 layer, fp16 [B,Hi,Wi,Cin] -> [B,2 Hi,2 Wi,Cout] (csrc/fs2_h16.hip, pack_fs2); `inp2`: 1 x 1 second source at the output's size."""
+    b, hi, wi, cin = inp.shape
+    cin2 = inp2.shape[3] if inp2 is not None else 0
+    _lib.call('spaa_fs2_h16', _lib.hptr(inp), cin, cin, _lib.hptr(w_img), _lib.hptr(inp2), cin2, cin2, _lib.hptr(w2_img), _lib.ptr(bias),
+              _lib.hptr(add), _lib.ptr(gate_bits), int(relu), _lib.hptr(out), _lib.ptr(mask_out), out.shape[3], b, hi, wi)
+
+
+def conv1_pair_fwd(xw, scene, pair1, s1, x1, mask_s1, mask_x1):
+    """S1 = relu(conv1_s(cat[s, xw * s])), X1 = relu(conv1(xw) + S1) (fp32 or fp16) and their gate bytes in one launch (csrc/conv1pair.hip)."""
+    _lib.call('spaa_conv1_pair_fwd', _lib.ptr(xw), _lib.ptr(scene), *map(_lib.ptr, pair1), _lib.ptr(s1), _lib.ptr(x1), C_ptr(mask_s1), C_ptr(mask_x1),
+              *xw.shape[:3], int(x1.dtype == torch.float16))
+
+
+def conv1_pair_bwd(g_x1, g_s1, scene, w_img, g_xw):
+    """The pair's adjoint in fp16 storage, g_xw = conv1^T(g_x1) + scene * conv1_s^T(g_s1)[rough channels] (`w_img` from pack_pair1_bwd)."""
+    _lib.call('spaa_conv1_pair_bwd_f16', _lib.hptr(g_x1), _lib.hptr(g_s1), _lib.ptr(scene), _lib.hptr(w_img), _lib.ptr(g_xw), *g_xw.shape[:3])
+
+
 class PCNetEngine:
     """Packed weights, sampling grid and workspaces of one PCNet for a fixed batch size; HIP forward and
     input-gradient passes over NHWC4 tensors."""
 
-    def __init__(self, pcnet, batch, prj_size, storage='f32', fuse_skip2=None):
-        """`fuse_skip2`: None = where it applies (fp32 storage, enough pixels), False = never (the training step: weight gradients
-        and weight refreshes work on the separate layers' plans)."""
-        if storage not in ('f32', 'f16'):
-            raise ValueError("storage must be 'f32' or 'f16'")
-        self.storage = storage
-        hd = torch.float16 if storage == 'f16' else torch.float32   # activations / their gradients; images stay fp32
+    def __init__(self, pcnet, batch, prj_size, storage='f32', fuse_skip2=None, fuse_tail=None):
+        """`fuse_skip2`, `fuse_tail`: None = where it applies, False = never (the training step), see pcnet_routes."""
         wn, sn = pcnet.warping_net, pcnet.shading_net
         dev = sn.conv1.weight.device
         if dev.type != 'cuda':
@@ -443,12 +598,9 @@ class PCNetEngine:
         # models.py:342-345: with use_rough the surface branch sees cat([s, x_w * s]) and depends on the projector image;
         # without it the branch sees the scene alone: a constant of the attack, computed once in set_scene()
         self.rough = bool(pcnet.use_rough)
-        if sn.conv1_s.weight.shape[1] != (6 if self.rough else 3):
-            raise ValueError(f'shading_net.conv1_s takes {sn.conv1_s.weight.shape[1]} channels: use_rough={self.rough} needs {6 if self.rough else 3}')
-        self.Hp, self.Wp = prj_size
-        self.Hc, self.Wc = wn.out_size
-        if self.Hc % 4 or self.Wc % 4:
-            raise ValueError('camera size must be divisible by 4')
+        (self.Hp, self.Wp), (self.Hc, self.Wc) = prj_size, wn.out_size
+        r = pcnet_routes(sn, self.rough, batch, (self.Hc, self.Wc), storage, fuse_skip2, fuse_tail, dev)
+        vars(self).update(vars(r))   # f, d, fs2, s2fx, pair1, pair1_bwd, tail, fuse_skip2, fuse_skip3, fuse_tail, want_gate_y, _packed_from
         fg = getattr(wn, 'fine_grid', None)
         if fg is not None:
             self.grid = torch.zeros(self.Hc, self.Wc, 4, device=dev)
@@ -456,174 +608,51 @@ class PCNetEngine:
         else:
             self.grid = wn.build_fine_grid(prj_size)
         self.mask = pcnet.mask.detach().float().contiguous().view(-1).to(dev) if pcnet.use_mask else None
-        if self.mask is not None:
-            assert self.mask.numel() == self.Hc * self.Wc
+        assert self.mask is None or self.mask.numel() == self.Hc * self.Wc
         self.tap_off, self.tap_order, self.tap_wm, self.tap_src = transposed_taps(self.grid, prj_size, (self.Hc, self.Wc), self.mask, want_table=True)
         self.tiled = tiled_taps(self.tap_off, self.tap_order, self.tap_wm, prj_size, (self.Hc, self.Wc)) if TILED_WARP_BWD else None
-        f, d = {}, {}
-        for nm, st in (('conv1', 2), ('conv2', 2), ('conv3', 1), ('conv4', 1), ('conv5', 1), ('conv1_s', 2),
-                       ('conv2_s', 2), ('conv3_s', 1), ('conv4_s', 1), ('conv6', 1), ('skipConv3', 1)):
-            m = getattr(sn, nm)
-            f[nm] = cp.conv_fwd_plan(m.weight, m.bias, st, 1, dev, nm)
-            if nm.endswith('_s') and not self.rough:
-                continue   # (no gradient through a branch that does not depend on the projector image)
-            d[nm] = cp.conv_dgrad_plan(m.weight, st, 1, dev, nm + '_dgrad', in_ch=(3, 6) if nm == 'conv1_s' else None)
-        f['skipConv2'] = cp.conv_fwd_plan(sn.skipConv2.weight, sn.skipConv2.bias, 1, 0, dev, 'skipConv2')
-        d['skipConv2'] = cp.conv_dgrad_plan(sn.skipConv2.weight, 1, 0, dev, 'skipConv2_dgrad')
-        # (fp16 storage: the four parity classes folded into the GEMM columns -- the patch-staged fp16 kernel reads the input once;
-        # in fp32 the folded form is slower than the four classes: 16 instead of 9 (class, tap) products)
-        f['transConv1'] = cp.deconv_fwd_plan(sn.transConv1.weight, sn.transConv1.bias, 2, 1, dev, 'transConv1',
-                                             fold=True if storage == 'f16' else None)
-        d['transConv1'] = cp.deconv_dgrad_plan(sn.transConv1.weight, 2, 1, dev, 'transConv1_dgrad')
-        # fp32 storage: `transConv1(x5) + skipConv2(x1)` (models.py:293,299) as ONE launch of the patch-staged stride-2 kernel with
-        # the 1 x 1 convolution as its second source (csrc/tapconv_x6p.hip: no R2 tensor, no separate launch), its mirror image in
-        # the backward pass (`conv2^T(g2) + skipConv2^T(g6)`), and the surface branch's conv2_s input gradient on the same kernel
-        self.fuse_skip2 = False
-        if FUSE_SKIP2 and fuse_skip2 is not False and storage == 'f32' and USE_GATE_MASKS and batch * (self.Hc // 4) * (self.Wc // 4) >= FUSE_SKIP2_MIN_PIXELS:
-            tc = cp.deconv_fwd_plan(sn.transConv1.weight, sn.transConv1.bias, 2, 1, dev, 'transConv1+skipConv2', fold=False)
-            c2 = cp.conv_dgrad_plan(sn.conv2.weight, 2, 1, dev, 'conv2_dgrad+skipConv2_dgrad', fold=False)
-            if tc.x6p_ok() and c2.x6p_ok() and tuple(sn.skipConv2.weight.shape) == (tc.cout, c2.cout, 1, 1) and c2.cout in (32, 64) and tc.cout in (32, 64):
-                tc.attach_second_source(sn.skipConv2.weight, sn.skipConv2.bias)
-                c2.attach_second_source(sn.skipConv2.weight.detach()[:, :, 0, 0].t().contiguous(), None)
-                if FUSE_SKIP2 & 1:
-                    f['transConv1x'] = tc
-                if FUSE_SKIP2 & 2:
-                    d['conv2x'] = c2
-                if self.rough and FUSE_SKIP2 & 4:
-                    d['conv2_s'] = cp.conv_dgrad_plan(sn.conv2_s.weight, 2, 1, dev, 'conv2_s_dgrad', fold=False)
-                    d['conv2_s'].fixed_tile = 74
-                self.fuse_skip2 = True
-        # fp16 storage: the same two fusions on the patch-staged fp16 kernel's folded form (csrc/tapconv_h16p.hip, second source of a
-        # folded stride-2 transposed layer: skipConv2 101 us + skipConv2^T 64 us of separate launches and the R2 / t1 round trips)
-        if FUSE_SKIP2 and fuse_skip2 is not False and storage == 'f16' and batch * (self.Hc // 4) * (self.Wc // 4) >= FUSE_SKIP2_MIN_PIXELS:
-            tc = cp.deconv_fwd_plan(sn.transConv1.weight, sn.transConv1.bias, 2, 1, dev, 'transConv1+skipConv2', fold=True)
-            c2 = cp.conv_dgrad_plan(sn.conv2.weight, 2, 1, dev, 'conv2_dgrad+skipConv2_dgrad', fold=True)
-            if (tc.nfold == 4 and c2.nfold == 4 and tuple(sn.skipConv2.weight.shape) == (tc.cout, c2.cout, 1, 1) and c2.cout in (32, 64)
-                    and tc.cout in (32, 64)):
-                tc.attach_second_source_h16(sn.skipConv2.weight, sn.skipConv2.bias)
-                c2.attach_second_source_h16(sn.skipConv2.weight.detach()[:, :, 0, 0].t().contiguous(), None)
-                if FUSE_SKIP2 & 1:
-                    f['transConv1x'] = tc
-                if FUSE_SKIP2 & 2:
-                    d['conv2x'] = c2
-                self.fuse_skip2 = True
-        # round 6, fp16 storage: the three fractional-stride layers (transConv1 + skipConv2, conv2^T + skipConv2^T, conv2_s^T) on the
-        # persistent per-input-pixel kernel: exactly the nine real (class, tap) products, all weights resident in LDS (csrc/fs2_h16.hip)
-        self.fs2 = None
-        small = batch * self.Hc * self.Wc * 32 < 2 ** 31      # (the persistent stride-2 kernels address every tensor with 32-bit byte offsets; the largest -- X6 in fp16, X1 in fp32 -- holds 32 bytes per camera pixel)
-        if (FS2_H16 and small and storage == 'f16' and self.fuse_skip2 and 'transConv1x' in f and 'conv2x' in d and self.rough
-                and tuple(sn.transConv1.weight.shape) == (128, 64, 3, 3) and tuple(sn.conv2.weight.shape) == (64, 32, 3, 3)
-                and tuple(sn.conv2_s.weight.shape) == (64, 32, 3, 3) and tuple(sn.skipConv2.weight.shape) == (64, 32, 1, 1)):
-            sk = sn.skipConv2.weight.detach()[:, :, 0, 0]
-            t_img, t_img2 = pack_fs2(sn.transConv1.weight.permute(2, 3, 1, 0), sk)
-            c_img, c_img2 = pack_fs2(sn.conv2.weight.permute(2, 3, 1, 0), sk.t())
-            s_img, _ = pack_fs2(sn.conv2_s.weight.permute(2, 3, 1, 0))
-            self.fs2 = dict(tc=(t_img.to(dev), t_img2.to(dev), (sn.transConv1.bias.detach().float() + sn.skipConv2.bias.detach().float()).contiguous().to(dev)),
-                            c2=(c_img.to(dev), c_img2.to(dev)), c2s=(s_img.to(dev),))
-            # ... and the three stride-2 FORWARD forms (conv2, conv2_s, transConv1's input gradient) on its sibling (csrc/s2f_h16.hip)
-            if S2F_H16 and self.Hc % 4 == 0 and self.Wc % 4 == 0:
-                self.fs2.update(f2=(pack_s2f(sn.conv2.weight.permute(2, 3, 0, 1)).to(dev), sn.conv2.bias.detach().float().contiguous().to(dev)),
-                                f2s=(pack_s2f(sn.conv2_s.weight.permute(2, 3, 0, 1)).to(dev), sn.conv2_s.bias.detach().float().contiguous().to(dev)),
-                                tcd=(pack_s2f(sn.transConv1.weight.permute(2, 3, 0, 1)).to(dev),))
-        # fp32: conv2 / conv2_s (32 -> 64, stride 2) on the persistent weights-in-LDS bf16x6 kernel (csrc/s2f_x6.hip).  Frozen weights only
-        # (its weight images are packed here, once: the training step, which refreshes the separate layers' plans, passes fuse_skip2=False)
-        self.s2fx = None
-        if (S2F_X6 and small and fuse_skip2 is not False and storage == 'f32' and self.Hc % 4 == 0 and self.Wc % 4 == 0 and tuple(sn.conv2.weight.shape) == (64, 32, 3, 3)
-                and tuple(sn.conv2_s.weight.shape) == (64, 32, 3, 3)):
-            self.s2fx = dict(f2=(pack_s2f_x6(sn.conv2.weight.permute(2, 3, 0, 1)).to(dev), sn.conv2.bias.detach().float().contiguous().to(dev)),
-                             f2s=(pack_s2f_x6(sn.conv2_s.weight.permute(2, 3, 0, 1)).to(dev), sn.conv2_s.bias.detach().float().contiguous().to(dev)))
-        # likewise `conv5(x4) + skipConv3(x2)` (models.py:294,298) and `conv3^T(g3) + skipConv3^T(g5)`: one Winograd launch each over
-        # the concatenated input channels, read from two tensors (cp.conv_fwd_plan_2src)
-        self.fuse_skip3 = False
-        if FUSE_SKIP2 & 8 and fuse_skip2 is not False and (USE_GATE_MASKS or storage == 'f16') and cp.WINOGRAD and self.fuse_skip2:
-            c5 = cp.conv_fwd_plan_2src(sn.conv5.weight, sn.skipConv3.weight, sn.conv5.bias.detach() + sn.skipConv3.bias.detach(), dev, 'conv5+skipConv3')
-            c3 = cp.conv_dgrad_plan_2src(sn.conv3.weight, sn.skipConv3.weight, dev, 'conv3_dgrad+skipConv3_dgrad')
-            if c5 is not None and c3 is not None:
-                f['conv5x'], d['conv3x'] = c5, c3
-                self.fuse_skip3 = True
-        # use_rough: `relu(conv1_s(cat[s, xw * s]))` and `relu(conv1(xw) + res1_s)` (models.py:284-285,295) as ONE launch that reads xw and
-        # s once, forms xw * s in registers and keeps res1_s there for conv1's epilogue (csrc/conv1pair.hip); the warp kernel then
-        # no longer writes the 8-channel concatenation.  Frozen weights only (the training step refreshes the separate plans).
-        self.pair1 = None
-        if FUSE_SKIP2 & 16 and fuse_skip2 is not False and self.rough and (USE_GATE_MASKS or storage == 'f16') \
-                and tuple(sn.conv1.weight.shape) == (32, 3, 3, 3) and tuple(sn.conv1_s.weight.shape) == (32, 6, 3, 3):
-            w1, ws = sn.conv1.weight.detach().float(), sn.conv1_s.weight.detach().float()
-            wp = torch.zeros(3, 32, 9, 4, device=dev)
-            for gi, wsrc in enumerate((w1, ws[:, 0:3], ws[:, 3:6])):
-                wp[gi, :, :, :3] = wsrc.permute(0, 2, 3, 1).reshape(32, 9, 3)
-            self.pair1 = (wp.contiguous(), sn.conv1.bias.detach().float().contiguous().to(dev),
-                          sn.conv1_s.bias.detach().float().contiguous().to(dev))
-        # fp16 storage: the ADJOINT of that pair as one launch too (csrc/conv1pair.hip: conv1^T(g_x1) + s * conv1_s^T(g_s1)[rough] on the
-        # fp16 matrix instruction: 268 MB instead of the two thin-output launches' 402 MB per step at batch 64); the raw fp32 weights
-        self.pair1_bwd = None
-        if FUSE_C1BWD and self.pair1 is not None and storage == 'f16':
-            self.pair1_bwd = pack_pair1_bwd(sn.conv1.weight, sn.conv1_s.weight).to(dev)
-        f['transConv2'] = cp.deconv_fwd_plan(sn.transConv2.weight, sn.transConv2.bias, 2, 0, dev, 'transConv2')
-        d['transConv2'] = cp.deconv_dgrad_plan(sn.transConv2.weight, 2, 0, dev, 'transConv2_dgrad')
-        sk = sn.skipConv1
-        f['skip1a'] = cp.conv_fwd_plan(sk[0].weight, sk[0].bias, 1, 0, dev, 'skipConv1.0')
-        f['skip1b'] = cp.conv_fwd_plan(sk[2].weight, sk[2].bias, 1, 1, dev, 'skipConv1.2')
-        f['skip1c'] = cp.conv_fwd_plan(sk[4].weight, sk[4].bias, 1, 1, dev, 'skipConv1.4')
-        self.f, self.d = f, d
+        self.scene = self._x = None
+        self._clamp = 1
+        self._x7_version = self._ypre_version = -1   # `version` for which a['X7'] / a['Ypre'] hold the activation / the pre-clamp output
+        self.owner = None    # weakref to the AttackState this engine is leased to (PCNet.engine)
+        self.version = 0     # bumped whenever the activation workspaces are overwritten (set_scene / forward)
         B, H, W = batch, self.Hc, self.Wc
         H2, W2, H4, W4 = H // 2, W // 2, H // 4, W // 4
-
-        def z(*shape):
-            return torch.zeros(*shape, device=dev)
-
-        def zh(*shape):
-            return torch.zeros(*shape, device=dev, dtype=hd)
-
-        a = _Activations(self)
+        hd = torch.float16 if storage == 'f16' else torch.float32   # activations / their gradients; images stay fp32
+        z, zh = functools.partial(torch.zeros, device=dev), functools.partial(torch.zeros, device=dev, dtype=hd)
+        a = self.a = _Activations(self)
         a['xw'], a['cat8'] = z(B, H, W, 4), z(B, H, W, 8)
         a['S1'], a['S2'], a['S3'], a['S4'] = zh(B, H2, W2, 32), zh(B, H4, W4, 64), zh(B, H4, W4, 128), zh(B, H4, W4, 256)
         a['X1'], a['R2'], a['X2'], a['R3'] = zh(B, H2, W2, 32), zh(B, H2, W2, 64), zh(B, H4, W4, 64), zh(B, H4, W4, 128)
         a['X3'], a['X4'], a['X5'] = zh(B, H4, W4, 128), zh(B, H4, W4, 256), zh(B, H4, W4, 128)
         a['X6'], a['X7'] = zh(B, H2, W2, 64), zh(B, H, W, 32)
         a['Y'], a['Ypre'], a['R1'] = z(B, H, W, 4), z(B, H, W, 4), z(B, H, W, 4)
-        self.a = a
-        # ReLU gates of the activations, one byte per 4 channels (include/spaa_hip.h: mask_out / gate_bits): written by
-        # the forward launches' epilogues, read by the input-gradient launches instead of the fp32 activations (for X7
-        # alone that is 34 MB instead of 537 MB per backward pass at batch 64)
+        # ReLU gates of the activations, one byte per 4 channels (include/spaa_hip.h: mask_out / gate_bits): written by the forward launches'
+        # epilogues, read by the input-gradient launches instead of the fp32 activations (X7 alone: 34 MB instead of 537 MB per pass at batch 64)
         self.m = {k: torch.zeros(*a[k].shape[:3], a[k].shape[3] // 4, dtype=torch.uint8, device=dev)
                   for k in ('S1', 'S2', 'S3', 'S4', 'X1', 'X2', 'X3', 'X4', 'X5', 'X6', 'X7')}
-        g = {}
+        g = self.g = {}
         g['P7'], g['P6'], g['P5'], g['P4'] = zh(B, H, W, 32), zh(B, H2, W2, 64), zh(B, H4, W4, 128), zh(B, H4, W4, 256)
         g['S4'], g['P3'], g['t2'], g['P2'] = zh(B, H4, W4, 256), zh(B, H4, W4, 128), zh(B, H4, W4, 64), zh(B, H4, W4, 64)
         g['t1'], g['P1'] = zh(B, H2, W2, 32), zh(B, H2, W2, 32)
         g['S3'], g['S2'], g['S1'] = zh(B, H4, W4, 128), zh(B, H4, W4, 64), zh(B, H2, W2, 32)
         g['xw'], g['xs'], g['x'] = z(B, H, W, 4), z(B, H, W, 4), z(B, self.Hp, self.Wp, 4)
-        self.g = g
-        self.scene = None
-        self._x = None
-        self._clamp = 1
-        # tail / head fusion (csrc/shading_tail.hip): X7 and its gradient never reach HBM.  Needs the byte gate masks; the
-        # training step (weight gradients read X7 and P7) switches it off
-        self.fuse_tail = FUSE_TAIL and (USE_GATE_MASKS or storage == 'f16') and H % 2 == 0 and W % 2 == 0
-        self._x7_version = -1    # `version` for which a['X7'] holds the activation
-        # the output's clamp gate (0 < pre <= 1 per channel) as one byte per pixel: written by the fused tail, read by the fused select head;
-        # the pre-clamp tensor a['Ypre'] is then produced on demand only (whoever asks gets it from the same kernel: _materialize_ypre)
-        self.gate_y = torch.zeros(B, H, W, dtype=torch.uint8, device=dev) if (self.fuse_tail and GATE_BYTE_Y) else None
-        self._ypre_version = -1  # `version` for which a['Ypre'] holds the pre-clamp output
-        wt, w6 = sn.transConv2.weight.detach().float().cpu(), sn.conv6.weight.detach().float().cpu()
-        assert wt.shape == (64, 32, 2, 2) and w6.shape == (3, 32, 3, 3)
-        self.tail = dict(
-            w2s=cp.split_planes(wt.permute(2, 3, 1, 0).reshape(128, 64)).to(dev),      # [3][32 (2 py + px) + c][k]
-            w2ts=cp.split_planes(wt.permute(0, 2, 3, 1).reshape(64, 128)).to(dev),     # [3][n][32 (2 py + px) + c]
-            # fp16 storage: the same two matrices rounded to fp16 (one MFMA per product, as the `w_half` of every other layer of the mode)
-            w2h=wt.permute(2, 3, 1, 0).reshape(128, 64).half().contiguous().to(dev) if storage == 'f16' else None,
-            w2th=wt.permute(0, 2, 3, 1).reshape(64, 128).half().contiguous().to(dev) if storage == 'f16' else None,
-            w6=w6.permute(0, 2, 3, 1).reshape(3, 9, 32).contiguous().to(dev),          # [o][3 ky + kx][c]
-            w6h=w6.permute(0, 2, 3, 1).reshape(3, 9, 32).half().contiguous().to(dev) if storage == 'f16' else None,   # (fp16 storage: rounded like every weight of the mode)
-            w6t=w6.flip(2, 3).permute(2, 3, 0, 1).reshape(27, 32).contiguous().to(dev),  # [3 t + o][c], taps mirrored
-            b2=sn.transConv2.bias.detach().float().contiguous().to(dev), b6=sn.conv6.bias.detach().float().contiguous().to(dev))
-        self.owner = None    # weakref to the AttackState this engine is leased to (PCNet.engine)
-        self.version = 0     # bumped whenever the activation workspaces are overwritten (set_scene / forward)
+        self.gate_y = torch.zeros(B, H, W, dtype=torch.uint8, device=dev) if self.want_gate_y else None
+
+    def describe(self):
+        """The route each family of launches takes on this engine as it stands (attributes switched on the live engine included)."""
+        return dict(describe_routes(self), select='head' if self.can_select() else 'separate',
+                    warp_bwd='tiled' if self.tiled is not None else 'gather', sumsq='fused' if self.sumsq_tiles() else 'separate')
 
     # ------------------------------------------------------------------------------------------------------
     def set_scene(self, scene4):
-        """scene4: [B,Hc,Wc,4] camera-captured scene(s); precomputes the loop-invariant skipConv1(s) (models.py:291)."""
+        """scene4: [B,Hc,Wc,4] camera-captured scene(s); precomputes the loop-invariant skipConv1(s) (models.py:291).
+        Raises when a parameter behind a weight image packed at construction (fs2, s2fx, pair1, pair1_bwd, the fused tail; switched
+        off since or not) has changed (torch's `_version` counter: a write through a raw pointer does not bump it)."""
         assert scene4.shape == (self.B, self.Hc, self.Wc, 4)
+        for nm, params in self._packed_from.items():
+            if any(p._version != v for p, v in params):
+                raise RuntimeError(f'shading_net.{nm} has changed since this engine packed its weights: build a new engine (PCNet.invalidate())')
         self.version += 1
         self.scene = scene4
         t0, t1 = torch.zeros_like(scene4), torch.zeros_like(scene4)
@@ -638,14 +667,9 @@ class PCNetEngine:
         m = self.m if (USE_GATE_MASKS or self.storage == 'f16') else {k: None for k in self.m}
         if inp is not None:   # (None: S1 already written by the fused conv1 pair)
             f['conv1_s'].run(inp, a['S1'], act=R, mask_out=m['S1'])
-        if self.fs2 is not None and 'f2s' in self.fs2:
-            w, bb = self.fs2['f2s']
-            _lib.call('spaa_s2f_h16', _lib.hptr(a['S1']), 32, 32, _lib.hptr(w), _lib.ptr(bb), None, None, 1, _lib.hptr(a['S2']), _lib.ptr(m['S2']), 64,
-                      self.B, self.Hc // 2, self.Wc // 2)
-        elif self.s2fx is not None:
-            w, bb = self.s2fx['f2s']
-            _lib.call('spaa_s2f_x6', _lib.ptr(a['S1']), 32, 32, C_ptr(w), _lib.ptr(bb), None, None, 1, _lib.ptr(a['S2']),
-                      _lib.ptr(m['S2']) if m['S2'] is not None else None, 64, self.B, self.Hc // 2, self.Wc // 2)
+        img = (self.fs2 or self.s2fx or {}).get('f2s')   # (fp16 / fp32 storage: at most one of the two exists)
+        if img is not None:
+            s2f(a['S1'], img[0], a['S2'], bias=img[1], relu=True, mask_out=m['S2'])
         else:
             f['conv2_s'].run(a['S1'], a['S2'], act=R, mask_out=m['S2'])
         f['conv3_s'].run(a['S2'], a['S3'], act=R, mask_out=m['S3'])
@@ -691,29 +715,21 @@ class PCNetEngine:
 
     def _shade(self):
         """ShadingNet on a['xw'] (/ a['cat8']) and the scene: everything of forward() after the warp."""
-        a, f = self.a, self.f
-        R, N = _lib.ACT_RELU, _lib.ACT_NONE
+        a, f, R, N = self.a, self.f, _lib.ACT_RELU, _lib.ACT_NONE
         m = self.m if (USE_GATE_MASKS or self.storage == 'f16') else {k: None for k in self.m}
+        skip2x = self.fuse_skip2 and 'transConv1x' in f   # skipConv2(x1) as the second source of transConv1's launch
         if self.pair1 is not None:
-            wp, b1, bs = self.pair1
-            _lib.call('spaa_conv1_pair_fwd', _lib.ptr(a['xw']), _lib.ptr(self.scene), _lib.ptr(wp), _lib.ptr(b1), _lib.ptr(bs),
-                      _lib.ptr(a['S1']), _lib.ptr(a['X1']), C_ptr(m['S1']), C_ptr(m['X1']), self.B, self.Hc, self.Wc,
-                      int(self.storage == 'f16'))
+            conv1_pair_fwd(a['xw'], self.scene, self.pair1, a['S1'], a['X1'], m['S1'], m['X1'])
             self._surface_branch(None)
         else:
             if self.rough:
                 self._surface_branch(a['cat8'])
             f['conv1'].run(a['xw'], a['X1'], add=a['S1'], act=R, mask_out=m['X1'])
-        if not (self.fuse_skip2 and 'transConv1x' in f):
+        if not skip2x:
             f['skipConv2'].run(a['X1'], a['R2'], act=N)
-        if self.fs2 is not None and 'f2' in self.fs2:
-            w, bb = self.fs2['f2']
-            _lib.call('spaa_s2f_h16', _lib.hptr(a['X1']), 32, 32, _lib.hptr(w), _lib.ptr(bb), _lib.hptr(a['S2']), None, 1, _lib.hptr(a['X2']),
-                      _lib.ptr(m['X2']), 64, self.B, self.Hc // 2, self.Wc // 2)
-        elif self.s2fx is not None:
-            w, bb = self.s2fx['f2']
-            _lib.call('spaa_s2f_x6', _lib.ptr(a['X1']), 32, 32, C_ptr(w), _lib.ptr(bb), _lib.ptr(a['S2']), None, 1, _lib.ptr(a['X2']),
-                      _lib.ptr(m['X2']) if m['X2'] is not None else None, 64, self.B, self.Hc // 2, self.Wc // 2)
+        img = (self.fs2 or self.s2fx or {}).get('f2')
+        if img is not None:
+            s2f(a['X1'], img[0], a['X2'], bias=img[1], add=a['S2'], relu=True, mask_out=m['X2'])
         else:
             f['conv2'].run(a['X1'], a['X2'], add=a['S2'], act=R, mask_out=m['X2'])
         if not self.fuse_skip3:
@@ -725,16 +741,13 @@ class PCNetEngine:
         else:
             f['conv5'].run(a['X4'], a['X5'], add=a['R3'], act=R, mask_out=m['X5'])
         if self.fs2 is not None:
-            w1, w2, bsum = self.fs2['tc']
-            _lib.call('spaa_fs2_h16', _lib.hptr(a['X5']), 128, 128, _lib.hptr(w1), _lib.hptr(a['X1']), 32, 32, _lib.hptr(w2), _lib.ptr(bsum), None,
-                      None, 1, _lib.hptr(a['X6']), _lib.ptr(m['X6']), 64, self.B, self.Hc // 4, self.Wc // 4)
-        elif self.fuse_skip2 and 'transConv1x' in f:
+            w, w2, bsum = self.fs2['tc']
+            fs2(a['X5'], w, a['X6'], inp2=a['X1'], w2_img=w2, bias=bsum, relu=True, mask_out=m['X6'])
+        elif skip2x:
             f['transConv1x'].run(a['X5'], a['X6'], inp2=a['X1'], act=R, mask_out=m['X6'])
         else:
             f['transConv1'].run(a['X5'], a['X6'], add=a['R2'], act=R, mask_out=m['X6'])
         if self.fuse_tail:
-            t = self.tail
-            f16 = self.storage == 'f16'   # (X6 and both layers' weights fp16, fp32 accumulation; X7 in LDS as the fp16 a separate launch would store)
             self._tail(dict.__getitem__(a, 'Y'), None if self.gate_y is not None else dict.__getitem__(a, 'Ypre'), m['X7'], self.gate_y)
             if self.gate_y is None:
                 self._ypre_version = self.version
@@ -749,20 +762,40 @@ class PCNetEngine:
         """The fused tail launch (csrc/shading_tail.hip) from a['X6'] into the given outputs; `ypre` or `gate_y` may be None."""
         a, t = self.a, self.tail
         f16 = self.storage == 'f16'   # (X6 and both layers' weights fp16, fp32 accumulation; X7 in LDS as the fp16 a separate launch would store)
-        args = [_lib.hptr(a['X6']) if f16 else _lib.ptr(a['X6']), _lib.hptr(t['w2h']) if f16 else _lib.ptr(t['w2s']), _lib.ptr(t['b2']),
-                _lib.hptr(t['w6h']) if f16 else _lib.ptr(t['w6']), _lib.ptr(t['b6']), _lib.ptr(a['R1']), _lib.ptr(y),
-                _lib.ptr(ypre) if ypre is not None else None, _lib.ptr(mask7)]
+        w = _lib.hptr if f16 else _lib.ptr
+        args = [_lib.hptr(a['X6']), w(t['w2']), _lib.ptr(t['b2']), w(t['w6']), _lib.ptr(t['b6']), _lib.ptr(a['R1']), _lib.ptr(y),
+                _lib.ptr(ypre), _lib.ptr(mask7)]
         if gate_y is not None:
             _lib.call('spaa_shading_tail_fwd_f16_g' if f16 else 'spaa_shading_tail_fwd_g', *args, _lib.ptr(gate_y), self.B, self.Hc // 2, self.Wc // 2)
         else:
             _lib.call('spaa_shading_tail_fwd_f16' if f16 else 'spaa_shading_tail_fwd', *args, self.B, self.Hc // 2, self.Wc // 2)
 
+    def _head_bwd(self, gP, select):
+        """The fused head launch (csrc/shading_tail.hip) into g['P6'], from `gP` or `select` (gated by the tail's byte or, without one, a['Ypre'])."""
+        t, m, f16 = self.tail, self.m, self.storage == 'f16'
+        rest = (_lib.ptr(t['w6t']), (_lib.hptr if f16 else _lib.ptr)(t['w2t']), _lib.ptr(m['X7']), _lib.ptr(m['X6']), _lib.hptr(self.g['P6']), self.B, self.Hc // 2, self.Wc // 2)
+        if select is None:
+            _lib.check_dev(gP)
+            assert gP.shape == (self.B, self.Hc, self.Wc, 4) and gP.dtype == torch.float32
+            return _lib.call('spaa_shading_head_bwd_f16' if f16 else 'spaa_shading_head_bwd', _lib.ptr(gP), *rest)
+        assert gP is None and self.can_select()
+        ga, gc, state = select
+        _lib.check_dev(ga, gc)
+        assert ga.shape == gc.shape == (self.B, self.Hc, self.Wc, 4)
+        assert state.shape == (self.B, 4) and state.dtype == torch.int32 and state.is_contiguous() and state.device == ga.device
+        if self.gate_y is not None:
+            name, gate = 'spaa_shading_head_bwd_select_f16_g' if f16 else 'spaa_shading_head_bwd_select_g', self.gate_y
+        else:
+            name, gate = 'spaa_shading_head_bwd_select_f16' if f16 else 'spaa_shading_head_bwd_select', self.a['Ypre']
+        _lib.call(name, _lib.ptr(ga), _lib.ptr(gc), _lib.ptr(state), _lib.ptr(gate), *rest)
+
     def _materialize_ypre(self):
-        """With the gate byte the pre-clamp output never reaches HBM in the loop; whoever asks for a['Ypre'] (parity tests, the unfused
-        select path, the autograd route) gets it from the SAME fused kernel run once more on the same X6 (deterministic: bitwise the values
-        the gate byte was formed from), into scratch outputs."""
-        if self.gate_y is None or self._ypre_version == self.version or self.scene is None:
+        """With the gate byte the pre-clamp output never reaches HBM in the loop; whoever asks for a['Ypre'] (parity tests, the unfused select path, the
+        autograd route) gets it from the SAME fused kernel run once more on the same X6 (bitwise the values the byte was formed from), into scratch outputs."""
+        if self.gate_y is None or self._ypre_version == self.version:
             return
+        if self.scene is None:
+            raise RuntimeError('call set_scene() first')
         if getattr(self, '_ypre_scratch', None) is None:
             self._ypre_scratch = (torch.zeros_like(dict.__getitem__(self.a, 'Y')), torch.zeros_like(self.m['X7']), torch.zeros_like(self.gate_y))
         ys, ms, gs = self._ypre_scratch
@@ -790,40 +823,16 @@ class PCNetEngine:
             return self._backward_float_gates(gP)
         g, d, m = self.g, self.d, self.m
         if self.fuse_tail:
-            t = self.tail
-            p6 = _lib.hptr(g['P6']) if self.storage == 'f16' else _lib.ptr(g['P6'])
-            w2t = _lib.hptr(t['w2th']) if self.storage == 'f16' else _lib.ptr(t['w2ts'])
-            if select is not None:
-                assert gP is None and self.can_select()
-                ga, gc, state = select
-                _lib.check_dev(ga, gc)
-                assert ga.shape == gc.shape == (self.B, self.Hc, self.Wc, 4)
-                assert state.shape == (self.B, 4) and state.dtype == torch.int32 and state.is_contiguous() and state.device == ga.device
-                if self.gate_y is not None:   # (the clamp gate as the tail's byte per pixel)
-                    _lib.call('spaa_shading_head_bwd_select_g' if self.storage == 'f32' else 'spaa_shading_head_bwd_select_f16_g', _lib.ptr(ga),
-                              _lib.ptr(gc), _lib.ptr(state), _lib.ptr(self.gate_y), _lib.ptr(t['w6t']), w2t,
-                              _lib.ptr(m['X7']), _lib.ptr(m['X6']), p6, self.B, self.Hc // 2, self.Wc // 2)
-                else:
-                    _lib.call('spaa_shading_head_bwd_select' if self.storage == 'f32' else 'spaa_shading_head_bwd_select_f16', _lib.ptr(ga),
-                              _lib.ptr(gc), _lib.ptr(state), _lib.ptr(self.a['Ypre']), _lib.ptr(t['w6t']), w2t,
-                              _lib.ptr(m['X7']), _lib.ptr(m['X6']), p6, self.B, self.Hc // 2, self.Wc // 2)
-            else:
-                _lib.check_dev(gP)
-                assert gP.shape == (self.B, self.Hc, self.Wc, 4) and gP.dtype == torch.float32
-                _lib.call('spaa_shading_head_bwd' if self.storage == 'f32' else 'spaa_shading_head_bwd_f16', _lib.ptr(gP), _lib.ptr(t['w6t']),
-                          w2t, _lib.ptr(m['X7']), _lib.ptr(m['X6']), p6, self.B, self.Hc // 2, self.Wc // 2)
+            self._head_bwd(gP, select)
         else:
             d['conv6'].run(gP, g['P7'], gate_bits=m['X7'])
             d['transConv2'].run(g['P7'], g['P6'], gate_bits=m['X6'])
-        if self.fs2 is not None and 'tcd' in self.fs2:
-            _lib.call('spaa_s2f_h16', _lib.hptr(g['P6']), 64, 64, _lib.hptr(self.fs2['tcd'][0]), None, None, _lib.ptr(m['X5']), 0, _lib.hptr(g['P5']), None,
-                      128, self.B, self.Hc // 2, self.Wc // 2)
+        img = (self.fs2 or {}).get('tcd')
+        if img is not None:
+            s2f(g['P6'], img[0], g['P5'], gate_bits=m['X5'])
         else:
             d['transConv1'].run(g['P6'], g['P5'], gate_bits=m['X5'])
-        if self.rough:
-            d['conv5'].run(g['P5'], g['P4'], gate_bits=m['X4'], aux_out=g['S4'], gate2_bits=m['S4'])
-        else:
-            d['conv5'].run(g['P5'], g['P4'], gate_bits=m['X4'])
+        d['conv5'].run(g['P5'], g['P4'], gate_bits=m['X4'], **(dict(aux_out=g['S4'], gate2_bits=m['S4']) if self.rough else {}))
         d['conv4'].run(g['P4'], g['P3'], gate_bits=m['X3'])
         if self.fuse_skip3:
             d['conv3x'].run(g['P3'], g['P2'], inp2=g['P5'], gate_bits=m['X2'])
@@ -831,9 +840,8 @@ class PCNetEngine:
             d['skipConv3'].run(g['P5'], g['t2'])
             d['conv3'].run(g['P3'], g['P2'], add=g['t2'], gate_bits=m['X2'])
         if self.fs2 is not None:
-            w1, w2 = self.fs2['c2']
-            _lib.call('spaa_fs2_h16', _lib.hptr(g['P2']), 64, 64, _lib.hptr(w1), _lib.hptr(g['P6']), 64, 64, _lib.hptr(w2), None, None,
-                      _lib.ptr(m['X1']), 0, _lib.hptr(g['P1']), None, 32, self.B, self.Hc // 4, self.Wc // 4)
+            w, w2 = self.fs2['c2']
+            fs2(g['P2'], w, g['P1'], inp2=g['P6'], w2_img=w2, gate_bits=m['X1'])
         elif self.fuse_skip2 and 'conv2x' in d:
             d['conv2x'].run(g['P2'], g['P1'], inp2=g['P6'], gate_bits=m['X1'])
         else:
@@ -846,15 +854,13 @@ class PCNetEngine:
         d['conv4_s'].run(g['S4'], g['S3'], add=g['P3'], gate_bits=m['S3'])
         d['conv3_s'].run(g['S3'], g['S2'], add=g['P2'], gate_bits=m['S2'])
         if self.fs2 is not None:
-            _lib.call('spaa_fs2_h16', _lib.hptr(g['S2']), 64, 64, _lib.hptr(self.fs2['c2s'][0]), None, 0, 0, None, None, _lib.hptr(g['P1']),
-                      _lib.ptr(m['S1']), 0, _lib.hptr(g['S1']), None, 32, self.B, self.Hc // 4, self.Wc // 4)
+            fs2(g['S2'], self.fs2['c2s'][0], g['S1'], add=g['P1'], gate_bits=m['S1'])
         else:
             d['conv2_s'].run(g['S2'], g['S1'], add=g['P1'], gate_bits=m['S1'])
         # the two 3-channel gradients meet at the warped image: d/d(x_w) = g_direct + g_rough * s (models.py:342); the
         # product and the sum are epilogues of the two thin convolutions instead of extra reads in the gather
         if self.pair1_bwd is not None:
-            _lib.call('spaa_conv1_pair_bwd_f16', _lib.hptr(g['P1']), _lib.hptr(g['S1']), _lib.ptr(self.scene), _lib.hptr(self.pair1_bwd),
-                      _lib.ptr(g['xw']), self.B, self.Hc, self.Wc)
+            conv1_pair_bwd(g['P1'], g['S1'], self.scene, self.pair1_bwd, g['xw'])
         else:
             d['conv1_s'].run(g['S1'], g['xs'], gate=self.scene, gate_mode=_lib.GATE_MUL)
             d['conv1'].run(g['P1'], g['xw'], add=g['xs'])
@@ -893,7 +899,7 @@ class PCNetEngine:
     def _materialize_x7(self):
         """With the fused tail X7 lives in LDS only; whoever asks for a['X7'] (parity tests, tools) gets it recomputed from X6
         by the stand-alone transConv2 launch."""
-        if getattr(self, 'fuse_tail', False) and self._x7_version != self.version and self.scene is not None:
+        if self.fuse_tail and self._x7_version != self.version and self.scene is not None:
             self.f['transConv2'].run(dict.__getitem__(self.a, 'X6'), dict.__getitem__(self.a, 'X7'), act=_lib.ACT_RELU)
             self._x7_version = self.version
 
@@ -902,34 +908,28 @@ class PCNetEngine:
         mask is folded into the tap weights.  `sumsq` = (partial [B, sumsq_tiles()], gray, prjl2_scale, state): spaa_grad_sumsq folded
         into the tiled kernel's epilogue (only with sumsq_tiles() > 0); prjl2_scale a float or a [B] device tensor (one per sample).  `clamp_bits` [B, Hp * Wp] uint8 (with `sumsq` only): the clamp
         gate's comparisons for the x of the last forward pass, as spaa_step_and_track_n wrote them (the caller answers for that)."""
-        g = self.g
-        if sumsq is not None:
-            assert self.sumsq_tiles() > 0
-            part, gray, scale, state = sumsq
-            assert part.shape == (self.B, self.sumsq_tiles()) and part.dtype == torch.float32 and part.is_contiguous()
-            if clamp_bits is not None:
-                assert clamp_bits.shape == (self.B, self.Hp * self.Wp) and clamp_bits.dtype == torch.uint8 and clamp_bits.is_contiguous()
-            lidx, w_e, tbox, cap = self.tiled
-            if isinstance(scale, torch.Tensor):   # one prjl2 scale per sample (several attack configurations in one batch)
-                assert scale.shape == (self.B,) and scale.dtype == torch.float32 and scale.is_contiguous()
-                _lib.call('spaa_warp_bwd_tiled_sumsq_ps', _lib.ptr(g_xw), _lib.ptr(self._x), C_ptr(self.tap_off), C_ptr(lidx),
-                          _lib.ptr(w_e), C_ptr(tbox), cap, _lib.ptr(g['x']), self.B, self.Hp, self.Wp, self.Hc, self.Wc, self._clamp,
-                          float(gray), _lib.ptr(scale), _lib.ptr(state), _lib.ptr(part),
-                          _lib.ptr(clamp_bits) if clamp_bits is not None else None)
-                return g['x']
-            _lib.call('spaa_warp_bwd_tiled_sumsq', _lib.ptr(g_xw), _lib.ptr(self._x), C_ptr(self.tap_off), C_ptr(lidx), _lib.ptr(w_e),
-                      C_ptr(tbox), cap, _lib.ptr(g['x']), self.B, self.Hp, self.Wp, self.Hc, self.Wc, self._clamp, float(gray), float(scale),
-                      _lib.ptr(state), _lib.ptr(part), _lib.ptr(clamp_bits) if clamp_bits is not None else None)
-            return g['x']
-        if self.tiled is not None:
-            lidx, w_e, tbox, cap = self.tiled
-            _lib.call('spaa_warp_bwd_tiled', _lib.ptr(g_xw), _lib.ptr(self._x), C_ptr(self.tap_off), C_ptr(lidx), _lib.ptr(w_e),
-                      C_ptr(tbox), cap, _lib.ptr(g['x']), self.B, self.Hp, self.Wp, self.Hc, self.Wc, self._clamp)
-            return g['x']
-        _lib.call('spaa_warp_bwd_gather', _lib.ptr(g_xw), None, _lib.ptr(self._x), None, None, C_ptr(self.tap_off),
-                  C_ptr(self.tap_order), _lib.ptr(self.tap_wm), _lib.ptr(g['x']), self.B, self.Hp, self.Wp, self.Hc,
-                  self.Wc, self._clamp)
-        return g['x']
+        assert sumsq is None or self.sumsq_tiles() > 0
+        if self.tiled is None:
+            _lib.call('spaa_warp_bwd_gather', _lib.ptr(g_xw), None, _lib.ptr(self._x), None, None, C_ptr(self.tap_off), C_ptr(self.tap_order),
+                      _lib.ptr(self.tap_wm), _lib.ptr(self.g['x']), self.B, self.Hp, self.Wp, self.Hc, self.Wc, self._clamp)
+            return self.g['x']
+        lidx, w_e, tbox, cap = self.tiled   # (tiled_taps: 16 x 16 projector tiles staged in LDS)
+        args = (_lib.ptr(g_xw), _lib.ptr(self._x), C_ptr(self.tap_off), C_ptr(lidx), _lib.ptr(w_e), C_ptr(tbox), cap, _lib.ptr(self.g['x']),
+                self.B, self.Hp, self.Wp, self.Hc, self.Wc, self._clamp)
+        if sumsq is None:
+            _lib.call('spaa_warp_bwd_tiled', *args)
+            return self.g['x']
+        part, gray, scale, state = sumsq
+        assert part.shape == (self.B, self.sumsq_tiles()) and part.dtype == torch.float32 and part.is_contiguous()
+        if clamp_bits is not None:
+            assert clamp_bits.shape == (self.B, self.Hp * self.Wp) and clamp_bits.dtype == torch.uint8 and clamp_bits.is_contiguous()
+        if isinstance(scale, torch.Tensor):   # one prjl2 scale per sample (several attack configurations in one batch)
+            assert scale.shape == (self.B,) and scale.dtype == torch.float32 and scale.is_contiguous()
+            name, scale = 'spaa_warp_bwd_tiled_sumsq_ps', _lib.ptr(scale)
+        else:
+            name, scale = 'spaa_warp_bwd_tiled_sumsq', float(scale)
+        _lib.call(name, *args, float(gray), scale, _lib.ptr(state), _lib.ptr(part), _lib.ptr(clamp_bits))
+        return self.g['x']
 
     def flops_fwd(self):
         B, H, W = self.B, self.Hc, self.Wc

@@ -263,8 +263,7 @@ class PCNetTrainer:
     def _make_engine(self, prj_size):
         """PCNetEngine + index maps to refresh its packed weights, wgrad plans (unfolded geometry), the WarpingNet's grid."""
         sn, dev = self.pc.shading_net, self.dev
-        eng = PCNetEngine(self.pc, self.B, prj_size, fuse_skip2=False)
-        eng.fuse_tail = False   # the weight gradients of conv6 / transConv2 read X7 and its gradient
+        eng = PCNetEngine(self.pc, self.B, prj_size, fuse_skip2=False, fuse_tail=False)   # (the weight gradients of conv6 / transConv2 read X7 and its gradient)
         plans = self.plans = _TrainedPlans(dev)
 
         def layers():

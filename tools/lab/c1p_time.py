@@ -15,7 +15,6 @@ eng = M.PCNetEngine(pc, B, sz, storage)
 eng.set_scene(M.to_nhwc4(syn.scenes(1, 1, sz).repeat(B, 1, 1, 1).to(DEV)))
 x = M.to_nhwc4(torch.rand(B, 3, *sz).to(DEV))
 a, f, m = eng.a, eng.f, eng.m
-wp, b1, bs = eng.pair1
 
 
 def timeit(fn, n=20):
@@ -32,8 +31,7 @@ def timeit(fn, n=20):
 
 
 def pair():
-    _lib.call('spaa_conv1_pair_fwd', _lib.ptr(a['xw']), _lib.ptr(eng.scene), _lib.ptr(wp), _lib.ptr(b1), _lib.ptr(bs), _lib.ptr(a['S1']),
-              _lib.ptr(a['X1']), M.C_ptr(m['S1']), M.C_ptr(m['X1']), B, sz[0], sz[1], int(storage == 'f16'))
+    M.conv1_pair_fwd(a['xw'], eng.scene, eng.pair1, a['S1'], a['X1'], m['S1'], m['X1'])
 
 
 def sep():

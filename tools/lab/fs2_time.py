@@ -40,9 +40,7 @@ for name, ci, co, ci2, relu, use_bias, use_add, use_gate, use_mask in (('transCo
     mask = torch.zeros(B, 2 * H, 2 * W, co // 4, device=DEV, dtype=torch.uint8) if use_mask else None
 
     def run():
-        _lib.call('spaa_fs2_h16', _lib.hptr(x), ci, ci, _lib.hptr(w_img), _lib.hptr(x2) if ci2 else None, ci2, ci2, _lib.hptr(w2_img) if ci2 else None,
-                  _lib.ptr(bias) if use_bias else None, _lib.hptr(add) if use_add else None, _lib.ptr(gate) if use_gate else None, relu, _lib.hptr(out),
-                  _lib.ptr(mask) if use_mask else None, co, B, H, W)
+        M.fs2(x, w_img, out, inp2=x2, w2_img=w2_img, bias=bias, add=add, gate_bits=gate, relu=relu, mask_out=mask)
     us = timeit(run)
     gf = 2 * B * H * W * (9 * ci * co + 4 * ci2 * co) / 1e9
     mb = (x.numel() + (x2.numel() if ci2 else 0) + out.numel() + (add.numel() if use_add else 0)) * 2 / 1e6
@@ -63,8 +61,7 @@ for name, ci, co, hi, use_add, use_gate, use_mask, relu in (('conv2 (+res2_s, Re
     mask = torch.zeros(B, ho, ho, co // 4, device=DEV, dtype=torch.uint8) if use_mask else None
 
     def run():
-        _lib.call('spaa_s2f_h16', _lib.hptr(x), ci, ci, _lib.hptr(w_img), _lib.ptr(bias), _lib.hptr(add) if use_add else None,
-                  _lib.ptr(gate) if use_gate else None, relu, _lib.hptr(out), _lib.ptr(mask) if use_mask else None, co, B, hi, hi)
+        M.s2f(x, w_img, out, bias=bias, add=add, gate_bits=gate, relu=relu, mask_out=mask)
     us = timeit(run)
     mb = (x.numel() + out.numel() + (add.numel() if use_add else 0)) * 2 / 1e6
     print(f'{name:28s} {us:7.1f} us  ({mb:.0f} MB)', flush=True)
@@ -81,8 +78,7 @@ for name, use_add, use_mask, relu in (('conv2 (+res2_s, ReLU, mask)', 1, 1, 1), 
     mask = torch.zeros(B, ho, ho, co // 4, device=DEV, dtype=torch.uint8) if use_mask else None
 
     def run():
-        _lib.call('spaa_s2f_x6', _lib.ptr(x), ci, ci, M.C_ptr(w_img), _lib.ptr(bias), _lib.ptr(add) if use_add else None, None, relu, _lib.ptr(out),
-                  _lib.ptr(mask) if use_mask else None, co, B, hi, hi)
+        M.s2f(x, w_img, out, bias=bias, add=add, relu=relu, mask_out=mask)
     us = timeit(run)
     mb = (x.numel() + out.numel() + (add.numel() if use_add else 0)) * 4 / 1e6
     print(f'{name:28s} {us:7.1f} us  ({mb:.0f} MB)', flush=True)
