@@ -18,6 +18,7 @@ import torch
 
 from . import _lib
 from . import convplan as cp
+from . import pooling
 from .models import to_nhwc4, to_nchw, USE_GATE_MASKS
 
 FUSE_POOL = os.environ.get('SPAA_FUSE_POOL', '1') != '0'   # VGG-16, fp16 storage: the 2 x 2 max-pools in the epilogue of the convolution before them
@@ -48,37 +49,85 @@ def _strip(sd):
     return out
 
 
-class ResNet18Body:
+class ClassifierBody:
+    """What the three bodies share: the storage mode and its allocators, the layer-size and BatchNorm-folding helpers, the ReLU-gate
+    switches, the global-average-pool + `fc` head of ResNet-18 and Inception-v3, and flops_fwd() over `fwd_plans()`.
+    A body provides forward(x4) -> logits [B, ncls], backward(g_logits) -> gradient w.r.t. x4, refresh_masks() and fwd_plans()."""
+    body_masks_switch = True   # SPAA_BODY_MASKS=0 applies (VGG-16, Inception-v3: the A/B switch never covered ResNet-18)
+
+    def __init__(self, sd, batch, in_hw, dev, storage):
+        self.sd = _strip(sd)
+        self.B, self.dev, self.storage, self.in_hw = batch, dev, storage, tuple(in_hw)
+        self.h16 = storage == 'f16'
+        self.act_dtype = torch.float16 if self.h16 else torch.float32   # activations / gradients; input image, features, logits fp32
+        # ReLU gates as byte masks (1 byte per 4 channels) written by the forward epilogues: an input-gradient launch reads 2 bits per
+        # element instead of the activation and stays on the branch-free epilogue (epilogue.hpp fast_epi_*;
+        # profiles/r05_configs4_f16s_tapconv_layers.json: VGG-16 features.2_dgrad 689 us against 477 forward with the activation as gate)
+        self.masks = (USE_GATE_MASKS or self.h16) and (BODY_GATE_MASKS or not self.body_masks_switch)
+        self.write_masks = True       # (ClassifierEngine clears it for a forward pass nobody differentiates: the masks are skipped)
+
+    def z(self, *shape):
+        return torch.zeros(*shape, device=self.dev, dtype=self.act_dtype)
+
+    def zf(self, *shape):
+        return torch.zeros(*shape, device=self.dev)
+
+    def zb(self, *shape):
+        return torch.zeros(*shape, device=self.dev, dtype=torch.uint8)
+
+    @staticmethod
+    def out_size(n, k, s, p):
+        return (n + 2 * p - k) // s + 1
+
+    def folded(self, conv, bn, eps=1e-5):
+        """Weight and bias of the convolution `conv` with its eval-mode BatchNorm `bn` folded in."""
+        sd = self.sd
+        return cp.fold_bn(sd[conv + '.weight'], sd[bn + '.weight'], sd[bn + '.bias'], sd[bn + '.running_mean'], sd[bn + '.running_var'], eps=eps)
+
+    def build_head(self, c):
+        """adaptive_avg_pool2d(1) over `c` channels + `fc` (ResNet-18, Inception-v3)."""
+        sd, B = self.sd, self.B
+        self.ncls = sd['fc.weight'].shape[0]
+        self.pooled, self.g_pooled = self.zf(B, 1, 1, c), self.zf(B, 1, 1, c)
+        self.fc_f = cp.linear_fwd_plan(sd['fc.weight'], sd['fc.bias'], self.dev, 'fc')
+        self.fc_d = cp.linear_dgrad_plan(sd['fc.weight'], self.dev, 'fc_dgrad')
+        self.logits = self.zf(B, 1, 1, self.ncls)
+
+    def head_fwd(self, last):
+        pooling.global_avgpool_fwd(last, self.pooled)
+        self.fc_f.run(self.pooled, self.logits)
+        return self.logits.view(self.B, self.ncls)
+
+    def head_bwd(self, g_logits, last, g_last):
+        """g_logits [B, ncls] -> `g_last`, the gradient w.r.t. the pre-activation of `last` (a ReLU output: gated)."""
+        self.fc_d.run(g_logits.view(self.B, 1, 1, self.ncls), self.g_pooled)
+        pooling.global_avgpool_bwd(self.g_pooled, last, g_last)
+
+    def flops_fwd(self):
+        return sum(plan.flops(self.B, h, w) for plan, (h, w) in self.fwd_plans())
+
+
+# layer2.0.conv1's input gradient (128 -> 64 channels, 28^2 -> 56^2) at benchmark batches: the patch-staged stride-2 kernel with its
+# four parity classes in one launch (tools/lab/x6p_resnet.py: 79 -> 71 us), from this many input pixels (batch x 56 x 56) on
+X6P_DGRAD_MIN_PIXELS = 100000
+
+
+class ResNet18Body(ClassifierBody):
     """torchvision.models.resnet18 (eval) forward + input-gradient on tapconv/maxpool/avgpool kernels."""
+    body_masks_switch = False
 
     def __init__(self, sd, batch, in_hw, dev, storage='f32'):
-        sd = _strip(sd)
-        self.B, self.dev, self.storage = batch, dev, storage
-        hd = torch.float16 if storage == 'f16' else torch.float32   # activations / gradients; input image, features, logits fp32
+        super().__init__(sd, batch, in_hw, dev, storage)
+        sd, z, osz = self.sd, self.z, self.out_size
         h, w = in_hw
-
-        def folded(conv, bn):
-            return cp.fold_bn(sd[conv + '.weight'], sd[bn + '.weight'], sd[bn + '.bias'], sd[bn + '.running_mean'],
-                              sd[bn + '.running_var'])
-
-        def zf(*shape):
-            return torch.zeros(*shape, device=dev)
-
-        def z(*shape):
-            return torch.zeros(*shape, device=dev, dtype=hd)
-
-        def osz(n, k, s, p):
-            return (n + 2 * p - k) // s + 1
-
-        wgt, b = folded('conv1', 'bn1')
+        wgt, b = self.folded('conv1', 'bn1')
         self.stem_f = cp.conv_fwd_plan(wgt, b, 2, 3, dev, 'stem')
         self.stem_d = cp.conv_dgrad_plan(wgt, 2, 3, dev, 'stem_dgrad')
-        self.in_hw = (h, w)
         h1, w1 = osz(h, 7, 2, 3), osz(w, 7, 2, 3)
         self.c1 = z(batch, h1, w1, 64)
         h2, w2 = osz(h1, 3, 2, 1), osz(w1, 3, 2, 1)
         self.mp = z(batch, h2, w2, 64)
-        self.mp_arg = torch.zeros(batch, h2, w2, 64, dtype=torch.uint8, device=dev)
+        self.mp_arg = self.zb(batch, h2, w2, 64)
         self.blocks = []
         cin, hh, ww = 64, h2, w2
         x_buf = self.mp
@@ -88,62 +137,49 @@ class ResNet18Body:
                 stride = 2 if (li > 1 and bi == 0) else 1
                 ho, wo = osz(hh, 3, stride, 1), osz(ww, 3, stride, 1)
                 blk = dict(name=p, stride=stride, x=x_buf)
-                w1_, b1_ = folded(p + '.conv1', p + '.bn1')
-                w2_, b2_ = folded(p + '.conv2', p + '.bn2')
+                w1_, b1_ = self.folded(p + '.conv1', p + '.bn1')
+                w2_, b2_ = self.folded(p + '.conv2', p + '.bn2')
                 blk['f1'] = cp.conv_fwd_plan(w1_, b1_, stride, 1, dev, p + '.conv1')
-                blk['d1'] = cp.conv_dgrad_plan(w1_, stride, 1, dev, p + '.conv1_dgrad',
-                                               fold=True if (FOLD_S2_F16 and storage == 'f16' and stride == 2 and (cin <= 64 or FOLD_S2_F16 > 1)) else None)
-                if stride == 2 and cin in (32, 64) and storage == 'f32' and batch * hh * ww >= 100000:
-                    # layer2.0.conv1's input gradient (128 -> 64 channels, 28^2 -> 56^2) at benchmark batches: the patch-staged
-                    # stride-2 kernel with its four parity classes in one launch (tools/lab/x6p_resnet.py: 79 -> 71 us)
-                    d74 = cp.conv_dgrad_plan(w1_, stride, 1, dev, p + '.conv1_dgrad', fold=False)
-                    if d74.x6p_ok():
-                        d74.fixed_tile = 74
-                        blk['d1'] = d74
+                blk['d1'] = self.conv1_dgrad_plan(w1_, stride, cin, batch * hh * ww, p + '.conv1_dgrad')
                 blk['f2'] = cp.conv_fwd_plan(w2_, b2_, 1, 1, dev, p + '.conv2')
                 blk['d2'] = cp.conv_dgrad_plan(w2_, 1, 1, dev, p + '.conv2_dgrad')
                 if p + '.downsample.0.weight' in sd:
-                    wd, bd = folded(p + '.downsample.0', p + '.downsample.1')
+                    wd, bd = self.folded(p + '.downsample.0', p + '.downsample.1')
                     blk['fd'] = cp.conv_fwd_plan(wd, bd, stride, 0, dev, p + '.downsample')
                     blk['dd'] = cp.conv_dgrad_plan(wd, stride, 0, dev, p + '.downsample_dgrad')
                     blk['idt'] = z(batch, ho, wo, cout)
                     blk['g_t'] = z(batch, hh, ww, cin)
                 blk['o1'] = z(batch, ho, wo, cout)
                 blk['out'] = z(batch, ho, wo, cout)
-                # ReLU gates as byte masks (1 byte per 4 channels), written by the forward epilogues
-                blk['m_o1'] = torch.zeros(batch, ho, wo, cout // 4, dtype=torch.uint8, device=dev)
-                blk['m_out'] = torch.zeros(batch, ho, wo, cout // 4, dtype=torch.uint8, device=dev)
+                blk['m_o1'] = self.zb(batch, ho, wo, cout // 4)
+                blk['m_out'] = self.zb(batch, ho, wo, cout // 4)
                 blk['g_o1'] = z(batch, ho, wo, cout)
                 blk['g_x'] = z(batch, hh, ww, cin)
                 self.blocks.append(blk)
                 x_buf, cin, hh, ww = blk['out'], cout, ho, wo
-        self.feat_hw = hh * ww
-        self.feat = zf(batch, 1, 1, 512)
-        ncls = sd['fc.weight'].shape[0]
-        self.ncls = ncls
-        self.fc_f = cp.linear_fwd_plan(sd['fc.weight'], sd['fc.bias'], dev, 'fc')
-        self.fc_d = cp.linear_dgrad_plan(sd['fc.weight'], dev, 'fc_dgrad')
-        self.logits = zf(batch, 1, 1, ncls)
-        self.g_feat = zf(batch, 1, 1, 512)
+        self.build_head(512)
         self.g_last = z(batch, hh, ww, 512)
         self.g_c1 = z(batch, h1, w1, 64)
-        self.g_in = zf(batch, h, w, 4)
-        self.write_masks = True
+        self.g_in = self.zf(batch, h, w, 4)
+
+    def conv1_dgrad_plan(self, w1, stride, cin, in_pixels, name):
+        """The input-gradient plan `d1` of a block's conv1 (`cin` channels on `in_pixels` = batch x H x W pixels): the two routes that
+        are not the plan's own choice are decided here."""
+        # fp16 storage: the stride-2 input gradients with the four parity classes folded into N (FOLD_S2_F16: 1 layer2.0, 2 all three)
+        fold = True if (FOLD_S2_F16 and self.storage == 'f16' and stride == 2 and (cin <= 64 or FOLD_S2_F16 > 1)) else None
+        d1 = cp.conv_dgrad_plan(w1, stride, 1, self.dev, name, fold=fold)
+        if stride == 2 and cin in (32, 64) and self.storage == 'f32' and in_pixels >= X6P_DGRAD_MIN_PIXELS:
+            d74 = cp.conv_dgrad_plan(w1, stride, 1, self.dev, name, fold=False)
+            if d74.x6p_ok():
+                d74.fixed_tile = 74
+                return d74
+        return d1
 
     def forward(self, x4):
         R = _lib.ACT_RELU
-        B = self.B
         self.stem_f.run(x4, self.c1, act=R)
-        _, h1, w1, _ = self.c1.shape
-        _, h2, w2, _ = self.mp.shape
-        h16 = self.storage == 'f16'
-        if h16:
-            _lib.call('spaa_maxpool_fwd_f16', _lib.hptr(self.c1), _lib.hptr(self.mp), _lib.ptr(self.mp_arg), B, h1, w1, 64,
-                      h2, w2, 3, 2, 1, 64, 0)
-        else:
-            _lib.call('spaa_maxpool3s2_fwd', _lib.ptr(self.c1), _lib.ptr(self.mp), _lib.ptr(self.mp_arg), B, h1, w1, 64,
-                      h2, w2)
-        masks = (USE_GATE_MASKS or h16) and getattr(self, 'write_masks', True)   # (write_masks False: a forward pass nobody differentiates)
+        pooling.maxpool_fwd(self.c1, self.mp, self.mp_arg, 3, 2, 1)
+        masks = self.masks and self.write_masks
         for blk in self.blocks:
             blk['f1'].run(blk['x'], blk['o1'], act=R, mask_out=blk['m_o1'] if masks else None)
             if 'fd' in blk:
@@ -152,31 +188,16 @@ class ResNet18Body:
             else:
                 idt = blk['x']
             blk['f2'].run(blk['o1'], blk['out'], add=idt, act=R, mask_out=blk['m_out'] if masks else None)
-        last = self.blocks[-1]['out']
-        if h16:
-            _lib.call('spaa_avgpool_fwd_f16', _lib.hptr(last), _lib.ptr(self.feat), B, self.feat_hw, 512)
-        else:
-            _lib.call('spaa_avgpool_fwd', _lib.ptr(last), _lib.ptr(self.feat), B, self.feat_hw, 512)
-        self.fc_f.run(self.feat, self.logits)
-        return self.logits.view(B, self.ncls)
+        return self.head_fwd(self.blocks[-1]['out'])
 
     def backward(self, g_logits):
         """g_logits [B,ncls] -> gradient w.r.t. the normalised input [B,h,w,4]."""
-        B = self.B
-        self.fc_d.run(g_logits.view(B, 1, 1, self.ncls), self.g_feat)
-        last = self.blocks[-1]['out']
-        h16 = self.storage == 'f16'
-        if h16:
-            _lib.call('spaa_avgpool_bwd_f16', _lib.ptr(self.g_feat), _lib.hptr(last), _lib.hptr(self.g_last), B,
-                      self.feat_hw, 512)
-        else:
-            _lib.call('spaa_avgpool_bwd', _lib.ptr(self.g_feat), _lib.ptr(last), _lib.ptr(self.g_last), B, self.feat_hw,
-                      512)
+        self.head_bwd(g_logits, self.blocks[-1]['out'], self.g_last)
         gP = self.g_last
         for i in range(len(self.blocks) - 1, -1, -1):
             blk = self.blocks[i]
             # the block's input is the previous block's output; block 0's is the max-pool output (gated in maxpool_bwd)
-            if USE_GATE_MASKS or h16:
+            if self.masks:
                 kw2, kw1 = dict(gate_bits=blk['m_o1']), dict(gate_bits=self.blocks[i - 1]['m_out'] if i > 0 else None)
             else:
                 kw2, kw1 = dict(gate=blk['o1']), dict(gate=blk['x'] if i > 0 else None)
@@ -187,19 +208,12 @@ class ResNet18Body:
             else:
                 blk['d1'].run(blk['g_o1'], blk['g_x'], add=gP, **kw1)
             gP = blk['g_x']
-        _, h1, w1, _ = self.c1.shape
-        _, h2, w2, _ = self.mp.shape
-        if h16:
-            _lib.call('spaa_maxpool_bwd_f16', _lib.hptr(gP), _lib.ptr(self.mp_arg), 1, _lib.hptr(self.g_c1), B, h1, w1, 64,
-                      h2, w2, 3, 2, 1, 64, 0)
-        elif FUSE_POOL_ADJOINT and gP.is_contiguous() and gP.shape[3] == 64:
+        if FUSE_POOL_ADJOINT and not self.h16 and gP.is_contiguous() and gP.shape[3] == 64:
             # the pool's adjoint as the prologue of the stem's input gradient (csrc/tapconv_thinmf.hip, POOL): g_c1 -- 205 MB at batch
             # 64 -- is neither written nor read (measured slower, see FUSE_POOL_ADJOINT)
-            self.stem_d.run(gP, self.g_in, pool_adjoint=(self.mp_arg, (h1, w1), True))
+            self.stem_d.run(gP, self.g_in, pool_adjoint=(self.mp_arg, tuple(self.c1.shape[1:3]), True))
             return self.g_in
-        else:
-            _lib.call('spaa_maxpool3s2_bwd', _lib.ptr(gP), _lib.ptr(self.mp_arg), 1, _lib.ptr(self.g_c1),
-                      B, h1, w1, 64, h2, w2)
+        pooling.maxpool_bwd(gP, self.mp_arg, self.g_c1, 3, 2, 1, True)
         self.stem_d.run(self.g_c1, self.g_in)
         return self.g_in
 
@@ -209,65 +223,54 @@ class ResNet18Body:
             blk['m_o1'].copy_(_lib.pack_gate_mask(blk['o1'].float()))
             blk['m_out'].copy_(_lib.pack_gate_mask(blk['out'].float()))
 
-    def flops_fwd(self):
-        h, w = self.in_hw
-        t = self.stem_f.flops(self.B, *self.c1.shape[1:3])
+    def fwd_plans(self):
+        yield self.stem_f, self.c1.shape[1:3]
         for blk in self.blocks:
-            ho, wo = blk['out'].shape[1:3]
-            t += blk['f1'].flops(self.B, ho, wo) + blk['f2'].flops(self.B, ho, wo)
-            if 'fd' in blk:
-                t += blk['fd'].flops(self.B, ho, wo)
-        return t + self.fc_f.flops(self.B, 1, 1)
+            for k in ('f1', 'f2', 'fd'):
+                if k in blk:
+                    yield blk[k], blk['out'].shape[1:3]
+        yield self.fc_f, (1, 1)
 
 
 VGG16_CFG = [64, 64, 'M', 128, 128, 'M', 256, 256, 256, 'M', 512, 512, 512, 'M', 512, 512, 512, 'M']
 
 
-class VGG16Body:
+class VGG16Body(ClassifierBody):
     """torchvision.models.vgg16 (eval: dropout is the identity) forward + input-gradient."""
 
     def __init__(self, sd, batch, in_hw, dev, storage='f32'):
-        sd = _strip(sd)
-        self.B, self.dev, self.storage = batch, dev, storage
-        hd = torch.float16 if storage == 'f16' else torch.float32   # activations / gradients; input image and logits fp32
+        super().__init__(sd, batch, in_hw, dev, storage)
+        sd, z, zf = self.sd, self.z, self.zf
         h, w = in_hw
-        self.in_hw = (h, w)
-
-        def zf(*shape):
-            return torch.zeros(*shape, device=dev)
-
-        def z(*shape):
-            return torch.zeros(*shape, device=dev, dtype=hd)
-
+        # `ops` in layer order.  Neighbours are facts of construction: a convolution knows the pool that follows it (`pool`) and the
+        # convolution directly below it (`below`: its input is that layer's ReLU output and carries its gate); a pool knows the
+        # convolution it pools (`conv`).  Everything else is None.
         self.ops = []
-        cin, idx = 3, 0
+        cin, idx, last = 3, 0, None
         for v in VGG16_CFG:
             if v == 'M':
                 ho, wo = h // 2, w // 2
-                self.ops.append(dict(kind='pool', hin=h, win=w, c=cin, out=z(batch, ho, wo, cin),
-                                     arg=torch.zeros(batch, ho, wo, cin, dtype=torch.uint8, device=dev),
-                                     g=z(batch, h, w, cin)))
+                op = dict(kind='pool', hin=h, win=w, c=cin, out=z(batch, ho, wo, cin), arg=self.zb(batch, ho, wo, cin), g=z(batch, h, w, cin), conv=last)
+                last['pool'] = op
                 h, w = ho, wo
                 idx += 1
             else:
                 wt, bs = sd[f'features.{idx}.weight'], sd[f'features.{idx}.bias']
-                self.ops.append(dict(kind='conv', f=cp.conv_fwd_plan(wt, bs, 1, 1, dev, f'features.{idx}'),
-                                     d=cp.conv_dgrad_plan(wt, 1, 1, dev, f'features.{idx}_dgrad'),
-                                     out=z(batch, h, w, v), g=zf(batch, h, w, 4) if cin == 3 else z(batch, h, w, cin)))
+                op = dict(kind='conv', f=cp.conv_fwd_plan(wt, bs, 1, 1, dev, f'features.{idx}'),
+                          d=cp.conv_dgrad_plan(wt, 1, 1, dev, f'features.{idx}_dgrad'),
+                          out=z(batch, h, w, v), g=zf(batch, h, w, 4) if cin == 3 else z(batch, h, w, cin),
+                          pool=None, below=last if (last is not None and last['kind'] == 'conv') else None)
+                # the ReLU gate of a conv -> conv transition as a byte mask (ClassifierBody.masks), written by the lower layer's epilogue
+                if op['below'] is not None and self.masks:
+                    op['below']['m'] = self.zb(batch, h, w, cin // 4)
                 cin = v
                 idx += 2
+            self.ops.append(op)
+            last = op
         self.feat_hw = (h, w)
-        # ReLU gates of the conv -> conv transitions as byte masks (1 byte per 4 channels, written by the forward epilogue): the input
-        # gradient then reads 2 bits per element instead of the activation and stays on the branch-free epilogue
-        # (profiles/r05_configs4_f16s_tapconv_layers.json: features.2_dgrad 689 us against 477 forward with the activation as gate)
-        self.masks = BODY_GATE_MASKS and (USE_GATE_MASKS or storage == 'f16')
-        self.write_masks = True       # (ClassifierEngine.forward(need_grad=False): a forward pass nobody differentiates skips them)
         # fp16 storage: conv -> ReLU -> 2 x 2 max-pool in ONE launch (csrc/tapconv_h16p.hip POOL); tests that read the convolution's own
-        # activation switch it off
+        # activation switch it off on the live body
         self.fuse_pool = FUSE_POOL and storage == 'f16'
-        for i, op in enumerate(self.ops[:-1]):
-            if op['kind'] == 'conv' and self.ops[i + 1]['kind'] == 'conv' and self.masks:
-                op['m'] = torch.zeros(*op['out'].shape[:3], op['out'].shape[3] // 4, dtype=torch.uint8, device=dev)
         self.pool7 = z(batch, 7, 7, 512)
         self.g_pool7 = z(batch, 7, 7, 512)
         self.g_feat = z(batch, h, w, 512)
@@ -285,33 +288,30 @@ class VGG16Body:
         self.logits = zf(batch, 1, 1, self.ncls)
         self.g_h1, self.g_h2 = z(batch, 1, 1, fcw), z(batch, 1, 1, fcw)
 
+    def pool_fused(self, conv):
+        """Does the convolution's own launch pool (forward) / unpool (backward)?  `fuse_pool` is read at run time: tests switch it on a
+        live body.  (ConvPlan.run falls back to the separate pooling launch wherever its fused kernel form does not serve the layer.)"""
+        return self.fuse_pool and conv['pool'] is not None
+
     def forward(self, x4):
         B, R = self.B, _lib.ACT_RELU
         t = x4
-        fused_pool = False
-        for i, op in enumerate(self.ops):
-            if op['kind'] == 'conv':
-                nxt = self.ops[i + 1] if i + 1 < len(self.ops) else None
-                if self.fuse_pool and nxt is not None and nxt['kind'] == 'pool' and 'm' not in op:
-                    # conv -> ReLU -> MaxPool2d(2, 2) as one launch where the patch-staged fp16 kernel serves the layer (its epilogue pools: the
-                    # full-size activation is not written; ConvPlan.run falls back to conv + spaa_maxpool_fwd anywhere else)
-                    op['f'].run(t, op['out'], act=R, pool=(nxt['out'], nxt['arg'], self.write_masks))
-                    fused_pool = True
-                else:
-                    op['f'].run(t, op['out'], act=R, mask_out=op.get('m') if self.write_masks else None)
-            elif fused_pool:
-                fused_pool = False       # (pooled by the convolution's launch)
+        for op in self.ops:
+            if op['kind'] == 'pool':
+                if not self.pool_fused(op['conv']):
+                    pooling.maxpool_fwd(t, op['out'], op['arg'], 2, 2, 0)
+            elif self.pool_fused(op):
+                # conv -> ReLU -> MaxPool2d(2, 2) as one launch where the patch-staged fp16 kernel serves the layer (its epilogue pools:
+                # the full-size activation is not written)
+                op['f'].run(t, op['out'], act=R, pool=(op['pool']['out'], op['pool']['arg'], self.write_masks))
             else:
-                _lib.call('spaa_maxpool_fwd_f16' if self.storage == 'f16' else 'spaa_maxpool_fwd', _lib.hptr(t),
-                          _lib.hptr(op['out']), _lib.ptr(op['arg']), B, op['hin'], op['win'], op['c'], op['hin'] // 2,
-                          op['win'] // 2, 2, 2, 0, op['c'], 0)
+                op['f'].run(t, op['out'], act=R, mask_out=op.get('m') if self.write_masks else None)
             op['inp'] = t
             t = op['out']
-        fh, fw = self.feat_hw
-        if (fh, fw) != (7, 7):
-            if self.storage == 'f16':
+        if self.feat_hw != (7, 7):
+            if self.h16:
                 raise NotImplementedError('fp16-storage VGG-16 needs a 224x224 input (7x7 features: no adaptive pooling)')
-            _lib.call('spaa_adaptive_avgpool_fwd', _lib.ptr(t), _lib.ptr(self.pool7), B, fh, fw, 512, 7, 7)
+            pooling.adaptive_avgpool_fwd(t, self.pool7)
             t = self.pool7
         flat = t.view(B, 1, 1, 49 * 512)
         self.fc[0][0].run(flat, self.h1, act=R)
@@ -324,34 +324,24 @@ class VGG16Body:
         self.fc[2][1].run(g_logits.view(B, 1, 1, self.ncls), self.g_h2, gate=self.h2)
         self.fc[1][1].run(self.g_h2, self.g_h1, gate=self.h1)
         self.fc[0][1].run(self.g_h1, self.g_pool7.view(B, 1, 1, 49 * 512))
-        fh, fw = self.feat_hw
         g = self.g_pool7
-        if (fh, fw) != (7, 7):
-            _lib.call('spaa_adaptive_avgpool_bwd', _lib.ptr(g), None, _lib.ptr(self.g_feat), B, fh, fw, 512, 7, 7)
+        if self.feat_hw != (7, 7):
+            pooling.adaptive_avgpool_bwd(g, None, self.g_feat)
             g = self.g_feat
         # g is the gradient w.r.t. the last pool's output
-        pending = None     # (fp16 storage: a pool whose adjoint runs as the prologue of the convolution's input gradient below it)
-        for i in range(len(self.ops) - 1, -1, -1):
-            op = self.ops[i]
+        for op in reversed(self.ops):
             if op['kind'] == 'pool':
-                if self.fuse_pool and i > 0 and self.ops[i - 1]['kind'] == 'conv':
-                    pending = (g, op)       # (ConvPlan.run(unpool=...) falls back to spaa_maxpool_bwd where the fused form does not apply)
-                    continue
+                if self.pool_fused(op['conv']):
+                    continue       # (g stays the gradient w.r.t. the pool's output: the convolution below unpools it in its prologue)
                 # input of a pool is a conv+ReLU output: gather + ReLU gate -> gradient w.r.t. that conv's pre-activation
-                _lib.call('spaa_maxpool_bwd_f16' if self.storage == 'f16' else 'spaa_maxpool_bwd', _lib.hptr(g),
-                          _lib.ptr(op['arg']), 1, _lib.hptr(op['g']), B, op['hin'], op['win'], op['c'], op['hin'] // 2,
-                          op['win'] // 2, 2, 2, 0, op['c'], 0)
+                pooling.maxpool_bwd(g, op['arg'], op['g'], 2, 2, 0, True)
             else:
-                prev = self.ops[i - 1] if i > 0 else None
-                kw = {}
-                if pending is not None:
-                    g, pop = pending
-                    kw, pending = dict(unpool=(pop['arg'], pop['g'])), None
-                if prev is not None and prev['kind'] == 'conv' and 'm' in prev:
-                    op['d'].run(g, op['g'], gate_bits=prev['m'], **kw)
+                kw = dict(unpool=(op['pool']['arg'], op['pool']['g'])) if self.pool_fused(op) else {}
+                below = op['below']
+                if below is not None and 'm' in below:
+                    op['d'].run(g, op['g'], gate_bits=below['m'], **kw)
                 else:
-                    gate = op['inp'] if (prev is not None and prev['kind'] == 'conv') else None
-                    op['d'].run(g, op['g'], gate=gate, **kw)
+                    op['d'].run(g, op['g'], gate=below['out'] if below is not None else None, **kw)
             g = op['g']
         return g
 
@@ -361,12 +351,12 @@ class VGG16Body:
             if 'm' in op:
                 op['m'].copy_(_lib.pack_gate_mask(op['out'].float()))
 
-    def flops_fwd(self):
-        t = 0
+    def fwd_plans(self):
         for op in self.ops:
             if op['kind'] == 'conv':
-                t += op['f'].flops(self.B, *op['out'].shape[1:3])
-        return t + sum(f.flops(self.B, 1, 1) for f, _ in self.fc)
+                yield op['f'], op['out'].shape[1:3]
+        for f, _ in self.fc:
+            yield f, (1, 1)
 
 
 def _inception_body(sd, batch, in_hw, dev, storage='f32'):
@@ -398,6 +388,7 @@ class ClassifierEngine:
         self.ncls = self.body.ncls
         self.owner = None   # weakref to the attack state this engine is leased to (Classifier.engine)
         self.version = 0    # bumped whenever the activation workspaces are overwritten
+        self._grad_ready = False   # the last forward pass wrote what backward() reads (gate masks, arg-max bytes)
 
     def forward(self, y4, need_grad=True):
         """`need_grad=False`: nobody will call backward() on this pass (PerC-AL's second, decision-only forward pass on the quantised
@@ -405,9 +396,7 @@ class ClassifierEngine:
         _lib.check_dev(y4)
         assert y4.shape == (self.B, self.H, self.W, 4)
         self.version += 1
-        self._grad_ready = bool(need_grad)
-        if hasattr(self.body, 'write_masks'):
-            self.body.write_masks = bool(need_grad)
+        self._grad_ready = self.body.write_masks = bool(need_grad)
         _lib.call('spaa_preproc_fwd', _lib.ptr(y4), _lib.ptr(self.pre), self.B, self.H, self.W, self.cy0, self.cx0,
                   self.ch, self.cw, self.oh, self.ow, self._mean, self._std)
         return self.body.forward(self.pre)
@@ -416,13 +405,11 @@ class ClassifierEngine:
         """The body's forward pass on `pre` as the caller filled it (the One-pixel attacker's spaa_onepixel_preproc writes its
         candidates there): logits [B, ncls].  A decision-only pass, as forward(need_grad=False)."""
         self.version += 1
-        self._grad_ready = False
-        if hasattr(self.body, 'write_masks'):
-            self.body.write_masks = False
+        self._grad_ready = self.body.write_masks = False
         return self.body.forward(self.pre)
 
     def backward(self, g_logits):
-        if not getattr(self, '_grad_ready', False):
+        if not self._grad_ready:
             # (a need_grad=False pass overwrote the activations but left the ReLU-gate masks / pool arg-max bytes of the pass before it)
             raise RuntimeError('ClassifierEngine.backward(): the last forward() ran with need_grad=False (its gate masks were not '
                                'written); run forward(..., need_grad=True) first')

@@ -17,6 +17,7 @@ import os
 import torch
 
 from . import _lib
+from . import pooling
 
 BK = 32
 NPAD = 128
@@ -346,12 +347,12 @@ class ConvPlan:
         prologue of the thin-output matrix-core kernel (tile 72, fp32) instead of as a launch of its own.
         `pool` = (pooled [B,Hout/2,Wout/2,C], arg-max bytes uint8 [B,Hout/2,Wout/2,C], want_arg): this layer's ReLU is followed by a 2 x 2 /
         stride-2 max-pool (torchvision VGG-16): where the patch-staged fp16 kernel serves the layer (tile 68, image-aligned regions) the pool
-        runs in its epilogue and `out` is NOT written; anywhere else the layer runs as usual and spaa_maxpool_fwd follows -- the same pooled
+        runs in its epilogue and `out` is NOT written; anywhere else the layer runs as usual and pooling.maxpool_fwd follows -- the same pooled
         values and arg-max bytes either way.
         `unpool` = (arg-max bytes uint8 [B,Hin/2,Win/2,C], full-size gradient buffer [B,Hin,Win,Cs]): `inp` is the gradient w.r.t. the OUTPUT of
         the 2 x 2 / stride-2 max-pool that followed this layer's input (an input-gradient plan of torchvision VGG-16): where the
         two-workgroup form of the patch-staged fp16 kernel serves the layer the pool's adjoint (with its ReLU gate) runs as the patch
-        prologue and the full-size gradient is never written; anywhere else spaa_maxpool_bwd fills the buffer first.
+        prologue and the full-size gradient is never written; anywhere else pooling.maxpool_bwd fills the buffer first.
         Four steps: `_check` (operands -> shape facts), `_choose` (the kernel: tile, K split), `_describe` (the TapConv descriptor),
         `_launch` (launcher plan, workspace, launch, profile record)."""
         s = self._check(inp, out, add, gate, aux_out, gate2, mask_out, gate_bits, gate2_bits, inp2, in_coff, in2_coff, out_coff,
@@ -725,8 +726,7 @@ class ConvPlan:
                 d.reserved1 |= 128
                 unpool_fused = True
             else:
-                _lib.call('spaa_maxpool_bwd_f16', _lib.hptr(inp), _lib.ptr(parg), 1, _lib.hptr(gfull), b, hin, win, self.cin_p, hin // 2, win // 2,
-                          2, 2, 0, s.cs_in, 0)
+                pooling.maxpool_bwd(inp, parg, gfull, 2, 2, 0, True, c=self.cin_p)
                 d.inp, d.in_cstride = gfull.data_ptr(), gfull.shape[3]
         self.last_unpool_fused = unpool_fused
         pool_fused = False
@@ -754,8 +754,7 @@ class ConvPlan:
             fl, nbytes = self._profile_work(s, inp2 is not None, unpool_fused, pool_fused)
             PROFILE.append((self.name, s.key, fl, e0, e1, tid, nbytes))
         if pool is not None and not pool_fused:
-            _lib.call('spaa_maxpool_fwd_f16' if s.out_f16 else 'spaa_maxpool_fwd', _lib.hptr(out), _lib.hptr(pooled), _lib.ptr(parg), b, hout, wout,
-                      self.cout, hout // 2, wout // 2, 2, 2, 0, pooled.shape[3], 0)
+            pooling.maxpool_fwd(out, pooled, parg, 2, 2, 0)
 
     def _profile_tid(self, d, h16p_cv, wino_bn, cin2k):
         """The kernel id bench.py reports: tile + 100 x K ranges (9: stream-K), + 1 / 1000 / 2000 for forms that are kernels of their own."""

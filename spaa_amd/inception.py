@@ -17,11 +17,11 @@ import torch
 
 from . import _lib
 from . import convplan as cp
-from .models import USE_GATE_MASKS
+from . import pooling
+from .classifier import ClassifierBody
 
 PAD32_F32 = int(os.environ.get('SPAA_INCEPTION_PAD32', '1'))
 FUSE_ENTRY = os.environ.get('SPAA_INCEPTION_FUSE_ENTRY', '1') != '0'
-BODY_GATE_MASKS = os.environ.get('SPAA_BODY_MASKS', '1') != '0'   # 0: the activation itself as the ReLU gate (A/B measurements)
 
 # layer table: name -> builder spec.  conv spec = (name, cout, (kh, kw), stride, (ph, pw))
 A_ = lambda pf: dict(kind='A', pf=pf)  # noqa: E731
@@ -87,33 +87,17 @@ class Ten:
         return self.coff == 0 and self.c == self.buf.shape[3]
 
 
-def _osz(n, k, s, p):
-    return (n + 2 * p - k) // s + 1
+_osz = ClassifierBody.out_size
 
 
-class InceptionV3Body:
+class InceptionV3Body(ClassifierBody):
     def __init__(self, sd, batch, in_hw, dev, storage='f32'):
-        from .classifier import _strip
-        sd = _strip(sd)
-        self.B, self.dev, self.sd, self.storage = batch, dev, sd, storage
-        self.h16 = storage == 'f16'
-        hd = torch.float16 if self.h16 else torch.float32
+        super().__init__(sd, batch, in_hw, dev, storage)
+        zf = self.zf
         self.ops = []
         h, w = in_hw
-        self.in_hw = (h, w)
-
-        def zf(*shape):
-            return torch.zeros(*shape, device=dev)
-
-        def z(*shape):
-            return torch.zeros(*shape, device=dev, dtype=hd)
-
-        self.z = z
-        # ReLU gates as byte masks written by the forward epilogues (and by spaa_gate_mask for the max-pool outputs): an input-gradient
-        # launch reads 2 bits per element instead of the activation and stays on the branch-free epilogue (epilogue.hpp fast_epi_*)
-        self.masks = BODY_GATE_MASKS and (USE_GATE_MASKS or self.h16)
-        self.write_masks = True       # (ClassifierEngine.forward(need_grad=False) clears it for a pass nobody differentiates)
-        self.zm = lambda *shape: torch.zeros(*shape, dtype=torch.uint8, device=dev) if self.masks else None
+        # gate-mask bytes of a buffer (ClassifierBody.masks: written by the forward epilogues, and by pooling.gate_mask for the max-pool outputs)
+        self.zm = lambda *shape: self.zb(*shape) if self.masks else None
         # transform_input=True (torchvision): per-channel affine on the already-normalised image, folded into the
         # first convolution:  x' = a_c * x + b_c  =>  W' = W * a_c, bias' += sum_taps W * b_c  -- valid only where no
         # zero padding is involved: Conv2d_1a has padding 0, so the folding is exact.
@@ -130,20 +114,11 @@ class InceptionV3Body:
         for name, kind, arg in BLOCKS:
             t = self.add_block(name, kind, arg, t)
         self.feat = t
-        fh, fw = t.hw
-        self.feat_hw = fh * fw
-        self.pooled = zf(batch, 1, 1, 2048)
-        self.g_pooled = zf(batch, 1, 1, 2048)
-        self.ncls = sd['fc.weight'].shape[0]
-        self.fc_f = cp.linear_fwd_plan(sd['fc.weight'], sd['fc.bias'], dev, 'fc')
-        self.fc_d = cp.linear_dgrad_plan(sd['fc.weight'], dev, 'fc_dgrad')
-        self.logits = zf(batch, 1, 1, self.ncls)
+        self.build_head(2048)
 
     # ---- graph construction ------------------------------------------------------------------------------------
-    def folded(self, name, fold_input_affine=False):
-        sd = self.sd
-        wgt, b = cp.fold_bn(sd[name + '.conv.weight'], sd[name + '.bn.weight'], sd[name + '.bn.bias'],
-                            sd[name + '.bn.running_mean'], sd[name + '.bn.running_var'], eps=1e-3)
+    def folded_conv(self, name, fold_input_affine=False):
+        wgt, b = self.folded(name + '.conv', name + '.bn', eps=1e-3)
         if fold_input_affine:
             a = torch.tensor([0.229 / 0.5, 0.224 / 0.5, 0.225 / 0.5], dtype=torch.float64)
             c = torch.tensor([(0.485 - 0.5) / 0.5, (0.456 - 0.5) / 0.5, (0.406 - 0.5) / 0.5], dtype=torch.float64)
@@ -155,7 +130,7 @@ class InceptionV3Body:
     def add_conv(self, name, inp, cout, k, stride, pad, out=None, fold_input_affine=False):
         hin, win = inp.hw
         ho, wo = _osz(hin, k[0], stride, pad[0]), _osz(win, k[1], stride, pad[1])
-        wgt, b = self.folded(name, fold_input_affine)
+        wgt, b = self.folded_conv(name, fold_input_affine)
         # fp32 storage: Conv2d_3b_1x1's 80 channels are built 96 wide as well (SPAA_INCEPTION_PAD32: 0 never, 1 widths above 64 --
         # the default --, 2 every width): Conv2d_4a_3x3 (80 -> 192, unpadded 3x3 on 73 x 73) then reads whole 32-channel blocks and
         # runs on the Winograd kernel's pad-0 form instead of the register-staged tile
@@ -189,7 +164,7 @@ class InceptionV3Body:
                       mbuf=self.zm(self.B, ho, wo, inp.c // 4) if mode == 'max' else None)
         op = dict(kind=mode, inp=inp, out=out, k=k, s=s, p=p)
         if mode == 'max':
-            op['arg'] = torch.zeros(self.B, ho, wo, inp.c, dtype=torch.uint8, device=self.dev)
+            op['arg'] = self.zb(self.B, ho, wo, inp.c)
         inp.consumers.append(op)
         self.ops.append(op)
         return out
@@ -252,7 +227,7 @@ class InceptionV3Body:
             ws, bs, widths = [], [], []
             for bi in entries:
                 o = spec[bi][0]
-                wgt, b = self.folded(f'{name}.{o[1]}')
+                wgt, b = self.folded_conv(f'{name}.{o[1]}')
                 c = o[2]
                 cp_ = -(-c // 32) * 32 if (self.h16 or PAD32_F32 == 2) else c      # (zero pad channels, as add_conv)
                 if cp_ != c:
@@ -286,7 +261,6 @@ class InceptionV3Body:
 
     # ---- execution ---------------------------------------------------------------------------------------------
     def forward(self, x4):
-        B = self.B
         self.x_in.buf = x4
         wm = self.masks and self.write_masks
         for op in self.ops:
@@ -295,29 +269,17 @@ class InceptionV3Body:
                 if i is self.x_in:
                     i.buf = x4
                 op['f'].run(i.buf, o.buf, act=_lib.ACT_RELU, in_coff=i.coff, out_coff=o.coff, mask_out=o.mbuf if wm else None)
-            elif op['kind'] == 'max':
-                hin, win = i.hw
-                ho, wo = o.hw
-                _lib.call('spaa_maxpool_fwd_f16' if self.h16 else 'spaa_maxpool_fwd', _lib.hptr(i.buf), _lib.hptr(o.buf),
-                          _lib.ptr(op['arg']), B, hin, win, i.c, ho, wo, op['k'], op['s'], op['p'], o.buf.shape[3], o.coff)
+            elif op['kind'] == 'max':       # (pool inputs are whole buffers: add_pool)
+                pooling.maxpool_fwd(i.buf, o.buf, op['arg'], op['k'], op['s'], op['p'], o.coff)
                 if wm:   # the pooled values gate the layers that consume them like every other ReLU output
-                    _lib.call('spaa_gate_mask', _lib.hptr(o.buf), int(self.h16), _lib.ptr(o.mbuf), B * ho * wo, i.c, o.buf.shape[3], o.coff)
+                    pooling.gate_mask(o.buf, o.mbuf, o.c, o.coff)
             else:
-                hin, win = i.hw
-                ho, wo = o.hw
-                _lib.call('spaa_avgpool2d_fwd_f16' if self.h16 else 'spaa_avgpool2d_fwd', _lib.hptr(i.buf), _lib.hptr(o.buf), B,
-                          hin, win, i.c, ho, wo, op['k'], op['s'], op['p'], o.buf.shape[3], o.coff)
-        _lib.call('spaa_avgpool_fwd_f16' if self.h16 else 'spaa_avgpool_fwd', _lib.hptr(self.feat.buf), _lib.ptr(self.pooled), B,
-                  self.feat_hw, 2048)
-        self.fc_f.run(self.pooled, self.logits)
-        return self.logits.view(B, self.ncls)
+                pooling.avgpool2d_fwd(i.buf, o.buf, op['k'], op['s'], op['p'], o.coff)
+        return self.head_fwd(self.feat.buf)
 
     def backward(self, g_logits):
-        B = self.B
-        self.fc_d.run(g_logits.view(B, 1, 1, self.ncls), self.g_pooled)
         # gradient w.r.t. the pre-activations of the last concat (all four slices are ReLU outputs)
-        _lib.call('spaa_avgpool_bwd_f16' if self.h16 else 'spaa_avgpool_bwd', _lib.ptr(self.g_pooled), _lib.hptr(self.feat.buf),
-                  _lib.hptr(self.feat.gbuf), B, self.feat_hw, 2048)
+        self.head_bwd(g_logits, self.feat.buf, self.feat.gbuf)
         written = set()
         for op in reversed(self.ops):
             i, o = op['inp'], op['out']
@@ -331,16 +293,11 @@ class InceptionV3Body:
                             out_coff=i.coff, add_coff=i.coff, gate_coff=i.coff)
             else:
                 assert key not in written, 'pool branches must be the first gradient contribution of their input'
-                hin, win = i.hw
-                ho, wo = o.hw
                 if op['kind'] == 'max':
-                    _lib.call('spaa_maxpool_bwd_f16' if self.h16 else 'spaa_maxpool_bwd', _lib.hptr(o.gbuf), _lib.ptr(op['arg']),
-                              int(gated), _lib.hptr(i.gbuf), B, hin, win, i.c, ho, wo,
-                              op['k'], op['s'], op['p'], o.gbuf.shape[3], o.coff)
+                    pooling.maxpool_bwd(o.gbuf, op['arg'], i.gbuf, op['k'], op['s'], op['p'], gated, o.coff)
                 else:
                     assert not gated, 'avg-pool is never the only consumer in Inception-v3'
-                    _lib.call('spaa_avgpool2d_bwd_f16' if self.h16 else 'spaa_avgpool2d_bwd', _lib.hptr(o.gbuf), _lib.hptr(i.gbuf), B,
-                              hin, win, i.c, ho, wo, op['k'], op['s'], op['p'], o.gbuf.shape[3], o.coff)
+                    pooling.avgpool2d_bwd(o.gbuf, i.gbuf, op['k'], op['s'], op['p'], o.coff)
             written.add(key)
         return self.x_in.gbuf
 
@@ -353,9 +310,8 @@ class InceptionV3Body:
             if op['kind'] in ('conv', 'max') and o.mbuf is not None:
                 o.mbuf[..., o.coff // 4:(o.coff + o.c) // 4] = _lib.pack_gate_mask(o.buf[..., o.coff:o.coff + o.c].float())
 
-    def flops_fwd(self):
-        t = 0
+    def fwd_plans(self):
         for op in self.ops:
             if op['kind'] == 'conv':
-                t += op['f'].flops(self.B, *op['out'].hw)
-        return t + self.fc_f.flops(self.B, 1, 1)
+                yield op['f'], op['out'].hw
+        yield self.fc_f, (1, 1)
