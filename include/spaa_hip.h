@@ -32,7 +32,7 @@ enum { SPAA_ACT_NONE = 0, SPAA_ACT_RELU = 1, SPAA_ACT_RELU_CLAMP1 = 2, SPAA_ACT_
 enum { SPAA_IO_IN_F16 = 1, SPAA_IO_OUT_F16 = 2 };
 /* gate applied last (ReLU / clamp backward):  out = pass(gate) ? v : 0 */
 enum { SPAA_GATE_NONE = 0, SPAA_GATE_POS = 1 /* gate > 0 */, SPAA_GATE_POS_LE1 = 2 /* 0 < gate <= 1 */,
-       SPAA_GATE_MUL = 3 /* value * gate: the chain rule through `x * s` (models.py:342); tiles 25.. only */ };
+       SPAA_GATE_MUL = 3 /* value * gate: the chain rule through `x * s` (models.py:342); SPAA_TILE_GATE_MUL tiles only */ };
 
 typedef struct {
     int32_t oy0, ox0;  /* output offset of this parity class */
@@ -61,7 +61,7 @@ typedef struct {
     int32_t B, Hm, Wm, s_in, s_out;
     const float* weights; /* packed, see spaa_tapclass_t.w_off; rows padded to a multiple of 128 */
     const uint16_t* w_split; /* optional: the same weights as three bf16 planes per class, [3][Npad][Kpad] with
-                                w == h + m + l exactly (tiles 12-14: fp32 emulated on the bf16 matrix cores); class c
+                                w == h + m + l exactly (the bf16x6 families: fp32 emulated on the bf16 matrix cores); class c
                                 starts at element 3 * cls[c].w_off */
     const uint16_t* w_half; /* SPAA_IO_IN_F16: the weights rounded to fp16, per class [Npad][Kpad64] (Kpad64 = K rounded up to 64,
                                zero padded); class c starts at element cls[c].w_off / Kpad * Kpad64 */
@@ -72,8 +72,10 @@ typedef struct {
     const float* gate;    /* indexed like `out`, or NULL */
     int32_t gate_cstride, gate_coff, gate_mode;
     int32_t act;
-    int32_t tile;         /* 0 = auto; 1..54, 60..65, 68, 70, 71, 72, 73, 74 = explicit kernel / workgroup tile (the dispatcher in tapconv.hip lists them;
-                             spaa_amd/convplan.py: TILE_NAMES; chosen per layer shape by tools/autotune.py) */
+    int32_t tile;         /* 0 = auto; else an explicit kernel / workgroup tile: an id of the tile table (csrc/tiles.hpp, read through
+                             spaa_tapconv_tile_info below; chosen per layer shape by tools/autotune.py).  Which tiles serve byte masks, fp16
+                             storage, K ranges, folded classes, a multiplicative gate or a second source is stated there, once, as the
+                             SPAA_TILE_* capability bits -- the field comments below name the bit, not the ids. */
     float* aux_out;       /* optional second output (indexed like `out`):
                              act == SPAA_ACT_RELU_CLAMP1: the value BEFORE the clamp;
                              otherwise, with gate2: (gate2 > 0) ? out_value : 0  (a second ReLU-backward gate) */
@@ -82,20 +84,20 @@ typedef struct {
     uint8_t* mask_out;         /* optional ReLU-gate mask of this launch's output: one BYTE per 4 consecutive channels, bit e =
                                   (out[n0 + e] > 0), at index (o * out_cstride + out_coff + n0) >> 2 (o = output pixel).  A
                                   dgrad launch then reads 2 bits per element instead of the 32-bit activation.  Needs Cout,
-                                  out_cstride, out_coff % 4 == 0 and a tile of the families 15..27, 30..46, 48..54 */
+                                  out_cstride, out_coff % 4 == 0 and a SPAA_TILE_BYTE_MASKS tile */
     const uint8_t* gate_bits;  /* alternative to `gate` (meaning SPAA_GATE_POS): a mask written through `mask_out` by the
                                   launch that produced the activation; indexed with gate_cstride / gate_coff */
     const uint8_t* gate2_bits; /* likewise for `gate2` (gate2_cstride / gate2_coff) */
     int32_t tap_range[4]; /* (dy_min, dy_max, dx_min, dx_max) over the taps of all classes: patch-staged kernels */
     float* splitk_ws;     /* split-K workspace, ksplit * B*Hm*Wm * Npad floats (Npad = Cout rounded up to 128), or NULL */
     int32_t ksplit;       /* 0, 1: off.
-                             > 1 (tiles 25.., one class): K is cut into `ksplit` ranges computed by separate workgroups into
+                             > 1 (the families with a second pass, one class): K is cut into `ksplit` ranges computed by separate workgroups into
                              splitk_ws; a second kernel adds them in fixed order and applies the epilogue (layers with few
                              output pixels and long K, e.g. ResNet layer4: fills the chip).
-                             -1 (persistent tiles 48..54, one class): stream-K — the K-steps of all tiles are cut into equal
+                             -1 (SPAA_TILE_PERSISTENT tiles, one class): stream-K — the K-steps of all tiles are cut into equal
                              ranges per workgroup; splitk_ws must hold 2 * 768 * 128 * 128 floats; cut tiles are summed in
                              segment order by a second kernel. */
-    int32_t nfold;        /* <= 1: off.  4 (tiles 25.., one class, s_out == 2, Cout % 4 == 0): the four output-parity classes of
+    int32_t nfold;        /* <= 1: off.  4 (SPAA_TILE_NFOLD tiles, one class, s_out == 2, Cout % 4 == 0): the four output-parity classes of
                              a kernel-2 stride-2 ConvTranspose2d share their single tap, so they are folded into the GEMM N
                              dimension: weight rows [nfold*Cout], row c*Cout + n -> output pixel (2y + c/2, 2x + c%2),
                              channel n.  The input is read once instead of once per class. */
@@ -103,14 +105,14 @@ typedef struct {
                            * except bits 27-28 of a Winograd launch (tiles 70 / 71 / 73): the layer's zero padding, 0 = 1 (same-size
                            * output), 1 = 0 (unpadded: output 2 smaller), 2 = 2 (that layer's input gradient: 2 larger) */
     int32_t io_dtype;     /* fp16-STORAGE mode (BASELINE.json configs[4]: "fp16 with fp32 dE2000"), bit flags:
-                             SPAA_IO_IN_F16  (tiles 60..65; tile 68: 3x3 / stride-1 layers with the input patch staged once in LDS;
-                                             tile 72: thin outputs with the parity classes folded into N, fp32 out (with a
+                             SPAA_IO_IN_F16  (SPAA_TILE_F16_IN tiles: the fp16 implicit-GEMM tiles; tile 68: 3x3 / stride-1 layers with the input
+                                             patch staged once in LDS; tile 72: thin outputs with the parity classes folded into N, fp32 out (with a
                                              4-channel pixel stride, offset 0 and Cout < 4 its 16-byte stores write ZERO into
                                              the pad channels Cout..3; every other tile leaves channels >= Cout untouched);
                                              tile 29 with an fp32 output of at most 4 channels: the image-side input
                                              gradients): `in` is fp16 NHWC (strides / offsets still in elements) and the
                                              weights come from `w_half`; fp32 accumulation on v_mfma_f32_16x16x32_f16;
-                             SPAA_IO_OUT_F16 (tiles 60..65, 68, and the kernels that read fp32 IMAGES: 15..24, 38):
+                             SPAA_IO_OUT_F16 (SPAA_TILE_F16_OUT tiles: the fp16 kernels and the kernels that read fp32 IMAGES):
                                              `out`, `add`, `gate`, `aux_out`, `gate2` are fp16.
                              0 = everything fp32 (the default path; dtype "f32" in bench.py). */
     int32_t reserved1;    /* tiles 70 / 71 / 73 (and tile 68's K-range form): bit 8 = `splitk_ws` BEGINS with SPAA_SPLITK_HDR_FLOATS floats of arrival
@@ -150,6 +152,36 @@ typedef struct {
 } spaa_tapconv_t;
 
 int spaa_tapconv_f32(const spaa_tapconv_t* desc, spaa_stream_t stream);
+
+/* The tile table (csrc/tiles.hpp; mirrored by spaa_amd/tiles.py, tests/test_tiles_cpu.py pins the two to each other): what a tile id is
+ * and what the kernel behind it can do.  Kernel family of a tile: */
+enum { SPAA_FAM_F32 = 0 /* fp32 MFMA */, SPAA_FAM_DIRECT, SPAA_FAM_THIN, SPAA_FAM_X6, SPAA_FAM_X6D, SPAA_FAM_THINPATCH, SPAA_FAM_SMALLCIN,
+       SPAA_FAM_H16, SPAA_FAM_H16P, SPAA_FAM_WINO, SPAA_FAM_THINMF, SPAA_FAM_X6P, SPAA_FAM_C3 };
+/* capability bits of a tile: what the descriptor may ask of it (everything else is refused before any launch) */
+enum { SPAA_TILE_BYTE_MASKS = 1,        /* `mask_out` / `gate_bits` / `gate2_bits`: the epilogues built on csrc/epilogue.hpp */
+       SPAA_TILE_F16_IN = 2,            /* SPAA_IO_IN_F16 */
+       SPAA_TILE_F16_IN_F32_OUT = 4,    /* ... but only together with an fp32 output */
+       SPAA_TILE_F16_IN_REQUIRED = 8,   /* no fp32-input form */
+       SPAA_TILE_F16_OUT = 16,          /* SPAA_IO_OUT_F16 */
+       SPAA_TILE_F16_OUT_KSPLIT = 32,   /* ... together with `ksplit` > 1 (never with stream-K) */
+       SPAA_TILE_GATE_MUL = 64,         /* SPAA_GATE_MUL */
+       SPAA_TILE_NFOLD = 128,           /* `nfold` > 1 */
+       SPAA_TILE_IN2 = 256,             /* a second source `in2` */
+       SPAA_TILE_IN2_OF_CIN = 512,      /* ... whose Cin2 channels are the LAST of the Cin input channels (unfolded launches) */
+       SPAA_TILE_PERSISTENT = 1024 };   /* persistent workgroups: stream-K (`ksplit` == -1) capable */
+typedef struct {
+    int32_t id;
+    int32_t family;    /* SPAA_FAM_* */
+    int32_t bm, bn;    /* the workgroup's GEMM tile where the id fixes one (fp32 MFMA, x6, x6d, h16 families), else 0 */
+    uint32_t caps;     /* SPAA_TILE_* */
+    const char* name;  /* static storage */
+} spaa_tile_info_t;
+/* Host-side queries: nothing is launched.  The table entry of `tile` (0 = ok, non-zero = no such tile; the small-linear route, reported
+ * as 75 by spaa_amd/convplan.py, is no tile of this dispatcher). */
+int spaa_tapconv_tile_info(int tile, spaa_tile_info_t* out);
+/* Every host-side check spaa_tapconv_f32 makes before it dispatches: pointers, shapes, 32-bit offset ranges and what the tile's
+ * capability bits allow.  0 or hipErrorInvalidValue (1); spaa_tapconv_f32 calls it first and returns its code. */
+int spaa_tapconv_check(const spaa_tapconv_t* desc);
 /* Weight and bias gradients of the layer `desc` describes in its FORWARD form (same geometry / taps / packing fields;
  * `in` = the layer's input activation; `out_cstride` / `out_coff` / Hout / Wout describe `gout`, the gradient w.r.t. the
  * layer's pre-activation [B,Hout,Wout,out_cstride]); fp32 only, nfold <= 1.

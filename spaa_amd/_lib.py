@@ -46,6 +46,11 @@ class TapConv(C.Structure):
     ]
 
 
+class TileInfo(C.Structure):
+    """spaa_tile_info_t: one entry of the tile table (include/spaa_hip.h; spaa_amd/tiles.py holds the same rows)."""
+    _fields_ = [('id', C.c_int32), ('family', C.c_int32), ('bm', C.c_int32), ('bn', C.c_int32), ('caps', C.c_uint32), ('name', C.c_char_p)]
+
+
 class ImgPair(C.Structure):
     """spaa_img_pair_t: one image pair of spaa_img_stats (include/spaa_hip.h)."""
     _fields_ = [('x_off', C.c_int64), ('y_off', C.c_int64),
@@ -153,7 +158,8 @@ _SIGNATURES = {
     'spaa_zero': [_p, _l, _p],
 }
 
-EXPORTS = sorted(list(_SIGNATURES) + ['spaa_version', 'spaa_tapconv_sizeof', 'spaa_tapconv_offsetof', 'spaa_tapconv_wino_plan', 'spaa_tapconv_h16p_plan'])
+EXPORTS = sorted(list(_SIGNATURES) + ['spaa_version', 'spaa_tapconv_sizeof', 'spaa_tapconv_offsetof', 'spaa_tapconv_wino_plan', 'spaa_tapconv_h16p_plan',
+                                         'spaa_tapconv_tile_info', 'spaa_tapconv_check'])
 
 _lib = None
 
@@ -179,6 +185,10 @@ def load():
     lib.spaa_tapconv_wino_plan.restype = C.c_int
     lib.spaa_tapconv_h16p_plan.argtypes = [C.POINTER(TapConv), C.POINTER(C.c_int32)]   # (host-side query: no stream)
     lib.spaa_tapconv_h16p_plan.restype = C.c_int
+    lib.spaa_tapconv_tile_info.argtypes = [C.c_int, C.POINTER(TileInfo)]               # (host-side query: no stream)
+    lib.spaa_tapconv_tile_info.restype = C.c_int
+    lib.spaa_tapconv_check.argtypes = [C.POINTER(TapConv)]                             # (host-side query: no stream)
+    lib.spaa_tapconv_check.restype = C.c_int
     _lib = lib
     return lib
 

@@ -18,31 +18,26 @@ import torch
 
 from . import _lib
 from . import pooling
+from . import tiles
 
 BK = 32
 NPAD = 128
 PROFILE = None  # set to a list by bench.py to time every tapconv launch with HIP events
 PROFILE_ONLY = None  # ... or only the launches of these reported tile ids (events inside bench.py's timed region)
 FORCE_TILE = 0  # tools/autotune.py: force one workgroup tile for every launch
-TILE_NAMES = {1: '128x128', 2: '256x64', 3: '256x32', 4: '128x64a', 5: '128x32', 6: '64x64', 7: '64x128', 8: '128x64b',
-              9: 'direct4', 10: 'direct32', 11: 'thin4', 12: 'x6_64x64', 13: 'x6_128x32', 14: 'x6_32x128',
-              15: 'x6v2_128x64g3', 16: 'x6v2_128x64g2', 17: 'x6v2_128x128g1', 18: 'x6v2_64x64g3', 19: 'x6v2_64x128g2',
-              20: 'x6v3_128x64g3', 21: 'x6v3_128x64g2', 22: 'x6v3_64x64g3', 23: 'x6v3_128x128g1', 24: 'x6v3_64x128g2',
-              25: 'x6d_128x128', 26: 'x6d_256x128', 27: 'x6d_128x64', 28: 'thinpatch32', 29: 'thinpatch16',
-              30: 'x6d_128x32', 31: 'x6d_64x64', 32: 'x6d_64x128', 33: 'x6d_256x64',
-              34: 'x6d16_128x128', 35: 'x6d16_256x128', 36: 'x6d16_128x64', 37: 'x6d16_128x32', 38: 'smallcin',
-              39: 'x6d16co_128x128', 40: 'x6d16co_128x64', 41: 'x6d16co_128x32',
-              42: 'x6d16a3_128x64', 43: 'x6d16a3_128x32', 44: 'x6da3_128x64', 45: 'x6d16coa3_128x64', 46: 'x6d16coa3_128x32', 47: 'thinpatch16x2',
-              48: 'x6d16p_128x128', 49: 'x6d16p_128x64', 50: 'x6d16a3p_128x64', 51: 'x6da3p_128x64', 52: 'x6d16p_256x128',
-              53: 'x6d16p_128x32', 54: 'x6dp_128x128',
-              60: 'h16_128x128', 61: 'h16_128x64', 62: 'h16_128x32', 63: 'h16_128x16', 64: 'h16_256x128', 65: 'h16_256x256', 68: 'h16p_16x32x128', 72: 'thinmf_12x32',
-              73: 'wino_x6_8x32x64', 74: 'x6p_4x32', 76: 'c3conv_16x32',
-              70: 'wino_x6_16x32x128', 71: 'wino_x6_16x32x64'}   # (70: the launcher chooses the N tile -- reported as 71 when it took 64; 71: 64-wide forced)
-X6D_TILES = set(range(25, 28)) | set(range(30, 38)) | set(range(39, 47)) | set(range(48, 55))   # DMA-staged bf16x6 kernels (csrc/tapconv_x6d.hip)
-X6D_PERSISTENT = set(range(48, 55))      # ... of which the persistent ones (stream-K capable)
-H16_TILES = set(range(60, 66))           # fp16 implicit-GEMM kernels (csrc/tapconv_h16.hip); 68 = patch-staged 3x3 (tapconv_h16p.hip)
-STORE4_TILES = set(range(15, 28)) | set(range(30, 47)) | set(range(48, 55)) | set(range(60, 66)) | {68, 70, 71, 73, 74, 76}  # shared epilogue (epilogue.hpp)
-F16OUT_TILES = set(range(15, 25)) | {38, 76} | set(range(60, 66))  # ... of which these may write fp16 (fp32 image in, fp16 activation out)
+# what a tile id is and can do: one table (tiles.py, the mirror of csrc/tiles.hpp); the sets the planner asks are derived from it
+TILE_NAMES = {t.id: t.name for t in tiles.TABLE}   # (70: the launcher chooses the N tile -- reported as 71 when it took 64; 71: 64-wide forced)
+X6D_TILES = tiles.of_family(tiles.X6D)             # DMA-staged bf16x6 kernels (csrc/tapconv_x6d.hip)
+X6D_PERSISTENT = tiles.with_caps(tiles.PERSIST)    # ... of which the persistent ones (stream-K capable)
+H16_TILES = tiles.of_family(tiles.H16)             # fp16 implicit-GEMM kernels (csrc/tapconv_h16.hip); 68 = patch-staged 3x3 (tapconv_h16p.hip)
+H16_SPLITK_BN = {t.id: t.bn for t in tiles.TABLE if t.family == tiles.H16 and t.caps & tiles.F16OUT_KSPLIT}   # ... of which these take K ranges: their N tile
+WINO_TILES = tiles.of_family(tiles.WINO)           # Winograd F(2x2,3x3) kernels (csrc/tapconv_wino.hip)
+STORE4_TILES = tiles.with_caps(tiles.MASKS)        # shared epilogue (epilogue.hpp): byte masks
+# ... of which these may write fp16 (fp32 image in, fp16 activation out).  Without 68, which the C side allows: the patch-staged fp16
+# kernel needs an fp16 input as well, and `_choose` has sent such launches its way before it asks this set
+F16OUT_TILES = tiles.with_caps(tiles.F16OUT) - tiles.of_family(tiles.H16P)
+GATE_MUL_TILES = tiles.with_caps(tiles.GATEMUL)    # epilogues that know the multiplicative gate
+X6_TILES = tiles.of_family(tiles.X6, tiles.X6D, tiles.THINPATCH, tiles.SMALLCIN, tiles.THINMF, tiles.X6P, tiles.C3)   # fp32-exact operands outside the fp32-MFMA / VALU / Winograd kernels (tests: the tolerance family)
 DEFAULT_DISABLE = set(os.environ.get('SPAA_DEFAULT_DISABLE', '').split(','))
 X6P_STD = os.environ.get('SPAA_X6P_STD', '1') != '0'   # 0: the stride-2 patch kernel's run-time schedule (A/B measurements)
 DEBUG_TAPMAJOR = int(os.environ.get('SPAA_X6D_TAPMAJOR', '0'))      # 1: tap-major K order (A/B measurements only)
@@ -80,6 +75,13 @@ def _load_tune():
 
 TUNE = _load_tune()  # shape key -> tile id, measured on MI355X by tools/autotune.py (absent key = heuristic)
 _NEAREST = {}
+
+
+def split_tune_value(v):
+    """A tune value `tile + 100 * k` (tapconv_tune.json, FORCE_TILE, `_default_tile`) -> (tile, k).  k = 0 or 1: no K split; 2..8: that
+    many K ranges; 9: stream-K (persistent x6d tiles).  Winograd tiles read the hundreds digit as the K ranges asked of the launcher's
+    plan: 0 = the plan chooses, 1 = never split, k > 1 = k ranges (clamped by the plan to whole 32-channel blocks)."""
+    return v % 100, v // 100
 
 
 def tuned_tile(key):
@@ -445,7 +447,7 @@ class ConvPlan:
             # entry (batch 64) took tile 76, a batch of 8 ran the same layer on fp32-exact operands, and a sub-batch did not reproduce its
             # rows of the full batch to the mode's own noise (profiles/r06_vgg_f16_bisect.txt)
             tile = 76
-        if cin2k and self.wino is not None and tile % 100 not in (70, 71, 73) and not in_f16:
+        if cin2k and self.wino is not None and split_tune_value(tile)[0] not in WINO_TILES and not in_f16:
             tile = 70      # (two sources: only the Winograd kernel reads them -- and, in fp16 storage, the patch-staged fp16 kernel below)
         thin_mf = (forced in (0, 72) and 'thinmf' not in DEFAULT_DISABLE and not out_f16 and not masked and self.thin_ok())
         if thin_mf and not in_f16:
@@ -455,10 +457,10 @@ class ConvPlan:
             # always (55 against 306 us).
             if forced == 72 or self.s_out == 2:
                 tile = 72   # thin output: the parity classes folded into the N dimension of a matrix-core tile (csrc/tapconv_thinmf.hip)
-        if tile % 100 in (70, 71, 73):   # Winograd form of a 3x3 / stride-1 layer (csrc/tapconv_wino.hip): fp32 storage, same-size output
-            # (tune values: 70 = the launcher's choice of N tile and K ranges, 71 = 64-wide N tile, 73 = 64-wide, four-wave workgroups; + 100 k = k K ranges, k = 1: none)
+        if split_tune_value(tile)[0] in WINO_TILES:   # Winograd form of a 3x3 / stride-1 layer (csrc/tapconv_wino.hip): fp32 storage, same-size output
+            # (tune values: 70 = the launcher's choice of N tile and K ranges, 71 = 64-wide N tile, 73 = 64-wide, four-wave workgroups; K ranges: split_tune_value)
             if self.wino is not None and WINOGRAD and not (in_f16 or out_f16) and (s.hout, s.wout) == (hin + 2 * self.wino_pad - 2, win + 2 * self.wino_pad - 2):
-                return _Choice(tile % 100, tile // 100, False, True)
+                return _Choice(*split_tune_value(tile), False, True)
             tile = 0 if forced else self._default_tile(m_all, winograd=False)
         h16p_cv = False
         if in_f16:    # fp16 activations: the h16 kernels, N tile by the GEMM's width
@@ -507,15 +509,16 @@ class ConvPlan:
                 # (the 256-row tiles 64 / 65 paid on the 64 x 64 3x3 layers, which the patch-staged kernel serves now; for what is
                 # left -- strided and folded layers -- 128 x 128 is as good or better: tools/lab/f16_tiles.py)
         elif out_f16:  # fp32 image in, fp16 activation out: any kernel built on the shared epilogue, without split-K
-            tile %= 100
+            tile = split_tune_value(tile)[0]
             # (the patch kernel's two-half form, Cout <= 64, is NOT preferred for VGG-16's first layer: measured on one box, VGG-16
             # PerC-AL fp16 storage 88.9 it/s with the layer on the register-staged bf16x6 tile against 86.4 on tile 38 -- 72 fp32 MFMAs
             # of 64 cycles per 64 pixels; tools/lab/body_masks_ab.sh, profiles/r05_body_masks_ab.txt)
             sc_ok = len(self.cls) == 1 and self.cin_p in (4, 8) and self.cout <= 64 and self.ntaps_total <= 9 and self.s_in <= 2
             if tile not in F16OUT_TILES or tile in H16_TILES:   # (the fp16 implicit-GEMM tiles need an fp16 input as well)
                 tile = 38 if (sc_ok and self.cout <= 32) else (18 if self.cout > 32 else 16)
-        # tune values >= 100 encode split-K: tile + 100 * ksplit (x6d tiles, one class, enough K-steps per split)
-        ksplit, tile = (tile // 100, tile % 100) if tile >= 100 else (1, tile)
+        # tune values >= 100 encode split-K (x6d tiles, one class, enough K-steps per split)
+        tile, ksplit = split_tune_value(tile)
+        ksplit = max(ksplit, 1)
         dks = 0     # (what the descriptor gets)
         if self.nfold > 1:  # only the DMA-staged kernels know the folded epilogue
             ksplit = 1
@@ -528,30 +531,30 @@ class ConvPlan:
                 ksplit, dks = 1, -1
         if in_f16 or out_f16:
             ksplit = 1
-            if (in_f16 and tile in (60, 61, 62, 63) and len(self.cls) == 1 and self.nfold == 1 and 'h16splitk' not in DEFAULT_DISABLE
+            if (in_f16 and tile in H16_SPLITK_BN and len(self.cls) == 1 and self.nfold == 1 and 'h16splitk' not in DEFAULT_DISABLE
                     and (forced == 0 or FORCE_KSPLIT)):
                 # skinny GEMMs of the fp16 path (VGG-16's fully connected layers at batch 64: ONE row tile, K = 25088; ResNet layer4):
                 # split K until the grid covers the chip about twice, at least eight 64-deep steps per split
-                bn = {60: 128, 61: 64, 62: 32, 63: 16}[tile]
+                bn = H16_SPLITK_BN[tile]
                 wgs = (m_all + 127) // 128 * ((self.cout + bn - 1) // bn)
                 nk = (self.cls[0]['K'] + 63) // 64
                 ksplit = FORCE_KSPLIT if FORCE_KSPLIT else max(1, min(16, 512 // max(wgs, 1), nk // 8))
         if ksplit > 1:
             nk = self.cls[0]['Kpad'] // BK
-            if len(self.cls) != 1 or nk < 2 * ksplit or (tile not in X6D_TILES and not (in_f16 and tile in (60, 61, 62, 63))) or self.cin_p % 32:
+            if len(self.cls) != 1 or nk < 2 * ksplit or (tile not in X6D_TILES and not (in_f16 and tile in H16_SPLITK_BN)) or self.cin_p % 32:
                 ksplit, tile = 1, (0 if forced else tile)
         if ksplit > 1:
             dks = ksplit
             # (sized here, the step's one side effect: a split that a reroute below drops again, or a launch that they refuse, has
             # grown the plan's workspace all the same -- as it always did)
             self._kws(ksplit * m_all * ((self.cout + 127) // 128 * 128), False)
-        if gate_mul and tile < 25:  # multiplicative gate: newer epilogues only
-            tile, dks = self._default_tile(m_all, winograd=False) % 100, 0
-            if tile < 25:
+        if gate_mul and tile not in GATE_MUL_TILES:  # multiplicative gate: newer epilogues only
+            tile, dks = split_tune_value(self._default_tile(m_all, winograd=False))[0], 0
+            if tile not in GATE_MUL_TILES:
                 raise ValueError('GATE_MUL needs a layer shape served by the DMA-staged kernels')
         if masked and tile not in STORE4_TILES:
             # byte masks live in the shared 4-channel epilogue (epilogue.hpp): thin / fp32-MFMA kernels do not have it
-            tile, dks = self._default_tile(m_all, winograd=False) % 100, 0
+            tile, dks = split_tune_value(self._default_tile(m_all, winograd=False))[0], 0
             if tile not in STORE4_TILES:
                 raise ValueError(f'{self.name}: gate masks need a layer shape served by the bf16x6 / smallcin kernels')
         if self.fixed_tile:
@@ -561,7 +564,7 @@ class ConvPlan:
         if cin2k:
             if in_f16 and self.nfold == 1:
                 tile, dks = 68, 0      # (fp16 storage: the patch-staged fp16 kernel's two-source form)
-            elif tile not in (70, 71, 73):
+            elif tile not in WINO_TILES:
                 raise ValueError(f'{self.name}: a two-source plan runs on the Winograd kernel (fp32 storage, same-size output) or the patch-staged fp16 kernel')
         elif has_inp2 and in_f16:
             # second source of a folded fp16 layer (attach_second_source_h16): the patch-staged fp16 kernel only
@@ -576,7 +579,7 @@ class ConvPlan:
         if has_pool_adjoint and tile != 72:
             raise ValueError(f'{self.name}: pool_adjoint is served by the thin-output matrix-core kernel only (tile 72; got {tile})')
         if tile == 74 and not (self.x6p_ok() and not (in_f16 or out_f16)):
-            tile = 0 if forced else self._default_tile(m_all, winograd=False) % 100
+            tile = 0 if forced else split_tune_value(self._default_tile(m_all, winograd=False))[0]
         return _Choice(tile, dks, h16p_cv, False)
 
     def _geometry(self, inp, b, hin, win, cs_in, in_coff, hout, wout, cs_out, out_coff):
@@ -655,7 +658,7 @@ class ConvPlan:
         d.tile = tile
         d.reserved0 = (DEBUG_TAPMAJOR | (DEBUG_PERSIST_CAP << 8) | (DEBUG_WINO << 16) | (DEBUG_H16_2STAGE << 25) | (DEBUG_SMALLCIN_NOSLAB << 26)
                        | (((DEBUG_THINMF & 7) << 27) if tile == 72 else 0)
-                       | (((DEBUG_WINO_NOCANVAS & 1) << 30 | (DEBUG_WINO_NOCANVAS >> 1 & 1) << 29 | {1: 0, 0: 1, 2: 2}[getattr(self, 'wino_pad', 1)] << 27) if tile in (70, 71, 73) else 0))  # measurement / test switches; bits 27-28 of a Winograd launch: its zero padding (1 / 0 / 2)
+                       | (((DEBUG_WINO_NOCANVAS & 1) << 30 | (DEBUG_WINO_NOCANVAS >> 1 & 1) << 29 | {1: 0, 0: 1, 2: 2}[getattr(self, 'wino_pad', 1)] << 27) if tile in WINO_TILES else 0))  # measurement / test switches; bits 27-28 of a Winograd launch: its zero padding (1 / 0 / 2)
         return d
 
     def _kws(self, need, fixup):
@@ -691,7 +694,7 @@ class ConvPlan:
         if ch.ksplit > 1:
             d.splitk_ws, d.ksplit = self._ws.data_ptr(), ch.ksplit     # (the workspace `_choose` has sized)
         wino_bn = 0
-        if tile in (70, 71, 73):
+        if tile in WINO_TILES:
             # the launcher's plan (csrc/tapconv_wino.hip: N tile, canvas layout for small images, K ranges for few workgroups with
             # long K) -- asked for here because the K ranges need a workspace; its K-range count is then passed back explicitly
             want = _wino[1] if _wino else getattr(self, 'wino_ksplit', 0)
@@ -707,7 +710,7 @@ class ConvPlan:
             d.ksplit = wp[1]
             d.reserved1 = (d.reserved1 & 8) | 4 | {64: 1, 128: 2}[wp[0]]
             self.last_h16p_plan = wp
-        if (tile in (70, 71, 73) or (tile == 68 and h16p_cv)) and d.ksplit > 1:
+        if (tile in WINO_TILES or (tile == 68 and h16p_cv)) and d.ksplit > 1:
             # (round 6, WINO_SPLITK_FIXUP: the K ranges meet inside the kernel -- the workspace with the arrival-counter header)
             d.splitk_ws = self._kws(d.ksplit * b * hout * wout * ((self.cout + 127) // 128 * 128), WINO_SPLITK_FIXUP)
             if WINO_SPLITK_FIXUP:
@@ -763,7 +766,7 @@ class ConvPlan:
             tid += 1000
         if d.tile == 70 and wino_bn == 64:   # the launcher's choice of the N tile: a kernel of its own for rocprofv3
             tid += 1
-        if d.tile in (70, 71, 73):           # ... and so are the canvas / K-range form (+ 1000) and the two-source form (+ 2000)
+        if d.tile in WINO_TILES:             # ... and so are the canvas / K-range form (+ 1000) and the two-source form (+ 2000)
             tid += 2000 if cin2k else (1000 if (self.last_wino_plan[2] or d.ksplit > 1) else 0)
         return tid
 

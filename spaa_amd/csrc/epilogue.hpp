@@ -40,6 +40,14 @@ struct io4<_Float16> {
     }
 };
 
+// May an epilogue take store4_t's 4-channel-vector path?  Every tensor it touches must keep channel quads 16-byte (fp16: 8-byte) aligned.
+__device__ __forceinline__ bool store4_vec_ok(const spaa_tapconv_t& p) {
+    return !((p.Cout | p.out_cstride | p.out_coff) & 3) &&
+           (p.add == nullptr || !((p.add_cstride | p.add_coff) & 3)) &&
+           (p.gate == nullptr || !((p.gate_cstride | p.gate_coff) & 3)) &&
+           (p.gate2 == nullptr || !((p.gate2_cstride | p.gate2_coff) & 3));
+}
+
 // fused epilogue for 4 consecutive output channels n0..n0+3 of output pixel o; T = storage type of out / add / gate /
 // aux_out / gate2 (bias is always fp32).  The mask bits and the value handed back in `v` are those of the STORED value.
 template <typename T>

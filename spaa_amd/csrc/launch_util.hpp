@@ -1,6 +1,13 @@
 // launch_util.hpp — host-side helpers shared by the launchers.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "../../include/spaa_hip.h"
+
+// Second pass of a K-split layer (tapconv_splitk.hip): adds the `d.ksplit` partial sums of `splitk_ws` [range][M rows][Npad] in fixed
+// order and applies the layer's epilogue; fp16 or fp32 output by `io_dtype`, one thread per 4 channels.  `class_map`: row m is pixel m of
+// class 0's grid (implicit-GEMM kernels), else output pixel m itself.  Enqueues only: the caller reads hipGetLastError.
+void spaa_launch_splitk_reduce(const spaa_tapconv_t& d, int64_t M, bool class_map, hipStream_t stream);
 
 namespace {
 

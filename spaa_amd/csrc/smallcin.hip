@@ -103,10 +103,7 @@ __global__ __launch_bounds__(256) void smallcin_kernel(const spaa_tapconv_t p, c
         const int tt = t < cl.ntaps ? t : 0;
         toff[t] = ((taps[2 * tt] - dymin) * PW + (taps[2 * tt + 1] - dxmin)) * PIXB;
     }
-    const bool vec = !((p.Cout | p.out_cstride | p.out_coff) & 3) &&
-                     (p.add == nullptr || !((p.add_cstride | p.add_coff) & 3)) &&
-                     (p.gate == nullptr || !((p.gate_cstride | p.gate_coff) & 3)) &&
-                     (p.gate2 == nullptr || !((p.gate2_cstride | p.gate2_coff) & 3));
+    const bool vec = store4_vec_ok(p);
     const int HWm = p.Hm * p.Wm;
     const int M = p.B * HWm;
 

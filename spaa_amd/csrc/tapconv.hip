@@ -18,6 +18,7 @@
 #include <stdint.h>
 #include "../../include/spaa_hip.h"
 #include "device_util.hpp"
+#include "tiles.hpp"
 
 int spaa_launch_tapconv_x6(const spaa_tapconv_t& d, int tile, hipStream_t stream);   // tapconv_x6.hip
 int spaa_launch_tapconv_x6d(const spaa_tapconv_t& d, int tile, hipStream_t stream);  // tapconv_x6d.hip
@@ -533,13 +534,25 @@ extern "C" int spaa_tapconv_offsetof(int field) {
     }
 }
 
-extern "C" int spaa_tapconv_f32(const spaa_tapconv_t* desc, spaa_stream_t stream_) {
+extern "C" int spaa_tapconv_tile_info(int tile, spaa_tile_info_t* out) {
+    const spaa_tiles::entry_t* e = spaa_tiles::find(tile);
+    if (e == nullptr || out == nullptr) return hipErrorInvalidValue;
+    *out = spaa_tile_info_t{e->id, e->family, e->bm, e->bn, e->caps, e->name};
+    return 0;
+}
+
+// host-side shape checks: a faulting kernel can take the whole node down.  What a tile may be asked for comes from its capability
+// bits (tiles.hpp); tile 0 (the heuristic below picks an fp32-MFMA tile) has none.
+extern "C" int spaa_tapconv_check(const spaa_tapconv_t* desc) {
     const spaa_tapconv_t& d = *desc;
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    // host-side shape checks: a faulting kernel can take the whole node down
+    const spaa_tiles::entry_t* te = spaa_tiles::find(d.tile);
+    const unsigned caps = te != nullptr ? te->caps : 0u;
+    const auto can = [caps](unsigned bits) { return (caps & bits) == bits; };
+    const bool in_f16 = d.io_dtype & SPAA_IO_IN_F16, out_f16 = d.io_dtype & SPAA_IO_OUT_F16;
     if (d.in == nullptr || d.out == nullptr || d.weights == nullptr || d.taps == nullptr) return hipErrorInvalidValue;
-    // (Winograd with two sources: the last Cin2 of the Cin input channels are read from `in2`)
-    const int cin_main = (d.in2 != nullptr && (d.tile == 70 || d.tile == 71 || d.tile == 73 || (d.tile == 68 && d.nfold <= 1))) ? d.Cin - d.Cin2 : d.Cin;
+    // (two sources over concatenated channels: the last Cin2 of the Cin input channels are read from `in2`; a folded launch's second
+    // source is a tensor at output resolution instead)
+    const int cin_main = (d.in2 != nullptr && can(SPAA_TILE_IN2_OF_CIN) && !(can(SPAA_TILE_NFOLD) && d.nfold > 1)) ? d.Cin - d.Cin2 : d.Cin;
     if (d.Cin <= 0 || (d.Cin & 3) || (d.in_cstride & 3) || (d.in_coff & 3) || cin_main <= 0 || d.in_coff + cin_main > d.in_cstride)
         return hipErrorInvalidValue;
     if (d.Cout <= 0 || d.out_coff + d.Cout > d.out_cstride) return hipErrorInvalidValue;
@@ -547,8 +560,7 @@ extern "C" int spaa_tapconv_f32(const spaa_tapconv_t* desc, spaa_stream_t stream
     if (d.mask_out != nullptr || d.gate_bits != nullptr || d.gate2_bits != nullptr) {
         // byte masks (1 byte per 4 channels): only the epilogues built on epilogue.hpp's store4 know them, and only in its
         // 4-channel-vector form
-        const int t = d.tile;
-        if (!((t >= 15 && t <= 27) || (t >= 30 && t <= 46) || (t >= 48 && t <= 54) || (t >= 60 && t <= 65) || t == 68 || t == 70 || t == 71 || t == 73 || t == 74 || t == 76)) return hipErrorInvalidValue;
+        if (!can(SPAA_TILE_BYTE_MASKS)) return hipErrorInvalidValue;
         if ((d.Cout | d.out_cstride | d.out_coff) & 3) return hipErrorInvalidValue;
         if (d.add != nullptr && ((d.add_cstride | d.add_coff) & 3)) return hipErrorInvalidValue;
         if (d.gate_bits != nullptr && (d.gate != nullptr || ((d.gate_cstride | d.gate_coff) & 3))) return hipErrorInvalidValue;
@@ -569,91 +581,54 @@ extern "C" int spaa_tapconv_f32(const spaa_tapconv_t* desc, spaa_stream_t stream
     if ((int64_t)d.B * d.Hin * d.Win * d.in_cstride * 4 >= (int64_t)1 << 31) return hipErrorInvalidValue;
     for (int c = 0; c < d.nclass; ++c)
         if ((int64_t)((d.Cout + 127) & ~127) * d.cls[c].Kpad * 4 >= (int64_t)1 << 31) return hipErrorInvalidValue;
+    if (d.in2 != nullptr && !can(SPAA_TILE_IN2)) return hipErrorInvalidValue;   // (second source: the patch-staged kernels and the Winograd kernel)
+    // fp16-storage mode: fp16 inputs only through the fp16 kernels; fp16 outputs only through the shared epilogue
+    if (in_f16 && !(can(SPAA_TILE_F16_IN) && !(can(SPAA_TILE_F16_IN_F32_OUT) && out_f16))) return hipErrorInvalidValue;
+    if (!in_f16 && can(SPAA_TILE_F16_IN_REQUIRED)) return hipErrorInvalidValue;
+    if (out_f16 && !can(SPAA_TILE_F16_OUT)) return hipErrorInvalidValue;
+    if (out_f16 && (d.ksplit < 0 || (d.ksplit > 1 && !can(SPAA_TILE_F16_OUT_KSPLIT)))) return hipErrorInvalidValue;  // (fp32 partial sums: only the fp16 kernels' own second passes write fp16)
+    if (d.gate != nullptr && d.gate_mode == SPAA_GATE_MUL && !can(SPAA_TILE_GATE_MUL)) return hipErrorInvalidValue;
+    if (d.nfold > 1 && !can(SPAA_TILE_NFOLD)) return hipErrorInvalidValue;
+    if (d.tile != 0 && te == nullptr) return hipErrorInvalidValue;   // (no such tile)
+    return 0;
+}
+
+extern "C" int spaa_tapconv_f32(const spaa_tapconv_t* desc, spaa_stream_t stream_) {
+    if (const int rc = spaa_tapconv_check(desc)) return rc;
+    const spaa_tapconv_t& d = *desc;
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
     int tile = d.tile;
-    if (d.in2 != nullptr && tile != 74 && tile != 68 && tile != 72 && tile != 70 && tile != 71 && tile != 73) return hipErrorInvalidValue;   // (second source: the patch-staged stride-2 kernels and the Winograd kernel)
-    // fp16-storage mode: fp16 inputs only through the h16 kernels; fp16 outputs only through the shared epilogue
-    if ((d.io_dtype & SPAA_IO_IN_F16) && !((tile >= 60 && tile <= 65) || tile == 68 || ((tile == 29 || tile == 72) && !(d.io_dtype & SPAA_IO_OUT_F16)))) return hipErrorInvalidValue;
-    if (!(d.io_dtype & SPAA_IO_IN_F16) && tile >= 60 && tile <= 63) return hipErrorInvalidValue;
-    if ((d.io_dtype & SPAA_IO_OUT_F16) && !((tile >= 15 && tile <= 24) || tile == 38 || (tile >= 60 && tile <= 65) || tile == 68 || tile == 76))
-        return hipErrorInvalidValue;
-    if ((d.io_dtype & SPAA_IO_OUT_F16) && (d.ksplit < 0 || (d.ksplit > 1 && !((tile >= 60 && tile <= 63) || tile == 68)))) return hipErrorInvalidValue;  // (fp32 partial sums: only the fp16 kernels' own second passes write fp16)
-    if (d.gate != nullptr && d.gate_mode == SPAA_GATE_MUL && tile < 25) return hipErrorInvalidValue;
-    if (d.nfold > 1 && !((tile >= 25 && tile <= 27) || (tile >= 30 && tile <= 37) || (tile >= 39 && tile <= 46) || (tile >= 48 && tile <= 54) || (tile >= 60 && tile <= 65) || tile == 68))
-        return hipErrorInvalidValue;
     if (tile == 0) {  // heuristic: widest N tile that fits Cout; shrink M when the grid would not fill 256 CUs twice
         const int64_t M = (int64_t)d.B * d.Hm * d.Wm * d.nclass;
         if (d.Cout > 64) tile = (M / 128) * ((d.Cout + 127) / 128) >= 512 ? 1 : 6;
         else if (d.Cout > 32) tile = (M / 128) >= 512 ? 4 : 6;
         else tile = 5;
     }
-    switch (tile) {
-        case 1: return launch<128, 128, 64, 64>(d, stream);
-        case 2: return launch<256, 64, 64, 64>(d, stream);
-        case 3: return launch<256, 32, 64, 32>(d, stream);
-        case 4: return launch<128, 64, 64, 32>(d, stream);
-        case 5: return launch<128, 32, 32, 32>(d, stream);
-        case 6: return launch<64, 64, 32, 32>(d, stream);
-        case 7: return launch<64, 128, 32, 64>(d, stream);
-        case 8: return launch<128, 64, 32, 64>(d, stream);
-        case 9: return launch_direct<4>(d, stream);
-        case 10: return launch_direct<32>(d, stream);
-        case 11: return launch_thin(d, stream);
-        case 12:
-        case 13:
-        case 14:
-        case 15:
-        case 16:
-        case 17:
-        case 18:
-        case 19:
-        case 20:
-        case 21:
-        case 22:
-        case 23:
-        case 24: return spaa_launch_tapconv_x6(d, tile, stream);
-        case 25:
-        case 26:
-        case 27: return spaa_launch_tapconv_x6d(d, tile, stream);
-        case 28:
-        case 29: return spaa_launch_thinpatch(d, stream);
-        case 30:
-        case 31:
-        case 32:
-        case 33:
-        case 34:
-        case 35:
-        case 36:
-        case 37: return spaa_launch_tapconv_x6d(d, tile, stream);
-        case 38: return spaa_launch_smallcin(d, stream);
-        case 39:
-        case 40:
-        case 41:
-        case 42:
-        case 43:
-        case 44:
-        case 45:
-        case 46: return spaa_launch_tapconv_x6d(d, tile, stream);
-        case 47: return spaa_launch_thinpatch(d, stream);
-        case 48:
-        case 49:
-        case 50:
-        case 51:
-        case 52:
-        case 53:
-        case 54: return spaa_launch_tapconv_x6d(d, tile, stream);
-        case 60:
-        case 61:
-        case 62:
-        case 63:
-        case 64:
-        case 65: return spaa_launch_tapconv_h16(d, tile, stream);
-        case 68: return spaa_launch_tapconv_h16p(d, stream);
-        case 70:
-        case 71:
-        case 73: return spaa_launch_tapconv_wino(d, stream);
-        case 72: return spaa_launch_tapconv_thinmf(d, stream);
-        case 74: return spaa_launch_tapconv_x6p(d, stream);
-        case 76: return spaa_launch_tapconv_c3(d, stream);
+    switch (spaa_tiles::find(tile)->family) {   // (the check has refused unknown ids)
+        case SPAA_FAM_F32:
+            switch (tile) {
+                case 1: return launch<128, 128, 64, 64>(d, stream);
+                case 2: return launch<256, 64, 64, 64>(d, stream);
+                case 3: return launch<256, 32, 64, 32>(d, stream);
+                case 4: return launch<128, 64, 64, 32>(d, stream);
+                case 5: return launch<128, 32, 32, 32>(d, stream);
+                case 6: return launch<64, 64, 32, 32>(d, stream);
+                case 7: return launch<64, 128, 32, 64>(d, stream);
+                case 8: return launch<128, 64, 32, 64>(d, stream);
+                default: return hipErrorInvalidValue;
+            }
+        case SPAA_FAM_DIRECT: return tile == 9 ? launch_direct<4>(d, stream) : launch_direct<32>(d, stream);
+        case SPAA_FAM_THIN: return launch_thin(d, stream);
+        case SPAA_FAM_X6: return spaa_launch_tapconv_x6(d, tile, stream);
+        case SPAA_FAM_X6D: return spaa_launch_tapconv_x6d(d, tile, stream);
+        case SPAA_FAM_THINPATCH: return spaa_launch_thinpatch(d, stream);
+        case SPAA_FAM_SMALLCIN: return spaa_launch_smallcin(d, stream);
+        case SPAA_FAM_H16: return spaa_launch_tapconv_h16(d, tile, stream);
+        case SPAA_FAM_H16P: return spaa_launch_tapconv_h16p(d, stream);
+        case SPAA_FAM_WINO: return spaa_launch_tapconv_wino(d, stream);
+        case SPAA_FAM_THINMF: return spaa_launch_tapconv_thinmf(d, stream);
+        case SPAA_FAM_X6P: return spaa_launch_tapconv_x6p(d, stream);
+        case SPAA_FAM_C3: return spaa_launch_tapconv_c3(d, stream);
         default: return hipErrorInvalidValue;
     }
 }

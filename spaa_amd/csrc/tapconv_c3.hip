@@ -133,8 +133,7 @@ __global__ __launch_bounds__(512, 4) void c3conv_tile_kernel(const spaa_tapconv_
     // ---- epilogue.  D layout of a 16 x 16 block: column (lane & 15) = pixel, rows 4 (lane >> 4) + e = 4 consecutive channels.  Through a
     // wave-private LDS region (free once every wave has left the K loop): a lane then owns 4 channels of a pixel and BN / 4 consecutive
     // lanes its whole channel row (tapconv_h16p.hip)
-    const bool vec = !((p.Cout | p.out_cstride | p.out_coff) & 3) && (p.add == nullptr || !((p.add_cstride | p.add_coff) & 3)) &&
-                     (p.gate == nullptr || !((p.gate_cstride | p.gate_coff) & 3)) && (p.gate2 == nullptr || !((p.gate2_cstride | p.gate2_coff) & 3));
+    const bool vec = store4_vec_ok(p);
     constexpr int ROWB = BN * 4 + 16;
     constexpr int LPP = BN / 4, PPI = 64 / LPP;
     __syncthreads();
@@ -255,8 +254,7 @@ __global__ __launch_bounds__(512, 2) void c3conv_kernel(const spaa_tapconv_t p, 
 #pragma unroll
     for (int b = 0; b < 4; ++b) pbase[b] = (((2 * wave + (b >> 1)) * S) * PW + (16 * (b & 1) + (lane & 15)) * S) * 16;
     const int w_addr_l = (lane & 15) * 64 + ((kq ^ swz_w16(lane & 15)) << 4);
-    const bool vec = !((p.Cout | p.out_cstride | p.out_coff) & 3) && (p.add == nullptr || !((p.add_cstride | p.add_coff) & 3)) &&
-                     (p.gate == nullptr || !((p.gate_cstride | p.gate_coff) & 3)) && (p.gate2 == nullptr || !((p.gate2_cstride | p.gate2_coff) & 3));
+    const bool vec = store4_vec_ok(p);
     constexpr int LPP = BN / 4, PPI = 64 / LPP;
     const int ch = 4 * (lane % LPP);
     const bool fast = fast_epi_ok(p, vec);

@@ -115,7 +115,7 @@ __global__ __launch_bounds__(64 * NW, (NW > 4 || NS > 2) ? 1 : 2) void tapconv_h
     const int nsub = cl.K / 32;          // real sub-steps
     const int nk_all = (nsub + 1) >> 1;  // K-steps (the last one may hold a single real sub-step)
     // split-K (p.ksplit > 1: skinny GEMMs -- few pixels, long K: the fully connected layers of VGG-16 at batch 64, ResNet layer4):
-    // grid.z workgroups take equal ranges of the K-steps and write raw fp32 partial sums; h16_splitk_reduce_kernel adds them in
+    // grid.z workgroups take equal ranges of the K-steps and write raw fp32 partial sums; splitk_reduce_kernel (tapconv_splitk.hip) adds them in
     // fixed order and applies the epilogue
     const int ksp = p.ksplit > 1 ? p.ksplit : 1;
     const int ks0 = (int)((int64_t)nk_all * blockIdx.z / ksp), ks1 = (int)((int64_t)nk_all * (blockIdx.z + 1) / ksp);
@@ -223,10 +223,7 @@ __global__ __launch_bounds__(64 * NW, (NW > 4 || NS > 2) ? 1 : 2) void tapconv_h
     }
 
     // ---- epilogue.  D layout of a 16x16 tile: column (lane & 15) = pixel, rows 4*(lane>>4) + i = 4 consecutive channels
-    const bool vec = !((p.Cout | p.out_cstride | p.out_coff) & 3) &&
-                     (p.add == nullptr || !((p.add_cstride | p.add_coff) & 3)) &&
-                     (p.gate == nullptr || !((p.gate_cstride | p.gate_coff) & 3)) &&
-                     (p.gate2 == nullptr || !((p.gate2_cstride | p.gate2_coff) & 3));
+    const bool vec = store4_vec_ok(p);
 #define H16_EPI_IB(T, ib)                                                                                          \
     {                                                                                                              \
         const int m = m_blk + 32 * wave + 16 * (ib) + (lane & 15);                                                 \
@@ -290,25 +287,6 @@ __global__ __launch_bounds__(64 * NW, (NW > 4 || NS > 2) ? 1 : 2) void tapconv_h
 #undef H16_EPI_IB
 }
 
-// second pass of split-K: out = epilogue( sum over the splits, in fixed order ), 4 channels per thread
-template <typename T>
-__global__ __launch_bounds__(256) void h16_splitk_reduce_kernel(const spaa_tapconv_t p, const int M, const int npad) {
-    const int nq = (p.Cout + 3) >> 2;
-    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= (int64_t)M * nq) return;
-    const int m = (int)(idx / nq), n0 = (int)(idx - (int64_t)m * nq) * 4;
-    f32x4 sum = {0.f, 0.f, 0.f, 0.f};
-    for (int s = 0; s < p.ksplit; ++s) sum += *reinterpret_cast<const f32x4*>(p.splitk_ws + ((size_t)s * M + m) * npad + n0);
-    size_t o;
-    if (!out_pixel(p, p.cls[0], m, M, p.Hm * p.Wm, o)) return;
-    const bool vec = !((p.Cout | p.out_cstride | p.out_coff) & 3) &&
-                     (p.add == nullptr || !((p.add_cstride | p.add_coff) & 3)) &&
-                     (p.gate == nullptr || !((p.gate_cstride | p.gate_coff) & 3)) &&
-                     (p.gate2 == nullptr || !((p.gate2_cstride | p.gate2_coff) & 3));
-    float v[4] = {sum[0], sum[1], sum[2], sum[3]};
-    store4_t<T>(p, o, n0, v, vec);
-}
-
 template <int NW, int BN, int NS = 2>
 int launch_h16(const spaa_tapconv_t& d, hipStream_t stream) {
     constexpr int BM = 32 * NW;
@@ -334,14 +312,7 @@ int launch_h16(const spaa_tapconv_t& d, hipStream_t stream) {
     if (ksp > 1 && (d.nclass != 1 || nfold > 1 || d.splitk_ws == nullptr)) return hipErrorInvalidValue;
     dim3 grid(m_tiles * n_tiles, d.nclass, ksp);
     hipLaunchKernelGGL((tapconv_h16_kernel<NW, BN, NS>), grid, dim3(64 * NW), smem, stream, d, m_tiles, n_tiles);
-    if (ksp > 1) {
-        const int npad = (d.Cout + 127) & ~127;
-        const int64_t nthr = M * ((d.Cout + 3) >> 2);
-        if (d.io_dtype & SPAA_IO_OUT_F16)
-            hipLaunchKernelGGL(h16_splitk_reduce_kernel<_Float16>, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, stream, d, (int)M, npad);
-        else
-            hipLaunchKernelGGL(h16_splitk_reduce_kernel<float>, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, stream, d, (int)M, npad);
-    }
+    if (ksp > 1) spaa_launch_splitk_reduce(d, M, true, stream);
     return (int)hipGetLastError();
 }
 

@@ -48,7 +48,7 @@ template <int S> struct h16p_geo {
 // region empty and too few workgroups for 256 compute units, and ran on the implicit-GEMM fp16 kernel at 270-580 TFLOP/s.  The images of
 // the batch lie on virtual canvases (gy x gx images with periods (H + 1, W + 1): the gap row / column is the zero padding of both
 // neighbours), the regions tile the CANVAS; `ks` of `ksplit` K ranges computes channel blocks [ks * kb_per, ...) into the fp32 workspace
-// [range][pixel][Npad], h16p_splitk_reduce_kernel adds the ranges in fixed order and applies the layer's epilogue.
+// [range][pixel][Npad], splitk_reduce_kernel (tapconv_splitk.hip) adds the ranges in fixed order and applies the layer's epilogue.
 struct h16p_cv_t {
     int ksplit, kb_per;        // K ranges (1 = off) and 32-channel blocks per range
     int gy, gx, py, px;        // canvas: images per canvas (rows x columns) and their periods in pixels
@@ -56,7 +56,7 @@ struct h16p_cv_t {
     int nsp;                   // workgroup regions of all canvases together
     int order;                 // 1: regions fastest in the workgroup order (an XCD shares one weight slice), 0: N tiles / K ranges fastest
     int fix;                   // K ranges: 1 = the last-arriving workgroup of a (region, N tile) adds the partial sums and applies the epilogue
-                               // itself (arrival counters at the head of the workspace), 0 = h16p_splitk_reduce_kernel does
+                               // itself (arrival counters at the head of the workspace), 0 = splitk_reduce_kernel does
 };
 
 // LEAN (round 5; S = 1, 64-wide N tile): TWO workgroups per compute unit -- one patch buffer (reloaded per 32-channel block behind a barrier,
@@ -416,10 +416,7 @@ __global__ __launch_bounds__(512, LEAN ? 4 : 1) void h16p_kernel(const spaa_tapc
         }
     }
     const spaa_tapconv_t& e = CV ? pq : p;
-    const bool vec = !((e.Cout | e.out_cstride | e.out_coff) & 3) &&
-                     (e.add == nullptr || !((e.add_cstride | e.add_coff) & 3)) &&
-                     (e.gate == nullptr || !((e.gate_cstride | e.gate_coff) & 3)) &&
-                     (e.gate2 == nullptr || !((e.gate2_cstride | e.gate2_coff) & 3));
+    const bool vec = store4_vec_ok(e);
     // through LDS (a private region per wave, free once every wave has left the K loop): a lane then owns 4 channels of a pixel
     // and BN / 4 consecutive lanes its whole channel row -- 256-byte (fp16) / 512-byte (fp32) contiguous segments per pixel for
     // the output and for every epilogue operand, instead of the MFMA layout's 16 pixels x 32 bytes per instruction
@@ -603,10 +600,7 @@ __global__ __launch_bounds__(512, LEAN ? 4 : 1) void h16p_kernel(const spaa_tapc
             if (*flag == 0) return;
             const int M = p.B * H * W, npad = (p.Cout + 127) & ~127;
             const auto rws = rsrc_or_empty(p.splitk_ws + SPAA_SPLITK_HDR_FLOATS, (int64_t)geo.ksplit * M * npad * 4);
-            const bool pvec = !((p.Cout | p.out_cstride | p.out_coff) & 3) &&
-                              (p.add == nullptr || !((p.add_cstride | p.add_coff) & 3)) &&
-                              (p.gate == nullptr || !((p.gate_cstride | p.gate_coff) & 3)) &&
-                              (p.gate2 == nullptr || !((p.gate2_cstride | p.gate2_coff) & 3));
+            const bool pvec = store4_vec_ok(p);
             for (int i = tid; i < OH * OW * LPP; i += 512) {
                 const int qd = i % LPP, pxl = i / LPP;
                 const int n0 = n_blk + 4 * qd;
@@ -623,23 +617,6 @@ __global__ __launch_bounds__(512, LEAN ? 4 : 1) void h16p_kernel(const spaa_tapc
             }
         }
     }
-}
-
-// second pass of a K-split layer: out = epilogue( sum over the K ranges, in fixed order ), 4 channels per thread
-template <typename T>
-__global__ __launch_bounds__(256) void h16p_splitk_reduce_kernel(const spaa_tapconv_t p, const int M, const int npad) {
-    const int nq = (p.Cout + 3) >> 2;
-    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= (int64_t)M * nq) return;
-    const int m = (int)(idx / nq), n0 = (int)(idx - (int64_t)m * nq) * 4;
-    f32x4 sum = {0.f, 0.f, 0.f, 0.f};
-    for (int s = 0; s < p.ksplit; ++s) sum += *reinterpret_cast<const f32x4*>(p.splitk_ws + ((size_t)s * M + m) * npad + n0);
-    const bool vec = !((p.Cout | p.out_cstride | p.out_coff) & 3) &&
-                     (p.add == nullptr || !((p.add_cstride | p.add_coff) & 3)) &&
-                     (p.gate == nullptr || !((p.gate_cstride | p.gate_coff) & 3)) &&
-                     (p.gate2 == nullptr || !((p.gate2_cstride | p.gate2_coff) & 3));
-    float v[4] = {sum[0], sum[1], sum[2], sum[3]};
-    store4_t<T>(p, (size_t)m, n0, v, vec);
 }
 
 // ---- launch plan of the canvas / K-range form: N tile, canvas layout, K ranges (one decision for the launcher and for
@@ -828,14 +805,7 @@ int spaa_launch_tapconv_h16p(const spaa_tapconv_t& d, hipStream_t stream) {
     }
         if (pl.bn == 64) H16P_LAUNCH_CV(64, 4) else H16P_LAUNCH_CV(128, 5)
 #undef H16P_LAUNCH_CV
-        if (pl.ksplit > 1 && !geo.fix) {
-            const int npad = (d.Cout + 127) & ~127;
-            const int64_t M = (int64_t)d.B * d.Hout * d.Wout, nthr = M * ((d.Cout + 3) >> 2);
-            if (d.io_dtype & SPAA_IO_OUT_F16)
-                hipLaunchKernelGGL(h16p_splitk_reduce_kernel<_Float16>, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, stream, dd, (int)M, npad);
-            else
-                hipLaunchKernelGGL(h16p_splitk_reduce_kernel<float>, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, stream, dd, (int)M, npad);
-        }
+        if (pl.ksplit > 1 && !geo.fix) spaa_launch_splitk_reduce(dd, (int64_t)d.B * d.Hout * d.Wout, false, stream);
         return (int)hipGetLastError();
     }
     if (d.ksplit > 1) return hipErrorInvalidValue;

@@ -270,10 +270,7 @@ __global__ __launch_bounds__(512, PDB ? 1 : 2) void thinmf_kernel(const spaa_tap
         }
         return;
     }
-    const bool vec = !((p.Cout | p.out_cstride | p.out_coff) & 3) &&
-                     (p.add == nullptr || !((p.add_cstride | p.add_coff) & 3)) &&
-                     (p.gate == nullptr || !((p.gate_cstride | p.gate_coff) & 3)) &&
-                     (p.gate2 == nullptr || !((p.gate2_cstride | p.gate2_coff) & 3));
+    const bool vec = store4_vec_ok(p);
 #pragma unroll
     for (int r = 0; r < RW; ++r) {
         const int yg = y0 + RW * wrow + r, oy = S * yg + cy;

@@ -60,7 +60,7 @@ __device__ __forceinline__ void wg_barrier() {
 // the CANVAS: Winograd tiles that straddle a gap compute a discarded output next to a real one, nothing else changes (the patch
 // DMA maps a canvas pixel to (image, y, x) or to the out-of-range offset, the epilogue maps it back).  Few workgroups with long K
 // (layer4: 8 regions x 4 N tiles, 16 channel blocks) are cut along K: split ks computes channel blocks [ks * kb_per, ...) into
-// the fp32 workspace [split][pixel][Npad], wino_splitk_reduce_kernel adds the splits in fixed order and applies the epilogue.
+// the fp32 workspace [split][pixel][Npad], splitk_reduce_kernel (tapconv_splitk.hip) adds the splits in fixed order and applies the epilogue.
 struct wino_geo_t {
     int ksplit, kb_per;        // K ranges (1 = off) and 32-channel blocks per range
     int gy, gx, py, px;        // canvas: images per canvas (rows x columns) and their periods in pixels
@@ -68,7 +68,7 @@ struct wino_geo_t {
     int nsp;                   // workgroup regions of all canvases together
     int order;                 // 1: regions fastest in the workgroup order, 0: N tiles fastest (as in the image-aligned form)
     int fix;                   // K ranges: 1 = the last-arriving workgroup of a (region, N tile) sums the partial sums and applies the
-                               // epilogue itself (arrival counters at the head of the workspace), 0 = wino_splitk_reduce_kernel does
+                               // epilogue itself (arrival counters at the head of the workspace), 0 = splitk_reduce_kernel does
 };
 
 // TWO: the layer's input channels come from TWO tensors of the same B x H x W (channel blocks [0, Cin - Cin2) from `in`, the rest from
@@ -424,10 +424,7 @@ __global__ __launch_bounds__(64 * NWT, NWT == 4 ? 2 : 1) void wino_x6_kernel(con
         }
     }
     const spaa_tapconv_t& e = CV ? pq : p;
-    const bool vec = !((e.Cout | e.out_cstride | e.out_coff) & 3) &&
-                     (e.add == nullptr || !((e.add_cstride | e.add_coff) & 3)) &&
-                     (e.gate == nullptr || !((e.gate_cstride | e.gate_coff) & 3)) &&
-                     (e.gate2 == nullptr || !((e.gate2_cstride | e.gate2_coff) & 3));
+    const bool vec = store4_vec_ok(e);
     if constexpr (DBG & 1) {
 #pragma unroll
         for (int i = 0; i < 4; ++i)
@@ -461,10 +458,7 @@ __global__ __launch_bounds__(64 * NWT, NWT == 4 ? 2 : 1) void wino_x6_kernel(con
             if (*flag == 0) return;
             const int M = p.B * H * W;
             const auto rws = rsrc_or_empty(p.splitk_ws + SPAA_SPLITK_HDR_FLOATS, (int64_t)geo.ksplit * M * npad * 4);
-            const bool pvec = !((p.Cout | p.out_cstride | p.out_coff) & 3) &&
-                              (p.add == nullptr || !((p.add_cstride | p.add_coff) & 3)) &&
-                              (p.gate == nullptr || !((p.gate_cstride | p.gate_coff) & 3)) &&
-                              (p.gate2 == nullptr || !((p.gate2_cstride | p.gate2_coff) & 3));
+            const bool pvec = store4_vec_ok(p);
             for (int i = tid; i < 2 * TY * 32 * LPP; i += 64 * NW) {
                 const int qd = i & (LPP - 1), pxl = i / LPP;
                 const int n0 = n_blk + 4 * qd;
@@ -575,22 +569,6 @@ __global__ __launch_bounds__(64 * NWT, NWT == 4 ? 2 : 1) void wino_x6_kernel(con
         }
     }
     splitk_fixup();
-}
-
-// second pass of a K-split layer: out = epilogue( sum over the splits, in fixed order ), 4 channels per thread
-__global__ __launch_bounds__(256) void wino_splitk_reduce_kernel(const spaa_tapconv_t p, const int M, const int npad) {
-    const int nq = (p.Cout + 3) >> 2;
-    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= (int64_t)M * nq) return;
-    const int m = (int)(idx / nq), n0 = (int)(idx - (int64_t)m * nq) * 4;
-    f32x4 sum = {0.f, 0.f, 0.f, 0.f};
-    for (int s = 0; s < p.ksplit; ++s) sum += *reinterpret_cast<const f32x4*>(p.splitk_ws + ((size_t)s * M + m) * npad + n0);
-    const bool vec = !((p.Cout | p.out_cstride | p.out_coff) & 3) &&
-                     (p.add == nullptr || !((p.add_cstride | p.add_coff) & 3)) &&
-                     (p.gate == nullptr || !((p.gate_cstride | p.gate_coff) & 3)) &&
-                     (p.gate2 == nullptr || !((p.gate2_cstride | p.gate2_coff) & 3));
-    float v[4] = {sum[0], sum[1], sum[2], sum[3]};
-    store4_t<float>(p, (size_t)m, n0, v, vec);
 }
 
 // ---- launch plan: N tile, canvas layout, K split (one decision for the launcher and for spaa_tapconv_wino_plan)
@@ -806,11 +784,7 @@ int spaa_launch_tapconv_wino(const spaa_tapconv_t& d, hipStream_t stream) {
             hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(&wino_x6_kernel<64, 2, 0, true, false, 4>), (int)smem, attr_set[14]);
             if (e != hipSuccess) return (int)e;
             hipLaunchKernelGGL((wino_x6_kernel<64, 2, 0, true, false, 4>), dim3((unsigned)nwg), dim3(256), smem, stream, dd, wg_y, wg_x, n_tiles, geo);
-            if (pl.ksplit > 1 && !geo.fix) {
-                const int npad = (d.Cout + 127) & ~127;
-                const int64_t M = (int64_t)d.B * d.Hout * d.Wout, nthr = M * ((d.Cout + 3) >> 2);
-                hipLaunchKernelGGL(wino_splitk_reduce_kernel, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, stream, dd, (int)M, npad);
-            }
+            if (pl.ksplit > 1 && !geo.fix) spaa_launch_splitk_reduce(dd, (int64_t)d.B * d.Hout * d.Wout, false, stream);
         } else {
             hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(&wino_x6_kernel<64, 2, 0, false, false, 4>), (int)smem, attr_set[12]);
             if (e != hipSuccess) return (int)e;
@@ -820,11 +794,7 @@ int spaa_launch_tapconv_wino(const spaa_tapconv_t& d, hipStream_t stream) {
         if (BN == 64) WINO_LAUNCH_T2(64, 2, 10) else WINO_LAUNCH_T2(128, 3, 11)
     } else if (cv) {   // canvas / K-split form: the default variants only
         if (BN == 64) WINO_LAUNCH_T(64, 2, true, 8) else WINO_LAUNCH_T(128, 3, true, 9)
-        if (pl.ksplit > 1 && !geo.fix) {
-            const int npad = (d.Cout + 127) & ~127;
-            const int64_t M = (int64_t)d.B * d.Hout * d.Wout, nthr = M * ((d.Cout + 3) >> 2);
-            hipLaunchKernelGGL(wino_splitk_reduce_kernel, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, stream, dd, (int)M, npad);
-        }
+        if (pl.ksplit > 1 && !geo.fix) spaa_launch_splitk_reduce(dd, (int64_t)d.B * d.Hout * d.Wout, false, stream);
     } else if (BN == 64) {
         if (var == 3) WINO_LAUNCH(64, 3, 4) else if (var == 2) WINO_LAUNCH(64, 2, 5) else if (var == 1) WINO_LAUNCH(64, 1, 6) else WINO_LAUNCH(64, 0, 7)
     } else if (var == 3) WINO_LAUNCH(128, 3, 3) else if (var == 2) WINO_LAUNCH(128, 2, 2) else if (var == 1) WINO_LAUNCH(128, 1, 1) else WINO_LAUNCH(128, 0, 0)

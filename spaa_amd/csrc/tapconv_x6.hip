@@ -455,10 +455,7 @@ __global__ __launch_bounds__(256, 2) void tapconv_x6v2_kernel(const spaa_tapconv
     // ---- epilogue.  D layout of the 32x32 tile: column (lane & 31) = pixel, row (r&3) + 8*(r>>2) + 4*(lane>>5) =
     // output channel: registers 4g..4g+3 of a lane are 4 consecutive channels of its pixel.
     const bool linear = (p.s_out == 1) && (cl.oy0 == 0) && (cl.ox0 == 0) && (p.Hm == p.Hout) && (p.Wm == p.Wout);
-    const bool vec = !((p.Cout | p.out_cstride | p.out_coff) & 3) &&
-                     (p.add == nullptr || !((p.add_cstride | p.add_coff) & 3)) &&
-                     (p.gate == nullptr || !((p.gate_cstride | p.gate_coff) & 3)) &&
-                     (p.gate2 == nullptr || !((p.gate2_cstride | p.gate2_coff) & 3));
+    const bool vec = store4_vec_ok(p);
     if (fast_epi_ok(p, vec)) {   // branch-free operand accesses, a pixel's four channel quads in flight (epilogue.hpp: fast_epi_*)
         const fast_epi_t fe = make_fast_epi(p, 0);
 #define V2_FAST(T)                                                                                                         \
@@ -741,10 +738,7 @@ __global__ __launch_bounds__(256, 2) void tapconv_x6v3_kernel(const spaa_tapconv
     // ---- epilogue.  D layout of the 32x32 tile: column (lane & 31) = pixel, row (r&3) + 8*(r>>2) + 4*(lane>>5) =
     // output channel: registers 4g..4g+3 of a lane are 4 consecutive channels of its pixel.
     const bool linear = (p.s_out == 1) && (cl.oy0 == 0) && (cl.ox0 == 0) && (p.Hm == p.Hout) && (p.Wm == p.Wout);
-    const bool vec = !((p.Cout | p.out_cstride | p.out_coff) & 3) &&
-                     (p.add == nullptr || !((p.add_cstride | p.add_coff) & 3)) &&
-                     (p.gate == nullptr || !((p.gate_cstride | p.gate_coff) & 3)) &&
-                     (p.gate2 == nullptr || !((p.gate2_cstride | p.gate2_coff) & 3));
+    const bool vec = store4_vec_ok(p);
     if (fast_epi_ok(p, vec)) {   // branch-free operand accesses, a pixel's four channel quads in flight (epilogue.hpp: fast_epi_*)
         const fast_epi_t fe = make_fast_epi(p, 0);
 #define V2_FAST(T)                                                                                                         \

@@ -204,10 +204,7 @@ __global__ __launch_bounds__(64 * NW, 2) void tapconv_x6d_kernel(const spaa_tapc
             }                                                                                                      \
     }
 
-    const bool vec = !((p.Cout | p.out_cstride | p.out_coff) & 3) &&
-                     (p.add == nullptr || !((p.add_cstride | p.add_coff) & 3)) &&
-                     (p.gate == nullptr || !((p.gate_cstride | p.gate_coff) & 3)) &&
-                     (p.gate2 == nullptr || !((p.gate2_cstride | p.gate2_coff) & 3));
+    const bool vec = store4_vec_ok(p);
 
     // fragment read addresses (bytes inside a stage).  Pixels: a lane holds 2 x 8 fp32 of its pixel(s) per K-step.
     int p_addr[2][2];
@@ -455,7 +452,7 @@ __global__ __launch_bounds__(64 * NW, 2) void tapconv_x6d_kernel(const spaa_tapc
         }
 
     if (p.ksplit > 1) {
-        // split-K: raw partial sums to the workspace [split][M][Npad]; splitk_reduce_kernel finishes the layer
+        // split-K: raw partial sums to the workspace [split][M][Npad]; splitk_reduce_kernel (tapconv_splitk.hip) finishes the layer
         float* ws = p.splitk_ws + (size_t)blockIdx.z * M * npad;
         if constexpr (SH == 32) {
             const int m = m_blk_e + 32 * wave + (lane & 31);
@@ -673,25 +670,6 @@ __global__ __launch_bounds__(64 * NW, 2) void tapconv_x6d_kernel(const spaa_tapc
 #undef X6D_MFMA6
 }
 
-// second pass of split-K: out = epilogue( sum over splits, in fixed order ), 4 channels per thread
-__global__ __launch_bounds__(256) void splitk_reduce_kernel(const spaa_tapconv_t p, const int M, const int npad) {
-    const int nq = (p.Cout + 3) >> 2;
-    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= (int64_t)M * nq) return;
-    const int m = (int)(idx / nq), n0 = (int)(idx - (int64_t)m * nq) * 4;
-    const spaa_tapclass_t cl = p.cls[0];
-    f4 sum = {0.f, 0.f, 0.f, 0.f};
-    for (int s = 0; s < p.ksplit; ++s) sum += *reinterpret_cast<const f4*>(p.splitk_ws + ((size_t)s * M + m) * npad + n0);
-    size_t o;
-    if (!out_pixel(p, cl, m, M, p.Hm * p.Wm, o)) return;
-    const bool vec = !((p.Cout | p.out_cstride | p.out_coff) & 3) &&
-                     (p.add == nullptr || !((p.add_cstride | p.add_coff) & 3)) &&
-                     (p.gate == nullptr || !((p.gate_cstride | p.gate_coff) & 3)) &&
-                     (p.gate2 == nullptr || !((p.gate2_cstride | p.gate2_coff) & 3));
-    float v[4] = {sum.x, sum.y, sum.z, sum.w};
-    store4_t<float>(p, o, n0, v, vec);
-}
-
 // second pass of stream-K: tiles that were cut into segments are summed in segment order and finished.  Workgroup s
 // of XCD x owns iterations [s*T/G, (s+1)*T/G) of that XCD's q_x*nk iterations; iteration I belongs to workgroup
 // ceil((I+1)*G/T) - 1.
@@ -722,10 +700,7 @@ __global__ __launch_bounds__(256) void streamk_reduce_kernel(const spaa_tapconv_
     const int M = p.B * p.Hm * p.Wm;
     size_t o;
     if (!out_pixel(p, cl, m, M, p.Hm * p.Wm, o)) return;
-    const bool vec = !((p.Cout | p.out_cstride | p.out_coff) & 3) &&
-                     (p.add == nullptr || !((p.add_cstride | p.add_coff) & 3)) &&
-                     (p.gate == nullptr || !((p.gate_cstride | p.gate_coff) & 3)) &&
-                     (p.gate2 == nullptr || !((p.gate2_cstride | p.gate2_coff) & 3));
+    const bool vec = store4_vec_ok(p);
     float v[4] = {sum.x, sum.y, sum.z, sum.w};
     store4_t<float>(p, o, n0, v, vec);
 }
@@ -778,11 +753,7 @@ int launch_x6d(const spaa_tapconv_t& d, hipStream_t stream, bool persistent = fa
         hipLaunchKernelGGL((streamk_reduce_kernel<BM, BN>), rgrid, dim3(256), 0, stream, d, m_tiles, n_tiles, gx,
                            d.cls[0].Kpad / BK);
     }
-    if (ksplit > 1) {
-        const int npad = (d.Cout + 127) & ~127;
-        const int64_t nthr = M * ((d.Cout + 3) >> 2);
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, stream, d, (int)M, npad);
-    }
+    if (ksplit > 1) spaa_launch_splitk_reduce(d, M, true, stream);
     return (int)hipGetLastError();
 }
 

@@ -390,10 +390,7 @@ __global__ __launch_bounds__(64 * NW, 2) void x6p_kernel(const spaa_tapconv_t p,
     // channels.  Through a wave-private LDS region in OUTPUT-pixel order: pass (cy, b) = output row 2 y + cy, output pixels
     // 2 (ox0 + 16 b) .. + 31 (the classes (cy, 0) and (cy, 1) interleaved): a store instruction writes whole BN-channel rows of
     // consecutive pixels
-    const bool vec = !((p.Cout | p.out_cstride | p.out_coff) & 3) &&
-                     (p.add == nullptr || !((p.add_cstride | p.add_coff) & 3)) &&
-                     (p.gate == nullptr || !((p.gate_cstride | p.gate_coff) & 3)) &&
-                     (p.gate2 == nullptr || !((p.gate2_cstride | p.gate2_coff) & 3));
+    const bool vec = store4_vec_ok(p);
     constexpr int ROWB = BN * 4 + 16;                  // (+16: the 16 pixels of a fragment write to distinct banks)
     constexpr int LPP = BN / 4, PPI = 64 / LPP;        // lanes per pixel, pixels per instruction
 #ifdef SPAA_X6P_STAMP

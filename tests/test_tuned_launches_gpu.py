@@ -45,8 +45,7 @@ CONFIGS = [('resnet18', 'f32', 'spaa'), ('resnet18', 'f16', 'spaa'), ('inception
            ('vgg16', 'f16', 'perc_al'), ('vgg16', 'f32', 'perc_al')]
 # VGG-16's full head (25088 -> 4096 -> 4096 -> 1000) at batch 64: the tune keys of its fully connected layers
 VGG_HEAD_KEYS = ('25088_4096_1_1_1_64', '4096_4096_1_1_1_64', '4096_25088_1_1_1_64')
-WINO_TILES = (70, 71, 73)
-X6_TILES = set(range(12, 55)) | {72, 74, 76}
+WINO_TILES, X6_TILES = cp.WINO_TILES, cp.X6_TILES      # (derived from the tile table: spaa_amd/tiles.py)
 
 
 def family(tile, in_f16, out_f16):

@@ -10,6 +10,23 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench  # noqa: E402
 from spaa_amd import convplan  # noqa: E402
+from spaa_amd import tiles as tile_table  # noqa: E402
+
+WINO_KRANGE_CANDIDATES = (70, 71)   # the eight-wave Winograd tiles: also with 1 (never split) / 2 / 4 / 8 K ranges
+SPLITK_CANDIDATES = (25, 27, 31, 34, 35, 36, 42, 48, 50, 52)   # the DMA-staged tiles worth measuring with 2 / 4 / 8 K ranges (one per shape of tile)
+
+
+def default_candidates():
+    """The tune values measured when SPAA_TUNE_TILES names none (`convplan.split_tune_value` reads them): every fp32-storage tile that
+    takes any layer it fits (the fp16 kernels are chosen by shape, the thin-output / stride-2-patch / first-layer kernels by the plan),
+    the Winograd tiles (WINO_KRANGE_CANDIDATES also with K ranges), the DMA-staged tiles with K ranges and
+    the persistent ones with stream-K."""
+    assert set(SPLITK_CANDIDATES) <= convplan.X6D_TILES and set(WINO_KRANGE_CANDIDATES) <= convplan.WINO_TILES
+    general = sorted(tile_table.of_family(tile_table.F32, tile_table.DIRECT, tile_table.THIN, tile_table.X6, tile_table.X6D, tile_table.THINPATCH,
+                                          tile_table.SMALLCIN))
+    wino = sorted(convplan.WINO_TILES)
+    return (general + wino + [100 * k + t for k in (1, 2, 4, 8) for t in WINO_KRANGE_CANDIDATES]
+            + [100 * k + t for k in (2, 4, 8) for t in SPLITK_CANDIDATES] + [900 + t for t in sorted(convplan.X6D_PERSISTENT)])
 
 
 def build_reference_shape(batch, classifier, cam, prj):
@@ -46,7 +63,7 @@ def main():
     torch.cuda.synchronize()
     res = {}
     names = {}
-    tiles = [int(t) for t in os.environ.get('SPAA_TUNE_TILES', '').split(',') if t] or (list(range(1, 55)) + [70, 71, 73, 170, 171, 270, 271, 470, 471, 870, 871] + [s * 100 + t for s in (2, 4, 8) for t in (25, 27, 31, 34, 35, 36, 42, 48, 50, 52)] + [900 + t for t in (48, 49, 50, 51, 52, 53, 54)])
+    tiles = [int(t) for t in os.environ.get('SPAA_TUNE_TILES', '').split(',') if t] or default_candidates()
     # the current choice (tune table / heuristic) per launch, measured in this same process: a candidate must beat it by 2 %
     cur = {}
     convplan.FORCE_TILE = 0
@@ -66,7 +83,8 @@ def main():
             st.iteration(**hp)
         torch.cuda.synchronize()
         for name, key, flops, e0, e1, used, _nbytes in convplan.PROFILE:
-            if (used % 100 not in (70, 71, 73) or (used % 100 == 73) != (tile % 100 == 73)) if tile % 100 in (70, 71, 73) else used != tile:   # (Winograd: the launcher's N tile / K ranges are reported, not the request)
+            asked, ran = convplan.split_tune_value(tile)[0], convplan.split_tune_value(used)[0]
+            if (ran not in convplan.WINO_TILES or (ran == 73) != (asked == 73)) if asked in convplan.WINO_TILES else used != tile:   # (Winograd: the launcher's N tile / K ranges are reported, not the request)
                 continue  # this tile is not valid for the layer (ConvPlan.run fell back)
             res.setdefault(key, {}).setdefault(tile, []).append(e0.elapsed_time(e1))
             names.setdefault(key, set()).add(name)
@@ -79,7 +97,7 @@ def main():
         # a key may be launched several times per iteration; compare mean time per launch
         avg = {t: sum(v) / len(v) for t, v in per.items()}
         # ties (run-to-run noise is ~1-2 %) go to the plainer kernel: the LDS-coalesced-epilogue variants must win by 2 %
-        best = min(avg, key=lambda t: avg[t] * (1.02 if t % 100 in (39, 40, 41, 45, 46) else 1.0))
+        best = min(avg, key=lambda t: avg[t] * (1.02 if convplan.split_tune_value(t)[0] in (39, 40, 41, 45, 46) else 1.0))
         if key in cur and key in convplan.TUNE and sum(cur[key]) / len(cur[key]) <= 1.02 * avg[best]:
             best = convplan.TUNE[key]      # (not beaten: the entry stays)
             avg.setdefault(best, sum(cur[key]) / len(cur[key]))

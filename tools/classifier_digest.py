@@ -19,6 +19,9 @@ sys.path.insert(0, HERE)
 import classifier_sequences as seq  # noqa: E402
 
 
+NCLS = 12   # (the backward pass reads the logit gradient as a [B, 1, 1, classes] activation: channel quads)
+
+
 def digest(t):
     return hashlib.sha256(t.detach().cpu().contiguous().view(torch.uint8).numpy().tobytes()).hexdigest()[:32]
 
@@ -33,11 +36,11 @@ def main():
     sds = {}
     for c in seq.CONFIGS:
         name, b, hw = seq.config_name(c), c['batch'], c['hw']
-        sd = sds.setdefault(c['body'], seq.state_dict(c['body']))
+        sd = sds.setdefault(c['body'], seq.state_dict(c['body'], NCLS))
         gen = torch.Generator().manual_seed(11)
         x4 = torch.randn(b, hw, hw, 4, generator=gen)
         x4[..., 3] = 0
-        x4, g = x4.cuda(), torch.randn(b, 10, generator=gen).cuda()
+        x4, g = x4.cuda(), torch.randn(b, NCLS, generator=gen).cuda()
         with seq.switched(c['switches']):
             body = classifier.BODIES[c['body']](sd, b, (hw, hw), torch.device('cuda'), c['storage'])
             for k, v in c['live'].items():

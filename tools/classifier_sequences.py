@@ -51,11 +51,11 @@ def config_name(c):
     return '-'.join([c['body'], c['storage'], f"b{c['batch']}", str(c['hw'])] + extra)
 
 
-def state_dict(body):
+def state_dict(body, num_classes=10):
     from spaa_amd import synthetic as syn
     if body == 'vgg16':
-        return syn.vgg16_state_dict(num_classes=10, fc_width=64)
-    return dict(resnet18=syn.resnet18_state_dict, inception_v3=syn.inception_v3_state_dict)[body](num_classes=10)
+        return syn.vgg16_state_dict(num_classes=num_classes, fc_width=64)
+    return dict(resnet18=syn.resnet18_state_dict, inception_v3=syn.inception_v3_state_dict)[body](num_classes=num_classes)
 
 
 class Recorder:
