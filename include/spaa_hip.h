@@ -704,6 +704,49 @@ int spaa_png_pack(const uint8_t* streams, int64_t stream_bytes, int N, const uin
                   const int32_t* hdr_bits, const int64_t* offsets, uint32_t* chunk_bits, uint8_t* out, int64_t out_bytes,
                   spaa_stream_t stream);
 
+/* ---- PNG decoding to device-resident images (spaa_amd/png.py holds the host half: chunks, CRCs, the zlib header and trailer) ----
+ * One descriptor per image; offsets are bytes into the buffers the entry points name. */
+typedef struct {
+    int64_t src_off;      /* the raw deflate payload (zlib header and Adler-32 trailer stripped): a multiple of 4 */
+    int64_t src_len;
+    int32_t H, W;
+    int32_t channels;     /* 1 (grey), 3 (RGB) or 4 (RGBA) */
+    int32_t reserved;
+    int64_t ws_off;       /* the image's scanlines, H (1 + W channels) bytes, in the workspace: a multiple of 16 */
+    int64_t out_off;      /* its planar output [3][H][W] */
+    int64_t row0;         /* index of its first row in the Adler array */
+} spaa_png_img_t;
+
+/* status of one image: 0, or the first rule its stream broke */
+#define SPAA_PNG_OK 0
+#define SPAA_PNG_BAD_BLOCK_TYPE 1   /* reserved block type 3 */
+#define SPAA_PNG_STORED_LEN 2       /* stored block: LEN is not the complement of NLEN */
+#define SPAA_PNG_OVERSUBSCRIBED 3   /* code lengths that no prefix code has */
+#define SPAA_PNG_INCOMPLETE 4       /* an incomplete code set other than one code of length 1, or no end-of-block code */
+#define SPAA_PNG_BAD_REPEAT 5       /* repeat code with nothing to repeat, or running past HLIT + HDIST */
+#define SPAA_PNG_BAD_SYMBOL 6       /* literal/length symbol 286 / 287, distance code 30 / 31, a bit pattern that is no code */
+#define SPAA_PNG_DIST_TOO_FAR 7     /* distance beyond the output produced so far */
+#define SPAA_PNG_OUTPUT_LONG 8      /* more output than H (1 + W channels) bytes */
+#define SPAA_PNG_INPUT_END 9        /* the payload ended inside a block */
+#define SPAA_PNG_OUTPUT_SHORT 10    /* the final block ended before H (1 + W channels) bytes */
+#define SPAA_PNG_BAD_FILTER 11      /* a scanline's filter type above 4 */
+#define SPAA_PNG_BAD_DESC 12        /* a descriptor that points outside the buffers, or a size out of range */
+
+/* Inflates every image's payload into its scanline area: one wave per image, one launch.  Handles all of RFC 1951 (stored, fixed
+ * and dynamic blocks, any number of them, distances to 32768).  Nothing outside [src_off, src_off + src_len) is read and nothing
+ * outside the scanline area is written; the work per image is bounded by 8 src_len + H (1 + W channels).  status [N] int32 is
+ * written for every image; a failed image leaves its scanlines unspecified and does not disturb the others.  payload 4-byte and
+ * workspace 16-byte aligned. */
+int spaa_png_inflate(const uint8_t* payload, int64_t payload_bytes, const spaa_png_img_t* imgs, int N, uint8_t* workspace,
+                     int64_t workspace_bytes, int32_t* status, spaa_stream_t stream);
+/* Scanlines -> planar bytes [3][H][W] per image (grey replicated, alpha dropped): filters 0..4 of the PNG specification, arithmetic
+ * mod 256, Paeth ties left, up, upper-left, bytes left of a row and above row 0 counting as 0.  adler [adler_rows][2] uint32: per
+ * row (sum of its 1 + W channels scanline bytes, sum of byte j times (1 + W channels - j)), both mod 65521, as the encoder's filter
+ * entry writes them.  Images whose status is not 0 are skipped; a filter type above 4 sets SPAA_PNG_BAD_FILTER.  max_w: the widest
+ * image of the batch, <= 16000.  One launch. */
+int spaa_png_unfilter(const uint8_t* workspace, int64_t workspace_bytes, const spaa_png_img_t* imgs, int N, int max_w, uint8_t* out,
+                      int64_t out_bytes, uint32_t* adler, int64_t adler_rows, int32_t* status, spaa_stream_t stream);
+
 /* misc */
 int spaa_zero(void* p, int64_t bytes, spaa_stream_t stream);
 const char* spaa_version(void);

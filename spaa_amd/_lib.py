@@ -60,6 +60,12 @@ class ImgPair(C.Structure):
                 ('y_rgb', C.c_float * 3), ('reserved', C.c_int32)]
 
 
+class PngImg(C.Structure):
+    """spaa_png_img_t: one image of spaa_png_inflate / spaa_png_unfilter (include/spaa_hip.h)."""
+    _fields_ = [('src_off', C.c_int64), ('src_len', C.c_int64), ('H', C.c_int32), ('W', C.c_int32), ('channels', C.c_int32),
+                ('reserved', C.c_int32), ('ws_off', C.c_int64), ('out_off', C.c_int64), ('row0', C.c_int64)]
+
+
 _i, _f, _p, _l, _d = C.c_int, C.c_float, C.c_void_p, C.c_int64, C.c_double
 
 # name -> argument types (all return int)
@@ -155,6 +161,8 @@ _SIGNATURES = {
     'spaa_montage_compose': [_p, _i, _i, _i, _i, _p, _p, _i, _i, _i, _i, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _i, _p, _i, _i, _p, _p],
     'spaa_png_filter_hist': [_p, _i, _i, _i, _i, _p, _p, _p, _p],
     'spaa_png_pack': [_p, _l, _i, _p, _p, _p, _p, _p, _p, _l, _p],
+    'spaa_png_inflate': [_p, _l, _p, _i, _p, _l, _p, _p],
+    'spaa_png_unfilter': [_p, _l, _p, _i, _i, _p, _l, _p, _l, _p, _p],
     'spaa_zero': [_p, _l, _p],
 }
 

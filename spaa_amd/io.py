@@ -1,5 +1,5 @@
 """On-disk formats either side of the attack path, with the reference's conventions (host side; PNG encoding of device tensors aside,
-no GPU work).
+PNG decoding to device tensors aside, no GPU work).
 
 Mirrors /root/reference/src/python:
   utils.py:84-167     SimpleDataset / torch_imread / torch_imread_mt / save_imgs  (PNG via OpenCV there: BGR on disk order
@@ -29,27 +29,77 @@ def _imread_rgb(filename):
         return np.asarray(im.convert('RGB'))  # cv.imread(...)[..., ::-1]: 8-bit, 3 channels, alpha dropped
 
 
-def torch_imread(filename):
-    """utils.py:116-117: float tensor [3,H,W] in [0,1]."""
+def _read_bytes(path):
+    with open(path, 'rb') as fh:
+        return fh.read()
+
+
+def _imread_device(paths, device):
+    """The files as uint8 tensors [3,H,W] on `device`: those `png.parse_png` accepts are decoded there in one `png.decode_records`
+    batch, the rest (palette, 16-bit, interlaced, not PNG at all) are read through Pillow and copied over.  A PNG file that is
+    broken raises ValueError with its path; it is never handed to Pillow instead."""
+    device = torch.device(device)
+    if device.type != 'cuda':
+        raise RuntimeError(f'spaa_amd.io decodes on the GPU or, with device=None, through Pillow; got device={device}')
+    out, records, where = [None] * len(paths), [], []
+    for i, path in enumerate(paths):
+        data = _read_bytes(path)
+        rec = None
+        if data[:8] == png.PNG_SIGNATURE:
+            try:
+                rec = png.parse_png(data)
+            except ValueError as e:
+                raise ValueError(f'{path}: {e}') from None
+        if rec is None:
+            out[i] = torch.from_numpy(_imread_rgb(path).transpose(2, 0, 1).copy()).to(device)
+        else:
+            records.append(rec)
+            where.append(i)
+    images, status = png.decode_records(records, device)
+    bad = [f'{paths[where[k]]}: {png.STATUS_TEXT.get(int(st), "status " + str(int(st)))}' for k, st in enumerate(status) if st]
+    if bad:
+        raise ValueError('PNG decode failed: ' + '; '.join(bad))
+    for k, im in zip(where, images):
+        out[k] = im
+    return out
+
+
+def _div255(x):
+    """x / 255 with the host's rounding.  On a GPU, torch divides by a Python number by multiplying with its reciprocal, which is
+    one rounding more than the host's division; dividing by a tensor on the device is a true division there."""
+    return x / torch.full((), 255.0, device=x.device) if x.is_cuda else x.div(255)
+
+
+def torch_imread(filename, *, device=None):
+    """utils.py:116-117: float tensor [3,H,W] in [0,1].  `device`: a CUDA device decodes the file there (spaa_amd.png) and returns a
+    tensor on it, bit-equal to the host result."""
+    if device is not None:
+        return _div255(_imread_device([filename], device)[0].float())
     return torch.from_numpy(_imread_rgb(filename).transpose(2, 0, 1).copy()).float() / 255
 
 
-def torch_imread_mt(img_dir, size=None, index=None, gray_scale=False, normalize=False):
+def torch_imread_mt(img_dir, size=None, index=None, gray_scale=False, normalize=False, *, device=None):
     """utils.py:120-143: every image of a directory in sorted order -> [N,3,H,W] (or [N,1,H,W]) in [0,1] ([-1,1]).
     `size` is (h, w); resizing is bilinear with half-pixel centres like cv.resize's default (the reference resizes the
-    uint8 image in fixed point: results can differ by one grey level)."""
+    uint8 image in fixed point: results can differ by one grey level).
+    `device=None`: Pillow, one file after the other, a host tensor.  A CUDA device: the files are read as bytes and decoded on that
+    device in one batch (spaa_amd.png.decode_records; files its parser declines go through Pillow one by one), and the same
+    expressions run there: the result is a tensor on the device, bit-equal to the host result moved over, except after a resize,
+    where the two bilinear kernels may round differently before the `round()` (one grey level)."""
     names = sorted(os.listdir(img_dir))
     if index is not None:
         names = [names[i] for i in index]
-    ims = []
-    for n in names:
-        path = join(img_dir, n)
+    paths = [join(img_dir, n) for n in names]
+    for path in paths:
         assert os.path.isfile(path), path + ' does not exist'
-        im = torch.from_numpy(_imread_rgb(path).transpose(2, 0, 1).copy()).float()
+    ims = []
+    for im in (_imread_device(paths, device) if device is not None else
+               (torch.from_numpy(_imread_rgb(path).transpose(2, 0, 1).copy()) for path in paths)):
+        im = im.float()
         if size is not None and tuple(im.shape[-2:]) != tuple(size):
             im = F.interpolate(im[None], tuple(size), mode='bilinear', align_corners=False)[0].round().clamp(0, 255)
         ims.append(im)
-    imgs = torch.stack(ims).div(255)
+    imgs = _div255(torch.stack(ims))
     if gray_scale:
         imgs = (0.2989 * imgs[:, 0] + 0.5870 * imgs[:, 1] + 0.1140 * imgs[:, 2])[:, None]
     if normalize:

@@ -1,12 +1,17 @@
-"""PNG encoding of device-resident images: the host half (pure Python / numpy; importing it needs no GPU) and `encode_png`,
-which drives the two entry points of csrc/png.hip.
+"""PNG encoding and decoding of device-resident images: the host half (pure Python / numpy; importing it needs no GPU), `encode_png`,
+which drives the two entry points of csrc/png.hip, and `decode_png`, which drives the two of csrc/png_decode.hip.
 
 The scheme: per row the cheapest of the five PNG filters, then ONE dynamic-Huffman deflate block of literals
 only -- no LZ77 matching.  The device filters the images, counts the bytes and packs the bits; the host builds, per image, a
 length-limited Huffman code from the 257 counts (`huffman_lengths`), the block header (`deflate_tables`) and the PNG container
 (`wrap_png`).  Because the code lengths are known before the bits are packed, every image's stream size is exact before the
 second launch.
+
+Decoding ("The read side"): the host walks the chunks, checks their CRCs and the zlib header (`parse_png`) and packs
+the raw deflate payloads of a batch into one pinned buffer; the device inflates them, one wave per image, and undoes the row
+filters; the Adler-32 of every image's scanlines comes back as per-row sums and is compared with the stream's trailer.
 """
+import collections
 import heapq
 import struct
 import zlib
@@ -270,3 +275,179 @@ def encode_png(images, timings=None):
     if timings is not None:
         timings.update(t)
     return files
+
+
+# ---- the read side -------------------------------------------------------------------------------------------------------------
+
+PNG_SIGNATURE = b'\x89PNG\r\n\x1a\n'
+MAX_DECODE_WIDTH = 16000             # csrc/png_decode.hip: the unfilter kernel keeps one row of packed pixels in LDS
+ST_ADLER = 100                       # host-side status: the scanlines' Adler-32 is not the stream's trailer
+STATUS_TEXT = {                      # include/spaa_hip.h, SPAA_PNG_*
+    1: 'reserved deflate block type 3',
+    2: 'stored block whose LEN and NLEN do not match',
+    3: 'over-subscribed Huffman code set',
+    4: 'incomplete Huffman code set',
+    5: 'code-length repeat with nothing to repeat or past the end of the table',
+    6: 'invalid literal/length or distance symbol',
+    7: 'match distance beyond the start of the output',
+    8: 'more scanline data than the header announces',
+    9: 'deflate stream ends early',
+    10: 'less scanline data than the header announces',
+    11: 'scanline filter type above 4',
+    12: 'image descriptor out of range',
+    ST_ADLER: 'Adler-32 of the scanlines does not match the stream trailer',
+}
+
+PngRecord = collections.namedtuple('PngRecord', 'width height channels deflate adler')
+PngRecord.__doc__ = """What the device needs of one PNG file: size, channels (1, 3 or 4), the raw deflate payload of the concatenated
+IDAT chunks (zlib header and trailer stripped) and the trailer's Adler-32."""
+
+
+def parse_png(data):
+    """The container of one PNG file -> PngRecord, or None for a well-formed file the device path does not take (palette, 16-bit,
+    1/2/4-bit, interlaced, wider than MAX_DECODE_WIDTH: read those with Pillow).  Checks the signature, every chunk's CRC, IHDR
+    first, at least one IDAT, IEND, and the zlib header (deflate, window <= 32 KiB, FCHECK, no preset dictionary); ancillary chunks
+    are skipped.  A broken container raises ValueError."""
+    data = bytes(data)
+    if data[:8] != PNG_SIGNATURE:
+        raise ValueError('not a PNG file: bad signature')
+    i, hdr, idat, seen_idat, ended = 8, None, [], False, False
+    while i < len(data):
+        if i + 12 > len(data):
+            raise ValueError('truncated chunk header')
+        n = int.from_bytes(data[i:i + 4], 'big')
+        tag = data[i + 4:i + 8]
+        if i + 12 + n > len(data):
+            raise ValueError(f'chunk {tag!r} runs past the end of the file')
+        body = data[i + 8:i + 8 + n]
+        if zlib.crc32(data[i + 4:i + 8 + n]) != int.from_bytes(data[i + 8 + n:i + 12 + n], 'big'):
+            raise ValueError(f'chunk {tag!r}: bad CRC')
+        i += 12 + n
+        if hdr is None and tag != b'IHDR':
+            raise ValueError('missing IHDR: the first chunk is ' + repr(tag))
+        if tag == b'IHDR':
+            if hdr is not None or n != 13:
+                raise ValueError('bad IHDR')
+            hdr = struct.unpack('>IIBBBBB', body)
+        elif tag == b'IDAT':
+            idat.append(body)
+            seen_idat = True
+        elif tag == b'IEND':
+            ended = True
+            break
+        elif not tag[0] & 0x20 and tag != b'PLTE':
+            raise ValueError(f'unknown critical chunk {tag!r}')
+    if hdr is None:
+        raise ValueError('missing IHDR')
+    if not seen_idat:
+        raise ValueError('missing IDAT')
+    if not ended:
+        raise ValueError('missing IEND')
+    w, h, depth, ctype, comp, filt, interlace = hdr
+    if w == 0 or h == 0:
+        raise ValueError(f'zero dimension: {w} x {h}')
+    if depth not in (1, 2, 4, 8, 16) or ctype not in (0, 2, 3, 4, 6) or comp != 0 or filt != 0 or interlace not in (0, 1):
+        raise ValueError(f'bad IHDR fields: depth {depth}, colour type {ctype}, compression {comp}, filter {filt}, interlace {interlace}')
+    if depth != 8 or interlace != 0 or ctype not in (0, 2, 6) or w > MAX_DECODE_WIDTH or h * (1 + 4 * w) >= 1 << 31:
+        return None
+    z = b''.join(idat)
+    if len(z) < 6:
+        raise ValueError('IDAT: no room for a zlib header and trailer')
+    cmf, flg = z[0], z[1]
+    if cmf & 15 != 8 or cmf >> 4 > 7 or (cmf << 8 | flg) % 31 or flg & 0x20:
+        raise ValueError(f'IDAT: bad zlib header {cmf:02x} {flg:02x}')
+    return PngRecord(w, h, {0: 1, 2: 3, 6: 4}[ctype], z[2:-4], int.from_bytes(z[-4:], 'big'))
+
+
+def _pin(t):
+    try:
+        return t.pin_memory()
+    except RuntimeError:         # (no pinned allocation available: the copy is then staged by the runtime)
+        return t
+
+
+def decode_records(records, device, timings=None):
+    """The device half of `decode_png` for PngRecords: -> (list of uint8 CUDA tensors [3,H,W], status int array [N]).  One pinned
+    host block (descriptors, then every deflate payload on a 4-byte boundary), one copy to the device, spaa_png_inflate,
+    spaa_png_unfilter, one copy back (the status words and the Adler row sums); status is 0, a SPAA_PNG_* code of
+    include/spaa_hip.h, or ST_ADLER.  Images with a non-zero status hold unspecified bytes.  `timings`: a dict that receives
+    the milliseconds of 'h2d', 'inflate', 'unfilter', 'd2h' measured with events on the stream."""
+    import ctypes
+    import torch
+    from . import _lib
+    device = torch.device(device)
+    if device.type != 'cuda':
+        raise RuntimeError(f'spaa_amd.png decodes on the GPU only (no CPU fallback): device is {device}')
+    n = len(records)
+    if n == 0:
+        return [], np.zeros(0, np.int32)
+    descs = (_lib.PngImg * n)()
+    dbytes = (ctypes.sizeof(descs) + 15) & ~15
+    src, ws, out, row = dbytes, 0, 0, 0
+    for d, r in zip(descs, records):
+        d.src_off, d.src_len, d.H, d.W, d.channels = src - dbytes, len(r.deflate), r.height, r.width, r.channels
+        d.ws_off, d.out_off, d.row0 = ws, out, row
+        src += (len(r.deflate) + 3) & ~3
+        ws += (r.height * (1 + r.width * r.channels) + 15) & ~15
+        out += 3 * r.height * r.width
+        row += r.height
+    host = torch.empty(max(src, dbytes + 4), dtype=torch.uint8)
+    host = _pin(host)
+    hv = host.numpy()
+    hv[:ctypes.sizeof(descs)] = np.frombuffer(descs, dtype=np.uint8)
+    for d, r in zip(descs, records):
+        hv[dbytes + d.src_off:dbytes + d.src_off + d.src_len] = np.frombuffer(r.deflate, dtype=np.uint8)
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(5)] if timings is not None else None
+    with _lib.on_device(device):
+        if ev:
+            ev[0].record()
+        dev = host.to(device, non_blocking=True)
+        work = torch.empty(ws, dtype=torch.uint8, device=device)
+        pixels = torch.empty(out, dtype=torch.uint8, device=device)
+        back = torch.empty(n + 2 * row, dtype=torch.int32, device=device)         # status [N] | Adler row sums [rows][2]
+        if ev:
+            ev[1].record()
+        _lib.call('spaa_png_inflate', _lib.ptr(dev[dbytes:]), src - dbytes, _lib.ptr(dev), n, _lib.ptr(work), ws, _lib.ptr(back))
+        if ev:
+            ev[2].record()
+        _lib.call('spaa_png_unfilter', _lib.ptr(work), ws, _lib.ptr(dev), n, max(r.width for r in records), _lib.ptr(pixels), out,
+                  _lib.ptr(back[n:]), row, _lib.ptr(back))
+        if ev:
+            ev[3].record()
+        back_h = back.cpu().numpy()
+        if ev:
+            ev[4].record()
+            ev[4].synchronize()
+            for k, name in enumerate(('h2d', 'inflate', 'unfilter', 'd2h')):
+                timings[name] = ev[k].elapsed_time(ev[k + 1])
+    status = back_h[:n].copy()
+    sums = back_h[n:].view(np.uint32).reshape(row, 2)
+    images = []
+    for i, (d, r) in enumerate(zip(descs, records)):
+        images.append(pixels[d.out_off:d.out_off + 3 * r.height * r.width].view(3, r.height, r.width))
+        if status[i] == 0 and int(adler32_from_rows(sums[d.row0:d.row0 + r.height], 1 + r.width * r.channels)) != r.adler:
+            status[i] = ST_ADLER
+    return images, status
+
+
+def decode_png(blobs, device, *, names=None):
+    """PNG files (`bytes`) -> a list of uint8 CUDA tensors [3,H,W] on `device`, the pixels of `Image.open(...).convert('RGB')`: grey
+    is replicated, alpha dropped.  The files of one call may differ in size and colour type; each must be one `parse_png`
+    accepts (8-bit grey / RGB / RGBA, not interlaced).  One host-to-device copy and two launches whatever the number of files.
+    A broken container, a deflate stream that breaks a rule, a bad filter type or an Adler-32 mismatch raises ValueError naming
+    the file (`names[i]`, else its index) and the reason; nothing falls back to another decoder."""
+    label = (lambda i: str(names[i])) if names is not None else (lambda i: f'image {i}')
+    records = []
+    for i, b in enumerate(blobs):
+        try:
+            r = parse_png(b)
+        except ValueError as e:
+            raise ValueError(f'decode_png: {label(i)}: {e}') from None
+        if r is None:
+            raise ValueError(f'decode_png: {label(i)}: not an 8-bit non-interlaced grey / RGB / RGBA file (parse_png declines it)')
+        records.append(r)
+    images, status = decode_records(records, device)
+    bad = [f'{label(i)}: {STATUS_TEXT.get(int(s), "status " + str(int(s)))}' for i, s in enumerate(status) if s]
+    if bad:
+        raise ValueError('decode_png: ' + '; '.join(bad))
+    return images

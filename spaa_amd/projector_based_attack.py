@@ -818,7 +818,8 @@ def _nonempty(d):
 MONTAGE_CHUNK = 264   # montages per attack_montages call in the summary (24 configurations; bounds the output buffer, ~300 MB at 256^2 tiles)
 
 
-def summarize_single_attacker(attacker_name, data_root, setup_list, device='cuda', device_ids=[0], *, classifiers=None, montages=False):
+def summarize_single_attacker(attacker_name, data_root, setup_list, device='cuda', device_ids=[0], *, classifiers=None, montages=False,
+                              gpu_decode=False):
     """projector_based_attack.py:417-574: per setup, one row per attack configuration (stealth loss x d_thr x classifier) of
     `attacker_name` found on disk -- targeted top-1 / top-5 and untargeted top-1 success of the inferred and the real
     camera-captured attacks, and PSNR / RMSE / SSIM / L2 / L_inf / dE2000 of the projector images (vs the grey illumination), the
@@ -836,6 +837,8 @@ def summarize_single_attacker(attacker_name, data_root, setup_list, device='cuda
         (split only every MONTAGE_CHUNK montages to bound memory), with the labels' top-1 probabilities from the softmax computed
         for the success rates and the L2 values from the img_stats sums.  Their text is a bitmap font at the tiles' edges and the
         colour map a restatement of Jet (spaa_amd/montage.py); the tiles have the projector images' own size.
+      * `gpu_decode=True` decodes the attack results and the validation pair on `device` (io.torch_imread_mt(..., device=): one
+        batch per folder, the same values) instead of through Pillow one file after the other.
     Mechanism: all images of a setup are loaded at once, each classifier sees them in chunks of SUMMARY_CHUNK, and every image
     metric of the setup comes from ONE metrics.img_stats launch, grouped on the host with metrics.dists_from_sums."""
     import itertools
@@ -880,9 +883,10 @@ def summarize_single_attacker(attacker_name, data_root, setup_list, device='cuda
             raise ValueError(f'summarize_single_attacker: [{setup_name}] has attack results for {no_clf}: pass classifiers={{name: '
                              'spaa_amd.Classifier} for them (weights cannot be downloaded here)')
 
-        prj = [io.torch_imread_mt(c[3]).to(device) for c in cfgs]
-        real = [io.torch_imread_mt(c[4]).to(device) for c in cfgs]
-        infer = [io.torch_imread_mt(c[5]).to(device) for c in cfgs] if dl_based else real
+        rd = (lambda d: io.torch_imread_mt(d, device=device)) if gpu_decode else (lambda d: io.torch_imread_mt(d).to(device))
+        prj = [rd(c[3]) for c in cfgs]
+        real = [rd(c[4]) for c in cfgs]
+        infer = [rd(c[5]) for c in cfgs] if dl_based else real
         for c, p, r, i in zip(cfgs, prj, real, infer):
             if not p.shape[0] == r.shape[0] == i.shape[0] > n:
                 raise ValueError(f'{join(*map(str, c[:3]))}: expected the same number (> {n}) of prj / cam images, got '
@@ -932,7 +936,7 @@ def summarize_single_attacker(attacker_name, data_root, setup_list, device='cuda
             else:
                 vx, vy, vcrop = join(setup_path, 'prj/infer/test', model_cfg_str), join(data_root, 'prj_share/test'), None
             if _nonempty(vx) and _nonempty(vy):
-                a, b = io.torch_imread_mt(vx).to(device), io.torch_imread_mt(vy).to(device)
+                a, b = rd(vx), rd(vy)
                 if a.shape[0] != b.shape[0]:
                     raise ValueError(f'{vx} and {vy} hold {a.shape[0]} and {b.shape[0]} images')
                 add('valid', a, lambda o: M.stack_pairs(a.shape[0], a.shape[-2:], b.shape[-2:], crop=vcrop, x_off=o, y_off=yoff))

@@ -855,12 +855,14 @@ LOG_COLUMNS = ['Setup', 'Model', 'Loss', 'Num train', 'Batch', 'Iters', 'PSNR', 
 PCNET_MODELS = ('PCNet', 'PCNet_no_mask', 'PCNet_no_rough', 'PCNet_no_mask_no_rough', 'PCNet_w/o_refine')
 
 
-def load_data(data_root, setup_name, input_size=None, compensation=False, *, device='cuda'):
+def load_data(data_root, setup_name, input_size=None, compensation=False, *, device='cuda', gpu_decode=False):
     """train_network.py:39-82: reads `<data_root>/setups/<setup_name>/cam/raw/{ref,train,test,cb}` and `<data_root>/prj_share/
     {train,test}` and returns (cam_scene [1,3,H,W] = ref/img_0002, cam_train, cam_valid, prj_train, prj_valid (as many as cam_valid),
     im_mask bool [H,W], mask_corners, setup_info), all on the host like the reference's.  The direct-light mask of the checkerboard
     captures (Nayar's separation with backlight 0.9, then img_proc.threshold_im's chain) is three launches of csrc/direct_mask.hip on
-    `device`; there is no CPU fallback.  `compensation=True` (unused by the reference) is not implemented."""
+    `device`; there is no CPU fallback.  `compensation=True` (unused by the reference) is not implemented.
+    `gpu_decode=True` decodes the PNG files on `device` as well (io.torch_imread_mt(..., device=)) and copies the batches back: the same
+    values on the same devices."""
     from os.path import join
     from . import io, img_proc
     if compensation:
@@ -869,14 +871,16 @@ def load_data(data_root, setup_name, input_size=None, compensation=False, *, dev
     setup_path = join(data_root, 'setups', setup_name)
     print(f"Loading data from '{setup_path}'")
     setup_info = io.load_setup_info(setup_path)
-    cam_ref = io.torch_imread_mt(join(setup_path, 'cam/raw/ref'), size=input_size)
+    rd = (lambda *a, **kw: io.torch_imread_mt(*a, device=dev, **kw)) if gpu_decode else io.torch_imread_mt
+    host = (lambda t: t.cpu()) if gpu_decode else (lambda t: t)
+    cam_ref = host(rd(join(setup_path, 'cam/raw/ref'), size=input_size))
     gray_idx = 1                                   # ref/img_0002: the surface lit by prj_brightness
     cam_scene = cam_ref[gray_idx].unsqueeze(0)
-    cam_train = io.torch_imread_mt(join(setup_path, 'cam/raw/train'), size=input_size)
-    prj_train = io.torch_imread_mt(join(data_root, 'prj_share/train'))
-    cam_valid = io.torch_imread_mt(join(setup_path, 'cam/raw/test'), size=input_size)
-    prj_valid = io.torch_imread_mt(join(data_root, 'prj_share/test'), index=list(range(cam_valid.shape[0])))
-    im_cb = io.torch_imread_mt(join(setup_path, 'cam/raw/cb'), size=input_size)
+    cam_train = host(rd(join(setup_path, 'cam/raw/train'), size=input_size))
+    prj_train = host(rd(join(data_root, 'prj_share/train')))
+    cam_valid = host(rd(join(setup_path, 'cam/raw/test'), size=input_size))
+    prj_valid = host(rd(join(data_root, 'prj_share/test'), index=list(range(cam_valid.shape[0]))))
+    im_cb = rd(join(setup_path, 'cam/raw/cb'), size=input_size)      # (stays where it was decoded: the mask kernels take either)
     if im_cb.shape[0] < 2:
         raise ValueError(f'load_data: the direct-light separation needs at least two checkerboard captures, found {im_cb.shape[0]}')
     im_mask, _, mask_corners = img_proc._finish(img_proc.direct_mask(im_cb, img_proc.BACKLIGHT, device=dev))

@@ -48,6 +48,7 @@ def main():
     ap.add_argument('--valid', type=int, default=20)
     ap.add_argument('--cb', type=int, default=10)
     ap.add_argument('--repeat', type=int, default=3)
+    ap.add_argument('--gpu-decode', action='store_true', help='decode the PNG files on the device (load_data(gpu_decode=True))')
     a = ap.parse_args()
     assert torch.cuda.is_available(), 'time_load_data needs a GPU'
     decode_s, launches = [0.0], []
@@ -68,12 +69,12 @@ def main():
             decode_s[0], launches[:] = 0.0, []
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            out = tn.load_data(root, 'synth', device='cuda')
+            out = tn.load_data(root, 'synth', device='cuda', gpu_decode=a.gpu_decode)
             torch.cuda.synchronize()
             total = time.perf_counter() - t0
             rec = dict(total_s=total, png_decode_s=decode_s[0], **{name + '_us': 1e3 * e0.elapsed_time(e1) for name, e0, e1 in launches})
             best = rec if best is None or _ == 1 or rec['total_s'] < best['total_s'] else best
-    rec = dict(tool='time_load_data', cam_sz=list(a.cam), prj_sz=list(a.prj), n_train=a.train, n_valid=a.valid, n_cb=a.cb,
+    rec = dict(tool='time_load_data', gpu_decode=a.gpu_decode, cam_sz=list(a.cam), prj_sz=list(a.prj), n_train=a.train, n_valid=a.valid, n_cb=a.cb,
                mask_pixels=int(out[5].sum()), **{k: round(v, 6 if k.endswith('_s') else 1) for k, v in best.items()},
                device=torch.cuda.get_device_name(0))
     os.makedirs(os.path.dirname(a.out), exist_ok=True)

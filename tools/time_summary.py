@@ -100,7 +100,9 @@ def main():
                    'vgg16': Classifier('vgg16', dev, state_dict=syn.vgg16_state_dict(3, logit_gain=5.0))}
     with tempfile.TemporaryDirectory() as root:
         setup_path = make_setup(root)
-        routes = {'summary': lambda: A.summarize_single_attacker('SPAA', root, ['synth'], classifiers=classifiers),
+        routes = {'summary': lambda: A.summarize_single_attacker('SPAA', root, ['synth'], classifiers=classifiers, gpu_decode=False),
+                  'summary_gpu_decode': lambda: A.summarize_single_attacker('SPAA', root, ['synth'], classifiers=classifiers,
+                                                                           gpu_decode=True),
                   'per_configuration': lambda: per_configuration(setup_path, classifiers)}
         best, out = {}, {}
         for name, fn in routes.items():
@@ -117,7 +119,8 @@ def main():
     got = table[A.SUMMARY_COLUMNS[5:]].to_numpy(dtype=np.float64)
     want = out['per_configuration']
     line = dict(tool='time_summary', configurations=int(len(table)), images_per_configuration=11, prj_sz=[256, 256], crop=[240, 240],
-                summary_s=round(best['summary'], 3), per_configuration_s=round(best['per_configuration'], 3),
+                summary_s=round(best['summary'], 3), summary_gpu_decode_s=round(best['summary_gpu_decode'], 3),
+                gpu_decode_equal=bool(out['summary_gpu_decode'].equals(table)), per_configuration_s=round(best['per_configuration'], 3),
                 ratio=round(best['per_configuration'] / best['summary'], 2),
                 success_equal=bool(np.array_equal(got[:, :6], want[:, :6])),
                 metrics_max_rel=float(np.max(np.abs(got[:, 6:] / want[:, 6:] - 1))),
