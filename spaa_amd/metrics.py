@@ -10,7 +10,7 @@ Every metric is a ratio of sums that add over images (mse = sum d^2 / 3N, SSIM =
 L_inf = sum max|d| / N, dE = sum dE / N over the N pixels of a group), so one launch (`spaa_img_stats`) returns the five
 sums of each image pair over its crop rectangle, and any group of pairs is formed from them on the host in float64
 (`dists_from_sums`).  `calc_img_dists` is the group "the whole batch"; the attack summary
-(projector_based_attack.summarize_single_attacker) forms all groups of a setup from one `img_stats` call.
+(attack_summary.summarize_single_attacker) forms all groups of a setup from one `img_stats` call.
 """
 import ctypes as C
 import math

@@ -288,33 +288,49 @@ def _result_frame(classifier, p, pixel_count, target_idx, targeted_attack):
                         columns=['classifier', 'pixel_count', 'true_idx', 'pred_idx', 'success', 'true_p', 'pred_p', 'cdiff'])
 
 
-class DigitalOnePixelAttacker:
+class _OnePixelAttacker:
+    """What the two attackers share: the verbose line, the DE callback and the call.  A subclass supplies `_predict(x, im, classifier,
+    pixel_size) -> p` (one candidate through its route), `_gt(true_label)` (the line's GT field) and `attack`."""
+    last_result = None     # the DE result of the last attack (x, fun, nfev, nit, success, message, evaluated, ...)
+
+    def _report(self, target_idx, p_target, pred, p_max, targeted_attack, true_label):
+        if targeted_attack:
+            print(f'Target: {self.class_names[target_idx]:<20} ({p_target:.2f}) | '
+                  f'Pred: {self.class_names[pred]:<20} ({p_max:.2f}) | '
+                  f'GT: {self._gt(true_label)}')
+        else:
+            print(f'Untargeted | Pred: {self.class_names[pred]:<20} ({p_max:.2f}) | GT: {self._gt(true_label)}')
+
+    def attack_success(self, x, im, target_idx, classifier, pixel_size, targeted_attack=False, verbose=False, true_label=None):
+        p = self._predict(x, im, classifier, pixel_size)
+        if verbose:
+            self._report(target_idx, p[0, target_idx], p[0].argmax(), p[0].max(), targeted_attack, true_label)
+        if (targeted_attack and p[0].argmax() == target_idx) or (not targeted_attack and p[0].argmax() != target_idx):
+            return True
+
+    def __call__(self, im, classifier, targeted_attack=False, target_idx=None, pixel_count=1, pixel_size=1, maxiter=75, popsize=400,
+                 verbose=False, true_label=None, **kw):
+        return self.attack(im, classifier, targeted_attack, target_idx, pixel_count, pixel_size, maxiter, popsize, verbose,
+                           true_label, **kw)
+
+
+class DigitalOnePixelAttacker(_OnePixelAttacker):
     """one_pixel_attacker/__init__.py:47-108."""
 
     def __init__(self, class_names, classifier_crop_sz):
         self.class_names = class_names
         self.classifier_crop_sz = classifier_crop_sz
-        self.last_result = None     # the DE result of the last attack (x, fun, nfev, nit, success, message, evaluated, ...)
 
     def perturb_and_predict(self, x, im, classifier, pixel_size):
         im_adv = perturb_image(x, im, pixel_size)
         _, p, _ = classifier(im_adv, self.classifier_crop_sz)
         return p
 
-    def _report(self, target_idx, p_target, pred, p_max, targeted_attack, true_label):
-        if targeted_attack:
-            print(f'Target: {self.class_names[target_idx]:<20} ({p_target:.2f}) | '
-                  f'Pred: {self.class_names[pred]:<20} ({p_max:.2f}) | '
-                  f'GT: {self.class_names[true_label]:<20}')
-        else:
-            print(f'Untargeted | Pred: {self.class_names[pred]:<20} ({p_max:.2f}) | GT: {self.class_names[true_label]:<20}')
+    def _predict(self, x, im, classifier, pixel_size):
+        return self.perturb_and_predict(x, im, classifier, pixel_size)
 
-    def attack_success(self, x, im, target_idx, classifier, pixel_size, targeted_attack=False, verbose=False, true_label=None):
-        p = self.perturb_and_predict(x, im, classifier, pixel_size)
-        if verbose:
-            self._report(target_idx, p[0, target_idx], p[0].argmax(), p[0].max(), targeted_attack, true_label)
-        if (targeted_attack and p[0].argmax() == target_idx) or (not targeted_attack and p[0].argmax() != target_idx):
-            return True
+    def _gt(self, true_label):       # (the digital attack is given the true class id)
+        return f'{self.class_names[true_label]:<20}'
 
     def attack(self, im, classifier, targeted_attack=False, target_idx=None, pixel_count=1, pixel_size=1, maxiter=75, popsize=400,
                verbose=False, true_label=None, *, updating='immediate', seed=None, max_batch=None, trace=None):
@@ -336,13 +352,8 @@ class DigitalOnePixelAttacker:
         _, p, _ = classifier(torch.stack((im, im_adv), 0), self.classifier_crop_sz)  # p and idx are sorted, not the original orders.
         return _result_frame(classifier, p, pixel_count, target_idx, targeted_attack), im_adv
 
-    def __call__(self, im, classifier, targeted_attack=False, target_idx=None, pixel_count=1, pixel_size=1, maxiter=75, popsize=400,
-                 verbose=False, true_label=None, **kw):
-        return self.attack(im, classifier, targeted_attack, target_idx, pixel_count, pixel_size, maxiter, popsize, verbose,
-                           true_label, **kw)
 
-
-class ProjectorOnePixelAttacker:
+class ProjectorOnePixelAttacker(_OnePixelAttacker):
     """one_pixel_attacker/__init__.py:123-245 without the hardware: `cfg` is the setup info (`prj_im_sz`, `prj_brightness`,
     `cam_im_sz`, `classifier_crop_sz` are read; `prj_screen_sz`, `prj_offset`, `cam_raw_sz`, `cam_crop_sz`, `delay_*` are accepted and
     ignored), `capture` the project-and-capture step: a SimulatedCapture or any callable
@@ -358,7 +369,6 @@ class ProjectorOnePixelAttacker:
         self.class_names = class_names
         self.im_prj_org = None
         self.im_cam_org = None
-        self.last_result = None     # the DE result of the last attack, as on DigitalOnePixelAttacker
 
     def perturb_project_capture(self, x, im, pixel_size):
         im_prj_adv = perturb_image(x, im, pixel_size)
@@ -371,20 +381,11 @@ class ProjectorOnePixelAttacker:
             _, p, _ = classifier(im_cam_adv, self.classifier_crop_sz)
         return p
 
-    def _report(self, target_idx, p_target, pred, p_max, targeted_attack, true_label):
-        if targeted_attack:
-            print(f'Target: {self.class_names[target_idx]:<20} ({p_target:.2f}) | '
-                  f'Pred: {self.class_names[pred]:<20} ({p_max:.2f}) | '
-                  f'GT: {true_label:<15}')
-        else:
-            print(f'Untargeted | Pred: {self.class_names[pred]:<20} ({p_max:.2f}) | GT: {true_label:<15}')
+    def _predict(self, x, im, classifier, pixel_size):
+        return self.step_and_predict(x, im, classifier, pixel_size)
 
-    def attack_success(self, x, im, target_idx, classifier, pixel_size, targeted_attack=False, verbose=False, true_label=None):
-        p = self.step_and_predict(x, im, classifier, pixel_size)
-        if verbose:
-            self._report(target_idx, p[0, target_idx], p[0].argmax(), p[0].max(), targeted_attack, true_label)
-        if (targeted_attack and p[0].argmax() == target_idx) or (not targeted_attack and p[0].argmax() != target_idx):
-            return True
+    def _gt(self, true_label):       # (the driver passes the true class's name)
+        return f'{true_label:<15}'
 
     def attack(self, im, classifier, targeted_attack=False, target_idx=None, pixel_count=1, pixel_size=1, maxiter=75, popsize=400,
                verbose=False, true_label=None, *, updating='immediate', seed=None, max_batch=None, trace=None):
@@ -409,8 +410,3 @@ class ProjectorOnePixelAttacker:
             _, p, _ = classifier(torch.stack((cc(self.im_cam_org.to(im_cam_adv.device), self.classifier_crop_sz),
                                               cc(im_cam_adv, self.classifier_crop_sz)), 0), self.classifier_crop_sz)
         return _result_frame(classifier, p, pixel_count, target_idx, targeted_attack), im_prj_adv, im_cam_adv
-
-    def __call__(self, im, classifier, targeted_attack=False, target_idx=None, pixel_count=1, pixel_size=1, maxiter=75, popsize=400,
-                 verbose=False, true_label=None, **kw):
-        return self.attack(im, classifier, targeted_attack, target_idx, pixel_count, pixel_size, maxiter, popsize, verbose,
-                           true_label, **kw)

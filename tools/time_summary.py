@@ -1,4 +1,4 @@
-"""Wall time of summarize_single_attacker (spaa_amd/projector_based_attack.py) on a synthetic SPAA setup at the reference's geometry,
+"""Wall time of summarize_single_attacker (spaa_amd/attack_summary.py) on a synthetic SPAA setup at the reference's geometry,
 against the same summary computed the way the reference's loop does it (projector_based_attack.py:448-541: per configuration, the
 classifier on the scene, the inferred and the captured images, and one metrics.calc_img_dists per group).
 
