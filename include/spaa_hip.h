@@ -591,6 +591,31 @@ int spaa_step_and_track_n(float* x, const float* g, const float* partial, int np
                           float col_lr, float* x_best, const float* cam, float* cam_best, int B, int HWp, int HWc,
                           uint8_t* clamp_bits, spaa_stream_t stream);
 
+/* ---- ensemble SPAA: one projection against K classifiers on the same camera image, 2 <= K <= SPAA_ENS_MAX ----------------- */
+#define SPAA_ENS_MAX 4
+/* Member tensors are passed as HOST arrays of K device pointers (copied into the launch's arguments: no device pointer table).
+ * Any other K is hipErrorInvalidValue and nothing is launched.
+ *
+ * The decision over K members' logits ([B][ncls] each), per-sample table form only (params, flags as spaa_decide_ps).  Member k of
+ * sample b: top1, p1 and the target logit by the arithmetic of spaa_decide; succ = (top1 == target) if targeted else (top1 != target);
+ * fooled = succ && p1 > p_thresh if targeted else succ.  Outputs:
+ *   state [B][4]: 0 every member succ, 1 best_adv = every member fooled && caml2 * 255 > d_thr, 2 best, 3 number of fooled members
+ *   stats [B][8]: 0 min over members of p1, 6 mean over members of the target logit, 1..5 as spaa_decide
+ *   ens_state int32 [B][K][2] = (bit 0 succ | bit 1 fooled, top1)    ens_stats float [B][K][2] = (p1, target logit)
+ *   ens_w float [B][K]: the member weights of spaa_ens_combine -- 1, or with focus != 0: 0 for a fooled member unless all are fooled
+ *   g_logits: K seeds [B][ncls], (c == target_b) ? -1 (targeted) / +1 : 0 */
+int spaa_decide_ens(const float* const* logits, int K, int ncls, const int32_t* target, const float* partial, int nblk, int HW,
+                    const float* prjl2, const float* params, const int32_t* flags, float p_thresh, int focus, int32_t* state,
+                    float* stats, int32_t* ens_state, float* ens_stats, float* ens_w, float* const* g_logits, int B,
+                    spaa_stream_t stream);
+/* 256-pixel block partials of the K gradient images' squared norms over the colour channels (g[k]: [B][HW][4], the pad channel is
+ * ignored) -> partial [B][K][ceil(HW / 256)] */
+int spaa_ens_sumsq(const float* const* g, int K, float* partial, int B, int HW, spaa_stream_t stream);
+/* g_adv_b = sum over k in index order of ens_w[b][k] * g_bk / ||g_bk||_2 in fp32; a member with zero norm contributes 0; the pad
+ * channel of g_adv [B][HW][4] is 0.  partial from spaa_ens_sumsq with nblk = ceil(HW / 256); run-to-run bitwise reproducible */
+int spaa_ens_combine(const float* const* g, int K, const float* partial, int nblk, const float* ens_w, float* g_adv, int B, int HW,
+                     spaa_stream_t stream);
+
 /* ---- PerC_AL.adversary_projector (perc_al/__init__.py:133-256) ------------------------------------------ */
 /* x = a + b (inputs + delta), NHWC4 */
 int spaa_add_nhwc4(const float* a, const float* b, float* x, int npix, spaa_stream_t stream);

@@ -67,6 +67,7 @@ class PngImg(C.Structure):
 
 
 _i, _f, _p, _l, _d = C.c_int, C.c_float, C.c_void_p, C.c_int64, C.c_double
+_pp = C.POINTER(C.c_void_p)   # a HOST array of device pointers (ptr_array)
 
 # name -> argument types (all return int)
 _SIGNATURES = {
@@ -150,6 +151,9 @@ _SIGNATURES = {
     'spaa_grad_sumsq_ps': [_p, _p, _f, _p, _p, _p, _i, _i, _p],
     'spaa_step_and_track': [_p, _p, _p, _p, _f, _f, _p, _p, _p, _i, _i, _i, _p],
     'spaa_step_and_track_n': [_p, _p, _p, _i, _p, _f, _f, _p, _p, _p, _i, _i, _i, _p, _p],
+    'spaa_decide_ens': [_pp, _i, _i, _p, _p, _i, _i, _p, _p, _p, _f, _i, _p, _p, _p, _p, _p, _pp, _i, _p],
+    'spaa_ens_sumsq': [_pp, _i, _p, _i, _i, _p],
+    'spaa_ens_combine': [_pp, _i, _p, _i, _p, _p, _i, _i, _p],
     'spaa_onepixel_preproc': [_p, _p, _i, _i, _i, _p, _i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_float), C.POINTER(C.c_float), _p],
     'spaa_onepixel_score': [_p, _i, _i, _i, _p, _p, _p, _i, _p],
     'spaa_onepixel_warp': [_p, _p, _i, _i, _i, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p],
@@ -227,6 +231,11 @@ def ptr(t):
         return None
     _same_device(t)
     return C.c_void_p(t.data_ptr())
+
+
+def ptr_array(tensors):
+    """The HOST array of device pointers that the ensemble entry points take (one per member tensor)."""
+    return (C.c_void_p * len(tensors))(*[ptr(t).value for t in tensors])
 
 
 def hptr(t):

@@ -100,8 +100,18 @@ def _one_setup(cfg, who=''):
     return cfg.setup_list[0]
 
 
+def ensemble_members(classifier_name):
+    """The member names of an entry of cfg.classifier_names: 'a+b+c' is the ensemble of a, b and c, in the written order; a name
+    without '+' is its own only member."""
+    members = classifier_name.split('+')
+    if not all(members):
+        raise ValueError(f'classifier name {classifier_name!r}: an empty member name')
+    return members
+
+
 def _require_classifiers(cfg, classifiers):
-    missing = [c for c in cfg.classifier_names if c not in (classifiers or {})]
+    names = [m for c in cfg.classifier_names for m in ensemble_members(c)]
+    missing = [c for c in dict.fromkeys(names) if c not in (classifiers or {})]
     if missing:
         raise ValueError(f'run_projector_based_attack: pass classifiers={{name: spaa_amd.Classifier}} for {missing} '
                          '(weights cannot be downloaded here)')
@@ -152,6 +162,9 @@ def run_projector_based_attack(cfg, *, models=None, classifiers=None, iters=50, 
     imagenet10 classes) and 1 untargeted attack (the scene's top-1) for every stealth loss x d_thr; results under
     <setup>/prj/adv and <setup>/cam/infer/adv / <attacker_cfg_str>/<loss>/<d_thr>/<classifier>/img_0001..0011.png (1-10 targeted,
     11 untargeted).  For SPAA one classifier's whole sweep is ONE spaa_sweep call.
+    A name with '+' in cfg.classifier_names, such as 'inception_v3+resnet18+vgg16', is the ensemble of the named members of
+    `classifiers` (SPAA only): one projection per sample against all of them, written to a folder of that name like any classifier's.
+    Its untargeted label is the scene's top-1 under the FIRST member; a warning is printed when the members disagree on the scene.
     `models`: setup name -> trained PCNet (SPAA) / CompenNetPlusplus (PerC-AL+CompenNet++); `classifiers`: classifier name ->
     spaa_amd.Classifier (the reference downloads the classifier weights here; that is not done).
     `train=True`: a setup without an entry in `models` is trained, or with cfg.load_pretrained loaded from its checkpoint, as the
@@ -189,8 +202,19 @@ def run_projector_based_attack(cfg, *, models=None, classifiers=None, iters=50, 
         imagenet_labels, target_idx = setup.imagenet_labels(), setup.target_idx()
         _freeze(model)
         for classifier_name in cfg.classifier_names:
-            classifier = classifiers[classifier_name]
-            true_idx, _ = _scene_top1(classifier, cam_scene, setup.crop_sz)
+            members = ensemble_members(classifier_name)
+            if len(members) > 1:
+                if name != 'SPAA':
+                    raise NotImplementedError(f'{name}: classifier ensembles ({classifier_name!r}) are attacked by SPAA only')
+                classifier = [classifiers[m] for m in members]
+                tops = [_scene_top1(c, cam_scene, setup.crop_sz)[0] for c in classifier]
+                true_idx = tops[0]
+                if any(t != true_idx for t in tops):
+                    print(f'warning: the members of [{classifier_name}] disagree on the unattacked scene (top-1 {dict(zip(members, tops))}); '
+                          f'the untargeted attack uses {members[0]}\'s label {true_idx}')
+            else:
+                classifier = classifiers[classifier_name]
+                true_idx, _ = _scene_top1(classifier, cam_scene, setup.crop_sz)
             if name == 'SPAA':
                 configs = [c for loss, d_thr in grid for c in ((loss, d_thr, True, target_idx), (loss, d_thr, False, [true_idx]))]
                 res = core.spaa_sweep(model, classifier, imagenet_labels, cam_scene, setup.info, device, configs, iters=iters)

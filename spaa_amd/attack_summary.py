@@ -62,6 +62,22 @@ def attack_success(idx_infer, idx_real, idx_scene, target_idx):
             int(np.count_nonzero(idx_real[n, 0] != true_idx)))
 
 
+def attack_transfer(ims, classifiers, target_idx, targeted, crop_sz):
+    """Which classifier each adversarial image fools: bool [N][K] for the images `ims` [N,3,H,W], the K `classifiers` and one class id
+    per image in `target_idx`; `targeted` (one flag, or one per image): top-1 == target, else top-1 != target (the image's true class).
+    The evaluation hook of an ensemble attack: column k is member k.  Top-1 through _sorted_classes, as the summary's rates."""
+    n = ims.shape[0]
+    tgt = np.asarray([int(t) for t in target_idx])
+    tg = np.full(n, bool(targeted)) if np.ndim(targeted) == 0 else np.asarray([bool(t) for t in targeted])
+    if tgt.shape != (n,) or tg.shape != (n,):
+        raise ValueError(f'attack_transfer: {n} images, {tgt.size} targets, {tg.size} targeted flags')
+    out = np.zeros((n, len(classifiers)), dtype=bool)
+    for k, clf in enumerate(classifiers):
+        top1 = _sorted_classes(clf, [ims], crop_sz)[0][:, 0]
+        out[:, k] = np.where(tg, top1 == tgt, top1 != tgt)
+    return out
+
+
 def write_stats(table, path):
     """The reference's table files: tab-separated, 4 decimals (stats.txt, stats_all.txt)."""
     table.to_csv(path, index=False, float_format='%.4f', sep='\t')

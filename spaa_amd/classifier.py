@@ -466,6 +466,11 @@ class Classifier(object):
         self.state_dict = {k: v.detach().float().cpu() for k, v in _strip(state_dict).items()}
         self._engines = {}
 
+    @property
+    def num_classes(self):
+        """Rows of the last linear layer (what an engine reports as `ncls`), read from the weights: no engine is built."""
+        return int(self.state_dict['classifier.6.weight' if self.name == 'vgg16' else 'fc.weight'].shape[0])
+
     def engine(self, batch, im_hw, crop_sz, owner=None, storage='f32'):
         """Cached engine for a batch size / geometry; an engine leased to an `owner` (attack state) is not handed to
         anyone else while the owner lives (see PCNet.engine).  `storage`: 'f32' or 'f16' (fp16 activations in HBM)."""

@@ -11,6 +11,7 @@
 #include <stdint.h>
 #include "../../include/spaa_hip.h"
 #include "device_util.hpp"
+#include "decide_util.hpp"
 
 namespace {
 
@@ -24,9 +25,7 @@ __global__ __launch_bounds__(256) void decide_kernel(const float* __restrict__ l
                                                      int32_t* __restrict__ state, float* __restrict__ stats,
                                                      float* __restrict__ g_logits, const float* __restrict__ params,
                                                      const int32_t* __restrict__ flags) {
-    __shared__ float red[4];
-    __shared__ float s_max[4];
-    __shared__ int s_arg[4];
+    __shared__ DecideLds lds;
     const int b = blockIdx.x;
     // spaa_decide_ps: this sample's (prjl2_w, caml2_w, camdE_w, d_thr) and targeted flag replace the scalars (uniform per workgroup)
     if (params != nullptr) {
@@ -37,77 +36,27 @@ __global__ __launch_bounds__(256) void decide_kernel(const float* __restrict__ l
         targeted = flags[b] & 1;
     }
     const float* lg = logits + (size_t)b * ncls;
-    // argmax (first maximum) and max
-    float mx = -INFINITY;
-    int am = 0x7fffffff;
-    for (int i = threadIdx.x; i < ncls; i += 256) {
-        const float v = lg[i];
-        if (v > mx) {
-            mx = v;
-            am = i;
-        }
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const float ov = __shfl_down(mx, off, 64);
-        const int oa = __shfl_down(am, off, 64);
-        if (ov > mx || (ov == mx && oa < am)) {
-            mx = ov;
-            am = oa;
-        }
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) {
-        s_max[wave] = mx;
-        s_arg[wave] = am;
-    }
-    __syncthreads();
-    mx = s_max[0];
-    am = s_arg[0];
-    for (int w = 1; w < 4; ++w) {
-        if (s_max[w] > mx || (s_max[w] == mx && s_arg[w] < am)) {
-            mx = s_max[w];
-            am = s_arg[w];
-        }
-    }
-    // softmax top-1 probability = 1 / sum exp(l - max)   (classifier.py:64)
-    float se = 0.f;
-    for (int i = threadIdx.x; i < ncls; i += 256) se += expf(lg[i] - mx);
-    se = block_sum(se, red);
-    const float p1 = 1.f / se;
-    // loss sums (fixed order)
-    float a = 0.f, d = 0.f;
-    const float* pp = partial + 3 * (size_t)b * nblk;
-    for (int i = threadIdx.x; i < nblk; i += 256) {
-        a += pp[3 * i];
-        d += pp[3 * i + 1];
-    }
-    a = block_sum(a, red);
-    d = block_sum(d, red);
+    // argmax (first maximum), softmax top-1 probability and the loss sums (fixed order): decide_util.hpp, shared with the ensemble form
+    int am;
+    float p1, a, d;
+    decide_top1(lg, ncls, lds, am, p1);
+    decide_loss_sums(partial + 3 * (size_t)b * nblk, nblk, lds, a, d);
     const int tgt = target[b];
     // d adv_loss / d logits: adv_loss = -/+ mean_b logit[b, target_b]   (:269-272)
     for (int i = threadIdx.x; i < ncls; i += 256)
         g_logits[(size_t)b * ncls + i] = (i == tgt) ? (targeted ? -adv_scale : adv_scale) : 0.f;
     if (threadIdx.x == 0) {
-        const float caml2 = a / (float)HW;
-        const float camdE = d / (float)HW;
         // (per-sample mode: a sample without the prjl2 term reads 0, as the scalar launch whose caller passes prjl2 = NULL)
         const float pl2 = (prjl2 != nullptr && (params == nullptr || prjl2_w != 0.f)) ? prjl2[b] : 0.f;
-        float col = prjl2_w * pl2;
-        col += caml2_w * caml2;
-        col += camdE_w * camdE;
+        float* st = stats + 8 * (size_t)b;
+        float col;
+        const bool high_pert = decide_losses(a, d, HW, pl2, prjl2_w, caml2_w, camdE_w, d_thr, st, col);
         const bool high_conf = p1 > p_thresh;
-        const bool high_pert = caml2 * 255.f > d_thr;
         const bool succ = targeted ? (am == tgt) : (am != tgt);
         const bool best_adv = targeted ? (succ && high_conf && high_pert) : (succ && high_pert);
-        float* st = stats + 8 * (size_t)b;
         const bool best = best_adv && (col < st[5]);
         if (best) st[5] = col;
         st[0] = p1;
-        st[1] = caml2;
-        st[2] = camdE;
-        st[3] = col;
-        st[4] = pl2;
         st[6] = lg[tgt];
         int32_t* s = state + 4 * (size_t)b;
         s[0] = succ;

@@ -142,16 +142,16 @@ class AttackState:
         self.ps_flags = torch.zeros(B, dtype=torch.int32, device=dev)
         self.ps_prjl2_scale = torch.zeros(B, device=dev)
 
-    def _per_sample(self, targeted, d_thr):
+    def _per_sample(self, targeted, d_thr, table=False):
         """The batch's (targeted, d_thr) as scalars when every sample agrees and the loss weights are uniform (the launches of a single
-        attack, unchanged); else uploads the per-sample table (once per distinct setting: a captured graph replays the table it
-        read) and returns None."""
+        attack, unchanged); else, or with `table` always, uploads the per-sample table (once per distinct setting: a captured graph
+        replays the table it read) and returns None."""
         B = self.B
         tg = [bool(targeted)] * B if _is_scalar(targeted) else [bool(t) for t in targeted]
         dt = [float(d_thr)] * B if _is_scalar(d_thr) else [float(d) for d in d_thr]
         if len(tg) != B or len(dt) != B:
             raise ValueError(f'targeted / d_thr: one value or {B} values')
-        if self.caml2_w is not None and all(t == tg[0] for t in tg) and all(d == dt[0] for d in dt):
+        if not table and self.caml2_w is not None and all(t == tg[0] for t in tg) and all(d == dt[0] for d in dt):
             return tg[0], dt[0]
         key = (tuple(tg), tuple(dt))
         if key != self._ps_key:
@@ -205,9 +205,17 @@ class AttackState:
                   self.camdE_w, float(d_thr), float(p_thresh), adv_w / B * self.gs_adv, p(self.state), p(self.stats),
                   p(self.g_logits), B)                                               # :269-272, :290-299, :318-320
 
+    def _adv_gradient(self):
+        """The adversarial loss's gradient at the camera image [B,Hc,Wc,4]: the classifier's backward pass from the seed of the decision."""
+        return self.clf.backward(self.g_logits)                                      # :302 (classifier part)
+
+    def trace_entry(self):
+        """What spaa()'s `trace` records per iteration (copies; no sync)."""
+        return self.state.clone(), self.stats.clone()
+
     def _backward_step(self, adv_lr, col_lr):
         B, p, y = self.B, _lib.ptr, self._y
-        g_adv = self.clf.backward(self.g_logits)                                     # :302 (classifier part)
+        g_adv = self._adv_gradient()
         # (mixed configurations: the prjl2 scale is a [B] device tensor, and the sums of squares take the _ps launches)
         prjl2_scale = self.prjl2_w / (B * self.HWp) * self.gs_col if self._uniform else self.ps_prjl2_scale
         ss = (self.partial_ss, self.gray, prjl2_scale, self.state) if self.ss_tiles else None   # (||g||^2 from the adjoint's epilogue)
@@ -233,12 +241,101 @@ class AttackState:
             return to_nchw(self.cam_best), to_nchw(self.x_best, clamp01=True)        # :337
 
 
+ENS_MAX = 4   # SPAA_ENS_MAX of include/spaa_hip.h
+
+
+def _ensemble_members(classifier, storage, who):
+    """The members of a list / tuple `classifier`, checked (before anything is allocated or launched): each a spaa_amd.Classifier (no
+    foreign-callable route for ensembles), at most ENS_MAX of them, no object twice, one number of classes; fp32 storage."""
+    members = [_unwrap(c) for c in classifier]
+    if not members:
+        raise ValueError(f'{who}: the classifier sequence is empty')
+    for c in members:
+        if not isinstance(c, Classifier):
+            raise TypeError(f'{who}: every member of a classifier ensemble must be a spaa_amd.Classifier, got {type(c).__name__} '
+                            '(a foreign callable can only be attacked alone)')
+    if len(members) > ENS_MAX:
+        raise ValueError(f'{who}: an ensemble holds at most {ENS_MAX} classifiers, got {len(members)}')
+    if len({id(c) for c in members}) != len(members):
+        raise ValueError(f'{who}: the same Classifier object is listed twice in the ensemble')
+    ncls = [c.num_classes for c in members]
+    if any(n != ncls[0] for n in ncls):
+        raise ValueError(f'{who}: the members of an ensemble must have the same number of classes, got {ncls}')
+    if len(members) >= 2 and storage != 'f32':
+        raise NotImplementedError(f"{who}: storage={storage!r} is not implemented for an ensemble (the members' unit vectors need a loss "
+                                  "scale of their own); use storage='f32'")
+    return members
+
+
+class EnsembleAttackState(AttackState):
+    """One batched attack against K = 2..ENS_MAX classifiers that see the same camera image ("Ensemble attack"): AttackState
+    with one leased engine per member, the decision over all members (spaa_decide_ens) and, as adversarial cotangent, the weighted sum
+    of the members' unit gradient images (spaa_ens_sumsq + spaa_ens_combine).  PCNet's passes, the stealth loss, the colour step, the
+    normalised step and the best tracking are AttackState's.  `state[:, 3]` counts the fooled members; each member's top-1 is in
+    `ens_state`.  `focus`: a member that is already fooled rests (weight 0) until all are."""
+
+    def __init__(self, pcnet, classifiers, target_idx, cam_scene, stealth_loss, setup_info, device, storage='f32', focus=False):
+        self.members = _ensemble_members(classifiers, storage, 'EnsembleAttackState')
+        if len(self.members) < 2:
+            raise ValueError('EnsembleAttackState needs at least two classifiers (AttackState attacks one)')
+        self.focus = bool(focus)
+        super().__init__(pcnet, self.members[0], target_idx, cam_scene, stealth_loss, setup_info, device, storage=storage)
+
+    def _build(self, pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, dev):
+        super()._build(pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, dev)   # (leases member 0's engine: self.clf)
+        B, K = self.B, len(self.members)
+        self.K = K
+        self.clfs = [self.clf] + [c.engine(B, (self.eng.Hc, self.eng.Wc), self.cp_sz, owner=self, storage=self.storage)
+                                  for c in self.members[1:]]
+        self.ens_g_logits = [self.g_logits] + [torch.zeros_like(self.g_logits) for _ in range(K - 1)]
+        self.ens_state = torch.zeros(B, K, 2, dtype=torch.int32, device=dev)
+        self.ens_stats = torch.zeros(B, K, 2, device=dev)
+        self.ens_w = torch.ones(B, K, device=dev)
+        self.ens_partial = torch.zeros(B, K, self.nblk_c, device=dev)
+        self.g_adv = torch.zeros(B, self.eng.Hc, self.eng.Wc, 4, device=dev)
+
+    def _forward_decide(self, targeted, d_thr, p_thresh, adv_w):
+        B, p = self.B, _lib.ptr
+        self._per_sample(targeted, d_thr, table=True)   # (the ensemble decision has the per-sample table form only)
+        y = self.eng.forward(self.x, clamp01=True)                                   # :265
+        logits = [e.forward(y) for e in self.clfs]                                   # :266, once per member
+        self._y, self._uniform = y, False
+        if self.any_prjl2:
+            _lib.call('spaa_prjl2_fwd', p(self.x), self.gray, p(self.prjl2), B, self.HWp)
+        _lib.call('spaa_stealth_loss_fwd_bwd_ps', p(y), p(self.scene4), p(self.scene_lab), p(self.ps_params),
+                  self.gs_col / (B * self.HWc), p(self.g_col), None, p(self.partial_loss), B, self.HWc)
+        _lib.call('spaa_decide_ens', _lib.ptr_array(logits), self.K, self.clf.ncls, p(self.target), p(self.partial_loss), self.nblk_c,
+                  self.HWc, p(self.prjl2) if self.any_prjl2 else None, p(self.ps_params), p(self.ps_flags), float(p_thresh),
+                  int(self.focus), p(self.state), p(self.stats), p(self.ens_state), p(self.ens_stats), p(self.ens_w),
+                  _lib.ptr_array(self.ens_g_logits), B)
+
+    def _adv_gradient(self):
+        gs = _lib.ptr_array([e.backward(g) for e, g in zip(self.clfs, self.ens_g_logits)])
+        _lib.call('spaa_ens_sumsq', gs, self.K, _lib.ptr(self.ens_partial), self.B, self.HWc)
+        _lib.call('spaa_ens_combine', gs, self.K, _lib.ptr(self.ens_partial), self.nblk_c, _lib.ptr(self.ens_w), _lib.ptr(self.g_adv),
+                  self.B, self.HWc)
+        return self.g_adv
+
+    def trace_entry(self):
+        return super().trace_entry() + (self.ens_state.clone(), self.ens_stats.clone())
+
+
+def _attack_state(pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, device, storage, focus):
+    """AttackState for one Classifier, EnsembleAttackState for a checked list of several."""
+    if isinstance(classifier, list):
+        return EnsembleAttackState(pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, device, storage=storage,
+                                   focus=focus)
+    return AttackState(pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, device, storage=storage)
+
+
 def spaa(pcnet, classifier, imagenet_labels, target_idx, targeted, cam_scene, d_thr, stealth_loss, device, setup_info,
-         *, iters=50, adv_lr=2, col_lr=1, p_thresh=0.9, trace=None, verbose=False, storage='f32'):
+         *, iters=50, adv_lr=2, col_lr=1, p_thresh=0.9, trace=None, verbose=False, storage='f32', focus=False):
     """Stealthy Projector-based Adversarial Attack (SPAA Algorithm 1) — see module docstring.
 
     :param pcnet: spaa_amd.PCNet (optionally wrapped in DataParallel-like `.module`)
-    :param classifier: spaa_amd.Classifier
+    :param classifier: spaa_amd.Classifier, or a list / tuple of 2..4 of them with the same classes: ONE projection against all of them
+        (EnsembleAttackState; fp32 storage only).  A sequence of one is that classifier.
+    :param focus: ensembles only: members that are already fooled rest until all are (default: every member pulls all the time)
     :param imagenet_labels: dict idx -> name (only used when verbose)
     :param target_idx: list of B class ids (true label if untargeted)
     :param targeted: bool
@@ -246,24 +343,32 @@ def spaa(pcnet, classifier, imagenet_labels, target_idx, targeted, cam_scene, d_
     :param d_thr: SPAA Algorithm 1's threshold on the mean per-pixel L2 perturbation (x255)
     :param stealth_loss: string containing any of 'prjl2', 'caml2', 'camdE'
     :param setup_info: {'classifier_crop_sz', 'prj_brightness', 'prj_im_sz'}
-    :param trace: optional list; receives per-iteration (state, stats) device tensors (no sync inside the loop)
+    :param trace: optional list; receives per-iteration (state, stats) device tensors (no sync inside the loop); for an ensemble
+        (state, stats, ens_state, ens_stats), where state[:, 3] counts the fooled members and ens_state holds each member's top-1
     :return: (cam_infer_best [B,3,Hc,Wc], prj_adv_best [B,3,Hp,Wp] in [0,1])
     """
     pcnet, classifier = _unwrap(pcnet), _unwrap(classifier)
     if not isinstance(pcnet, PCNet):
         raise TypeError('spaa_amd.spaa needs a spaa_amd.PCNet (the HIP path has no generic PCNet fallback)')
-    if not isinstance(classifier, Classifier):
+    if isinstance(classifier, (list, tuple)):
+        classifier = _ensemble_members(classifier, storage, 'spaa')
+        if len(classifier) == 1:
+            classifier = classifier[0]
+    if not isinstance(classifier, (Classifier, list)):
         if not callable(classifier):
             raise TypeError('classifier must be a spaa_amd.Classifier or a callable (im, crop_sz) -> (raw_score, p, idx)')
         return _spaa_foreign_classifier(pcnet, classifier, imagenet_labels, target_idx, targeted, cam_scene, d_thr,
                                         stealth_loss, device, setup_info, iters, adv_lr, col_lr, p_thresh, trace)
-    st = AttackState(pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, device, storage=storage)
+    st = _attack_state(pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, device, storage, focus)
 
     def report(i):
         if i % 30 == 0 or i == iters - 1:
             s, f = st.state.cpu(), st.stats.cpu()
             v = 7 if (targeted and st.B > 7) else 0
-            name = imagenet_labels[int(s[v, 3])] if imagenet_labels else ''
+            if isinstance(st, EnsembleAttackState):   # (p = the least confident member's; y = how many members are fooled)
+                name = f'of {st.K} members fooled'
+            else:
+                name = imagenet_labels[int(s[v, 3])] if imagenet_labels else ''
             print(f'col_loss = {f[:, 3].mean():<9.4f} | prjl2 = {f[:, 4].mean() * 255:<9.4f} | caml2 = '
                   f'{f[:, 1].mean() * 255:<9.4f} | camdE = {f[:, 2].mean():<9.4f} | p = {f[v, 0]:.4f} | y = '
                   f'{int(s[v, 3]):3d} ({name})')
@@ -305,7 +410,7 @@ def _run(st, targeted, d_thr, iters, adv_lr, col_lr, p_thresh, trace=None, repor
     for i in range(iters):
         st.iteration(targeted, d_thr, adv_lr, col_lr, p_thresh)
         if trace is not None:
-            trace.append((st.state.clone(), st.stats.clone()))
+            trace.append(st.trace_entry())
         if report is not None:
             report(i)
 
@@ -350,19 +455,25 @@ def split_sweep(samples, ncfg, chunk_results):
 
 
 def spaa_sweep(pcnet, classifier, imagenet_labels, cam_scene, setup_info, device, configs, *, iters=50, adv_lr=2, col_lr=1,
-               p_thresh=0.9, max_batch=64, storage='f32', trace=None):
+               p_thresh=0.9, max_batch=64, storage='f32', trace=None, focus=False):
     """Several SPAA attacks on one PCNet, scene and classifier as few batched attacks (the reference's driver makes one spaa() call
     per configuration: projector_based_attack.py:24-148).  `configs`: [(stealth_loss, d_thr, targeted, target_idx), ...]; returns one
     (cam_infer_best, prj_adv_best) per config, in order -- what spaa(pcnet, classifier, imagenet_labels, target_idx, targeted,
     cam_scene, d_thr, stealth_loss, device, setup_info) returns for it: samples do not interact, so only the batch differs.  The
     samples of all configs are flattened in order and cut into chunks of at most `max_batch` (one AttackState each, the loop of
     spaa() with its loss weights, targeted flag and d_thr per sample); `trace` receives one list per chunk, of the per-iteration
-    (state, stats) pairs spaa() records (the chunk's samples in flattened order)."""
+    (state, stats) pairs spaa() records (the chunk's samples in flattened order).  `classifier` may be a list / tuple of 2..4
+    Classifiers, as in spaa(): every sample then attacks all of them at once (`focus` as there), and the trace entries are
+    (state, stats, ens_state, ens_stats)."""
     samples, chunks = plan_sweep(configs, max_batch)
     pcnet, classifier = _unwrap(pcnet), _unwrap(classifier)
     if not isinstance(pcnet, PCNet):
         raise TypeError('spaa_sweep needs a spaa_amd.PCNet (the HIP path has no generic PCNet fallback)')
-    if not isinstance(classifier, Classifier):
+    if isinstance(classifier, (list, tuple)):
+        classifier = _ensemble_members(classifier, storage, 'spaa_sweep')
+        if len(classifier) == 1:
+            classifier = classifier[0]
+    if not isinstance(classifier, (Classifier, list)):
         raise TypeError('spaa_sweep needs a spaa_amd.Classifier')
     _require_gpu(device, 'spaa_sweep')
     sc = _scene_batch(cam_scene, 1)
@@ -372,7 +483,7 @@ def spaa_sweep(pcnet, classifier, imagenet_labels, cam_scene, setup_info, device
     results = []
     for a, b in chunks:
         part = samples[a:b]
-        st = AttackState(pcnet, classifier, [t for *_, t in part], sc, [s[1] for s in part], setup_info, device, storage=storage)
+        st = _attack_state(pcnet, classifier, [t for *_, t in part], sc, [s[1] for s in part], setup_info, device, storage, focus)
         tr = [] if trace is not None else None
         _run(st, [s[3] for s in part], [s[2] for s in part], iters, adv_lr, col_lr, p_thresh, tr)
         if trace is not None:
@@ -468,4 +579,4 @@ from .attack_driver import (ATTACKERS, MODEL_TRAIN_CFG, AttackSetup, get_attacke
                             run_projector_based_attack, _run_one_pixel_de, project_capture_real_attack)
 from .attack_summary import (SUMMARY_STEALTH_LOSSES, SUMMARY_D_THRESHES, SUMMARY_CLASSIFIERS, SUMMARY_CHUNK,   # noqa: E402,F401
                              SUMMARY_COLUMNS, MONTAGE_CHUNK, attack_success, write_stats, _sorted_classes, _nonempty,
-                             attack_results, summarize_single_attacker, summarize_all_attackers)
+                             attack_results, attack_transfer, summarize_single_attacker, summarize_all_attackers)

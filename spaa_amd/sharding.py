@@ -55,7 +55,9 @@ def spaa_sharded(pcnet, classifier, imagenet_labels, target_idx, targeted, cam_s
                  setup_info, dist=None, attack=None, always_collective=False, **kw):
     """`spaa()` over this rank's block of the batch, then one gather. `cam_scene`: [1|B,3,H,W].
     A rank whose block is empty (fewer samples than ranks) runs no attack and contributes zero-length blocks, so every
-    rank still enters the collective.  `attack` replaces `spaa` (the CPU tests pass a stand-in)."""
+    rank still enters the collective.  `attack` replaces `spaa` (the CPU tests pass a stand-in).  `classifier` is passed through as it
+    is, so a list of Classifiers (an ensemble, with `focus=` among the keywords) shards like a single one: every rank attacks all
+    members on its block of samples."""
     if attack is None:
         from .projector_based_attack import spaa as attack
     n = len(target_idx)
