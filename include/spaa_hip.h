@@ -24,7 +24,7 @@ typedef void* spaa_stream_t; /* hipStream_t */
 
 #define SPAA_MAX_CLASSES 4
 #define SPAA_MAX_TAPS 64
-#define SPAA_SPLITK_HDR_FLOATS 4096 /* arrival counters at the head of a K-range workspace (spaa_tapconv_t.reserved1 bit 8) */
+#define SPAA_SPLITK_HDR_FLOATS 4096 /* arrival counters at the head of a K-range workspace (SPAA_SPLITK_FIXUP) */
 
 /* activation applied after bias + residual add */
 enum { SPAA_ACT_NONE = 0, SPAA_ACT_RELU = 1, SPAA_ACT_RELU_CLAMP1 = 2, SPAA_ACT_LEAKY01 = 3 };
@@ -42,6 +42,62 @@ typedef struct {
     int32_t Kpad;      /* K rounded up to 32 */
     int64_t w_off;     /* float offset of this class's packed weights [Npad][Kpad] */
 } spaa_tapclass_t;
+
+/*
+ * Per-tile FORM FLAGS of a launch: the bits of spaa_tapconv_t.reserved0 / reserved1 / reserved2.  Which kernel form a tile runs is
+ * asked for here, by name; a name is the mask IN its word, and a field wider than one bit has a NAME_SHIFT next to it (value =
+ * (word & NAME) >> NAME_SHIFT).  A name holds for the tiles stated: the same bit means something else, or nothing, elsewhere.
+ * spaa_amd/_lib.py mirrors the names without the SPAA_ prefix (tests/test_cabi_cpu.py pins the two to each other).
+ *
+ * The product (spaa_amd/convplan.py with no switch set) sets SPAA_WINO_PAD, SPAA_C3_F16_OPERANDS, SPAA_H16P_CV with SPAA_H16P_CV_BN,
+ * SPAA_H16P_LEAN_WIDE, SPAA_H16P_POOL, SPAA_H16P_UNPOOL and SPAA_X6P_STD, and the Winograd launcher sets SPAA_WINO_NO_CANVAS on its
+ * own copy.  Everything else is a measurement (A/B run, timing ablation) or test switch, clear in a default launch.
+ */
+enum {
+    /* ---- reserved0, every tile: measurement and test switches (spaa_amd/convplan.py DEBUG_*) ---- */
+    SPAA_DBG_X6D_TAPMAJOR = 1 << 0,      /* x6d kernels: tap-major K order (A/B runs) */
+    SPAA_DBG_PERSIST_CAP = 0xff << 8, SPAA_DBG_PERSIST_CAP_SHIFT = 8,   /* persistent x6d launches: > 0 = that many workgroups (tests: several tiles per workgroup on small layers) */
+    SPAA_DBG_X6P_ABLATE = 0xff << 8, SPAA_DBG_X6P_ABLATE_SHIFT = 8,     /* the same bits in the -DSPAA_X6P_STAMP build of tile 74: timing-only ablation mask (wrong results) */
+    SPAA_DBG_WINO_VAR = 3 << 16, SPAA_DBG_WINO_VAR_SHIFT = 16,          /* Winograd tiles: flips the bits of the launcher's kernel variant (A/B runs) */
+    SPAA_DBG_WINO_ABLATE = 127 << 18, SPAA_DBG_WINO_ABLATE_SHIFT = 18,  /* Winograd tiles in a -DSPAA_WINO_ABLATE build: timing-only ablation mask (wrong results) */
+    SPAA_DBG_H16_2STAGE = 1 << 25,       /* fp16 implicit-GEMM tiles: never the four-stage form (A/B runs) */
+    SPAA_DBG_SMALLCIN_NOSLAB = 1 << 26,  /* smallcin tile: stride-2 layers with a residual store from the MFMA layout (A/B runs) */
+    /* ---- reserved0, tile 72 only ---- */
+    SPAA_DBG_THINMF = 7 << 27, SPAA_DBG_THINMF_SHIFT = 27,              /* -DSPAA_THINMF_ABLATE build: timing-only ablation mask (wrong results) */
+    /* ---- reserved0, Winograd tiles (70 / 71 / 73) only ---- */
+    SPAA_WINO_PAD = 3 << 27, SPAA_WINO_PAD_SHIFT = 27,   /* PRODUCT INPUT: the layer's zero padding as a code, 0 = pad 1 (same-size output), 1 = pad 0
+                                                            (unpadded: output 2 smaller), 2 = pad 2 (that layer's input gradient: 2 larger) */
+    SPAA_WINO_FORCE_CANVAS = 1 << 29,    /* tests: the canvas layout wherever it has fewer workgroup regions, whatever the cost model says */
+    SPAA_WINO_NO_CANVAS = 1 << 30,       /* A/B runs: small images keep the image-aligned regions (no canvas, no K ranges); the launcher sets it on
+                                            its own copy for two-source and unpadded layers */
+
+    /* ---- reserved1 ---- */
+    SPAA_C3_F16_OPERANDS = 1 << 0,       /* tile 76 (fp16-storage mode, fp16 output only): the image rounded to fp16 in registers, `w_split` = ONE plane of
+                                            fp16 weights in the layout of ConvPlan.c3_pack(half=True), products on v_mfma_f32_16x16x32_f16 */
+    SPAA_H16P_CV_BN = 3 << 0, SPAA_H16P_CV_BN_SHIFT = 0,   /* tile 68 with SPAA_H16P_CV: the N tile, 0 = the plan chooses, 1 = 64, 2 = 128 */
+    SPAA_H16P_CV = 1 << 2,               /* tile 68: the canvas / K-range form (small images with long K: spaa_tapconv_h16p_plan below; `ksplit` > 1 with
+                                            `splitk_ws` = that many K ranges) */
+    SPAA_H16P_CV_FORCE = 1 << 3,         /* tile 68 with SPAA_H16P_CV (tests): canvases wherever they have fewer regions */
+    SPAA_H16P_ONE_WG = 1 << 4,           /* tile 68 (A/B runs): 64-wide stride-1 layers as ONE workgroup per compute unit */
+    SPAA_H16P_LEAN_WIDE = 1 << 5,        /* tile 68: 64-wide N tiles (two workgroups per compute unit) for a layer wider than 64 GEMM columns */
+    SPAA_H16P_POOL = 1 << 6,             /* tile 68: the layer's ReLU and the 2 x 2 / stride-2 max-pool that follows it in the epilogue (stride 1, unfolded,
+                                            image-aligned regions, act = ReLU, no residual / gates, even Hout / Wout): `out` is then the POOLED tensor
+                                            [B, Hout / 2, Wout / 2, out_cstride] and `mask_out` the pool's arg-max bytes [B, Hout / 2, Wout / 2, Cout] in
+                                            spaa_maxpool_fwd's format (or NULL) -- torchvision VGG-16's conv -> ReLU -> MaxPool2d(2, 2), classifier.py:21-24 */
+    SPAA_H16P_UNPOOL = 1 << 7,           /* tile 68: the pool-adjoint PROLOGUE of that layer's input gradient (two-workgroup form only): `in` = the gradient
+                                            w.r.t. the pool's output [B, Hin / 2, Win / 2, in_cstride] fp16, `in2` = the pool's arg-max bytes [B, Hin / 2,
+                                            Win / 2, in2_cstride] -- spaa_maxpool_bwd with its ReLU gate applied while the patch is staged */
+    SPAA_SPLITK_FIXUP = 1 << 8,          /* Winograd tiles and tile 68's K-range form, `ksplit` > 1 (off by default): `splitk_ws` BEGINS with
+                                            SPAA_SPLITK_HDR_FLOATS floats of arrival counters (int32, all zero on first use; the kernels leave them zero), the
+                                            K ranges' partial sums follow: the last-arriving workgroup of a (region, N tile) adds the K ranges in fixed order
+                                            and applies the epilogue inside the kernel -- the same bits as the separate second pass, one launch less.  The
+                                            workspace is then SPAA_SPLITK_HDR_FLOATS + K ranges x B x H x W x Npad floats.  Clear: the two-pass form on a
+                                            workspace without header */
+
+    /* ---- reserved2 ---- */
+    SPAA_X6P_STD = 1 << 0                /* tile 74: the classes' tap lists have the canonical k3 / s2 order (csrc/tapconv_x6p.hip STD: the caller has
+                                            compared them; the launcher re-checks what the descriptor shows: tap counts 1 / 2 / 2 / 4, window (0..1)^2) */
+};
 
 /*
  * Generic "tap-list" convolution as an implicit GEMM on fp32 MFMA (v_mfma_f32_32x32x2_f32):
@@ -101,9 +157,9 @@ typedef struct {
                              a kernel-2 stride-2 ConvTranspose2d share their single tap, so they are folded into the GEMM N
                              dimension: weight rows [nfold*Cout], row c*Cout + n -> output pixel (2y + c/2, 2x + c%2),
                              channel n.  The input is read once instead of once per class. */
-    int32_t reserved0;    /* measurement switches (A/B runs of kernel variants: spaa_amd/convplan.py DEBUG_*); 0 in production,
-                           * except bits 27-28 of a Winograd launch (tiles 70 / 71 / 73): the layer's zero padding, 0 = 1 (same-size
-                           * output), 1 = 0 (unpadded: output 2 smaller), 2 = 2 (that layer's input gradient: 2 larger) */
+    int32_t reserved0;    /* per-tile form flags (the enum above), word 0: the measurement / test switches SPAA_DBG_* of every tile, SPAA_DBG_THINMF
+                             of tile 72, and of a Winograd launch SPAA_WINO_PAD (set by the product: the layer's zero padding), SPAA_WINO_FORCE_CANVAS
+                             and SPAA_WINO_NO_CANVAS */
     int32_t io_dtype;     /* fp16-STORAGE mode (BASELINE.json configs[4]: "fp16 with fp32 dE2000"), bit flags:
                              SPAA_IO_IN_F16  (SPAA_TILE_F16_IN tiles: the fp16 implicit-GEMM tiles; tile 68: 3x3 / stride-1 layers with the input
                                              patch staged once in LDS; tile 72: thin outputs with the parity classes folded into N, fp32 out (with a
@@ -115,23 +171,8 @@ typedef struct {
                              SPAA_IO_OUT_F16 (SPAA_TILE_F16_OUT tiles: the fp16 kernels and the kernels that read fp32 IMAGES):
                                              `out`, `add`, `gate`, `aux_out`, `gate2` are fp16.
                              0 = everything fp32 (the default path; dtype "f32" in bench.py). */
-    int32_t reserved1;    /* tiles 70 / 71 / 73 (and tile 68's K-range form): bit 8 = `splitk_ws` BEGINS with SPAA_SPLITK_HDR_FLOATS floats of arrival
-                             counters (int32, all zero on first use; the kernels leave them zero), the K ranges' partial sums follow: the
-                             last-arriving workgroup of a (region, N tile) adds the K ranges in fixed order and applies the epilogue inside the
-                             kernel -- the same bits as the separate second pass, one launch less.  The workspace is then SPAA_SPLITK_HDR_FLOATS +
-                             K ranges x B x H x W x Npad floats.  Bit 8 clear: the two-pass form on a workspace without header.
-                             tile 76: bit 0 = fp16 operands (fp16-storage mode, fp16 output only): the image rounded to fp16 in registers, `w_split` = ONE
-                             plane of fp16 weights in the layout of ConvPlan.c3_pack(half=True), products on v_mfma_f32_16x16x32_f16.
-                             tile 68: bit 2 = the canvas / K-range form (small images with long K: spaa_tapconv_h16p_plan below; `ksplit` > 1 with
-                             `splitk_ws` = that many K ranges), bits 0-1 = its N tile (0 chosen, 1 = 64, 2 = 128), bit 3 (tests) = canvases wherever they
-                             have fewer regions, bit 4 (A/B runs) = 64-wide stride-1 layers as ONE workgroup per compute unit, bit 5 = 64-wide N tiles (two
-                             workgroups per compute unit) for a wider layer, bit 6 = the layer's ReLU and the 2 x 2 / stride-2 max-pool that follows it in the epilogue
-                             (stride 1, unfolded, image-aligned regions, act = ReLU, no residual / gates, even Hout / Wout): `out` is then the POOLED tensor
-                             [B, Hout / 2, Wout / 2, out_cstride] and `mask_out` the pool's arg-max bytes [B, Hout / 2, Wout / 2, Cout] in spaa_maxpool_fwd's format
-                             (or NULL) -- torchvision VGG-16's conv -> ReLU -> MaxPool2d(2, 2), classifier.py:21-24; bit 7 = the
-                             pool-adjoint PROLOGUE of that layer's input gradient (two-workgroup form only): `in` = the gradient w.r.t. the pool's output [B, Hin / 2,
-                             Win / 2, in_cstride] fp16, `in2` = the pool's arg-max bytes [B, Hin / 2, Win / 2, in2_cstride] -- spaa_maxpool_bwd with its ReLU gate applied
-                             while the patch is staged.  0 otherwise. */
+    int32_t reserved1;    /* per-tile form flags, word 1: SPAA_C3_F16_OPERANDS (tile 76), the SPAA_H16P_* forms of tile 68 and SPAA_SPLITK_FIXUP
+                             (tile 68 and the Winograd tiles).  The product sets all but SPAA_H16P_CV_FORCE, SPAA_H16P_ONE_WG and SPAA_SPLITK_FIXUP */
     int32_t nclass;
     spaa_tapclass_t cls[SPAA_MAX_CLASSES];
     /* optional SECOND SOURCE (NULL = none).
@@ -146,8 +187,7 @@ typedef struct {
      * like `w_half`). */
     const float* in2;         /* [B, Hout, Wout, in2_cstride] */
     int32_t in2_cstride, in2_coff, Cin2;   /* Cin2 = 32 or 64 */
-    int32_t reserved2;        /* tile 74: bit 0 = the classes' tap lists have the canonical k3 / s2 order (csrc/tapconv_x6p.hip STD: the caller
-                                 has compared them; the launcher re-checks what the descriptor shows: tap counts 1 / 2 / 2 / 4, window (0..1)^2) */
+    int32_t reserved2;        /* per-tile form flags, word 2: SPAA_X6P_STD (tile 74; set by the product) */
     const uint16_t* w2_split; /* W2 as three bf16 planes [3][Npad][Cin2] with w == h + m + l exactly */
 } spaa_tapconv_t;
 
@@ -200,11 +240,11 @@ int spaa_tapconv_wgrad(const spaa_tapconv_t* desc, const float* gout, float* dw_
  * (plan[1] * B * H * W * Npad floats) from the plan and passes plan[1] back as `ksplit` (ksplit = 1: never split; 0 with a
  * workspace: the launcher's own choice, which this function reports). */
 int spaa_tapconv_wino_plan(const spaa_tapconv_t* desc, int32_t* plan);
-/* The same query for the canvas / K-range form of the patch-staged fp16 kernel (tile 68 with `reserved1` bit 2: 3 x 3 / stride-1 layers of
+/* The same query for the canvas / K-range form of the patch-staged fp16 kernel (tile 68 with SPAA_H16P_CV in `reserved1`: 3 x 3 / stride-1 layers of
  * the fp16-storage classifiers on 14 x 14 and 7 x 7 maps -- ResNet-18 layer3 / layer4, VGG-16's last block; classifier.py:26-28,
  * perc_al/__init__.py:181-238): plan[0..7] as above.  `desc->ksplit` > 1 asks for that many K ranges, 1 for none, 0 leaves the choice to
- * the plan; `reserved1` bits 0-1 likewise for the N tile.  The caller passes plan[1] back as `ksplit` (with `splitk_ws` of plan[1] * B * H *
- * W * Npad floats when > 1) and plan[0] in `reserved1`. */
+ * the plan; SPAA_H16P_CV_BN likewise for the N tile.  The caller passes plan[1] back as `ksplit` (with `splitk_ws` of plan[1] * B * H *
+ * W * Npad floats when > 1) and plan[0] as SPAA_H16P_CV_BN. */
 int spaa_tapconv_h16p_plan(const spaa_tapconv_t* desc, int32_t* plan);
 /* layout probes for language bindings: sizeof(spaa_tapconv_t) and the byte offset of field # `field`
  * (0 out, 1 weights, 2 taps, 3 gate2, 4 mask_out, 5 tap_range, 6 splitk_ws, 7 io_dtype, 8 nclass, 9 cls, 10 in2, 11 w2_split; else -1) */

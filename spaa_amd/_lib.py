@@ -16,6 +16,34 @@ MAX_TAPS = 64
 ACT_NONE, ACT_RELU, ACT_RELU_CLAMP1, ACT_LEAKY01 = 0, 1, 2, 3
 IO_IN_F16, IO_OUT_F16 = 1, 2
 GATE_NONE, GATE_POS, GATE_POS_LE1, GATE_MUL = 0, 1, 2, 3
+# per-tile form flags of TapConv.reserved0 / reserved1 / reserved2: the header's enum without the SPAA_ prefix (a name is the mask in its
+# word, NAME_SHIFT the position of a field wider than one bit; tests/test_cabi_cpu.py pins every value to include/spaa_hip.h)
+# reserved0, every tile: measurement and test switches
+DBG_X6D_TAPMAJOR = 1 << 0
+DBG_PERSIST_CAP, DBG_PERSIST_CAP_SHIFT = 0xff << 8, 8
+DBG_X6P_ABLATE, DBG_X6P_ABLATE_SHIFT = 0xff << 8, 8        # (the same bits in the stamp build of tile 74)
+DBG_WINO_VAR, DBG_WINO_VAR_SHIFT = 3 << 16, 16
+DBG_WINO_ABLATE, DBG_WINO_ABLATE_SHIFT = 127 << 18, 18
+DBG_H16_2STAGE = 1 << 25
+DBG_SMALLCIN_NOSLAB = 1 << 26
+# reserved0, tile 72 only
+DBG_THINMF, DBG_THINMF_SHIFT = 7 << 27, 27
+# reserved0, Winograd tiles only
+WINO_PAD, WINO_PAD_SHIFT = 3 << 27, 27                     # (the layer's zero padding as a code: set by the product)
+WINO_FORCE_CANVAS = 1 << 29
+WINO_NO_CANVAS = 1 << 30
+# reserved1
+C3_F16_OPERANDS = 1 << 0                                   # tile 76
+H16P_CV_BN, H16P_CV_BN_SHIFT = 3 << 0, 0                   # tile 68, as are the next six
+H16P_CV = 1 << 2
+H16P_CV_FORCE = 1 << 3
+H16P_ONE_WG = 1 << 4
+H16P_LEAN_WIDE = 1 << 5
+H16P_POOL = 1 << 6
+H16P_UNPOOL = 1 << 7
+SPLITK_FIXUP = 1 << 8                                      # tile 68 and the Winograd tiles
+# reserved2
+X6P_STD = 1 << 0                                           # tile 74
 
 
 class TapClass(C.Structure):

@@ -12,6 +12,7 @@ This module only rearranges weights (layout plumbing, on the host); the arithmet
 """
 import collections
 import ctypes as C
+import functools
 import os
 
 import torch
@@ -61,6 +62,48 @@ DEBUG_H16_2STAGE = int(os.environ.get('SPAA_H16_2STAGE', '0'))      # 1: the fp1
 FOLD_K3S2 = os.environ.get('SPAA_FOLD_K3S2', '1') != '0'   # 3x3 / s2 input gradients with few output channels: classes folded
 FOLD_K3S2_MAX_COUT = 32
 WINOGRAD = os.environ.get('SPAA_WINOGRAD', '1') != '0'  # 3x3/s1 layers: allow the Winograd F(2x2,3x3) kernel (tile 70)
+
+
+def _flag_field(switch, value, mask, shift=None):
+    """`value` of the switch `switch` at its place in a descriptor word (mask / shift: a form flag of _lib; a one-bit flag has no named
+    shift: its bit's position); ValueError if it does not fit."""
+    if shift is None:
+        shift = mask.bit_length() - 1
+    if not 0 <= value <= mask >> shift:
+        raise ValueError(f'{switch} = {value} does not fit its descriptor field (0..{mask >> shift})')
+    return value << shift
+
+
+def wino_pad_code(pad):
+    """The code of a Winograd layer's zero padding in `reserved0` (_lib.WINO_PAD): the inverse of wino_pad() in csrc/tapconv_wino.hip,
+    which maps code 0 / 1 / 2 to padding 1 / 0 / 2."""
+    return {1: 0, 0: 1, 2: 2}[pad]
+
+
+@functools.lru_cache(maxsize=None)
+def _debug_word(tile, wino_pad, tapmajor, persist_cap, wino, wino_nocanvas, h16_2stage, smallcin_noslab, thinmf):
+    """`debug_word` as a function of the switches' values (cached: a launch asks per call, the switches change between A/B runs)."""
+    w = (_flag_field('DEBUG_TAPMAJOR', tapmajor, _lib.DBG_X6D_TAPMAJOR)
+         | _flag_field('DEBUG_PERSIST_CAP', persist_cap, _lib.DBG_PERSIST_CAP, _lib.DBG_PERSIST_CAP_SHIFT)
+         # DEBUG_WINO: the variant bits below the ablation bits
+         | _flag_field('DEBUG_WINO & 3', wino & 3, _lib.DBG_WINO_VAR, _lib.DBG_WINO_VAR_SHIFT)
+         | _flag_field('DEBUG_WINO >> 2', wino >> 2, _lib.DBG_WINO_ABLATE, _lib.DBG_WINO_ABLATE_SHIFT)
+         | _flag_field('DEBUG_H16_2STAGE', h16_2stage, _lib.DBG_H16_2STAGE)
+         | _flag_field('DEBUG_SMALLCIN_NOSLAB', smallcin_noslab, _lib.DBG_SMALLCIN_NOSLAB))
+    if tile == 72:
+        w |= _flag_field('DEBUG_THINMF', thinmf, _lib.DBG_THINMF, _lib.DBG_THINMF_SHIFT)
+    if tile in WINO_TILES:
+        _flag_field('DEBUG_WINO_NOCANVAS', wino_nocanvas, 3, 0)   # 1: no canvas (A/B runs); 2: canvas wherever it has fewer regions (tests)
+        w |= ((_lib.WINO_NO_CANVAS if wino_nocanvas & 1 else 0) | (_lib.WINO_FORCE_CANVAS if wino_nocanvas & 2 else 0)
+              | wino_pad_code(wino_pad) << _lib.WINO_PAD_SHIFT)
+    return w
+
+
+def debug_word(tile, wino_pad=1):
+    """`reserved0` of a launch of `tile`: the measurement / test switches DEBUG_* at their named places -- and, of a Winograd launch, the
+    layer's zero padding (the one product input of the word).  A switch value that does not fit its field is a ValueError."""
+    return _debug_word(tile, wino_pad, DEBUG_TAPMAJOR, DEBUG_PERSIST_CAP, DEBUG_WINO, DEBUG_WINO_NOCANVAS, DEBUG_H16_2STAGE,
+                       DEBUG_SMALLCIN_NOSLAB, DEBUG_THINMF)
 
 
 def _load_tune():
@@ -202,6 +245,8 @@ class ConvPlan:
         self._npad, self._dev = npad, device
         self.w_half = None  # fp16 plane for the fp16-storage kernels, packed on first use (half_plane())
         self.wino = None    # the same layer in Winograd F(2x2,3x3) form (attach_winograd), run as tile 70
+        self.wino_pad = 1   # ... and its zero padding (attach_winograd: 1 / 0 / 2)
+        self.wino_ksplit = 0   # K ranges asked of the Winograd launcher's plan (0: the plan chooses)
         self.fixed_tile = 0
         self._wino_plans = {}   # spaa_tapconv_wino_plan results per launch shape (run)
         self.alg_taps = self.ntaps_total
@@ -636,7 +681,7 @@ class ConvPlan:
             if out_f16 and 'c3h' not in DEFAULT_DISABLE:
                 # fp16-storage mode: fp16 operands like every other layer of the mode (the image rounded in registers, one fp16 weight plane)
                 d.w_split = self.c3_pack(True).data_ptr()
-                d.reserved1 |= 1
+                d.reserved1 = _lib.C3_F16_OPERANDS
             else:
                 d.w_split = self.c3_pack().data_ptr()
         if tile == 72:
@@ -654,11 +699,9 @@ class ConvPlan:
         if pool_adjoint is not None:
             d.in2, d.in2_cstride, d.in2_coff, d.Cin2 = pool_adjoint[0].data_ptr(), inp.shape[1], inp.shape[2], int(bool(pool_adjoint[2]))
         if tile == 74 and X6P_STD and self.x6p_canonical():
-            d.reserved2 = 1      # (the kernel's compile-time schedule: x6p_canonical)
+            d.reserved2 = _lib.X6P_STD      # (the kernel's compile-time schedule: x6p_canonical)
         d.tile = tile
-        d.reserved0 = (DEBUG_TAPMAJOR | (DEBUG_PERSIST_CAP << 8) | (DEBUG_WINO << 16) | (DEBUG_H16_2STAGE << 25) | (DEBUG_SMALLCIN_NOSLAB << 26)
-                       | (((DEBUG_THINMF & 7) << 27) if tile == 72 else 0)
-                       | (((DEBUG_WINO_NOCANVAS & 1) << 30 | (DEBUG_WINO_NOCANVAS >> 1 & 1) << 29 | {1: 0, 0: 1, 2: 2}[getattr(self, 'wino_pad', 1)] << 27) if tile in WINO_TILES else 0))  # measurement / test switches; bits 27-28 of a Winograd launch: its zero padding (1 / 0 / 2)
+        d.reserved0 = debug_word(tile, self.wino_pad)
         return d
 
     def _kws(self, need, fixup):
@@ -697,36 +740,39 @@ class ConvPlan:
         if tile in WINO_TILES:
             # the launcher's plan (csrc/tapconv_wino.hip: N tile, canvas layout for small images, K ranges for few workgroups with
             # long K) -- asked for here because the K ranges need a workspace; its K-range count is then passed back explicitly
-            want = _wino[1] if _wino else getattr(self, 'wino_ksplit', 0)
+            want = _wino[1] if _wino else self.wino_ksplit
             d.ksplit = want if WINO_SPLITK else 1
             wp = self._launcher_plan('spaa_tapconv_wino_plan', (b, hin, win, hout, wout, s.cs_in, tile, d.ksplit, inp2 is not None, d.reserved0), d)
             wino_bn, d.ksplit = wp[0], wp[1]
             self.last_wino_plan = wp
+        # tile 68 (csrc/tapconv_h16p.hip): which form of the kernel this launch runs, decided here in named terms and written into
+        # `reserved1` once, below (the Winograd tiles share `fixup`)
+        cv_form = 0
         if tile == 68 and h16p_cv:
-            # the launcher's plan of the canvas / K-range form (csrc/tapconv_h16p.hip), cached per launch shape like the Winograd plans
-            d.reserved1 = 4 | {0: 0, 64: 1, 128: 2}[H16P_CV[0]] | (8 if len(H16P_CV) > 2 and H16P_CV[2] else 0)
-            d.ksplit, d.splitk_ws = H16P_CV[1], None
-            wp = self._launcher_plan('spaa_tapconv_h16p_plan', ('h16p', b, hin, win, s.cs_in, d.reserved1, d.ksplit), d)
+            # the launcher's plan of the canvas / K-range form, cached per launch shape like the Winograd plans: asked with the N tile,
+            # K ranges and canvas switch of H16P_CV; the N tile it chose is passed back explicitly
+            cv_force = _lib.H16P_CV_FORCE if len(H16P_CV) > 2 and H16P_CV[2] else 0
+            ask = _lib.H16P_CV | cv_force | {0: 0, 64: 1, 128: 2}[H16P_CV[0]] << _lib.H16P_CV_BN_SHIFT
+            d.reserved1, d.ksplit, d.splitk_ws = ask, H16P_CV[1], None
+            wp = self._launcher_plan('spaa_tapconv_h16p_plan', ('h16p', b, hin, win, s.cs_in, ask, d.ksplit), d)
             d.ksplit = wp[1]
-            d.reserved1 = (d.reserved1 & 8) | 4 | {64: 1, 128: 2}[wp[0]]
+            cv_form = _lib.H16P_CV | cv_force | {64: 1, 128: 2}[wp[0]] << _lib.H16P_CV_BN_SHIFT
             self.last_h16p_plan = wp
-        if (tile in WINO_TILES or (tile == 68 and h16p_cv)) and d.ksplit > 1:
-            # (round 6, WINO_SPLITK_FIXUP: the K ranges meet inside the kernel -- the workspace with the arrival-counter header)
-            d.splitk_ws = self._kws(d.ksplit * b * hout * wout * ((self.cout + 127) // 128 * 128), WINO_SPLITK_FIXUP)
-            if WINO_SPLITK_FIXUP:
-                d.reserved1 |= 256
-        if tile == 68 and 'h16plean' in DEFAULT_DISABLE:
-            d.reserved1 |= 16    # (A/B runs: the 64-wide stride-1 form as one workgroup per compute unit)
-        if tile == 68 and not h16p_cv and self.s_in == 1 and self.cout * self.nfold > 64 and self.h16p_lean_wide(b, d.Hm, d.Wm):
-            d.reserved1 |= 32    # (wider layers as 64-wide N tiles, two workgroups per compute unit)
+        # (round 6, WINO_SPLITK_FIXUP: the K ranges meet inside the kernel -- the workspace with the arrival-counter header)
+        k_ranges = (tile in WINO_TILES or (tile == 68 and h16p_cv)) and d.ksplit > 1
+        fixup = k_ranges and WINO_SPLITK_FIXUP
+        if k_ranges:
+            d.splitk_ws = self._kws(d.ksplit * b * hout * wout * ((self.cout + 127) // 128 * 128), fixup)
+        one_wg = tile == 68 and 'h16plean' in DEFAULT_DISABLE    # (A/B runs: the 64-wide stride-1 form as one workgroup per compute unit)
+        # wider layers as 64-wide N tiles, two workgroups per compute unit
+        lean_wide = tile == 68 and not h16p_cv and self.s_in == 1 and self.cout * self.nfold > 64 and self.h16p_lean_wide(b, d.Hm, d.Wm)
         unpool_fused = False
         if unpool is not None:
             parg, gfull = unpool
-            if (tile == 68 and not h16p_cv and self.s_in == 1 and self.nfold == 1 and (self.cout <= 64 or (d.reserved1 & 32)) and not (d.reserved1 & 16)
+            if (tile == 68 and not h16p_cv and self.s_in == 1 and self.nfold == 1 and (self.cout <= 64 or lean_wide) and not one_wg
                     and self.tap_range[0] >= -1 and self.tap_range[1] <= 1 and self.tap_range[2] >= -1 and self.tap_range[3] <= 1
                     and self.cin_p % 8 == 0 and 'h16punp' not in DEFAULT_DISABLE):
                 d.in2, d.in2_cstride, d.in2_coff, d.Cin2 = parg.data_ptr(), parg.shape[3], 0, 0
-                d.reserved1 |= 128
                 unpool_fused = True
             else:
                 pooling.maxpool_bwd(inp, parg, gfull, 2, 2, 0, True, c=self.cin_p)
@@ -740,9 +786,11 @@ class ConvPlan:
             if (tile == 68 and not h16p_cv and self.s_in == 1 and self.nfold == 1 and hout % 2 == 0 and wout % 2 == 0 and self.cout % 4 == 0
                     and s.cs_out == self.cout and 'h16ppool' not in DEFAULT_DISABLE):
                 d.out, d.mask_out = pooled.data_ptr(), (parg.data_ptr() if want_arg else None)
-                d.reserved1 |= 64
                 pool_fused = True
         self.last_pool_fused = pool_fused
+        if tile == 68 or tile in WINO_TILES:
+            d.reserved1 = (cv_form | (_lib.SPLITK_FIXUP if fixup else 0) | (_lib.H16P_ONE_WG if one_wg else 0) | (_lib.H16P_LEAN_WIDE if lean_wide else 0)
+                           | (_lib.H16P_UNPOOL if unpool_fused else 0) | (_lib.H16P_POOL if pool_fused else 0))
         # (for tests and reports, next to last_tile: the K split this launch runs with -- 1 none, k > 1 that many K ranges (x6d split-K,
         # fp16 split-K, the Winograd / tile-68 K-range forms), -1 stream-K)
         self.last_ksplit = d.ksplit if d.ksplit else 1

@@ -28,4 +28,11 @@ inline hipError_t ensure_dynamic_lds(const void* kernel, int bytes, bool (&done)
     return hipSuccess;
 }
 
+// The multi-bit form flags of a descriptor that launchers read (include/spaa_hip.h: SPAA_DBG_* / SPAA_H16P_*): shifted and masked here, once
+// per field.  (Fields a kernel reads have their accessor next to the kernel: wino_pad, thinmf_dbg, x6p_ablate.)
+inline int dbg_persist_cap(const spaa_tapconv_t& d) { return (d.reserved0 & SPAA_DBG_PERSIST_CAP) >> SPAA_DBG_PERSIST_CAP_SHIFT; }
+inline int dbg_wino_var(const spaa_tapconv_t& d) { return (d.reserved0 & SPAA_DBG_WINO_VAR) >> SPAA_DBG_WINO_VAR_SHIFT; }
+inline int dbg_wino_ablate(const spaa_tapconv_t& d) { return (d.reserved0 & SPAA_DBG_WINO_ABLATE) >> SPAA_DBG_WINO_ABLATE_SHIFT; }
+inline int h16p_cv_bn(const spaa_tapconv_t& d) { return (d.reserved1 & SPAA_H16P_CV_BN) >> SPAA_H16P_CV_BN_SHIFT; }   // 0 = chosen, 1 = 64, 2 = 128
+
 }  // namespace

@@ -226,7 +226,7 @@ int spaa_launch_smallcin(const spaa_tapconv_t& d, hipStream_t stream) {
     // (conv1: 145 -> 96 us; conv1_s without one: 112 -> 128 us)
     if (d.Cout > 32)   // two 32-channel halves per workgroup (always through the slab: 64-channel rows)
         return d.Cin == 4 ? launch_sc<1, true, 2>(d, dymin, dxmin, PH, PW, stream) : launch_sc<2, true, 2>(d, dymin, dxmin, PH, PW, stream);
-    if (d.s_in == 1 || (d.add != nullptr && !((d.reserved0 >> 26) & 1)))
+    if (d.s_in == 1 || (d.add != nullptr && !(d.reserved0 & SPAA_DBG_SMALLCIN_NOSLAB)))
         return d.Cin == 4 ? launch_sc<1, true>(d, dymin, dxmin, PH, PW, stream) : launch_sc<2, true>(d, dymin, dxmin, PH, PW, stream);
     return d.Cin == 4 ? launch_sc<1, false>(d, dymin, dxmin, PH, PW, stream) : launch_sc<2, false>(d, dymin, dxmin, PH, PW, stream);
 }

@@ -28,7 +28,7 @@ __device__ __forceinline__ int swz_w16(int n) { return ((n >> 3) & 1) << 1; }
 // ONE TILE PER WORKGROUP (the 3 x 3 layers: 12 KB of weights, two workgroups per compute unit cover each other's prologue and epilogue;
 // the persistent form below measured slower there -- VGG-16 features.0 217 -> 276 us: its tile loop costs registers the two-per-CU
 // occupancy does not have)
-// HO (round 5, fp16-STORAGE mode: `reserved1` bit 0): the image operand rounded to fp16 in registers and ONE plane of fp16 weights on
+// HO (round 5, fp16-STORAGE mode: SPAA_C3_F16_OPERANDS): the image operand rounded to fp16 in registers and ONE plane of fp16 weights on
 // v_mfma_f32_16x16x32_f16 -- what every other layer of the mode multiplies (fp16 operands, fp32 accumulation); the bf16x6 form spent six MFMAs
 // and a 44-instruction split per fragment on an output that is rounded to fp16.
 template <int NK, int BN, bool HO = false>
@@ -367,7 +367,7 @@ int spaa_launch_tapconv_c3(const spaa_tapconv_t& d, hipStream_t stream) {
     if ((int64_t)d.B * d.Hin * d.Win * d.in_cstride * 4 >= (int64_t)1 << 31) return hipErrorInvalidValue;
     const int PH = (OH - 1) * d.s_in + kh, PW = (OW - 1) * d.s_in + kw;
     const int BN = d.Cout <= 32 ? 32 : 64;
-    const bool ho = (d.reserved1 & 1) != 0;      // fp16 operands (fp16-storage mode): one fp16 weight plane
+    const bool ho = (d.reserved1 & SPAA_C3_F16_OPERANDS) != 0;      // fp16 operands (fp16-storage mode): one fp16 weight plane
     if (ho && !(d.io_dtype & SPAA_IO_OUT_F16)) return hipErrorInvalidValue;
     const int w_bytes = nk * (ho ? 1 : 3) * BN * 64;
     const int patch_bytes = (PH * PW * 16 + 1023) & ~1023;

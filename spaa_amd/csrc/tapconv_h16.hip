@@ -300,7 +300,7 @@ int launch_h16(const spaa_tapconv_t& d, hipStream_t stream) {
     if constexpr (NS == 2 && NW == 4 && BN >= 32 && BN <= 128) {
         int64_t kmin = 1 << 30;
         for (int c = 0; c < d.nclass; ++c) kmin = d.cls[c].K < kmin ? d.cls[c].K : kmin;
-        if ((int64_t)m_tiles * n_tiles * d.nclass * (d.ksplit > 1 ? d.ksplit : 1) <= 256 && kmin >= 16 * 64 * (d.ksplit > 1 ? d.ksplit : 1) && !((d.reserved0 >> 25) & 1)) return launch_h16<NW, BN, 4>(d, stream);
+        if ((int64_t)m_tiles * n_tiles * d.nclass * (d.ksplit > 1 ? d.ksplit : 1) <= 256 && kmin >= 16 * 64 * (d.ksplit > 1 ? d.ksplit : 1) && !(d.reserved0 & SPAA_DBG_H16_2STAGE)) return launch_h16<NW, BN, 4>(d, stream);
     }
     const size_t smem = NS * (size_t)(2 * BM * 64 + 2 * BN * 64);
     static bool attr_set[SPAA_MAX_DEVICES] = {};

@@ -64,7 +64,7 @@ struct h16p_cv_t {
 // KiB of LDS, at most 128 VGPRs.  The 64 -> 64-channel layers (VGG-16 features.2 at 224 x 224, ResNet-18 layer1) have two channel blocks:
 // with one workgroup per CU the patch load, six steps and a 64 KiB epilogue ran strictly one after the other (490 TFLOP/s); now one
 // workgroup's memory phases lie under the other's products.
-// UNP (round 5; LEAN only; `reserved1` bit 7): the layer is the input gradient of a convolution whose ReLU output fed a 2 x 2 / stride-2
+// UNP (round 5; LEAN only; SPAA_H16P_UNPOOL): the layer is the input gradient of a convolution whose ReLU output fed a 2 x 2 / stride-2
 // max-pool (torchvision VGG-16): `in` is the gradient w.r.t. the POOL's output [B, Hin / 2, Win / 2, in_cstride] and `in2` that pool's arg-max
 // bytes [B, Hin / 2, Win / 2, in2_cstride] (spaa_maxpool_fwd's format); the patch of the pool's INPUT gradient -- g if the pixel is the
 // window's first maximum and that maximum is positive, else 0: spaa_maxpool_bwd with its ReLU gate -- is formed in registers on its way
@@ -429,7 +429,7 @@ __global__ __launch_bounds__(512, LEAN ? 4 : 1) void h16p_kernel(const spaa_tapc
     // output) without a branch: absent tensors are zero-record buffer descriptors (loads give 0, stores are dropped), so that
     // the operand loads of four pixels per lane are in flight together; anything else: the shared store4_t
     const bool fast = fast_epi_ok(e, vec);
-    // ---- POOL (round 5; `reserved1` bit 6; S = 1, unfolded, image-aligned regions): the layer's ReLU and the 2 x 2 / stride-2 max-pool that
+    // ---- POOL (round 5; SPAA_H16P_POOL; S = 1, unfolded, image-aligned regions): the layer's ReLU and the 2 x 2 / stride-2 max-pool that
     // follows it (torchvision VGG-16 `features`: conv -> ReLU -> MaxPool2d(2, 2), /root/reference/src/python/classifier.py:21-24) in this
     // epilogue: `out` is the POOLED tensor [B, Hout / 2, Wout / 2, out_cstride], `mask_out` the pool's arg-max bytes [B, Hout / 2, Wout / 2,
     // Cout] (code 2 ky + kx of the first maximum | 0x80 if it is positive: spaa_maxpool_fwd's format; NULL = not needed) -- the full-size
@@ -438,7 +438,7 @@ __global__ __launch_bounds__(512, LEAN ? 4 : 1) void h16p_kernel(const spaa_tapc
     // (a quad-permute DPP move); values are rounded to the storage type BEFORE they are compared, in the window order of
     // maxpool2x2_fwd_kernel: bitwise the pooled values and arg-max bytes of the separate launches (finite values).
     if constexpr (S == 1 && !CV) {
-        if (p.reserved1 & 64) {
+        if (p.reserved1 & SPAA_H16P_POOL) {
             const bool o16 = (p.io_dtype & SPAA_IO_OUT_F16) != 0;
             const int Hp = p.Hout >> 1, Wp = p.Wout >> 1;
             const int64_t npool = (int64_t)p.B * Hp * Wp;
@@ -682,8 +682,8 @@ inline h16p_plan_t h16p_make_plan(const spaa_tapconv_t& d, const int ncu, const 
                 rounds = rounds < 1.0 ? 1.0 : rounds;
                 double cost = rounds * (kb_per * (bn == 128 ? 5.45 : 3.4) + (bn == 128 ? 22.3 : 16.7));
                 if (ksr > 1) cost += 5.0 + (double)ksr * (double)M * npad * 4.0 / 5e6;
-                if (cv && !(d.reserved1 & 8)) cost *= 1.05;
-                if (!cv && best < plain && (d.reserved1 & 8)) cost *= 1e6;   // (tests: canvas wherever it has fewer regions)
+                if (cv && !(d.reserved1 & SPAA_H16P_CV_FORCE)) cost *= 1.05;
+                if (!cv && best < plain && (d.reserved1 & SPAA_H16P_CV_FORCE)) cost *= 1e6;   // (tests: canvas wherever it has fewer regions)
                 if (ksr > 1) cost *= 1.02;
                 if (cost < best_cost) {
                     best_cost = cost;
@@ -700,7 +700,7 @@ inline h16p_plan_t h16p_make_plan(const spaa_tapconv_t& d, const int ncu, const 
 
 }  // namespace
 
-// The launcher's plan for the canvas / K-range form of tile 68 (`reserved1` bit 2 set; bits 0-1: N tile 0 = chosen, 1 = 64, 2 = 128;
+// The launcher's plan for the canvas / K-range form of tile 68 (SPAA_H16P_CV set; SPAA_H16P_CV_BN: N tile 0 = chosen, 1 = 64, 2 = 128;
 // desc->ksplit > 1: that many K ranges, 1: none, 0: chosen): plan[0..7] = {N tile, K ranges, canvas (0 / 1), images per canvas (rows),
 // (columns), workgroups, channel blocks per K range, canvases}.  A caller sizes `splitk_ws` (K ranges x B x H x W x Npad floats) from
 // plan[1] and passes plan[1] back as `ksplit`.
@@ -708,7 +708,7 @@ extern "C" int spaa_tapconv_h16p_plan(const spaa_tapconv_t* desc, int32_t* plan)
     if (desc == nullptr || plan == nullptr) return hipErrorInvalidValue;
     const spaa_tapconv_t& d = *desc;
     if (!h16p_cv_shape_ok(d) || d.ksplit < 0 || d.B < 1 || d.Cout < 1) return hipErrorInvalidValue;
-    const int fb = d.reserved1 & 3;
+    const int fb = h16p_cv_bn(d);
     const h16p_plan_t pl = h16p_make_plan(d, h16p_ncu(), fb == 1 ? 64 : fb == 2 ? 128 : 0, d.ksplit, true);
     if (pl.bn == 0 || pl.ksplit < 1 || pl.n_tiles < 1) return hipErrorInvalidValue;
     plan[0] = pl.bn, plan[1] = pl.ksplit, plan[2] = pl.canvas, plan[3] = pl.gy, plan[4] = pl.gx;
@@ -742,7 +742,7 @@ int spaa_launch_tapconv_h16p(const spaa_tapconv_t& d, hipStream_t stream) {
             d.tap_range[3] - d.tap_range[2] > 2)
             return hipErrorInvalidValue;
     }
-    if (d.reserved1 & 128) {
+    if (d.reserved1 & SPAA_H16P_UNPOOL) {
         // (`in2` = arg-max bytes of the pool-adjoint prologue: checked with the launch below)
     } else if (d.in2 != nullptr && nfold == 1) {   // two sources of an unfolded layer: the last Cin2 channels (whole 32-channel blocks) from `in2`
         if ((d.Cin2 & 31) || d.Cin2 <= 0 || d.Cin2 >= d.Cin || (d.in2_cstride & 7) || (d.in2_coff & 7) || d.in2_coff + d.Cin2 > d.in2_cstride ||
@@ -754,9 +754,9 @@ int spaa_launch_tapconv_h16p(const spaa_tapconv_t& d, hipStream_t stream) {
             (int64_t)d.B * d.Hout * d.Wout * d.in2_cstride * 2 >= (int64_t)1 << 31)
             return hipErrorInvalidValue;
     }
-    if (d.reserved1 & 64) {
+    if (d.reserved1 & SPAA_H16P_POOL) {
         // fused ReLU + 2 x 2 / stride-2 max-pool: `out` / `mask_out` are the POOLED tensor and its arg-max bytes
-        if (S != 1 || nfold != 1 || (d.reserved1 & 4) || d.act != SPAA_ACT_RELU || d.add != nullptr || d.gate != nullptr || d.gate2 != nullptr ||
+        if (S != 1 || nfold != 1 || (d.reserved1 & SPAA_H16P_CV) || d.act != SPAA_ACT_RELU || d.add != nullptr || d.gate != nullptr || d.gate2 != nullptr ||
             d.gate_bits != nullptr || d.gate2_bits != nullptr || d.aux_out != nullptr || (d.Hout & 1) || (d.Wout & 1) || (d.Cout & 3) ||
             (d.out_cstride & 3) || (d.out_coff & 3) || d.out_coff + d.Cout > d.out_cstride ||
             (int64_t)d.B * (d.Hout / 2) * (d.Wout / 2) * d.out_cstride * 4 >= (int64_t)1 << 31)
@@ -766,13 +766,13 @@ int spaa_launch_tapconv_h16p(const spaa_tapconv_t& d, hipStream_t stream) {
     if ((int64_t)d.B * d.Hin * d.Win * d.in_cstride * 2 >= (int64_t)1 << 31) return hipErrorInvalidValue;
     const h16p_cv_t nogeo = {};
     static bool attr_set[6][SPAA_MAX_DEVICES] = {};
-    if (d.reserved1 & 4) {
+    if (d.reserved1 & SPAA_H16P_CV) {
         // canvas / K-range form (small images, few workgroups with long K): the plan of spaa_tapconv_h16p_plan, recomputed here with
         // the caller's K ranges (`ksplit`, with its workspace) and N tile
         if (!h16p_cv_shape_ok(d)) return hipErrorInvalidValue;
         if (d.tap_range[0] < -1 || d.tap_range[1] > 1 || d.tap_range[2] < -1 || d.tap_range[3] > 1) return hipErrorInvalidValue;
         if (d.ksplit > 1 && d.splitk_ws == nullptr) return hipErrorInvalidValue;
-        const int fb = d.reserved1 & 3;
+        const int fb = h16p_cv_bn(d);
         const h16p_plan_t pl = h16p_make_plan(d, h16p_ncu(), fb == 1 ? 64 : fb == 2 ? 128 : 0, d.ksplit > 1 ? d.ksplit : 1, false);
         if (pl.nwg > 0x7fffffff || pl.bn == 0 || pl.ksplit < 1 || pl.n_tiles < 1 || pl.ksplit != (d.ksplit > 1 ? d.ksplit : 1)) return hipErrorInvalidValue;
         h16p_cv_t geo = {};
@@ -784,15 +784,15 @@ int spaa_launch_tapconv_h16p(const spaa_tapconv_t& d, hipStream_t stream) {
         geo.nsp = (int)(pl.nwg / ((int64_t)pl.n_tiles * pl.ksplit));
         // workgroup order by what an XCD's L2 should keep: the fp16 weights or the activations
         geo.order = (int64_t)((d.Cout + 127) & ~127) * ((d.cls[0].K + 63) & ~63) * 2 > (int64_t)d.B * d.Hin * d.Win * d.Cin * 2;
-        // `reserved1` bit 8: the workspace begins with SPAA_SPLITK_HDR_FLOATS zeroed counter slots -> the K ranges meet inside the kernel
+        // SPAA_SPLITK_FIXUP: the workspace begins with SPAA_SPLITK_HDR_FLOATS zeroed counter slots -> the K ranges meet inside the kernel
         // (and the partial sums leave through the branch-free epilogue's agent-scope stores: 4-channel quads, 32-bit offsets)
-        geo.fix = pl.ksplit > 1 && (d.reserved1 & 256) && (int64_t)geo.nsp * pl.n_tiles <= SPAA_SPLITK_HDR_FLOATS && !(d.Cout & 3) &&
+        geo.fix = pl.ksplit > 1 && (d.reserved1 & SPAA_SPLITK_FIXUP) && (int64_t)geo.nsp * pl.n_tiles <= SPAA_SPLITK_HDR_FLOATS && !(d.Cout & 3) &&
                   (int64_t)pl.ksplit * d.B * d.Hout * d.Wout * ((d.Cout + 127) & ~127) * 4 < ((int64_t)1 << 31);
         spaa_tapconv_t dd = d;
         dd.ksplit = pl.ksplit;
         // (bit 8 asked for the in-kernel fix-up but the launch declined it: the caller's workspace still begins with the counter header --
         // the partial sums and the second pass go past it, and the counters stay zero for the next launch that takes the fix-up)
-        if (pl.ksplit > 1 && (d.reserved1 & 256) && !geo.fix) dd.splitk_ws = d.splitk_ws + SPAA_SPLITK_HDR_FLOATS;
+        if (pl.ksplit > 1 && (d.reserved1 & SPAA_SPLITK_FIXUP) && !geo.fix) dd.splitk_ws = d.splitk_ws + SPAA_SPLITK_HDR_FLOATS;
 #define H16P_LAUNCH_CV(N, SLOT)                                                                                            \
     {                                                                                                                      \
         typedef h16p_geo<1> G;                                                                                             \
@@ -811,9 +811,9 @@ int spaa_launch_tapconv_h16p(const spaa_tapconv_t& d, hipStream_t stream) {
     if (d.ksplit > 1) return hipErrorInvalidValue;
     const int OH = S == 1 ? h16p_geo<1>::OH : h16p_geo<2>::OH;
     const int wg_y = (d.Hm + OH - 1) / OH, wg_x = (d.Wm + OW - 1) / OW;
-    // (`reserved1` bit 5: the 64-wide two-workgroups-per-CU form for wider layers too -- short K, where prologue and epilogue outweigh the
+    // (SPAA_H16P_LEAN_WIDE: the 64-wide two-workgroups-per-CU form for wider layers too -- short K, where prologue and epilogue outweigh the
     // products: chosen per layer shape by spaa_amd/convplan.py)
-    const int BN = (d.Cout * nfold <= 64 || (S == 1 && (d.reserved1 & 32) && !(d.reserved1 & 16))) ? 64 : 128;
+    const int BN = (d.Cout * nfold <= 64 || (S == 1 && (d.reserved1 & SPAA_H16P_LEAN_WIDE) && !(d.reserved1 & SPAA_H16P_ONE_WG))) ? 64 : 128;
     const int n_tiles = (d.Cout * nfold + BN - 1) / BN;
     const int64_t nwg = (int64_t)d.B * wg_y * wg_x * n_tiles;
     if (nwg > 0x7fffffff) return hipErrorInvalidValue;
@@ -827,14 +827,14 @@ int spaa_launch_tapconv_h16p(const spaa_tapconv_t& d, hipStream_t stream) {
         if (e != hipSuccess) return (int)e;                                                                                \
         hipLaunchKernelGGL((h16p_kernel<N, SS>), dim3((unsigned)nwg), dim3(512), smem, stream, d, wg_y, wg_x, n_tiles, nogeo); \
     }
-    const bool unp = (d.reserved1 & 128) != 0;
+    const bool unp = (d.reserved1 & SPAA_H16P_UNPOOL) != 0;
     if (unp) {
         // pool-adjoint prologue: `in` = the pooled gradient, `in2` = the pool's arg-max bytes; the two-workgroup form only
-        if (S != 1 || BN != 64 || (d.reserved1 & 16) || nfold != 1 || d.in2 == nullptr || (d.Hin & 1) || (d.Win & 1) || (d.in2_cstride & 7) || (d.in2_coff & 7) ||
+        if (S != 1 || BN != 64 || (d.reserved1 & SPAA_H16P_ONE_WG) || nfold != 1 || d.in2 == nullptr || (d.Hin & 1) || (d.Win & 1) || (d.in2_cstride & 7) || (d.in2_coff & 7) ||
             d.in2_coff + d.Cin > d.in2_cstride || d.tap_range[0] < -1 || d.tap_range[1] > 1 || d.tap_range[2] < -1 || d.tap_range[3] > 1)
             return hipErrorInvalidValue;
     }
-    if (S == 1 && BN == 64 && !(d.reserved1 & 16)) {
+    if (S == 1 && BN == 64 && !(d.reserved1 & SPAA_H16P_ONE_WG)) {
         // two workgroups per compute unit (LEAN): one 40 KiB patch buffer + three 12 KiB weight stages; epilogue 8 x 32 rows of 272 bytes
         typedef h16p_geo<1> G;
         const size_t mainb = (size_t)G::PATCH_BYTES + 3 * (size_t)(12 * 1024), epib = 8 * 32 * (size_t)(64 * 4 + 16);

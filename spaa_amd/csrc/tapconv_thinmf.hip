@@ -28,6 +28,11 @@ namespace {
 constexpr int TW = 32;   // class-grid columns of a workgroup (rows: 4 RW, RW = rows of a wave: template parameter)
 constexpr int NW = 8;
 
+#ifdef SPAA_THINMF_ABLATE
+// timing-only ablation mask of a -DSPAA_THINMF_ABLATE build (wrong results): 1 = no operand split
+__device__ __forceinline__ int thinmf_dbg(const int reserved0) { return (reserved0 & SPAA_DBG_THINMF) >> SPAA_DBG_THINMF_SHIFT; }
+#endif
+
 // HIN: fp16 input (one weight plane, one MFMA per product); TBH: rows of the tap box (2..4); RW: class-grid rows per wave (the
 // workgroup covers 4 RW rows); PDB: the patch double-buffered over the channel blocks.  fp32 input runs RW = 2 with a SINGLE patch
 // buffer (49 + 24 KiB: two workgroups per CU cover each other's load phases; 3 / double-buffered needs 156 KiB = one per CU)
@@ -207,7 +212,7 @@ __global__ __launch_bounds__(512, PDB ? 1 : 2) void thinmf_kernel(const spaa_tap
                 const f32x4 v0 = *reinterpret_cast<const f32x4*>(pbase + q * 128 + ((c0 ^ sw) << 4));
                 const f32x4 v1 = *reinterpret_cast<const f32x4*>(pbase + q * 128 + (((c0 + 1) ^ sw) << 4));
 #ifdef SPAA_THINMF_ABLATE
-                if ((p.reserved0 >> 27) & 1) {   // timing only: no operand split
+                if (thinmf_dbg(p.reserved0) & 1) {   // timing only: no operand split
                     bfr[j][0] = __builtin_bit_cast(bf16x8, v0);
                     bfr[j][1] = __builtin_bit_cast(bf16x8, v1);
                     bfr[j][2] = bfr[j][0];

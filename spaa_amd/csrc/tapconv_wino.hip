@@ -78,7 +78,7 @@ struct wino_geo_t {
 // compute unit -- the two waves of a SIMD belong to different workgroups, so one's prologue / epilogue runs under the other's main
 // loop (short-K layers: ResNet-18 layer1 spends a third of a launch in them).
 __host__ __device__ __forceinline__ int wino_pad(const int reserved0) {
-    const int c = (reserved0 >> 27) & 3;
+    const int c = (reserved0 & SPAA_WINO_PAD) >> SPAA_WINO_PAD_SHIFT;
     return c == 0 ? 1 : (c == 1 ? 0 : 2);
 }
 template <int BN, int VAR, int DBG = 0, bool CV = false, bool TWO = false, int NWT = 8>   // DBG: timing-only ablations (wrong results): 1 no epilogue, 2 no fold, 4 no V, 8 no barrier, 16 no DMA; 32: raw barrier.  CV: canvas / split-K form
@@ -101,7 +101,7 @@ __global__ __launch_bounds__(64 * NWT, NWT == 4 ? 2 : 1) void wino_x6_kernel(con
     const spaa_tapclass_t cl = p.cls[0];
     const int Cin = p.Cin, H = p.Hin, W = p.Win;
     // zero padding of the layer: 1 (same size), 0 (unpadded: the output is 2 smaller) or 2 (the unpadded layer's input gradient: 2 larger);
-    // `reserved0` bits 27-28 = 0 / 1 / 2.  The canvas / K-range form (CV) shares its gaps as padding: pad 1 only (the launcher sees to it).
+    // SPAA_WINO_PAD = 0 / 1 / 2.  The canvas / K-range form (CV) shares its gaps as padding: pad 1 only (the launcher sees to it).
     const int pad_ = CV ? 1 : wino_pad(p.reserved0);
 
     // XCD-aware order over (image, patch row, patch column, n tile): an XCD takes a contiguous range
@@ -602,7 +602,7 @@ inline wino_plan_t wino_make_plan(const spaa_tapconv_t& d, const int ncu_, const
     int cgy = 1, cgx = 1, cnc = B, cwy = pwy, cwx = pwx;
     const int py = H + 1, px = W + 1;
     const bool small = (int64_t)B * H * W < ((int64_t)1 << 24) && H <= 4095 && W <= 4095;   // (the canvas / K-range kernel's 24-bit index arithmetic)
-    if (py <= 255 && px <= 255 && small && !((d.reserved0 >> 30) & 1)) {
+    if (py <= 255 && px <= 255 && small && !(d.reserved0 & SPAA_WINO_NO_CANVAS)) {
         for (int gx = 1; gx <= B && gx * px - 1 <= 4095; ++gx) {
             const int wx = cdiv(gx * px - 1, 2 * TX);
             for (int gy = 1; gy * gx <= B + gx - 1 && gy * py - 1 <= 4095; ++gy) {   // (gy up to ceil(B / gx))
@@ -635,8 +635,8 @@ inline wino_plan_t wino_make_plan(const spaa_tapconv_t& d, const int ncu_, const
                 double cost = rounds * (kb_per * (bn == 128 ? 22.4 : 12.8) + (bn == 128 ? 20.0 : 12.0) + ((cv || ksr > 1) && bn == 64 ? 6.0 : 0.0));
                 if (nw == 4) cost = rounds * (kb_per * 12.8 + 6.0);   // (two half-size workgroups per CU share its rate: per slot the same time per block)
                 if (ksr > 1) cost += 5.0 + (double)ksr * (double)M * npad * 4.0 / 12e6;   // (second pass: the partial sums come from L2 / MALL)
-                if (cv && !((d.reserved0 >> 29) & 1)) cost *= nw == 4 ? 1.15 : 1.05;   // (the canvas form must win by 5 % -- 15 % with four-wave workgroups: 56 x 56, 798 against 896 workgroups, 73 against 69 us -- else the image-aligned regions)
-                if (!cv && best < plain && ((d.reserved0 >> 29) & 1)) cost *= 1e6;   // (tests: canvas wherever it has fewer regions)
+                if (cv && !(d.reserved0 & SPAA_WINO_FORCE_CANVAS)) cost *= nw == 4 ? 1.15 : 1.05;   // (the canvas form must win by 5 % -- 15 % with four-wave workgroups: 56 x 56, 798 against 896 workgroups, 73 against 69 us -- else the image-aligned regions)
+                if (!cv && best < plain && (d.reserved0 & SPAA_WINO_FORCE_CANVAS)) cost *= 1e6;   // (tests: canvas wherever it has fewer regions)
                 if (ksr > 1) cost *= 1.02;  // (ties: no split)
                 if (cost < best_cost) {
                     best_cost = cost;
@@ -688,7 +688,7 @@ extern "C" int spaa_tapconv_wino_plan(const spaa_tapconv_t* desc, int32_t* plan)
     if (d.w_split == nullptr) d.w_split = reinterpret_cast<const uint16_t*>(desc);   // (the plan does not depend on the pointers)
     if (!wino_shape_ok(d) || (d.tile != 70 && d.tile != 71 && d.tile != 73)) return hipErrorInvalidValue;
     const bool nosplit = d.in2 != nullptr || wino_pad(d.reserved0) != 1;   // (two sources / unpadded layers: image-aligned regions, no K ranges)
-    if (nosplit) d.reserved0 |= 1 << 30;
+    if (nosplit) d.reserved0 |= SPAA_WINO_NO_CANVAS;
     const wino_plan_t pl = wino_make_plan(d, wino_ncu(), d.tile == 70 ? 0 : 64, nosplit ? 1 : d.ksplit, !nosplit, d.tile == 73 ? 4 : 8);
     if (pl.bn == 0 || pl.ksplit < 1 || pl.n_tiles < 1) return hipErrorInvalidValue;   // (a forced K-range count with no admissible candidate)
     plan[0] = pl.bn, plan[1] = pl.ksplit, plan[2] = pl.canvas, plan[3] = pl.gy, plan[4] = pl.gx;
@@ -706,7 +706,7 @@ int spaa_launch_tapconv_wino(const spaa_tapconv_t& d, hipStream_t stream) {
     if (d.ksplit > 1 && !has_ws) return hipErrorInvalidValue;
     spaa_tapconv_t dp = d;
     const bool nosplit = d.in2 != nullptr || wino_pad(d.reserved0) != 1;
-    if (nosplit) dp.reserved0 |= 1 << 30;   // (two sources, unpadded layers: no canvas ...)
+    if (nosplit) dp.reserved0 |= SPAA_WINO_NO_CANVAS;   // (two sources, unpadded layers: no canvas ...)
     if (nosplit && d.ksplit > 1) return hipErrorInvalidValue;
     const wino_plan_t pl = wino_make_plan(dp, wino_ncu(), d.tile == 70 ? 0 : 64, (has_ws && !nosplit) ? d.ksplit : 1, has_ws && !nosplit,
                                           d.tile == 73 ? 4 : 8);   // (... and no K ranges)
@@ -728,21 +728,21 @@ int spaa_launch_tapconv_wino(const spaa_tapconv_t& d, hipStream_t stream) {
     geo.nsp = (int)(nwg / ((int64_t)n_tiles * pl.ksplit));
     // workgroup order by what an XCD's L2 should keep: the weight planes (16 positions x three bf16) or the activations
     geo.order = (int64_t)((d.Cout + 127) & ~127) * d.cls[0].Kpad * 6 > (int64_t)d.B * d.Hin * d.Win * d.Cin * 4;
-    // `reserved1` bit 8: the workspace begins with SPAA_SPLITK_HDR_FLOATS zeroed counter slots -> the K ranges meet inside the kernel
+    // SPAA_SPLITK_FIXUP: the workspace begins with SPAA_SPLITK_HDR_FLOATS zeroed counter slots -> the K ranges meet inside the kernel
     // (and the partial sums leave through the branch-free epilogue's agent-scope stores: 4-channel quads, 32-bit offsets)
-    geo.fix = pl.ksplit > 1 && (d.reserved1 & 256) && (int64_t)geo.nsp * n_tiles <= SPAA_SPLITK_HDR_FLOATS && !(d.Cout & 3) &&
+    geo.fix = pl.ksplit > 1 && (d.reserved1 & SPAA_SPLITK_FIXUP) && (int64_t)geo.nsp * n_tiles <= SPAA_SPLITK_HDR_FLOATS && !(d.Cout & 3) &&
               (int64_t)pl.ksplit * d.B * d.Hout * d.Wout * ((d.Cout + 127) & ~127) * 4 < ((int64_t)1 << 31);
     if (cv && !pl.canvas && (d.Hout > 4095 || d.Wout > 4095)) return hipErrorInvalidValue;
     if (cv && (int64_t)d.B * d.Hout * d.Wout >= ((int64_t)1 << 24)) return hipErrorInvalidValue;   // (the plan never asks for it: wino_make_plan)
     spaa_tapconv_t dd = d;
     dd.ksplit = pl.ksplit;
-    // (bit 8 asked for the in-kernel fix-up but the launch declined it: the caller's workspace still begins with the counter header --
+    // (SPAA_SPLITK_FIXUP asked for the in-kernel fix-up but the launch declined it: the caller's workspace still begins with the counter header --
     // the partial sums and the second pass go past it, and the counters stay zero for the next launch that takes the fix-up)
-    if (pl.ksplit > 1 && (d.reserved1 & 256) && !geo.fix) dd.splitk_ws = d.splitk_ws + SPAA_SPLITK_HDR_FLOATS;
+    if (pl.ksplit > 1 && (d.reserved1 & SPAA_SPLITK_FIXUP) && !geo.fix) dd.splitk_ws = d.splitk_ws + SPAA_SPLITK_HDR_FLOATS;
     static bool attr_set[15][SPAA_MAX_DEVICES] = {};
     // kernel variant: bit 0 = late V (waves 4-7 transform one step ahead), bit 1 = xi groups expanded.  Default 3 / 2 (measured:
-    // conv4 500 -> 462 us, conv5 461 -> 415 us against variant 0); `reserved0` bits 16-17 flip bits for A/B measurements
-    const int var = (BN == 64 ? 2 : 3) ^ ((d.reserved0 >> 16) & 3);   // (64-wide tile: late V does not pay: 168 / 167 / 159 us for 0 / 3 / 2)
+    // conv4 500 -> 462 us, conv5 461 -> 415 us against variant 0); SPAA_DBG_WINO_VAR flips bits for A/B measurements
+    const int var = (BN == 64 ? 2 : 3) ^ dbg_wino_var(d);   // (64-wide tile: late V does not pay: 168 / 167 / 159 us for 0 / 3 / 2)
 #define WINO_LAUNCH_T(N, V, C, SLOT)                                                                                      \
     {                                                                                                                     \
         const size_t smem = (size_t)PATCH_BYTES + 3 * (size_t)(((3 * N / 16 + 7) / 8) * 8 * 1024);                        \
@@ -759,7 +759,7 @@ int spaa_launch_tapconv_wino(const spaa_tapconv_t& d, hipStream_t stream) {
         hipLaunchKernelGGL((wino_x6_kernel<N, V, 0, false, true>), dim3((unsigned)nwg), dim3(512), smem, stream, dd, wg_y, wg_x, n_tiles, geo); \
     }
 #ifdef SPAA_WINO_ABLATE
-    const int dbg = (d.reserved0 >> 18) & 127;
+    const int dbg = dbg_wino_ablate(d);
 #define WINO_LAUNCH_DBG(D)                                                                                                \
     if (dbg == D) {                                                                                                       \
         static bool as_[SPAA_MAX_DEVICES] = {};                                                                           \

@@ -129,7 +129,7 @@ __global__ __launch_bounds__(64 * NW, 2) void tapconv_x6d_kernel(const spaa_tapc
     // the next chunk): the 128-byte slice of a pixel is then re-read by the 9 taps within 9 consecutive steps and stays
     // in the XCD's L2 (tap-major order re-reads every slice 12+ steps later, when 64 workgroups' traffic has evicted it).
     // The sum over K is the same set of products either way.
-    const bool chunk_major = (cl.ntaps > 1) && (Cin > BK) && !(p.reserved0 & 1);  // (reserved0 bit 0: tap-major, A/B runs)
+    const bool chunk_major = (cl.ntaps > 1) && (Cin > BK) && !(p.reserved0 & SPAA_DBG_X6D_TAPMAJOR);  // (tap-major: A/B runs)
 #define X6D_ADVANCE(tap, kc)                                                                                       \
     if (chunk_major) {                                                                                             \
         tap += 1;                                                                                                  \
@@ -734,7 +734,7 @@ int launch_x6d(const spaa_tapconv_t& d, hipStream_t stream, bool persistent = fa
         const int per_cu = (int)(160 * 1024 / smem) < 1 ? 1 : (int)(160 * 1024 / smem);
         const int resident = 256 * (per_cu > 8 * 4 / NW ? 8 * 4 / NW : per_cu);
         int cap = resident / (d.nclass * ksplit);
-        if ((d.reserved0 >> 8) > 0) cap = d.reserved0 >> 8;  // tests: force several tiles per workgroup on small layers
+        if (dbg_persist_cap(d) > 0) cap = dbg_persist_cap(d);  // tests: force several tiles per workgroup on small layers
         cap = cap < 8 ? 8 : (cap & ~7);
         if (streamk && cap > STREAMK_MAX_WG) cap = STREAMK_MAX_WG;
         if (streamk) {

@@ -55,11 +55,12 @@ __device__ __forceinline__ int swz_p(int q) { return ((q >> 1) & 3) << 1; }
 __device__ unsigned long long* g_x6p_stamps = nullptr;
 #define X6P_T() (stamp_on ? __builtin_amdgcn_s_memtime() : 0ull)
 #define X6P_ABL(bit) ((abl >> (bit)) & 1)
+__device__ __forceinline__ int x6p_ablate(const int reserved0) { return (reserved0 & SPAA_DBG_X6P_ABLATE) >> SPAA_DBG_X6P_ABLATE_SHIFT; }
 #else
 #define X6P_ABL(bit) 0
 #endif
 
-// STD (`reserved2` bit 0, vouched for by spaa_amd/convplan.py which sees the tap lists): the CANONICAL structure of a 3 x 3 / stride-2
+// STD (SPAA_X6P_STD, vouched for by spaa_amd/convplan.py which sees the tap lists): the CANONICAL structure of a 3 x 3 / stride-2
 // fractional layer -- tap window (0..1) x (0..1); class 0 = [(0,0)], class 1 = [(0,1), (0,0)], class 2 = [(1,0), (0,0)], class 3 =
 // [(1,1), (1,0), (0,1), (0,0)], which is what ConvTranspose2d(k3, s2, p1, op1) and the input gradient of Conv2d(k3, s2, p1) give.
 // The nine combos' (class, tap, window position) are then compile-time constants: no schedule words, no divisions by the combo
@@ -98,9 +99,9 @@ __global__ __launch_bounds__(64 * NW, 2) void x6p_kernel(const spaa_tapconv_t p,
         img = t / wg_y;
     }
 #ifdef SPAA_X6P_STAMP
-    // reserved0 bits 8-15 (this build only): timing ablations -- wrong results -- 1 no DMA after the first stages, 2 no fragment split,
+    // SPAA_DBG_X6P_ABLATE (this build only): timing ablations -- wrong results -- 1 no DMA after the first stages, 2 no fragment split,
     // 4 no barrier, 8 no MFMA, 16 no epilogue, 32 no fragment loads; 128: record the stamps
-    const int abl = (p.reserved0 >> 8) & 0xff;
+    const int abl = x6p_ablate(p.reserved0);
     const bool stamp_on = (abl & 128) != 0;
     const unsigned long long ts0 = X6P_T(), tr0 = __builtin_amdgcn_s_memrealtime();
     unsigned long long ts_wait = 0, ts_first = 0;
@@ -513,8 +514,8 @@ int spaa_launch_tapconv_x6p(const spaa_tapconv_t& d, hipStream_t stream) {
         if (e != hipSuccess) return (int)e;                                                                                \
         hipLaunchKernelGGL((x6p_kernel<N, T>), dim3((unsigned)nwg), dim3(64 * NW), smem, stream, d, wg_y, wg_x, n_tiles);      \
     }
-    // canonical (class, tap) structure (reserved2 bit 0: the caller has checked the tap lists; here: what the descriptor shows of it)
-    const bool std_ok = (d.reserved2 & 1) && d.cls[0].ntaps == 1 && d.cls[1].ntaps == 2 && d.cls[2].ntaps == 2 && d.cls[3].ntaps == 4 &&
+    // canonical (class, tap) structure (SPAA_X6P_STD: the caller has checked the tap lists; here: what the descriptor shows of it)
+    const bool std_ok = (d.reserved2 & SPAA_X6P_STD) && d.cls[0].ntaps == 1 && d.cls[1].ntaps == 2 && d.cls[2].ntaps == 2 && d.cls[3].ntaps == 4 &&
                         d.tap_range[0] == 0 && d.tap_range[1] == 1 && d.tap_range[2] == 0 && d.tap_range[3] == 1;
     if (std_ok) {
         if (BN == 32) X6P_LAUNCH_T(32, true, 2) else X6P_LAUNCH_T(64, true, 3)

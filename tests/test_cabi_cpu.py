@@ -50,6 +50,37 @@ def test_struct_layout_matches_c():
         assert lib.spaa_tapconv_offsetof(i) == getattr(_lib.TapConv, f).offset, f
 
 
+def header_form_flags():
+    """name -> value of the enum of form flags in include/spaa_hip.h (the one that begins with SPAA_DBG_X6D_TAPMAJOR): every value there is
+    written as an integer or as `integer << integer`."""
+    hdr = open(os.path.join(ROOT, 'include', 'spaa_hip.h')).read()
+    body = re.search(r'enum\s*\{([^}]*\bSPAA_DBG_X6D_TAPMAJOR\b[^}]*)\}', hdr).group(1)
+    flags = {}
+    for item in re.sub(r'/\*.*?\*/', '', body, flags=re.S).split(','):
+        if item.strip():
+            m = re.fullmatch(r'\s*(SPAA_[A-Z0-9_]+)\s*=\s*(\w+)(?:\s*<<\s*(\w+))?\s*', item)
+            assert m, item
+            flags[m.group(1)] = int(m.group(2), 0) << int(m.group(3) or '0', 0)
+    return flags
+
+
+def test_form_flags_match_header():
+    """The form flags of spaa_tapconv_t.reserved0 / reserved1 / reserved2: spaa_amd/_lib.py holds every name of the header's enum (without
+    the SPAA_ prefix) with the header's value, and nothing under those names that the header lacks; a field wider than one bit has its
+    mask at its shift."""
+    flags = header_form_flags()
+    assert len(flags) == 28 and flags['SPAA_WINO_PAD'] == 3 << 27 and flags['SPAA_SPLITK_FIXUP'] == 256
+    for name, value in flags.items():
+        assert getattr(_lib, name[len('SPAA_'):]) == value, name
+        assert 0 <= value < 1 << 31, name                       # (the words are int32)
+    mirrored = {n for n in vars(_lib) if re.match(r'(DBG|WINO|C3|H16P|SPLITK|X6P)_', n)}
+    assert mirrored == {n[len('SPAA_'):] for n in flags}
+    for name, shift in flags.items():
+        if name.endswith('_SHIFT'):
+            mask = flags[name[:-len('_SHIFT')]]
+            assert mask & -mask == 1 << shift and (mask >> shift) & ((mask >> shift) + 1) == 0, name   # contiguous bits from `shift` up
+
+
 def test_no_cpu_fallback():
     from spaa_amd.models import PCNet, WarpingNet, to_nhwc4
     from spaa_amd.classifier import Classifier
@@ -108,7 +139,7 @@ def test_torch_library_ops_are_registered():
 
 def _wino_plan(b, h, w, cin, cout, tile=70, ksplit=0, force_canvas=False):
     d = _lib.TapConv()
-    d.reserved0 = (1 << 29) if force_canvas else 0
+    d.reserved0 = _lib.WINO_FORCE_CANVAS if force_canvas else 0
     d.Hin = d.Hout = d.Hm = h
     d.Win = d.Wout = d.Wm = w
     d.Cin, d.Cout, d.B, d.s_in, d.s_out, d.nclass = cin, cout, b, 1, 1, 1
@@ -174,7 +205,7 @@ def _h16p_plan(b, h, w, cin, cout, ksplit=0, bn=0, force_canvas=False):
     d.Cin, d.Cout, d.B, d.s_in, d.s_out, d.nclass = cin, cout, b, 1, 1, 1
     d.in_cstride, d.out_cstride = cin, cout
     d.cls[0].ntaps, d.cls[0].K, d.cls[0].Kpad = 9, 9 * cin, 9 * cin
-    d.tile, d.ksplit, d.reserved1 = 68, ksplit, 4 | {0: 0, 64: 1, 128: 2}[bn] | (8 if force_canvas else 0)
+    d.tile, d.ksplit, d.reserved1 = 68, ksplit, _lib.H16P_CV | {0: 0, 64: 1, 128: 2}[bn] << _lib.H16P_CV_BN_SHIFT | (_lib.H16P_CV_FORCE if force_canvas else 0)
     wp = (ctypes.c_int32 * 8)()
     rc = _lib.load().spaa_tapconv_h16p_plan(ctypes.byref(d), wp)
     return rc, dict(zip(('bn', 'ksplit', 'canvas', 'gy', 'gx', 'nwg', 'kb_per', 'ncanvas'), wp))

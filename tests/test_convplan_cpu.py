@@ -287,3 +287,40 @@ def test_bf16_planes_one_split_everywhere():
     assert sorted(tot[tot != 0].tolist()) == sorted(c3.weights[c3.weights != 0].tolist())
     wino = cp.conv_fwd_plan(torch.randn(64, 32, 3, 3), None, 1, 1, device='cpu').wino
     check(wino.w_split, wino.weights)
+
+
+def test_debug_word_places_every_switch_in_its_field(monkeypatch):
+    """`reserved0` of a launch (convplan.debug_word): 0 but for the Winograd padding code with no switch set; every DEBUG_* value that
+    the tests and tools/lab use lands in its named field and nowhere else; a value that does not fit its field is refused instead of
+    running over into the next one."""
+    from spaa_amd import _lib
+    assert cp.debug_word(37) == cp.debug_word(72) == 0
+    assert [cp.debug_word(70, pad) >> _lib.WINO_PAD_SHIFT for pad in (1, 0, 2)] == [cp.wino_pad_code(pad) for pad in (1, 0, 2)] == [0, 1, 2]
+    for cap in (8, 24, 128, 1 | 2 | 4 | 8 | 32, 255):     # (tests: 8 / 24 workgroups; tools/lab/x6p_stamps.py: its ablation masks, 128 = stamps on)
+        monkeypatch.setattr(cp, 'DEBUG_PERSIST_CAP', cap)
+        assert cp.debug_word(51) == cap << _lib.DBG_PERSIST_CAP_SHIFT == cp.debug_word(51) & _lib.DBG_PERSIST_CAP
+    monkeypatch.setattr(cp, 'DEBUG_PERSIST_CAP', 256)
+    with pytest.raises(ValueError, match='DEBUG_PERSIST_CAP'):
+        cp.debug_word(51)
+    monkeypatch.setattr(cp, 'DEBUG_PERSIST_CAP', 0)
+    for dbg in (1, 33, 64, 96):                           # (tools/lab/wino_ablate.py: DEBUG_WINO = dbg << 2; wino_one.py: 256 = 64 << 2)
+        monkeypatch.setattr(cp, 'DEBUG_WINO', dbg << 2 | 3)
+        assert cp.debug_word(70) == dbg << _lib.DBG_WINO_ABLATE_SHIFT | _lib.DBG_WINO_VAR
+    monkeypatch.setattr(cp, 'DEBUG_WINO', 128 << 2)      # past bit 24
+    with pytest.raises(ValueError, match='DEBUG_WINO'):
+        cp.debug_word(70)
+    monkeypatch.setattr(cp, 'DEBUG_WINO', 0)
+    monkeypatch.setattr(cp, 'DEBUG_THINMF', 1)
+    assert cp.debug_word(72) == 1 << _lib.DBG_THINMF_SHIFT and cp.debug_word(70) == 0
+    monkeypatch.setattr(cp, 'DEBUG_THINMF', 0)
+    for nc, want in ((1, _lib.WINO_NO_CANVAS), (2, _lib.WINO_FORCE_CANVAS)):
+        monkeypatch.setattr(cp, 'DEBUG_WINO_NOCANVAS', nc)
+        assert cp.debug_word(71) == want and cp.debug_word(68) == 0
+    monkeypatch.setattr(cp, 'DEBUG_WINO_NOCANVAS', 0)
+    for name, flag in (('DEBUG_TAPMAJOR', _lib.DBG_X6D_TAPMAJOR), ('DEBUG_H16_2STAGE', _lib.DBG_H16_2STAGE), ('DEBUG_SMALLCIN_NOSLAB', _lib.DBG_SMALLCIN_NOSLAB)):
+        monkeypatch.setattr(cp, name, 1)
+        assert cp.debug_word(37) == flag
+        monkeypatch.setattr(cp, name, 2)
+        with pytest.raises(ValueError, match=name):
+            cp.debug_word(37)
+        monkeypatch.setattr(cp, name, 0)

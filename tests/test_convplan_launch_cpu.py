@@ -178,9 +178,11 @@ CASE_BY_NAME = {c['name']: c for c in CASES}
 assert len(CASE_BY_NAME) == len(CASES)
 
 # the coverage the fixture must show: (tile, sign of ksplit, reserved1) of a launch; messages raised
+_CV64 = _lib.H16P_CV | 1 << _lib.H16P_CV_BN_SHIFT    # tile 68's canvas / K-range form on the 64-wide N tile
 WANT_OUTCOMES = {(16, 0, 0), (18, 0, 0), (22, 0, 0), (29, 0, 0), (38, 0, 0), (34, 0, 0), (36, 0, 0), (37, 0, 0), (34, 1, 0), (36, 1, 0), (51, -1, 0),
-                 (60, 0, 0), (61, 0, 0), (62, 0, 0), (63, 0, 0), (60, 1, 0), (68, 0, 0), (68, 1, 5), (68, 1, 261), (68, 0, 32), (68, 0, 16),
-                 (68, 0, 64), (68, 0, 128), (70, 1, 0), (70, 1, 256), (71, 0, 0), (73, 0, 0), (72, 0, 0), (74, 0, 0), (76, 0, 0), (76, 0, 1), (0, 0, 0)}
+                 (60, 0, 0), (61, 0, 0), (62, 0, 0), (63, 0, 0), (60, 1, 0), (68, 0, 0), (68, 1, _CV64), (68, 1, _CV64 | _lib.SPLITK_FIXUP),
+                 (68, 0, _lib.H16P_LEAN_WIDE), (68, 0, _lib.H16P_ONE_WG), (68, 0, _lib.H16P_POOL), (68, 0, _lib.H16P_UNPOOL), (70, 1, 0),
+                 (70, 1, _lib.SPLITK_FIXUP), (71, 0, 0), (73, 0, 0), (72, 0, 0), (74, 0, 0), (76, 0, 0), (76, 0, _lib.C3_F16_OPERANDS), (0, 0, 0)}
 WANT_RAISES = {'must have the storage type of `out`', 'pool_adjoint needs fp32 tensors', 'a two-source plan needs `inp2`',
                'fp16-storage input needs Cin % 32 == 0', 'GATE_MUL needs a layer shape served by the DMA-staged kernels',
                'gate masks need a layer shape served by the bf16x6 / smallcin kernels', 'tile 76 serves 3-channel-image convolutions only',
@@ -418,8 +420,9 @@ def test_fixture_covers_every_route():
     raised = [c['raises'][1] for c in FIXTURE['cases'].values() if 'raises' in c]
     missing = [m for m in WANT_RAISES if not any(m in r for r in raised)]
     assert not missing, missing
-    assert {(d['reserved0'] >> 27) & 3 for d in launches if d['tile'] in (70, 71, 73)} == {0, 1, 2}      # Winograd paddings 1 / 0 / 2
-    assert {d['reserved2'] for d in launches if d['tile'] == 74} == {0, 1}
+    pad_codes = {(d['reserved0'] & _lib.WINO_PAD) >> _lib.WINO_PAD_SHIFT for d in launches if d['tile'] in (70, 71, 73)}
+    assert pad_codes == {cp.wino_pad_code(p) for p in (1, 0, 2)} == {0, 1, 2}      # Winograd paddings 1 / 0 / 2
+    assert {d['reserved2'] for d in launches if d['tile'] == 74} == {0, _lib.X6P_STD}
     entries = {r['entry'] for c in FIXTURE['cases'].values() for r in c['calls']}
     assert {'spaa_maxpool_bwd_f16', 'spaa_maxpool_fwd', 'spaa_maxpool_fwd_f16', 'spaa_linear_small', 'spaa_tapconv_wgrad'} <= entries
 

@@ -277,7 +277,7 @@ def test_winograd_is_fp32_accurate(hip, ci, co, h, w, b):
 def test_winograd_unpadded_layers(hip, ci, co, h, w, b, tile):
     """An UNPADDED 3x3 / s1 convolution (Inception-v3's Conv2d_2a / Conv2d_4a: classifier.py:29-33 of the reference) and its
     input gradient through the Winograd kernel: the output is 2 smaller (pad 0) resp. 2 larger (pad 2) than the input, which only
-    moves the patch origin (csrc/tapconv_wino.hip: `reserved0` bits 27-28).  Against fp64 at the padded layers' bound, bias + ReLU +
+    moves the patch origin (csrc/tapconv_wino.hip: SPAA_WINO_PAD in `reserved0`).  Against fp64 at the padded layers' bound, bias + ReLU +
     byte mask on the forward, byte-mask gate on the gradient."""
     cp, lib = hip['cp'], hip['lib']
     torch.manual_seed(ci + co + h)
@@ -3217,7 +3217,7 @@ def test_small_linear_route_boundaries(hip, m, k, n):
 
 
 def test_k_range_fixup_declined_leaves_header_alone(hip):
-    """`reserved1` bit 8 (SPAA_SPLITK_FIXUP=1): the K ranges meet inside the kernel behind a header of arrival counters -- unless the
+    """SPAA_SPLITK_FIXUP in `reserved1` (environment: SPAA_SPLITK_FIXUP=1): the K ranges meet inside the kernel behind a header of arrival counters -- unless the
     launcher declines (more (region, N tile) pairs than the header holds, Cout % 4, a workspace of 2 GiB or more).  A declined launch
     must run the two-pass form PAST the header: partial sums written over the counters would leave the next accepted launch on the
     same workspace with garbage counters, no workgroup seeing itself arrive last, and its output never written.  One plan each of the

@@ -29,7 +29,7 @@ def t_launch(plan, x, out, n=10, **kw):
 
 
 def ablate(name, plan, x, out, **kw):
-    """timing-only ablations of the diagnostic build (reserved0 bits 8-15 = convplan.DEBUG_PERSIST_CAP): wrong results"""
+    """timing-only ablations of the diagnostic build (SPAA_DBG_X6P_ABLATE in `reserved0`: the bits of convplan.DEBUG_PERSIST_CAP, values up to 255): wrong results"""
     cp.FORCE_TILE = 74
     res = []
     for label, bits in (('full', 0), ('no DMA', 1), ('no split', 2), ('no barrier', 4), ('no epilogue', 16), ('no frag loads+split', 34),
