@@ -656,6 +656,37 @@ int spaa_ens_sumsq(const float* const* g, int K, float* partial, int B, int HW, 
 int spaa_ens_combine(const float* const* g, int K, const float* partial, int nblk, const float* ens_w, float* g_adv, int B, int HW,
                      spaa_stream_t stream);
 
+/* ---- multi-view SPAA: one projection against V camera views of the same projector and scene, 2 <= V <= SPAA_VIEWS_MAX ------- */
+#define SPAA_VIEWS_MAX 4
+/* Per-view tensors are passed as HOST arrays of V device pointers, as the ensemble's member tensors.  Any other V is
+ * hipErrorInvalidValue and nothing is launched.
+ *
+ * The decision over V views: view v has its own logits [B][ncls] (one classifier looking at camera image v) and its own stealth-loss
+ * block partials [B][nblk][3] (spaa_stealth_loss_fwd_bwd_ps on camera image v).  Per-sample table form only (params, flags, adv_scale
+ * as spaa_decide_ps).  View v of sample b: top1, p1, the target logit and the means caml2_v, camdE_v by the arithmetic of spaa_decide;
+ * succ and fooled as in spaa_decide_ens.  Sample: caml2 = (sum over v in index order of caml2_v) / V, camdE likewise, col_loss =
+ * prjl2_w prjl2 + caml2_w caml2 + camdE_w camdE.  Outputs:
+ *   state [B][4]: 0 every view succ, 1 best_adv = every view fooled && caml2 * 255 > d_thr, 2 best, 3 number of fooled views
+ *   stats [B][8]: 0 min over views of p1, 6 mean over views of the target logit, 1..5 as spaa_decide on the sample's values
+ *   view_state int32 [B][V][2] = (bit 0 succ | bit 1 fooled, top1)    view_stats float [B][V][4] = (p1, target logit, caml2_v, camdE_v)
+ *   view_w float [B][V]: the view weights of spaa_views_combine -- 1, or with focus != 0: 0 for a fooled view unless all are fooled
+ *   g_logits: V seeds [B][ncls], (c == target_b) ? -adv_scale (targeted) / +adv_scale : 0
+ * With V identical views (V a power of two) state[.][0..2], stats[.][1..5] and the seeds are bitwise those of spaa_decide_ps. */
+int spaa_decide_views(const float* const* logits, int V, int ncls, const int32_t* target, const float* const* partial, int nblk, int HW,
+                      const float* prjl2, const float* params, const int32_t* flags, float p_thresh, float adv_scale, int focus,
+                      int32_t* state, float* stats, int32_t* view_state, float* view_stats, float* view_w, float* const* g_logits,
+                      int B, spaa_stream_t stream);
+/* The V views' input gradients at the projector image, g[v]: [B][HW][4], as one: for a colour-step sample (state[b][1] != 0)
+ * g_out_b = (sum over v in index order of g_bv) * (1 / V), the gradient of the mean of the views' stealth losses, not normalised (the
+ * prjl2 term that spaa_grad_sumsq adds afterwards keeps its scale); for every other sample g_out_b = sum over v in index order of
+ * view_w[b][v] * g_bv / ||g_bv||_2, a view with zero norm contributing 0.  The pad channel of g_out [B][HW][4] is 0.  partial
+ * [B][V][nblk] from spaa_ens_sumsq with the same HW, nblk = ceil(HW / 256); run-to-run bitwise reproducible */
+int spaa_views_combine(const float* const* g, int V, const float* partial, int nblk, const float* view_w, const int32_t* state,
+                       float* g_out, int B, int HW, spaa_stream_t stream);
+/* cam_best[v]_b = cam[v]_b where state[b][0] != 0 (succ), for the views v = 1 .. V-1 in one launch: what spaa_step_and_track_n does
+ * for the one camera image it is given (view 0's).  cam, cam_best: V pointers each to [B][HW][4]; entry 0 is not read */
+int spaa_views_track(const float* const* cam, float* const* cam_best, int V, const int32_t* state, int B, int HW, spaa_stream_t stream);
+
 /* ---- PerC_AL.adversary_projector (perc_al/__init__.py:133-256) ------------------------------------------ */
 /* x = a + b (inputs + delta), NHWC4 */
 int spaa_add_nhwc4(const float* a, const float* b, float* x, int npix, spaa_stream_t stream);

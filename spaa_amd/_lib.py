@@ -182,6 +182,9 @@ _SIGNATURES = {
     'spaa_decide_ens': [_pp, _i, _i, _p, _p, _i, _i, _p, _p, _p, _f, _i, _p, _p, _p, _p, _p, _pp, _i, _p],
     'spaa_ens_sumsq': [_pp, _i, _p, _i, _i, _p],
     'spaa_ens_combine': [_pp, _i, _p, _i, _p, _p, _i, _i, _p],
+    'spaa_decide_views': [_pp, _i, _i, _p, _pp, _i, _i, _p, _p, _p, _f, _f, _i, _p, _p, _p, _p, _p, _pp, _i, _p],
+    'spaa_views_combine': [_pp, _i, _p, _i, _p, _p, _p, _i, _i, _p],
+    'spaa_views_track': [_pp, _pp, _i, _p, _i, _i, _p],
     'spaa_onepixel_preproc': [_p, _p, _i, _i, _i, _p, _i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_float), C.POINTER(C.c_float), _p],
     'spaa_onepixel_score': [_p, _i, _i, _i, _p, _p, _p, _i, _p],
     'spaa_onepixel_warp': [_p, _p, _i, _i, _i, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p],
@@ -262,7 +265,7 @@ def ptr(t):
 
 
 def ptr_array(tensors):
-    """The HOST array of device pointers that the ensemble entry points take (one per member tensor)."""
+    """The HOST array of device pointers that the ensemble and multi-view entry points take (one per member / view tensor)."""
     return (C.c_void_p * len(tensors))(*[ptr(t).value for t in tensors])
 
 

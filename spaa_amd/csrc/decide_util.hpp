@@ -1,7 +1,8 @@
-// decide_util.hpp — the per-sample arithmetic of SPAA's decision step, shared by decide_kernel (attack_ops.hip: one classifier) and
-// decide_ens_kernel (ensemble_ops.hip: K classifiers on the same camera image): a classifier's first-maximum arg-max and softmax
-// top-1 probability, and the stealth-loss sums with the colour loss built from them.  One copy, so that a member of an ensemble gets
-// bitwise what spaa_decide / spaa_decide_ps give that classifier alone.  Workgroups of 256 threads.
+// decide_util.hpp — the per-sample arithmetic of SPAA's decision step, shared by decide_kernel (attack_ops.hip: one classifier),
+// decide_ens_kernel (ensemble_ops.hip: K classifiers on the same camera image) and decide_views_kernel (multiview_ops.hip: one
+// classifier on V camera images): a classifier's first-maximum arg-max and softmax top-1 probability, and the stealth-loss sums with
+// the colour loss built from them.  One copy, so that a member of an ensemble, or a view, gets bitwise what spaa_decide /
+// spaa_decide_ps give that classifier and camera image alone.  Workgroups of 256 threads.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -320,8 +320,166 @@ class EnsembleAttackState(AttackState):
         return super().trace_entry() + (self.ens_state.clone(), self.ens_stats.clone())
 
 
+VIEWS_MAX = 4   # SPAA_VIEWS_MAX of include/spaa_hip.h
+
+
+def _view_pcnets(pcnet, cam_scene, who):
+    """The views of a list / tuple `pcnet`, checked (before anything is allocated or launched): each a spaa_amd.PCNet, 2 to VIEWS_MAX of
+    them, no object twice, and `cam_scene` a list / tuple of as many scenes.  Returns (list of PCNets, list of scenes); a sequence of
+    one PCNet is that PCNet: (PCNet, its scene)."""
+    views = [_unwrap(m) for m in pcnet]
+    for m in views:
+        if not isinstance(m, PCNet):
+            raise TypeError(f'{who}: every view must be a spaa_amd.PCNet, got {type(m).__name__} (the HIP path has no generic PCNet '
+                            'fallback)')
+    if not views:
+        raise ValueError(f'{who}: the pcnet sequence is empty')
+    if len(views) == 1:
+        if isinstance(cam_scene, (list, tuple)):
+            if len(cam_scene) != 1:
+                raise ValueError(f'{who}: {len(cam_scene)} scenes for one view')
+            cam_scene = cam_scene[0]
+        return views[0], cam_scene
+    if len(views) > VIEWS_MAX:
+        raise ValueError(f'{who}: a multi-view attack holds at most {VIEWS_MAX} views, got {len(views)}')
+    if len({id(m) for m in views}) != len(views):
+        raise ValueError(f'{who}: the same PCNet object is listed twice among the views')
+    if not isinstance(cam_scene, (list, tuple)) or len(cam_scene) != len(views):
+        n = len(cam_scene) if isinstance(cam_scene, (list, tuple)) else 'one tensor'
+        raise ValueError(f'{who}: cam_scene must be a list of one scene per view ({len(views)}), got {n}')
+    return views, list(cam_scene)
+
+
+def _views_supported(views, classifier, storage, who):
+    """What a multi-view attack does not serve, said before anything is allocated or launched.  `classifier`: as spaa() holds it after
+    its own checks (a Classifier, a checked list of several, or anything else)."""
+    if isinstance(classifier, list):
+        raise NotImplementedError(f'{who}: an ensemble of classifiers against several views is not implemented; attack one '
+                                  'classifier from several views, or several classifiers from one')
+    if not isinstance(classifier, Classifier):
+        raise TypeError(f'{who}: a multi-view attack needs a spaa_amd.Classifier, got {type(classifier).__name__} (a foreign '
+                        'callable can only be attacked from one view)')
+    if storage != 'f32':
+        raise NotImplementedError(f"{who}: storage={storage!r} is not implemented for several views (the views' unit vectors need a "
+                                  "loss scale of their own); use storage='f32'")
+    sizes = [tuple(m.warping_net.out_size) for m in views]
+    if any(sz != sizes[0] for sz in sizes):
+        raise ValueError(f'{who}: the views must have the same camera size, got {sizes}')
+
+
+class MultiViewAttackState(AttackState):
+    """One batched attack against V = 2..VIEWS_MAX camera views of the same projector and scene ("Multi-view attack"): one
+    projector image x through V PCNets, each with its own scene, and one classifier looking at each of the V camera images.
+    AttackState (view 0's engines and buffers are its own) with one leased PCNet engine and one leased engine of the classifier per
+    further view, the decision over all views (spaa_decide_views), the V backward passes down to the projector image and their
+    combination there (spaa_ens_sumsq + spaa_views_combine): the mean of the views' stealth gradients on the colour step, the weighted
+    sum of the views' unit gradient images on the adversarial step.  `state[:, 3]` counts the fooled views; each view's top-1 is in
+    `view_state`, its p1, target logit, caml2 and camdE in `view_stats`.  `focus`: a view that is already fooled rests (weight 0) until
+    all are."""
+
+    def __init__(self, pcnets, classifier, target_idx, cam_scenes, stealth_loss, setup_info, device, storage='f32', focus=False):
+        views, scenes = _view_pcnets(pcnets, cam_scenes, 'MultiViewAttackState')
+        if not isinstance(views, list):
+            raise ValueError('MultiViewAttackState needs at least two views (AttackState attacks one)')
+        classifier = _unwrap(classifier)
+        _views_supported(views, classifier, storage, 'MultiViewAttackState')
+        self.pcnets, self._scenes, self.focus = views, scenes, bool(focus)
+        super().__init__(views[0], classifier, target_idx, scenes[0], stealth_loss, setup_info, device, storage=storage)
+
+    def _build(self, pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, dev):
+        super()._build(pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, dev)   # (view 0: self.eng, self.clf, ...)
+        B, V = self.B, len(self.pcnets)
+        self.V = V
+        Hc, Wc = self.eng.Hc, self.eng.Wc
+        # ||g||^2 of the COMBINED gradient comes from spaa_grad_sumsq_ps (a view's adjoint cannot sum it in its epilogue), and the
+        # views' backward passes read the clamp gate from x
+        self.ss_tiles, self.clamp_bits = 0, None
+        self.partial_ss = torch.zeros(B, self.nblk_p, device=dev)
+        self.engs, self.clfs = [self.eng], [self.clf]
+        self.scene4s, self.scene_labs, self.g_cols, self.gPs = [self.scene4], [self.scene_lab], [self.g_col], [self.gP]
+        self.partial_losses, self.view_g_logits, self.cam_bests = [self.partial_loss], [self.g_logits], [self.cam_best]
+        for m, sc in zip(self.pcnets[1:], self._scenes[1:]):
+            sc = _scene_batch(sc, B)
+            if sc.shape[0] != B:
+                raise ValueError('every view\'s cam_scene must hold 1 or len(target_idx) scenes')
+            eng = m.engine(B, tuple(setup_info['prj_im_sz']), owner=self, storage=self.storage)
+            if (eng.Hc, eng.Wc) != (Hc, Wc):
+                raise ValueError(f'the views must have the same camera size, got {(Hc, Wc)} and {(eng.Hc, eng.Wc)}')
+            if tuple(sc.shape[-2:]) != (Hc, Wc):
+                raise ValueError(f'cam_scene is {tuple(sc.shape[-2:])} but PCNet outputs {(Hc, Wc)}')
+            scene4 = to_nhwc4(sc.contiguous().to(dev))
+            eng.set_scene(scene4)
+            lab = torch.zeros_like(scene4)
+            _lib.call('spaa_rgb2lab', _lib.ptr(scene4), _lib.ptr(lab), B * Hc * Wc)
+            self.engs.append(eng)
+            self.clfs.append(classifier.engine(B, (Hc, Wc), self.cp_sz, owner=self, storage=self.storage))
+            self.scene4s.append(scene4)
+            self.scene_labs.append(lab)
+            self.g_cols.append(torch.zeros_like(self.g_col))
+            self.gPs.append(torch.zeros_like(self.gP))
+            self.partial_losses.append(torch.zeros_like(self.partial_loss))
+            self.view_g_logits.append(torch.zeros_like(self.g_logits))
+            self.cam_bests.append(scene4.clone())
+        self.view_state = torch.zeros(B, V, 2, dtype=torch.int32, device=dev)
+        self.view_stats = torch.zeros(B, V, 4, device=dev)
+        self.view_w = torch.ones(B, V, device=dev)
+        self.views_partial = torch.zeros(B, V, self.nblk_p, device=dev)
+        self.g = torch.zeros(B, self.x.shape[1], self.x.shape[2], 4, device=dev)
+        self._ys = None
+
+    def _forward_decide(self, targeted, d_thr, p_thresh, adv_w):
+        B, p = self.B, _lib.ptr
+        self._per_sample(targeted, d_thr, table=True)   # (the decision over views has the per-sample table form only)
+        ys, logits = [], []
+        for v in range(self.V):
+            y = self.engs[v].forward(self.x, clamp01=True)                           # :265, once per view
+            logits.append(self.clfs[v].forward(y))                                   # :266
+            _lib.call('spaa_stealth_loss_fwd_bwd_ps', p(y), p(self.scene4s[v]), p(self.scene_labs[v]), p(self.ps_params),
+                      self.gs_col / (B * self.HWc), p(self.g_cols[v]), None, p(self.partial_losses[v]), B, self.HWc)
+            ys.append(y)
+        self._ys, self._y, self._uniform = ys, ys[0], False
+        if self.any_prjl2:
+            _lib.call('spaa_prjl2_fwd', p(self.x), self.gray, p(self.prjl2), B, self.HWp)
+        _lib.call('spaa_decide_views', _lib.ptr_array(logits), self.V, self.clf.ncls, p(self.target),
+                  _lib.ptr_array(self.partial_losses), self.nblk_c, self.HWc, p(self.prjl2) if self.any_prjl2 else None,
+                  p(self.ps_params), p(self.ps_flags), float(p_thresh), adv_w / B * self.gs_adv, int(self.focus), p(self.state),
+                  p(self.stats), p(self.view_state), p(self.view_stats), p(self.view_w), _lib.ptr_array(self.view_g_logits), B)
+
+    def _backward_step(self, adv_lr, col_lr):
+        B, p = self.B, _lib.ptr
+        gxs = []
+        for v, eng in enumerate(self.engs):
+            g_adv = self.clfs[v].backward(self.view_g_logits[v])                     # :302 (classifier part), from view v's seed
+            if eng.can_select():
+                gxs.append(eng.backward(None, select=(g_adv, self.g_cols[v], self.state), sumsq=None, clamp_bits=None))
+            else:
+                _lib.call('spaa_select_grad', p(g_adv), p(self.g_cols[v]), p(self.state), p(eng.a['Ypre']), p(self.gPs[v]), B,
+                          self.HWc)
+                gxs.append(eng.backward(self.gPs[v], sumsq=None, clamp_bits=None))   # :302 / :310 (PCNet part)
+        gs = _lib.ptr_array(gxs)
+        _lib.call('spaa_ens_sumsq', gs, self.V, p(self.views_partial), B, self.HWp)
+        _lib.call('spaa_views_combine', gs, self.V, p(self.views_partial), self.nblk_p, p(self.view_w), p(self.state), p(self.g), B,
+                  self.HWp)
+        _lib.call('spaa_grad_sumsq_ps', p(self.g), p(self.x), self.gray, p(self.ps_prjl2_scale), p(self.state), p(self.partial_ss), B,
+                  self.HWp)
+        _lib.call('spaa_step_and_track_n', p(self.x), p(self.g), p(self.partial_ss), self.nblk_p, p(self.state), float(adv_lr),
+                  float(col_lr), p(self.x_best), p(self._ys[0]), p(self.cam_best), B, self.HWp, self.HWc, None)   # :307,315,323-328
+        _lib.call('spaa_views_track', _lib.ptr_array(self._ys), _lib.ptr_array(self.cam_bests), self.V, p(self.state), B, self.HWc)
+
+    def trace_entry(self):
+        return super().trace_entry() + (self.view_state.clone(), self.view_stats.clone())
+
+    def results(self):
+        with torch.cuda.device(self.dev):
+            return [to_nchw(c) for c in self.cam_bests], to_nchw(self.x_best, clamp01=True)
+
+
 def _attack_state(pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, device, storage, focus):
-    """AttackState for one Classifier, EnsembleAttackState for a checked list of several."""
+    """AttackState for one Classifier, EnsembleAttackState for a checked list of several, MultiViewAttackState for a checked list of
+    PCNets (with their list of scenes)."""
+    if isinstance(pcnet, list):
+        return MultiViewAttackState(pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, device, storage=storage,
+                                    focus=focus)
     if isinstance(classifier, list):
         return EnsembleAttackState(pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, device, storage=storage,
                                    focus=focus)
@@ -332,10 +490,14 @@ def spaa(pcnet, classifier, imagenet_labels, target_idx, targeted, cam_scene, d_
          *, iters=50, adv_lr=2, col_lr=1, p_thresh=0.9, trace=None, verbose=False, storage='f32', focus=False):
     """Stealthy Projector-based Adversarial Attack (SPAA Algorithm 1) — see module docstring.
 
-    :param pcnet: spaa_amd.PCNet (optionally wrapped in DataParallel-like `.module`)
+    :param pcnet: spaa_amd.PCNet (optionally wrapped in DataParallel-like `.module`), or a list / tuple of 2..4 of them: the same projector
+        and scene seen from as many camera poses, ONE projection against all of these views (MultiViewAttackState; one Classifier,
+        fp32 storage, one camera size).  `cam_scene` is then a list of one scene per view and the first return value a list of one
+        camera image batch per view.  A sequence of one is that PCNet.
     :param classifier: spaa_amd.Classifier, or a list / tuple of 2..4 of them with the same classes: ONE projection against all of them
         (EnsembleAttackState; fp32 storage only).  A sequence of one is that classifier.
-    :param focus: ensembles only: members that are already fooled rest until all are (default: every member pulls all the time)
+    :param focus: ensembles and views only: members / views that are already fooled rest until all are (default: every one pulls all
+        the time)
     :param imagenet_labels: dict idx -> name (only used when verbose)
     :param target_idx: list of B class ids (true label if untargeted)
     :param targeted: bool
@@ -344,16 +506,21 @@ def spaa(pcnet, classifier, imagenet_labels, target_idx, targeted, cam_scene, d_
     :param stealth_loss: string containing any of 'prjl2', 'caml2', 'camdE'
     :param setup_info: {'classifier_crop_sz', 'prj_brightness', 'prj_im_sz'}
     :param trace: optional list; receives per-iteration (state, stats) device tensors (no sync inside the loop); for an ensemble
-        (state, stats, ens_state, ens_stats), where state[:, 3] counts the fooled members and ens_state holds each member's top-1
-    :return: (cam_infer_best [B,3,Hc,Wc], prj_adv_best [B,3,Hp,Wp] in [0,1])
+        (state, stats, ens_state, ens_stats), where state[:, 3] counts the fooled members and ens_state holds each member's top-1;
+        for several views (state, stats, view_state, view_stats) in the same way
+    :return: (cam_infer_best [B,3,Hc,Wc], prj_adv_best [B,3,Hp,Wp] in [0,1]); for several views ([cam_infer_best per view], prj_adv_best)
     """
     pcnet, classifier = _unwrap(pcnet), _unwrap(classifier)
-    if not isinstance(pcnet, PCNet):
+    if isinstance(pcnet, (list, tuple)):
+        pcnet, cam_scene = _view_pcnets(pcnet, cam_scene, 'spaa')
+    if not isinstance(pcnet, (PCNet, list)):
         raise TypeError('spaa_amd.spaa needs a spaa_amd.PCNet (the HIP path has no generic PCNet fallback)')
     if isinstance(classifier, (list, tuple)):
         classifier = _ensemble_members(classifier, storage, 'spaa')
         if len(classifier) == 1:
             classifier = classifier[0]
+    if isinstance(pcnet, list):
+        _views_supported(pcnet, classifier, storage, 'spaa')
     if not isinstance(classifier, (Classifier, list)):
         if not callable(classifier):
             raise TypeError('classifier must be a spaa_amd.Classifier or a callable (im, crop_sz) -> (raw_score, p, idx)')
@@ -365,7 +532,9 @@ def spaa(pcnet, classifier, imagenet_labels, target_idx, targeted, cam_scene, d_
         if i % 30 == 0 or i == iters - 1:
             s, f = st.state.cpu(), st.stats.cpu()
             v = 7 if (targeted and st.B > 7) else 0
-            if isinstance(st, EnsembleAttackState):   # (p = the least confident member's; y = how many members are fooled)
+            if isinstance(st, MultiViewAttackState):   # (p = the least confident view's; y = how many views are fooled)
+                name = f'of {st.V} views fooled'
+            elif isinstance(st, EnsembleAttackState):   # (p = the least confident member's; y = how many members are fooled)
                 name = f'of {st.K} members fooled'
             else:
                 name = imagenet_labels[int(s[v, 3])] if imagenet_labels else ''
@@ -464,22 +633,33 @@ def spaa_sweep(pcnet, classifier, imagenet_labels, cam_scene, setup_info, device
     spaa() with its loss weights, targeted flag and d_thr per sample); `trace` receives one list per chunk, of the per-iteration
     (state, stats) pairs spaa() records (the chunk's samples in flattened order).  `classifier` may be a list / tuple of 2..4
     Classifiers, as in spaa(): every sample then attacks all of them at once (`focus` as there), and the trace entries are
-    (state, stats, ens_state, ens_stats)."""
+    (state, stats, ens_state, ens_stats).  `pcnet` may be a list / tuple of 2..4 PCNets with `cam_scene` a list of their scenes, as
+    in spaa(): every sample then attacks all views at once, each config's first return value is a list of one camera image batch
+    per view, and the trace entries are (state, stats, view_state, view_stats)."""
     samples, chunks = plan_sweep(configs, max_batch)
     pcnet, classifier = _unwrap(pcnet), _unwrap(classifier)
-    if not isinstance(pcnet, PCNet):
+    if isinstance(pcnet, (list, tuple)):
+        pcnet, cam_scene = _view_pcnets(pcnet, cam_scene, 'spaa_sweep')
+    if not isinstance(pcnet, (PCNet, list)):
         raise TypeError('spaa_sweep needs a spaa_amd.PCNet (the HIP path has no generic PCNet fallback)')
     if isinstance(classifier, (list, tuple)):
         classifier = _ensemble_members(classifier, storage, 'spaa_sweep')
         if len(classifier) == 1:
             classifier = classifier[0]
+    if isinstance(pcnet, list):
+        _views_supported(pcnet, classifier, storage, 'spaa_sweep')
     if not isinstance(classifier, (Classifier, list)):
         raise TypeError('spaa_sweep needs a spaa_amd.Classifier')
     _require_gpu(device, 'spaa_sweep')
-    sc = _scene_batch(cam_scene, 1)
-    cam_sz = tuple(pcnet.warping_net.out_size)
-    if sc.ndim != 4 or sc.shape[0] != 1 or tuple(sc.shape[1:]) != (3,) + cam_sz:
-        raise ValueError(f'cam_scene must be [3,H,W] or [1,3,H,W] with (H, W) = {cam_sz} (PCNet\'s output); got {tuple(cam_scene.shape)}')
+
+    def one_scene(m, scene):
+        sc = _scene_batch(scene, 1)
+        cam_sz = tuple(m.warping_net.out_size)
+        if sc.ndim != 4 or sc.shape[0] != 1 or tuple(sc.shape[1:]) != (3,) + cam_sz:
+            raise ValueError(f'cam_scene must be [3,H,W] or [1,3,H,W] with (H, W) = {cam_sz} (PCNet\'s output); got {tuple(scene.shape)}')
+        return sc
+
+    sc = [one_scene(m, s) for m, s in zip(pcnet, cam_scene)] if isinstance(pcnet, list) else one_scene(pcnet, cam_scene)
     results = []
     for a, b in chunks:
         part = samples[a:b]
@@ -490,6 +670,9 @@ def spaa_sweep(pcnet, classifier, imagenet_labels, cam_scene, setup_info, device
             trace.append(tr)
         results.append(st.results())
         del st
+    if isinstance(pcnet, list):   # (a chunk's result holds one camera image per view: split view by view)
+        per_view = [split_sweep(samples, len(configs), [(cams[v], prj) for cams, prj in results]) for v in range(len(pcnet))]
+        return [([pv[i][0] for pv in per_view], per_view[0][i][1]) for i in range(len(configs))]
     return split_sweep(samples, len(configs), results)
 
 
