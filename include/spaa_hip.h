@@ -687,6 +687,30 @@ int spaa_views_combine(const float* const* g, int V, const float* partial, int n
  * for the one camera image it is given (view 0's).  cam, cam_best: V pointers each to [B][HW][4]; entry 0 is not read */
 int spaa_views_track(const float* const* cam, float* const* cam_best, int V, const int32_t* state, int B, int HW, spaa_stream_t stream);
 
+/* ---- capture-robust SPAA: one projection against J randomly jittered captures of the camera image, 2 <= J <= SPAA_JITTER_MAX -- */
+#define SPAA_JITTER_MAX 4
+/* Per-draw tensors are passed as HOST arrays of J device pointers, as the ensemble's member tensors.  Any other J, or a null
+ * pointer, is hipErrorInvalidValue and nothing is launched.  Images are [B][H*W][4] fp32.
+ *
+ * The parameter rows of iteration t = counter[0] (device memory; t + 1 is stored after every thread of the one workgroup has read
+ * it, so a replayed graph advances the sequence without the host):
+ *   jit [B][J][8] = (gain_r, gain_g, gain_b, offset, dx, dy, sigma, 0) with gain_c = 1 + gain (2u - 1), offset (2u - 1),
+ *   dx, dy = shift (2u - 1) in camera pixels, sigma = noise;  key [B][J]: the draw's 32-bit noise key.
+ * Each u = (h >> 8) 2^-24 with h a pure function of (seed, t, b, j, column) by 32-bit integer mixing ("Capture-robust
+ * attack"; the key is column 7).  clean0 != 0: draw 0 of every sample is the identity row (1, 1, 1, 0, 0, 0, 0, 0). */
+int spaa_jitter_draw(uint32_t seed, int32_t* counter, float gain, float offset, float shift, float noise, int clean0, float* jit,
+                     uint32_t* key, int B, int J, spaa_stream_t stream);
+/* out[j] = clamp(pre, 0, 1), pre_c = gain_c S(y)_c + offset + sigma n_c, then with quantize != 0 floorf(out 255.f) / 255.f (the
+ * camera's 8-bit step); the pad channel of out is 0.  S: the bilinear translation by (dx, dy) with replicate border, per axis
+ * out[m] = (1 - f) in[clamp(m + k)] + f in[clamp(m + k + 1)], k = floor(d), f = d - k.  n: standard normal by Box-Muller from two
+ * uniforms of (key[b][j], pixel, c), none when sigma == 0.  gate[j] [B][H*W] bytes: bit c = (0 <= pre_c <= 1).  One launch. */
+int spaa_jitter_fwd(const float* y, const float* jit, const uint32_t* key, int J, int quantize, float* const* out,
+                    uint8_t* const* gate, int B, int H, int W, spaa_stream_t stream);
+/* The adjoint: g_y[j] = S^T(gain_c gate_c g_out[j]) (the quantisation straight-through, no gradient of the noise) as a gather
+ * without atomics: run-to-run bitwise reproducible.  The pad channel of g_y is 0.  One launch. */
+int spaa_jitter_bwd(const float* const* g_out, const float* jit, const uint8_t* const* gate, int J, float* const* g_y, int B, int H,
+                    int W, spaa_stream_t stream);
+
 /* ---- PerC_AL.adversary_projector (perc_al/__init__.py:133-256) ------------------------------------------ */
 /* x = a + b (inputs + delta), NHWC4 */
 int spaa_add_nhwc4(const float* a, const float* b, float* x, int npix, spaa_stream_t stream);

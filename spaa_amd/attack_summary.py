@@ -78,6 +78,59 @@ def attack_transfer(ims, classifiers, target_idx, targeted, crop_sz):
     return out
 
 
+SURVIVAL_CHUNK = 64   # images per launch of capture_survival
+SURVIVAL_ROUND = 4    # jittered captures per launch of capture_survival (SPAA_JITTER_MAX)
+
+
+def capture_survival(ims, classifier, target_idx, targeted, crop_sz, jitter, *, draws=32, seed=0):
+    """The fraction of `draws` randomly jittered captures of each camera image that still succeed: float [N] for the images `ims`
+    [N,3,H,W], one class id per image in `target_idx` and `targeted` (one flag, or one per image; success as in attack_transfer).
+    The evaluation hook of a jitter attack.  The captures are those of `jitter` (a CaptureJitter: its ranges and `quantize`; its
+    `draws` and `seed` belong to the attack) with the generator seeded by `seed`, none of them the clean one: spaa_jitter_draw +
+    spaa_jitter_fwd in rounds of four captures (round r is the generator's iteration r), on chunks of at most 64 images (an image's
+    captures depend on its place in its chunk)."""
+    from .models import to_nhwc4
+    from .projector_based_attack import CaptureJitter
+    if not isinstance(jitter, CaptureJitter):
+        raise TypeError(f'capture_survival: jitter must be a spaa_amd.CaptureJitter, got {type(jitter).__name__}')
+    n = ims.shape[0]
+    tgt = torch.as_tensor([int(t) for t in target_idx])
+    tg = torch.full((n,), bool(targeted)) if np.ndim(targeted) == 0 else torch.as_tensor([bool(t) for t in targeted])
+    if tuple(tgt.shape) != (n,) or tuple(tg.shape) != (n,) or int(draws) < 1:
+        raise ValueError(f'capture_survival: {n} images, {tgt.numel()} targets, {tg.numel()} targeted flags, {draws} draws')
+    dev = classifier.device
+    if dev.type != 'cuda':
+        raise RuntimeError(f'capture_survival runs on the GPU only (no CPU fallback); the classifier is on {dev}')
+    jt = CaptureJitter(jitter.gain, jitter.offset, jitter.shift, jitter.noise, jitter.quantize, SURVIVAL_ROUND, seed)
+    J, (H, W) = SURVIVAL_ROUND, ims.shape[-2:]
+    b = min(n, SURVIVAL_CHUNK)
+    hits = torch.zeros(n)
+    with _lib.on_device(dev):
+        eng = classifier.engine(b, (H, W), tuple(crop_sz))
+        jit = torch.zeros(b, J, 8, device=dev)
+        key = torch.zeros(b, J, dtype=torch.int32, device=dev)
+        outs = [torch.zeros(b, H, W, 4, device=dev) for _ in range(J)]
+        gates = [torch.zeros(b, H * W, dtype=torch.uint8, device=dev) for _ in range(J)]
+        for s in range(0, n, b):
+            part = ims[s:s + b].to(dev).float()
+            m = part.shape[0]
+            if m < b:   # (one engine geometry: the last chunk is padded)
+                part = torch.cat((part, part.new_zeros(b - m, *part.shape[1:])))
+            y4 = to_nhwc4(part.contiguous())
+            counter = torch.zeros(1, dtype=torch.int32, device=dev)
+            t_dev, tg_dev = tgt[s:s + m].to(dev), tg[s:s + m].to(dev)
+            count = torch.zeros(m, device=dev)
+            for done in range(0, int(draws), J):
+                jt.draw(counter, jit, key, b, J, clean0=False)
+                _lib.call('spaa_jitter_fwd', _lib.ptr(y4), _lib.ptr(jit), _lib.ptr(key), J, int(bool(jt.quantize)),
+                          _lib.ptr_array(outs), _lib.ptr_array(gates), b, H, W)
+                for j in range(min(J, int(draws) - done)):
+                    top1 = eng.forward(outs[j], need_grad=False)[:m].argmax(dim=1)
+                    count += torch.where(tg_dev, top1 == t_dev, top1 != t_dev).float()
+            hits[s:s + m] = count.cpu()
+    return (hits / int(draws)).numpy()
+
+
 def write_stats(table, path):
     """The reference's table files: tab-separated, 4 decimals (stats.txt, stats_all.txt)."""
     table.to_csv(path, index=False, float_format='%.4f', sep='\t')

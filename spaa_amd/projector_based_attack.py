@@ -12,6 +12,7 @@ with the reference values as defaults.  Differences in *mechanism*, not in resul
   * `cam_scene` may also be [B,3,H,W] (one scene per sample); the reference supports one scene x B targets (Q9),
     and its targeted mode needs B >= 8 because of a debug print (Q10) — not inherited.
 """
+import dataclasses
 import os
 import warnings
 
@@ -298,7 +299,7 @@ class EnsembleAttackState(AttackState):
         B, p = self.B, _lib.ptr
         self._per_sample(targeted, d_thr, table=True)   # (the ensemble decision has the per-sample table form only)
         y = self.eng.forward(self.x, clamp01=True)                                   # :265
-        logits = [e.forward(y) for e in self.clfs]                                   # :266, once per member
+        logits = self._member_logits(y)
         self._y, self._uniform = y, False
         if self.any_prjl2:
             _lib.call('spaa_prjl2_fwd', p(self.x), self.gray, p(self.prjl2), B, self.HWp)
@@ -309,8 +310,16 @@ class EnsembleAttackState(AttackState):
                   int(self.focus), p(self.state), p(self.stats), p(self.ens_state), p(self.ens_stats), p(self.ens_w),
                   _lib.ptr_array(self.ens_g_logits), B)
 
+    def _member_logits(self, y):
+        """Every member's logits of the camera image y."""
+        return [e.forward(y) for e in self.clfs]                                     # :266, once per member
+
+    def _member_gradients(self):
+        """Every member's gradient image at the camera image, from its seed of the decision."""
+        return [e.backward(g) for e, g in zip(self.clfs, self.ens_g_logits)]
+
     def _adv_gradient(self):
-        gs = _lib.ptr_array([e.backward(g) for e, g in zip(self.clfs, self.ens_g_logits)])
+        gs = _lib.ptr_array(self._member_gradients())
         _lib.call('spaa_ens_sumsq', gs, self.K, _lib.ptr(self.ens_partial), self.B, self.HWc)
         _lib.call('spaa_ens_combine', gs, self.K, _lib.ptr(self.ens_partial), self.nblk_c, _lib.ptr(self.ens_w), _lib.ptr(self.g_adv),
                   self.B, self.HWc)
@@ -474,9 +483,108 @@ class MultiViewAttackState(AttackState):
             return [to_nchw(c) for c in self.cam_bests], to_nchw(self.x_best, clamp01=True)
 
 
-def _attack_state(pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, device, storage, focus):
+JITTER_MAX = 4   # SPAA_JITTER_MAX of include/spaa_hip.h
+
+
+@dataclasses.dataclass(frozen=True)
+class CaptureJitter:
+    """What separates a real capture from the inferred one, as ranges of a random perturbation of the camera image (DESIGN.md,
+    "Capture-robust attack"): exposure / white balance `gain` (per channel, 1 +- gain) and `offset` (+- offset), a misregistration of
+    +- `shift` camera pixels per axis, sensor noise of standard deviation `noise`, the camera's 8-bit step (`quantize`).  `draws`:
+    captures attacked at once per iteration (2..4; the first one is the clean capture), `seed`: of the counter-based generator.
+    `shift` <= 2 and `noise` <= 0.1 are what the adjoint kernel's border loop and the tests' noise tolerance assume."""
+    gain: float = 0.1
+    offset: float = 0.03
+    shift: float = 0.75
+    noise: float = 0.01
+    quantize: bool = True
+    draws: int = 3
+    seed: int = 0
+
+    def __post_init__(self):
+        if not 2 <= int(self.draws) <= JITTER_MAX:
+            raise ValueError(f'CaptureJitter: draws must be 2..{JITTER_MAX}, got {self.draws}')
+        for name in ('gain', 'offset', 'shift', 'noise'):
+            if not float(getattr(self, name)) >= 0:
+                raise ValueError(f'CaptureJitter: {name} must be >= 0, got {getattr(self, name)}')
+        if self.gain >= 1:
+            raise ValueError(f'CaptureJitter: gain must be < 1 (a channel gain stays positive), got {self.gain}')
+        if self.shift > 2:
+            raise ValueError(f'CaptureJitter: shift must be <= 2 camera pixels, got {self.shift}')
+        if self.noise > 0.1:
+            raise ValueError(f'CaptureJitter: noise must be <= 0.1, got {self.noise}')
+
+    def draw(self, counter, jit, key, B, J, clean0):
+        """spaa_jitter_draw of these ranges: fills jit [B][J][8] / key [B][J] for iteration counter[0] and advances the counter."""
+        _lib.call('spaa_jitter_draw', int(self.seed) & 0xffffffff, _lib.ptr(counter), float(self.gain), float(self.offset),
+                  float(self.shift), float(self.noise), int(bool(clean0)), _lib.ptr(jit), _lib.ptr(key), B, J)
+
+
+def _jitter_supported(jitter, pcnet, classifier, storage, focus, who):
+    """What a jitter attack does not serve, said before anything is allocated or launched.  `pcnet` / `classifier`: as spaa() holds
+    them after its own checks."""
+    if not isinstance(jitter, CaptureJitter):
+        raise TypeError(f'{who}: jitter must be a spaa_amd.CaptureJitter, got {type(jitter).__name__}')
+    if isinstance(pcnet, list):
+        raise NotImplementedError(f'{who}: capture jitter against several views is not implemented; attack one view with jitter')
+    if isinstance(classifier, list):
+        raise NotImplementedError(f'{who}: capture jitter against an ensemble of classifiers is not implemented; attack one '
+                                  'classifier with jitter')
+    if not isinstance(classifier, Classifier):
+        raise TypeError(f'{who}: a jitter attack needs a spaa_amd.Classifier, got {type(classifier).__name__} (a foreign callable can '
+                        'only be attacked without jitter)')
+    if storage != 'f32':
+        raise NotImplementedError(f"{who}: storage={storage!r} is not implemented with jitter (the draws' unit vectors need a loss "
+                                  "scale of their own); use storage='f32'")
+    if focus:
+        raise ValueError(f'{who}: focus=True has no meaning with jitter (a sample must fool every draw of every iteration)')
+
+
+class JitterAttackState(EnsembleAttackState):
+    """One batched attack against J = jitter.draws randomly perturbed captures of the camera image per iteration (DESIGN.md,
+    "Capture-robust attack"): EnsembleAttackState whose members are J leased engines of ONE classifier, member j looking at draw j
+    of y = PCNet(x, s).  Draw 0 is the clean capture (the identity row), so a sample counts as successful only when the clean capture
+    and every jittered draw of that iteration are fooled; the stealth loss and `cam_best` stay the clean inference.  The draws'
+    parameters come from spaa_jitter_draw (a device-side counter: a replayed graph advances the sequence), the transform from
+    spaa_jitter_fwd, and the members' gradient images are pulled back to y by spaa_jitter_bwd before they are combined.  `state`,
+    `stats`, `ens_state`, `ens_stats` keep the ensemble's meaning with draws as members."""
+
+    def __init__(self, pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, device, jitter, storage='f32'):
+        pcnet, classifier = _unwrap(pcnet), _unwrap(classifier)
+        _jitter_supported(jitter, pcnet, classifier, storage, False, 'JitterAttackState')
+        self.jitter, self.focus = jitter, False
+        self.members = [classifier] * int(jitter.draws)   # (EnsembleAttackState._build leases one engine per entry)
+        AttackState.__init__(self, pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, device, storage=storage)
+
+    def _build(self, pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, dev):
+        super()._build(pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, dev)
+        B, J = self.B, self.K
+        self.counter = torch.zeros(1, dtype=torch.int32, device=dev)        # the iteration number the next draw reads
+        self.jit = torch.zeros(B, J, 8, device=dev)
+        self.key = torch.zeros(B, J, dtype=torch.int32, device=dev)         # (uint32 bit patterns)
+        self.draw_ims = [torch.zeros_like(self.g_adv) for _ in range(J)]
+        self.draw_gates = [torch.zeros(B, self.HWc, dtype=torch.uint8, device=dev) for _ in range(J)]
+        self.draw_grads = [torch.zeros_like(self.g_adv) for _ in range(J)]
+
+    def _member_logits(self, y):
+        jt, p = self.jitter, _lib.ptr
+        jt.draw(self.counter, self.jit, self.key, self.B, self.K, clean0=True)
+        _lib.call('spaa_jitter_fwd', p(y), p(self.jit), p(self.key), self.K, int(bool(jt.quantize)), _lib.ptr_array(self.draw_ims),
+                  _lib.ptr_array(self.draw_gates), self.B, self.eng.Hc, self.eng.Wc)
+        return [e.forward(im) for e, im in zip(self.clfs, self.draw_ims)]            # :266, once per draw
+
+    def _member_gradients(self):
+        gs = super()._member_gradients()
+        _lib.call('spaa_jitter_bwd', _lib.ptr_array(gs), _lib.ptr(self.jit), _lib.ptr_array(self.draw_gates), self.K,
+                  _lib.ptr_array(self.draw_grads), self.B, self.eng.Hc, self.eng.Wc)
+        return self.draw_grads
+
+
+def _attack_state(pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, device, storage, focus, jitter=None):
     """AttackState for one Classifier, EnsembleAttackState for a checked list of several, MultiViewAttackState for a checked list of
-    PCNets (with their list of scenes)."""
+    PCNets (with their list of scenes), JitterAttackState for one Classifier with a CaptureJitter."""
+    if jitter is not None:
+        return JitterAttackState(pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, device, jitter, storage=storage)
     if isinstance(pcnet, list):
         return MultiViewAttackState(pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, device, storage=storage,
                                     focus=focus)
@@ -487,7 +595,7 @@ def _attack_state(pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_
 
 
 def spaa(pcnet, classifier, imagenet_labels, target_idx, targeted, cam_scene, d_thr, stealth_loss, device, setup_info,
-         *, iters=50, adv_lr=2, col_lr=1, p_thresh=0.9, trace=None, verbose=False, storage='f32', focus=False):
+         *, iters=50, adv_lr=2, col_lr=1, p_thresh=0.9, trace=None, verbose=False, storage='f32', focus=False, jitter=None):
     """Stealthy Projector-based Adversarial Attack (SPAA Algorithm 1) — see module docstring.
 
     :param pcnet: spaa_amd.PCNet (optionally wrapped in DataParallel-like `.module`), or a list / tuple of 2..4 of them: the same projector
@@ -498,6 +606,9 @@ def spaa(pcnet, classifier, imagenet_labels, target_idx, targeted, cam_scene, d_
         (EnsembleAttackState; fp32 storage only).  A sequence of one is that classifier.
     :param focus: ensembles and views only: members / views that are already fooled rest until all are (default: every one pulls all
         the time)
+    :param jitter: a CaptureJitter: ONE projection against `jitter.draws` randomly perturbed captures of the camera image per iteration,
+        the first of them the clean one (JitterAttackState; one PCNet, one Classifier, fp32 storage, no `focus`).  The trace entries
+        are the ensemble's, with draws as members.  None (default): the attack on the noiseless inferred capture
     :param imagenet_labels: dict idx -> name (only used when verbose)
     :param target_idx: list of B class ids (true label if untargeted)
     :param targeted: bool
@@ -521,12 +632,14 @@ def spaa(pcnet, classifier, imagenet_labels, target_idx, targeted, cam_scene, d_
             classifier = classifier[0]
     if isinstance(pcnet, list):
         _views_supported(pcnet, classifier, storage, 'spaa')
+    if jitter is not None:
+        _jitter_supported(jitter, pcnet, classifier, storage, focus, 'spaa')
     if not isinstance(classifier, (Classifier, list)):
         if not callable(classifier):
             raise TypeError('classifier must be a spaa_amd.Classifier or a callable (im, crop_sz) -> (raw_score, p, idx)')
         return _spaa_foreign_classifier(pcnet, classifier, imagenet_labels, target_idx, targeted, cam_scene, d_thr,
                                         stealth_loss, device, setup_info, iters, adv_lr, col_lr, p_thresh, trace)
-    st = _attack_state(pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, device, storage, focus)
+    st = _attack_state(pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, device, storage, focus, jitter)
 
     def report(i):
         if i % 30 == 0 or i == iters - 1:
@@ -534,8 +647,8 @@ def spaa(pcnet, classifier, imagenet_labels, target_idx, targeted, cam_scene, d_
             v = 7 if (targeted and st.B > 7) else 0
             if isinstance(st, MultiViewAttackState):   # (p = the least confident view's; y = how many views are fooled)
                 name = f'of {st.V} views fooled'
-            elif isinstance(st, EnsembleAttackState):   # (p = the least confident member's; y = how many members are fooled)
-                name = f'of {st.K} members fooled'
+            elif isinstance(st, EnsembleAttackState):   # (p = the least confident member's / draw's; y = how many are fooled)
+                name = f'of {st.K} draws fooled' if isinstance(st, JitterAttackState) else f'of {st.K} members fooled'
             else:
                 name = imagenet_labels[int(s[v, 3])] if imagenet_labels else ''
             print(f'col_loss = {f[:, 3].mean():<9.4f} | prjl2 = {f[:, 4].mean() * 255:<9.4f} | caml2 = '
@@ -624,7 +737,7 @@ def split_sweep(samples, ncfg, chunk_results):
 
 
 def spaa_sweep(pcnet, classifier, imagenet_labels, cam_scene, setup_info, device, configs, *, iters=50, adv_lr=2, col_lr=1,
-               p_thresh=0.9, max_batch=64, storage='f32', trace=None, focus=False):
+               p_thresh=0.9, max_batch=64, storage='f32', trace=None, focus=False, jitter=None):
     """Several SPAA attacks on one PCNet, scene and classifier as few batched attacks (the reference's driver makes one spaa() call
     per configuration: projector_based_attack.py:24-148).  `configs`: [(stealth_loss, d_thr, targeted, target_idx), ...]; returns one
     (cam_infer_best, prj_adv_best) per config, in order -- what spaa(pcnet, classifier, imagenet_labels, target_idx, targeted,
@@ -635,7 +748,8 @@ def spaa_sweep(pcnet, classifier, imagenet_labels, cam_scene, setup_info, device
     Classifiers, as in spaa(): every sample then attacks all of them at once (`focus` as there), and the trace entries are
     (state, stats, ens_state, ens_stats).  `pcnet` may be a list / tuple of 2..4 PCNets with `cam_scene` a list of their scenes, as
     in spaa(): every sample then attacks all views at once, each config's first return value is a list of one camera image batch
-    per view, and the trace entries are (state, stats, view_state, view_stats)."""
+    per view, and the trace entries are (state, stats, view_state, view_stats).  `jitter`: a CaptureJitter, as in spaa(): every chunk
+    is a jitter attack with that seed (the draws of a sample depend on its place in its chunk), the trace entries the ensemble's."""
     samples, chunks = plan_sweep(configs, max_batch)
     pcnet, classifier = _unwrap(pcnet), _unwrap(classifier)
     if isinstance(pcnet, (list, tuple)):
@@ -648,6 +762,8 @@ def spaa_sweep(pcnet, classifier, imagenet_labels, cam_scene, setup_info, device
             classifier = classifier[0]
     if isinstance(pcnet, list):
         _views_supported(pcnet, classifier, storage, 'spaa_sweep')
+    if jitter is not None:
+        _jitter_supported(jitter, pcnet, classifier, storage, focus, 'spaa_sweep')
     if not isinstance(classifier, (Classifier, list)):
         raise TypeError('spaa_sweep needs a spaa_amd.Classifier')
     _require_gpu(device, 'spaa_sweep')
@@ -663,7 +779,8 @@ def spaa_sweep(pcnet, classifier, imagenet_labels, cam_scene, setup_info, device
     results = []
     for a, b in chunks:
         part = samples[a:b]
-        st = _attack_state(pcnet, classifier, [t for *_, t in part], sc, [s[1] for s in part], setup_info, device, storage, focus)
+        st = _attack_state(pcnet, classifier, [t for *_, t in part], sc, [s[1] for s in part], setup_info, device, storage, focus,
+                           jitter)
         tr = [] if trace is not None else None
         _run(st, [s[3] for s in part], [s[2] for s in part], iters, adv_lr, col_lr, p_thresh, tr)
         if trace is not None:
@@ -762,4 +879,5 @@ from .attack_driver import (ATTACKERS, MODEL_TRAIN_CFG, AttackSetup, get_attacke
                             run_projector_based_attack, _run_one_pixel_de, project_capture_real_attack)
 from .attack_summary import (SUMMARY_STEALTH_LOSSES, SUMMARY_D_THRESHES, SUMMARY_CLASSIFIERS, SUMMARY_CHUNK,   # noqa: E402,F401
                              SUMMARY_COLUMNS, MONTAGE_CHUNK, attack_success, write_stats, _sorted_classes, _nonempty,
-                             attack_results, attack_transfer, summarize_single_attacker, summarize_all_attackers)
+                             attack_results, attack_transfer, capture_survival, summarize_single_attacker,
+                             summarize_all_attackers)
