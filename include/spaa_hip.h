@@ -711,6 +711,24 @@ int spaa_jitter_fwd(const float* y, const float* jit, const uint32_t* key, int J
 int spaa_jitter_bwd(const float* const* g_out, const float* jit, const uint8_t* const* gate, int J, float* const* g_y, int B, int H,
                     int W, spaa_stream_t stream);
 
+/* ---- attention-weighted attack: Grad-CAM of the classifier weights its gradient image ---------------------------
+ * No atomics and fixed summation orders: bitwise repeatable.  One launch each, none syncs. */
+/* alpha [B][C] = the spatial mean of a gradient map G [B][HW][cstride] (channels 0 .. C - 1 of each position), positions added in
+ * index order, then one division by HW. */
+int spaa_cam_alpha(const float* G, float* alpha, int B, int HW, int C, int cstride, spaa_stream_t stream);
+/* Per sample b with t = target[b] and the seed s = g_logits[b][t] (0 where t is no class): c [B][HW] = max(0, sign(s) alpha_scale
+ * sum_k alpha[b][k] A[b][p][k]) of the feature map A [B][HW][C] (contiguous, C % 4 == 0), cmax [B] = max_p c.  s == 0: c = 0 and
+ * cmax = 0.  alpha_scale > 0: 1 for the channel means of spaa_cam_alpha, 1 / HW for the pooled gradient of a global-average head. */
+int spaa_cam_map(const float* A, const float* alpha, float alpha_scale, const float* g_logits, int ncls, const int32_t* target, float* c,
+                 float* cmax, int B, int HW, int C, spaa_stream_t stream);
+/* M = (c / cmax) [fh][fw] resampled bilinearly onto the ch x cw crop at (cy0, cx0) of the H x W camera frame (half-pixel centres, edge
+ * clamped: F.interpolate(mode='bilinear', align_corners=False)), at most 1; cmax <= 0: M = 1.  g_y [B][H][W][4] (may be NULL): the
+ * three colour channels inside the crop are multiplied by floor + (1 - floor) M in place, the pad channel and the pixels outside the
+ * crop are not written, and a sample with cmax <= 0 is not written at all.  M_out [B][H][W] (may be NULL): M, 0 outside the crop.
+ * 0 <= floor <= 1; sides up to 16384. */
+int spaa_attention_apply(const float* c, const float* cmax, float floor, float* g_y, float* M_out, int B, int H, int W, int cy0, int cx0,
+                         int ch, int cw, int fh, int fw, spaa_stream_t stream);
+
 /* ---- PerC_AL.adversary_projector (perc_al/__init__.py:133-256) ------------------------------------------ */
 /* x = a + b (inputs + delta), NHWC4 */
 int spaa_add_nhwc4(const float* a, const float* b, float* x, int npix, spaa_stream_t stream);

@@ -188,6 +188,9 @@ _SIGNATURES = {
     'spaa_jitter_draw': [C.c_uint32, _p, _f, _f, _f, _f, _i, _p, _p, _i, _i, _p],
     'spaa_jitter_fwd': [_p, _p, _p, _i, _i, _pp, _pp, _i, _i, _i, _p],
     'spaa_jitter_bwd': [_pp, _p, _pp, _i, _pp, _i, _i, _i, _p],
+    'spaa_cam_alpha': [_p, _p, _i, _i, _i, _i, _p],
+    'spaa_cam_map': [_p, _p, _f, _p, _i, _p, _p, _p, _i, _i, _i, _p],
+    'spaa_attention_apply': [_p, _p, _f, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p],
     'spaa_onepixel_preproc': [_p, _p, _i, _i, _i, _p, _i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_float), C.POINTER(C.c_float), _p],
     'spaa_onepixel_score': [_p, _i, _i, _i, _p, _p, _p, _i, _p],
     'spaa_onepixel_warp': [_p, _p, _i, _i, _i, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p],

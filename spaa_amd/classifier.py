@@ -10,6 +10,7 @@ them by URL, classifier.py:24-36): pass `state_dict=` (torchvision key names) or
 `ClassifierEngine` is what the fused attack loop drives: forward = crop + area-resize + normalise -> net -> logits;
 backward = input gradient only (all parameters frozen, classifier.py:41-44).
 """
+import dataclasses
 import os
 import weakref
 
@@ -34,6 +35,18 @@ IMAGENET_STD = (0.229, 0.224, 0.225)
 INPUT_SZ = {'resnet18': (224, 224), 'vgg16': (224, 224), 'inception_v3': (299, 299)}
 
 
+@dataclasses.dataclass(frozen=True)
+class Attention:
+    """Attention-weighted attack: the classifier's gradient image at the camera is multiplied by floor + (1 - floor) M,
+    M in [0, 1] the Grad-CAM map of the sample's class resampled onto the classifier crop.  `floor`: the weight where the classifier
+    does not look (0: the adversarial step puts nothing there; 1: the plain attack)."""
+    floor: float = 0.0
+
+    def __post_init__(self):
+        if isinstance(self.floor, bool) or not isinstance(self.floor, (int, float)) or not 0 <= float(self.floor) <= 1:
+            raise ValueError(f'Attention: floor must be a number in [0, 1], got {self.floor!r}')
+
+
 def center_crop_origin(h, w, size):
     """img_proc.py:126-132."""
     th, tw = size
@@ -52,7 +65,8 @@ def _strip(sd):
 class ClassifierBody:
     """What the three bodies share: the storage mode and its allocators, the layer-size and BatchNorm-folding helpers, the ReLU-gate
     switches, the global-average-pool + `fc` head of ResNet-18 and Inception-v3, and flops_fwd() over `fwd_plans()`.
-    A body provides forward(x4) -> logits [B, ncls], backward(g_logits) -> gradient w.r.t. x4, refresh_masks() and fwd_plans()."""
+    A body provides forward(x4) -> logits [B, ncls], backward(g_logits) -> gradient w.r.t. x4, refresh_masks(), fwd_plans() and
+    attention_source()."""
     body_masks_switch = True   # SPAA_BODY_MASKS=0 applies (VGG-16, Inception-v3: the A/B switch never covered ResNet-18)
 
     def __init__(self, sd, batch, in_hw, dev, storage):
@@ -98,10 +112,21 @@ class ClassifierBody:
         self.fc_f.run(self.pooled, self.logits)
         return self.logits.view(self.B, self.ncls)
 
+    def head_grad(self, g_logits):
+        """The head's part of the backward pass alone: g_logits [B, ncls] -> the gradient at the features the head pools (here
+        `g_pooled`; what attention_source() names as the gradient)."""
+        self.fc_d.run(g_logits.view(self.B, 1, 1, self.ncls), self.g_pooled)
+        return self.g_pooled
+
     def head_bwd(self, g_logits, last, g_last):
         """g_logits [B, ncls] -> `g_last`, the gradient w.r.t. the pre-activation of `last` (a ReLU output: gated)."""
-        self.fc_d.run(g_logits.view(self.B, 1, 1, self.ncls), self.g_pooled)
-        pooling.global_avgpool_bwd(self.g_pooled, last, g_last)
+        pooling.global_avgpool_bwd(self.head_grad(g_logits), last, g_last)
+
+    def attention_source(self):
+        """What Grad-CAM reads after a backward pass (or after head_grad alone): (A, G, pooled).  A [B, h, w, C]: the fp32 feature map
+        that enters the head's average pool.  G: the ungated gradient there -- with `pooled`, as the head's g_pooled [B, 1, 1, C] (the
+        gradient at every position is g_pooled / (h w)), else as the map [B, h, w, C] itself."""
+        raise NotImplementedError
 
     def flops_fwd(self):
         return sum(plan.flops(self.B, h, w) for plan, (h, w) in self.fwd_plans())
@@ -217,6 +242,9 @@ class ResNet18Body(ClassifierBody):
         self.stem_d.run(self.g_c1, self.g_in)
         return self.g_in
 
+    def attention_source(self):
+        return self.blocks[-1]['out'], self.g_pooled, True
+
     def refresh_masks(self):
         """Recompute the gate masks from the activation buffers (after a test has overwritten the activations)."""
         for blk in self.blocks:
@@ -319,7 +347,8 @@ class VGG16Body(ClassifierBody):
         self.fc[2][0].run(self.h2, self.logits)
         return self.logits.view(B, self.ncls)
 
-    def backward(self, g_logits):
+    def head_grad(self, g_logits):
+        """The head's part of the backward pass alone: g_logits [B, ncls] -> the (ungated) gradient w.r.t. the last pool's output."""
         B = self.B
         self.fc[2][1].run(g_logits.view(B, 1, 1, self.ncls), self.g_h2, gate=self.h2)
         self.fc[1][1].run(self.g_h2, self.g_h1, gate=self.h1)
@@ -328,6 +357,13 @@ class VGG16Body(ClassifierBody):
         if self.feat_hw != (7, 7):
             pooling.adaptive_avgpool_bwd(g, None, self.g_feat)
             g = self.g_feat
+        return g
+
+    def attention_source(self):
+        return self.ops[-1]['out'], self.g_pool7 if self.feat_hw == (7, 7) else self.g_feat, False
+
+    def backward(self, g_logits):
+        g = self.head_grad(g_logits)
         # g is the gradient w.r.t. the last pool's output
         for op in reversed(self.ops):
             if op['kind'] == 'pool':
@@ -389,6 +425,7 @@ class ClassifierEngine:
         self.owner = None   # weakref to the attack state this engine is leased to (Classifier.engine)
         self.version = 0    # bumped whenever the activation workspaces are overwritten
         self._grad_ready = False   # the last forward pass wrote what backward() reads (gate masks, arg-max bytes)
+        self._cam = None    # the Grad-CAM buffers (attention_buffers())
 
     def forward(self, y4, need_grad=True):
         """`need_grad=False`: nobody will call backward() on this pass (PerC-AL's second, decision-only forward pass on the quantised
@@ -408,7 +445,66 @@ class ClassifierEngine:
         self._grad_ready = self.body.write_masks = False
         return self.body.forward(self.pre)
 
-    def backward(self, g_logits):
+    def attention_buffers(self):
+        """Allocates what the Grad-CAM launches write (once; an attack state does it before its loop, so that a captured iteration
+        allocates nothing): c [B, h w], its maximum [B], the channel means [B, C] where the body hands over a gradient map, and the
+        map M [B, H, W] in the camera frame that attention_map() renders."""
+        if self.storage != 'f32':
+            raise NotImplementedError(f"ClassifierEngine: attention with storage={self.storage!r} is not implemented (the feature map and "
+                                      "its gradient are read as fp32); use storage='f32'")
+        if self._cam is None:
+            A, G, pooled = self.body.attention_source()
+            b, h, w, c = A.shape
+            self._cam = dict(c=torch.zeros(b, h * w, device=self.dev), max=torch.zeros(b, device=self.dev),
+                             alpha=None if pooled else torch.zeros(b, c, device=self.dev),
+                             M=torch.zeros(b, self.H, self.W, device=self.dev), hw=(h, w), valid=False)
+        return self._cam
+
+    def grad_cam(self, g_logits, target):
+        """c and its per-sample maximum from the feature map and the gradient of the last backward pass -- or of
+        body.head_grad(g_logits) alone -- with the seed g_logits[b, target[b]].  `target`: int32 [B] on the device."""
+        cam = self.attention_buffers()
+        A, G, pooled = self.body.attention_source()
+        _lib.check_dev(A, G, g_logits)
+        b, h, w, c = A.shape
+        if target.dtype != torch.int32 or tuple(target.shape) != (b,) or tuple(g_logits.shape) != (b, self.ncls) or c % 4:
+            raise ValueError(f'ClassifierEngine.grad_cam: target must be int32 [{b}] and g_logits [{b}, {self.ncls}] (got {target.dtype} '
+                             f'{tuple(target.shape)}, {tuple(g_logits.shape)}); the feature map needs whole channel quads (C = {c})')
+        p = _lib.ptr
+        if pooled:
+            if G.numel() != b * c:
+                raise ValueError(f'ClassifierEngine.grad_cam: the pooled gradient must hold {b} x {c} values, got {tuple(G.shape)}')
+            alpha, scale = G, 1.0 / (h * w)
+        else:
+            if G.shape != A.shape:
+                raise ValueError(f'ClassifierEngine.grad_cam: gradient map {tuple(G.shape)} against feature map {tuple(A.shape)}')
+            _lib.call('spaa_cam_alpha', p(G), p(cam['alpha']), b, h * w, c, c)
+            alpha, scale = cam['alpha'], 1.0
+        _lib.call('spaa_cam_map', p(A), p(alpha), scale, p(g_logits), self.ncls, p(target), p(cam['c']), p(cam['max']), b, h * w, c)
+        cam['valid'] = True
+        return cam
+
+    def attention_apply(self, floor, g_y=None, M_out=None):
+        """spaa_attention_apply of the last grad_cam(): weights `g_y` in place and / or writes M into `M_out` [B, H, W]."""
+        cam = self._cam
+        if cam is None or not cam['valid']:
+            raise RuntimeError('ClassifierEngine: no class-activation map yet (backward(..., attention=...) or grad_cam() computes one)')
+        fh, fw = cam['hw']
+        _lib.call('spaa_attention_apply', _lib.ptr(cam['c']), _lib.ptr(cam['max']), float(floor), _lib.ptr(g_y), _lib.ptr(M_out), self.B,
+                  self.H, self.W, self.cy0, self.cx0, self.ch, self.cw, fh, fw)
+
+    def attention_map(self):
+        """M of the last grad_cam() in the camera frame, [B, 1, H, W] (0 outside the classifier crop): a copy."""
+        self.attention_apply(0.0, None, self.attention_buffers()['M'])
+        return self._cam['M'].view(self.B, 1, self.H, self.W).clone()
+
+    def backward(self, g_logits, attention=None, target=None):
+        """The gradient image at the camera frame.  `attention` (an Attention; with `target`, the samples' classes as int32 [B]): the
+        image is weighted by floor + (1 - floor) M, M the Grad-CAM map of this pass (attention_map() returns it)."""
+        if attention is not None and not isinstance(attention, Attention):
+            raise TypeError(f'ClassifierEngine.backward: attention must be a spaa_amd.Attention or None, got {type(attention).__name__}')
+        if attention is not None and target is None:
+            raise ValueError('ClassifierEngine.backward: attention needs `target` (the class of every sample)')
         if not self._grad_ready:
             # (a need_grad=False pass overwrote the activations but left the ReLU-gate masks / pool arg-max bytes of the pass before it)
             raise RuntimeError('ClassifierEngine.backward(): the last forward() ran with need_grad=False (its gate masks were not '
@@ -416,6 +512,9 @@ class ClassifierEngine:
         g_pre = self.body.backward(g_logits)
         _lib.call('spaa_preproc_bwd', _lib.ptr(g_pre), _lib.ptr(self.g_y), self.B, self.H, self.W, self.cy0, self.cx0,
                   self.ch, self.cw, self.oh, self.ow, self._std)
+        if attention is not None:
+            self.grad_cam(g_logits, target)
+            self.attention_apply(attention.floor, g_y=self.g_y)
         return self.g_y
 
 
@@ -506,6 +605,32 @@ class Classifier(object):
 
     def __call__(self, im, crop_sz):
         return self.classify(im, crop_sz)
+
+    def grad_cam(self, im, class_idx, crop_sz=(240, 240)):
+        """Where the classifier looks for `class_idx` (a list of B classes) in `im` [B, 3, H, W] on the GPU: the Grad-CAM map M of
+        DESIGN.md 7h as float32 [B, 1, H, W] on the device, in [0, 1], 0 outside the classifier crop.  One forward pass and the
+        head's part of the backward pass (the body's backward pass does not run)."""
+        if self.device.type != 'cuda':
+            raise RuntimeError('spaa_amd.Classifier runs on the GPU only (no CPU fallback); got device=%s' % self.device)
+        if im.dtype == torch.uint8:
+            im = im.type(torch.float32) / 255
+        if im.ndim != 4 or im.shape[1] != 3:
+            raise ValueError(f'grad_cam: im must be [B, 3, H, W], got {tuple(im.shape)}')
+        classes = [int(c) for c in class_idx]
+        b, _, h, w = im.shape
+        if len(classes) != b or any(not 0 <= c < self.num_classes for c in classes):
+            raise ValueError(f'grad_cam: class_idx must hold {b} classes in [0, {self.num_classes}), got {classes}')
+        im = im.to(self.device)
+        with _lib.on_device(im.device):
+            eng = self.engine(b, (h, w), tuple(crop_sz))
+            eng.attention_buffers()
+            eng.forward(to_nhwc4(im.float().contiguous()), need_grad=False)
+            target = torch.tensor(classes, dtype=torch.int32, device=im.device)
+            seed = torch.zeros(b, eng.ncls, device=im.device)
+            seed[torch.arange(b, device=im.device), target.long()] = 1.0
+            eng.body.head_grad(seed)
+            eng.grad_cam(seed, target)
+            return eng.attention_map()
 
 
 def load_imagenet_labels(filename):

@@ -301,6 +301,10 @@ class InceptionV3Body(ClassifierBody):
             written.add(key)
         return self.x_in.gbuf
 
+    def attention_source(self):
+        assert self.feat.whole(), 'the last concatenation is a whole buffer'
+        return self.feat.buf, self.g_pooled, True
+
     def refresh_masks(self):
         """Recompute the gate masks from the activation buffers (after a test has overwritten the activations)."""
         if not self.masks:

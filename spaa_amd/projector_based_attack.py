@@ -20,7 +20,7 @@ import torch
 
 from . import _lib
 from .models import PCNet, to_nhwc4, to_nchw
-from .classifier import Classifier
+from .classifier import Attention, Classifier
 
 # B * Hc * Wc up to which spaa() replays the iteration as a captured HIP graph (0 disables); above it the GPU is busy for
 # longer than the host needs to enqueue an iteration and eager launches lose nothing (measured: < 1 % at B = 64, 256 x 256)
@@ -66,11 +66,13 @@ def _scene_batch(cam_scene, B):
 class AttackState:
     """Device-side state of one batched attack (everything the loop touches, allocated once)."""
 
-    def __init__(self, pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, device, storage='f32'):
+    def __init__(self, pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, device, storage='f32', attention=None):
         """`storage`: 'f32' (default; results identical to the reference to rounding) or 'f16' (fp16-storage mode of
         BASELINE.json configs[4]: network activations and their gradients are fp16 in HBM, images / losses / dE2000 /
-        norms / accumulation fp32)."""
-        self.storage = storage
+        norms / accumulation fp32).  `attention`: an Attention (fp32 storage): every classifier engine of the state
+        weights its gradient image by its own Grad-CAM map; attention_maps() returns the maps of the last iteration."""
+        _attention_checked(attention, storage, type(self).__name__)
+        self.storage, self.attention = storage, attention
         dev = _require_gpu(device, 'spaa')
         if dev.index is None:
             dev = torch.device('cuda', torch.cuda.current_device())
@@ -93,6 +95,8 @@ class AttackState:
         if tuple(cam_scene.shape[-2:]) != (Hc, Wc):
             raise ValueError(f'cam_scene is {tuple(cam_scene.shape[-2:])} but PCNet outputs {(Hc, Wc)}')
         self.clf = classifier.engine(B, (Hc, Wc), self.cp_sz, owner=self, storage=self.storage)
+        if self.attention is not None:
+            self.clf.attention_buffers()
         # fp16 gradients need a loss scale (fp16's smallest normal is 6e-5; the per-pixel loss gradients are ~1/(B*H*W)).
         # Each sample's gradient is normalised before the step (:307, :315), so a positive per-branch scale changes
         # nothing but the fp16 rounding: stealth branch: 1/16 per pixel instead of 1/(B*H*W); adversarial branch: +-16
@@ -208,7 +212,18 @@ class AttackState:
 
     def _adv_gradient(self):
         """The adversarial loss's gradient at the camera image [B,Hc,Wc,4]: the classifier's backward pass from the seed of the decision."""
-        return self.clf.backward(self.g_logits)                                      # :302 (classifier part)
+        return self.clf.backward(self.g_logits, self.attention, self.target)         # :302 (classifier part)
+
+    def _engine_maps(self, engines):
+        if self.attention is None:
+            raise RuntimeError('attention_maps(): this attack runs without attention (pass attention=Attention(...))')
+        with torch.cuda.device(self.dev):
+            return [e.attention_map() for e in engines]
+
+    def attention_maps(self):
+        """The Grad-CAM map M of the last iteration in the camera frame, [B, 1, Hc, Wc] in [0, 1] and 0 outside the classifier crop
+        (EnsembleAttackState: a list of one per member, MultiViewAttackState: of one per view)."""
+        return self._engine_maps([self.clf])[0]
 
     def trace_entry(self):
         """What spaa()'s `trace` records per iteration (copies; no sync)."""
@@ -275,12 +290,14 @@ class EnsembleAttackState(AttackState):
     normalised step and the best tracking are AttackState's.  `state[:, 3]` counts the fooled members; each member's top-1 is in
     `ens_state`.  `focus`: a member that is already fooled rests (weight 0) until all are."""
 
-    def __init__(self, pcnet, classifiers, target_idx, cam_scene, stealth_loss, setup_info, device, storage='f32', focus=False):
+    def __init__(self, pcnet, classifiers, target_idx, cam_scene, stealth_loss, setup_info, device, storage='f32', focus=False,
+                 attention=None):
         self.members = _ensemble_members(classifiers, storage, 'EnsembleAttackState')
         if len(self.members) < 2:
             raise ValueError('EnsembleAttackState needs at least two classifiers (AttackState attacks one)')
         self.focus = bool(focus)
-        super().__init__(pcnet, self.members[0], target_idx, cam_scene, stealth_loss, setup_info, device, storage=storage)
+        super().__init__(pcnet, self.members[0], target_idx, cam_scene, stealth_loss, setup_info, device, storage=storage,
+                         attention=attention)
 
     def _build(self, pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, dev):
         super()._build(pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, dev)   # (leases member 0's engine: self.clf)
@@ -288,6 +305,9 @@ class EnsembleAttackState(AttackState):
         self.K = K
         self.clfs = [self.clf] + [c.engine(B, (self.eng.Hc, self.eng.Wc), self.cp_sz, owner=self, storage=self.storage)
                                   for c in self.members[1:]]
+        if self.attention is not None:
+            for e in self.clfs[1:]:
+                e.attention_buffers()
         self.ens_g_logits = [self.g_logits] + [torch.zeros_like(self.g_logits) for _ in range(K - 1)]
         self.ens_state = torch.zeros(B, K, 2, dtype=torch.int32, device=dev)
         self.ens_stats = torch.zeros(B, K, 2, device=dev)
@@ -316,7 +336,10 @@ class EnsembleAttackState(AttackState):
 
     def _member_gradients(self):
         """Every member's gradient image at the camera image, from its seed of the decision."""
-        return [e.backward(g) for e, g in zip(self.clfs, self.ens_g_logits)]
+        return [e.backward(g, self.attention, self.target) for e, g in zip(self.clfs, self.ens_g_logits)]   # (each its own map)
+
+    def attention_maps(self):
+        return self._engine_maps(self.clfs)
 
     def _adv_gradient(self):
         gs = _lib.ptr_array(self._member_gradients())
@@ -386,14 +409,16 @@ class MultiViewAttackState(AttackState):
     `view_state`, its p1, target logit, caml2 and camdE in `view_stats`.  `focus`: a view that is already fooled rests (weight 0) until
     all are."""
 
-    def __init__(self, pcnets, classifier, target_idx, cam_scenes, stealth_loss, setup_info, device, storage='f32', focus=False):
+    def __init__(self, pcnets, classifier, target_idx, cam_scenes, stealth_loss, setup_info, device, storage='f32', focus=False,
+                 attention=None):
         views, scenes = _view_pcnets(pcnets, cam_scenes, 'MultiViewAttackState')
         if not isinstance(views, list):
             raise ValueError('MultiViewAttackState needs at least two views (AttackState attacks one)')
         classifier = _unwrap(classifier)
         _views_supported(views, classifier, storage, 'MultiViewAttackState')
         self.pcnets, self._scenes, self.focus = views, scenes, bool(focus)
-        super().__init__(views[0], classifier, target_idx, scenes[0], stealth_loss, setup_info, device, storage=storage)
+        super().__init__(views[0], classifier, target_idx, scenes[0], stealth_loss, setup_info, device, storage=storage,
+                         attention=attention)
 
     def _build(self, pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, dev):
         super()._build(pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, dev)   # (view 0: self.eng, self.clf, ...)
@@ -422,6 +447,8 @@ class MultiViewAttackState(AttackState):
             _lib.call('spaa_rgb2lab', _lib.ptr(scene4), _lib.ptr(lab), B * Hc * Wc)
             self.engs.append(eng)
             self.clfs.append(classifier.engine(B, (Hc, Wc), self.cp_sz, owner=self, storage=self.storage))
+            if self.attention is not None:
+                self.clfs[-1].attention_buffers()
             self.scene4s.append(scene4)
             self.scene_labs.append(lab)
             self.g_cols.append(torch.zeros_like(self.g_col))
@@ -458,7 +485,7 @@ class MultiViewAttackState(AttackState):
         B, p = self.B, _lib.ptr
         gxs = []
         for v, eng in enumerate(self.engs):
-            g_adv = self.clfs[v].backward(self.view_g_logits[v])                     # :302 (classifier part), from view v's seed
+            g_adv = self.clfs[v].backward(self.view_g_logits[v], self.attention, self.target)   # :302 (classifier part), view v's seed and map
             if eng.can_select():
                 gxs.append(eng.backward(None, select=(g_adv, self.g_cols[v], self.state), sumsq=None, clamp_bits=None))
             else:
@@ -474,6 +501,9 @@ class MultiViewAttackState(AttackState):
         _lib.call('spaa_step_and_track_n', p(self.x), p(self.g), p(self.partial_ss), self.nblk_p, p(self.state), float(adv_lr),
                   float(col_lr), p(self.x_best), p(self._ys[0]), p(self.cam_best), B, self.HWp, self.HWc, None)   # :307,315,323-328
         _lib.call('spaa_views_track', _lib.ptr_array(self._ys), _lib.ptr_array(self.cam_bests), self.V, p(self.state), B, self.HWc)
+
+    def attention_maps(self):
+        return self._engine_maps(self.clfs)
 
     def trace_entry(self):
         return super().trace_entry() + (self.view_state.clone(), self.view_stats.clone())
@@ -540,6 +570,31 @@ def _jitter_supported(jitter, pcnet, classifier, storage, focus, who):
         raise ValueError(f'{who}: focus=True has no meaning with jitter (a sample must fool every draw of every iteration)')
 
 
+def _attention_checked(attention, storage, who):
+    """An attack state's own check of its `attention` (the entry points say more, earlier: _attention_supported)."""
+    if attention is None:
+        return
+    if not isinstance(attention, Attention):
+        raise TypeError(f'{who}: attention must be a spaa_amd.Attention or None, got {type(attention).__name__}')
+    if storage != 'f32':
+        raise NotImplementedError(f"{who}: storage={storage!r} is not implemented with attention (the feature map and its gradient are "
+                                  "read as fp32); use storage='f32'")
+
+
+def _attention_supported(attention, classifier, storage, jitter, who):
+    """What an attention-weighted attack does not serve, said before anything is allocated or launched.  `classifier`: as spaa() holds
+    it after its own checks (a Classifier, a checked list of several, or anything else)."""
+    if not isinstance(attention, Attention):
+        raise TypeError(f'{who}: attention must be a spaa_amd.Attention or None, got {type(attention).__name__}')
+    if jitter is not None:
+        raise NotImplementedError(f'{who}: attention together with capture jitter is not implemented (every draw would need a map of '
+                                  'its own, pulled back through the jitter); use attention or jitter')
+    if not isinstance(classifier, (Classifier, list)):
+        raise TypeError(f'{who}: an attention-weighted attack needs a spaa_amd.Classifier, got {type(classifier).__name__} (a foreign '
+                        'callable has no feature map to read)')
+    _attention_checked(attention, storage, who)
+
+
 class JitterAttackState(EnsembleAttackState):
     """One batched attack against J = jitter.draws randomly perturbed captures of the camera image per iteration (DESIGN.md,
     "Capture-robust attack"): EnsembleAttackState whose members are J leased engines of ONE classifier, member j looking at draw j
@@ -580,22 +635,24 @@ class JitterAttackState(EnsembleAttackState):
         return self.draw_grads
 
 
-def _attack_state(pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, device, storage, focus, jitter=None):
+def _attack_state(pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, device, storage, focus, jitter=None,
+                  attention=None):
     """AttackState for one Classifier, EnsembleAttackState for a checked list of several, MultiViewAttackState for a checked list of
-    PCNets (with their list of scenes), JitterAttackState for one Classifier with a CaptureJitter."""
+    PCNets (with their list of scenes), JitterAttackState for one Classifier with a CaptureJitter (which takes no `attention`)."""
     if jitter is not None:
         return JitterAttackState(pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, device, jitter, storage=storage)
     if isinstance(pcnet, list):
         return MultiViewAttackState(pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, device, storage=storage,
-                                    focus=focus)
+                                    focus=focus, attention=attention)
     if isinstance(classifier, list):
         return EnsembleAttackState(pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, device, storage=storage,
-                                   focus=focus)
-    return AttackState(pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, device, storage=storage)
+                                   focus=focus, attention=attention)
+    return AttackState(pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, device, storage=storage, attention=attention)
 
 
 def spaa(pcnet, classifier, imagenet_labels, target_idx, targeted, cam_scene, d_thr, stealth_loss, device, setup_info,
-         *, iters=50, adv_lr=2, col_lr=1, p_thresh=0.9, trace=None, verbose=False, storage='f32', focus=False, jitter=None):
+         *, iters=50, adv_lr=2, col_lr=1, p_thresh=0.9, trace=None, verbose=False, storage='f32', focus=False, jitter=None,
+         attention=None):
     """Stealthy Projector-based Adversarial Attack (SPAA Algorithm 1) — see module docstring.
 
     :param pcnet: spaa_amd.PCNet (optionally wrapped in DataParallel-like `.module`), or a list / tuple of 2..4 of them: the same projector
@@ -609,6 +666,9 @@ def spaa(pcnet, classifier, imagenet_labels, target_idx, targeted, cam_scene, d_
     :param jitter: a CaptureJitter: ONE projection against `jitter.draws` randomly perturbed captures of the camera image per iteration,
         the first of them the clean one (JitterAttackState; one PCNet, one Classifier, fp32 storage, no `focus`).  The trace entries
         are the ensemble's, with draws as members.  None (default): the attack on the noiseless inferred capture
+    :param attention: an Attention: the classifier's gradient image is weighted by floor + (1 - floor) M, M the Grad-CAM map of the
+        sample's class on the classifier crop (fp32 storage, a spaa_amd.Classifier, no `jitter`).  In an ensemble every
+        member uses its own map, with several views every view its own.  None (default): the plain attack, launch for launch
     :param imagenet_labels: dict idx -> name (only used when verbose)
     :param target_idx: list of B class ids (true label if untargeted)
     :param targeted: bool
@@ -634,12 +694,14 @@ def spaa(pcnet, classifier, imagenet_labels, target_idx, targeted, cam_scene, d_
         _views_supported(pcnet, classifier, storage, 'spaa')
     if jitter is not None:
         _jitter_supported(jitter, pcnet, classifier, storage, focus, 'spaa')
+    if attention is not None:
+        _attention_supported(attention, classifier, storage, jitter, 'spaa')
     if not isinstance(classifier, (Classifier, list)):
         if not callable(classifier):
             raise TypeError('classifier must be a spaa_amd.Classifier or a callable (im, crop_sz) -> (raw_score, p, idx)')
         return _spaa_foreign_classifier(pcnet, classifier, imagenet_labels, target_idx, targeted, cam_scene, d_thr,
                                         stealth_loss, device, setup_info, iters, adv_lr, col_lr, p_thresh, trace)
-    st = _attack_state(pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, device, storage, focus, jitter)
+    st = _attack_state(pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, device, storage, focus, jitter, attention)
 
     def report(i):
         if i % 30 == 0 or i == iters - 1:
@@ -737,7 +799,7 @@ def split_sweep(samples, ncfg, chunk_results):
 
 
 def spaa_sweep(pcnet, classifier, imagenet_labels, cam_scene, setup_info, device, configs, *, iters=50, adv_lr=2, col_lr=1,
-               p_thresh=0.9, max_batch=64, storage='f32', trace=None, focus=False, jitter=None):
+               p_thresh=0.9, max_batch=64, storage='f32', trace=None, focus=False, jitter=None, attention=None):
     """Several SPAA attacks on one PCNet, scene and classifier as few batched attacks (the reference's driver makes one spaa() call
     per configuration: projector_based_attack.py:24-148).  `configs`: [(stealth_loss, d_thr, targeted, target_idx), ...]; returns one
     (cam_infer_best, prj_adv_best) per config, in order -- what spaa(pcnet, classifier, imagenet_labels, target_idx, targeted,
@@ -749,7 +811,8 @@ def spaa_sweep(pcnet, classifier, imagenet_labels, cam_scene, setup_info, device
     (state, stats, ens_state, ens_stats).  `pcnet` may be a list / tuple of 2..4 PCNets with `cam_scene` a list of their scenes, as
     in spaa(): every sample then attacks all views at once, each config's first return value is a list of one camera image batch
     per view, and the trace entries are (state, stats, view_state, view_stats).  `jitter`: a CaptureJitter, as in spaa(): every chunk
-    is a jitter attack with that seed (the draws of a sample depend on its place in its chunk), the trace entries the ensemble's."""
+    is a jitter attack with that seed (the draws of a sample depend on its place in its chunk), the trace entries the ensemble's.
+    `attention`: an Attention, as in spaa(): every chunk is an attention-weighted attack."""
     samples, chunks = plan_sweep(configs, max_batch)
     pcnet, classifier = _unwrap(pcnet), _unwrap(classifier)
     if isinstance(pcnet, (list, tuple)):
@@ -764,6 +827,8 @@ def spaa_sweep(pcnet, classifier, imagenet_labels, cam_scene, setup_info, device
         _views_supported(pcnet, classifier, storage, 'spaa_sweep')
     if jitter is not None:
         _jitter_supported(jitter, pcnet, classifier, storage, focus, 'spaa_sweep')
+    if attention is not None:
+        _attention_supported(attention, classifier, storage, jitter, 'spaa_sweep')
     if not isinstance(classifier, (Classifier, list)):
         raise TypeError('spaa_sweep needs a spaa_amd.Classifier')
     _require_gpu(device, 'spaa_sweep')
@@ -780,7 +845,7 @@ def spaa_sweep(pcnet, classifier, imagenet_labels, cam_scene, setup_info, device
     for a, b in chunks:
         part = samples[a:b]
         st = _attack_state(pcnet, classifier, [t for *_, t in part], sc, [s[1] for s in part], setup_info, device, storage, focus,
-                           jitter)
+                           jitter, attention)
         tr = [] if trace is not None else None
         _run(st, [s[3] for s in part], [s[2] for s in part], iters, adv_lr, col_lr, p_thresh, tr)
         if trace is not None:
