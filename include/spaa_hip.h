@@ -729,6 +729,31 @@ int spaa_cam_map(const float* A, const float* alpha, float alpha_scale, const fl
 int spaa_attention_apply(const float* c, const float* cmax, float floor, float* g_y, float* M_out, int B, int H, int W, int cy0, int cx0,
                          int ch, int cw, int fh, int fw, spaa_stream_t stream);
 
+/* ---- transferable attack: the adversarial step's direction is smoothed (TI-FGSM) and accumulated with momentum (MI-FGSM) at the
+ * projector image ---------------------------------------------------------------------------------------------------
+ * Images are [B][Hp][Wp][4] fp32, state is spaa_decide's [B][4].  A sample on the colour step (state[b][1] != 0) is skipped by both
+ * launches: none of its rows of g, t, m, partial_l1 or partial_ss is read or written.  No atomics and fixed summation orders: bitwise
+ * repeatable.  One launch each, none syncs. */
+#define SPAA_TRANSFER_RMAX 7
+/* tiles per image of the blur launch (16 x 32 pixel tiles, row-major); 0 for sizes that spaa_transfer_blur refuses */
+int spaa_transfer_tiles(int Hp, int Wp);
+/* t_b = K (*) g_b for every sample on the adversarial step: the separable filter with the 2 r + 1 taps `taps` (a HOST array, copied into
+ * the launch's arguments) along both axes, zero beyond the image border (F.conv2d with padding = r), each colour channel on its own in
+ * fp32 with fused multiply-adds, taps in index order, rows first.  The pad channel of g is not used and that of t is written 0.
+ * partial_l1 [B][tiles] = each tile's sum over pixels and colour channels of |t|, tiles = spaa_transfer_tiles(Hp, Wp).  Both passes run
+ * in one launch through LDS.  r == 0: t = taps[0] g.  Not in place.  r outside 0 .. SPAA_TRANSFER_RMAX, a non-positive size, B > 65535,
+ * Hp Wp > 2^30 or a null pointer: hipErrorInvalidValue and nothing is launched. */
+int spaa_transfer_blur(const float* g, const int32_t* state, const float* taps, int r, float* t, float* partial_l1, int B, int Hp, int Wp,
+                       spaa_stream_t stream);
+/* For every sample on the adversarial step: n1 = the sum of partial_l1[b][0 .. tiles - 1] in index order (accumulated in double, rounded
+ * once to fp32); m_b = fma(mu, m_b, t_b / n1) per colour channel, or mu m_b when n1 == 0; the pad channel of m_b is written 0; g_b = m_b.
+ * Block j of the sample handles the 256-pixel chunks j, j + npartial, ... and writes partial_ss[b][j] = its sum of m.r^2 + m.g^2 + m.b^2
+ * (the fixed-order block sum); all npartial entries of the row are written, those without a chunk as 0: spaa_step_and_track_n with the
+ * same npartial then steps by lr m_b / ||m_b||_2.  HW = Hp Wp.  0 <= mu <= 1; tiles, npartial >= 1; B <= 65535; HW <= 2^30; anything
+ * else, or a null pointer: hipErrorInvalidValue and nothing is launched. */
+int spaa_transfer_momentum(const float* t, const float* partial_l1, int tiles, float mu, const int32_t* state, float* m, float* g,
+                           float* partial_ss, int npartial, int B, int HW, spaa_stream_t stream);
+
 /* ---- PerC_AL.adversary_projector (perc_al/__init__.py:133-256) ------------------------------------------ */
 /* x = a + b (inputs + delta), NHWC4 */
 int spaa_add_nhwc4(const float* a, const float* b, float* x, int npix, spaa_stream_t stream);

@@ -191,6 +191,8 @@ _SIGNATURES = {
     'spaa_cam_alpha': [_p, _p, _i, _i, _i, _i, _p],
     'spaa_cam_map': [_p, _p, _f, _p, _i, _p, _p, _p, _i, _i, _i, _p],
     'spaa_attention_apply': [_p, _p, _f, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p],
+    'spaa_transfer_blur': [_p, _p, C.POINTER(C.c_float), _i, _p, _p, _i, _i, _i, _p],
+    'spaa_transfer_momentum': [_p, _p, _i, _f, _p, _p, _p, _p, _i, _i, _i, _p],
     'spaa_onepixel_preproc': [_p, _p, _i, _i, _i, _p, _i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_float), C.POINTER(C.c_float), _p],
     'spaa_onepixel_score': [_p, _i, _i, _i, _p, _p, _p, _i, _p],
     'spaa_onepixel_warp': [_p, _p, _i, _i, _i, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p],
@@ -208,7 +210,7 @@ _SIGNATURES = {
 }
 
 EXPORTS = sorted(list(_SIGNATURES) + ['spaa_version', 'spaa_tapconv_sizeof', 'spaa_tapconv_offsetof', 'spaa_tapconv_wino_plan', 'spaa_tapconv_h16p_plan',
-                                         'spaa_tapconv_tile_info', 'spaa_tapconv_check'])
+                                         'spaa_tapconv_tile_info', 'spaa_tapconv_check', 'spaa_transfer_tiles'])
 
 _lib = None
 
@@ -238,6 +240,8 @@ def load():
     lib.spaa_tapconv_tile_info.restype = C.c_int
     lib.spaa_tapconv_check.argtypes = [C.POINTER(TapConv)]                             # (host-side query: no stream)
     lib.spaa_tapconv_check.restype = C.c_int
+    lib.spaa_transfer_tiles.argtypes = [C.c_int, C.c_int]                              # (host-side query: no stream)
+    lib.spaa_transfer_tiles.restype = C.c_int
     _lib = lib
     return lib
 

@@ -131,6 +131,21 @@ def capture_survival(ims, classifier, target_idx, targeted, crop_sz, jitter, *, 
     return (hits / int(draws)).numpy()
 
 
+def transfer_success(cam, classifier, target_idx, targeted, crop_sz, p_thresh=0.9):
+    """Which camera images `cam` [B,3,H,W] fool `classifier`, by the success rule of the attack's own decision (spaa_decide): bool [B];
+    one class id per image in `target_idx` and `targeted` (one flag, or one per image): top-1 == target with p1 > `p_thresh`, else
+    top-1 != target (the image's true class).  The evaluation hook of a transferable attack (Transfer): `classifier` is one that took
+    no part in it.  Top-1 and p1 through _sorted_classes, as the summary's rates."""
+    n = cam.shape[0]
+    tgt = np.asarray([int(t) for t in target_idx])
+    tg = np.full(n, bool(targeted)) if np.ndim(targeted) == 0 else np.asarray([bool(t) for t in targeted])
+    if tgt.shape != (n,) or tg.shape != (n,):
+        raise ValueError(f'transfer_success: {n} images, {tgt.size} targets, {tg.size} targeted flags')
+    p1 = [None]
+    top1 = _sorted_classes(classifier, [cam], crop_sz, top1=p1)[0][:, 0]
+    return np.where(tg, (top1 == tgt) & (p1[0] > np.float32(p_thresh)), top1 != tgt)
+
+
 def write_stats(table, path):
     """The reference's table files: tab-separated, 4 decimals (stats.txt, stats_all.txt)."""
     table.to_csv(path, index=False, float_format='%.4f', sep='\t')

@@ -12,7 +12,9 @@ with the reference values as defaults.  Differences in *mechanism*, not in resul
   * `cam_scene` may also be [B,3,H,W] (one scene per sample); the reference supports one scene x B targets (Q9),
     and its targeted mode needs B >= 8 because of a debug print (Q10) — not inherited.
 """
+import ctypes
 import dataclasses
+import math
 import os
 import warnings
 
@@ -66,13 +68,17 @@ def _scene_batch(cam_scene, B):
 class AttackState:
     """Device-side state of one batched attack (everything the loop touches, allocated once)."""
 
-    def __init__(self, pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, device, storage='f32', attention=None):
+    def __init__(self, pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, device, storage='f32', attention=None,
+                 transfer=None):
         """`storage`: 'f32' (default; results identical to the reference to rounding) or 'f16' (fp16-storage mode of
         BASELINE.json configs[4]: network activations and their gradients are fp16 in HBM, images / losses / dE2000 /
         norms / accumulation fp32).  `attention`: an Attention (fp32 storage): every classifier engine of the state
-        weights its gradient image by its own Grad-CAM map; attention_maps() returns the maps of the last iteration."""
+        weights its gradient image by its own Grad-CAM map; attention_maps() returns the maps of the last iteration.  `transfer`: a
+        Transfer (fp32 storage): the adversarial step follows the smoothed, momentum-accumulated gradient image
+        `momentum` [B,Hp,Wp,4] instead of the raw one."""
         _attention_checked(attention, storage, type(self).__name__)
-        self.storage, self.attention = storage, attention
+        _transfer_checked(transfer, storage, type(self).__name__)
+        self.storage, self.attention, self.transfer = storage, attention, transfer
         dev = _require_gpu(device, 'spaa')
         if dev.index is None:
             dev = torch.device('cuda', torch.cuda.current_device())
@@ -146,6 +152,30 @@ class AttackState:
         self.ps_params = torch.zeros(B, 4, device=dev)
         self.ps_flags = torch.zeros(B, dtype=torch.int32, device=dev)
         self.ps_prjl2_scale = torch.zeros(B, device=dev)
+        if self.transfer is not None:
+            # the momentum image m (zero: the first adversarial step is the smoothed gradient's), the smoothed gradient t and its |.|
+            # sums per tile of the blur launch; the taps travel in the launch's arguments
+            self.momentum = torch.zeros(B, Hp, Wp, 4, device=dev)
+            self.transfer_t = torch.zeros(B, Hp, Wp, 4, device=dev)
+            self.transfer_tiles = _lib.load().spaa_transfer_tiles(Hp, Wp)
+            self.transfer_l1 = torch.zeros(B, self.transfer_tiles, device=dev)
+            taps = self.transfer.weights().tolist()
+            self._transfer_taps = (ctypes.c_float * len(taps))(*taps)
+
+    def _shape_direction(self, gx, partial_ss, npartial):
+        """The transferable step, directly before spaa_step_and_track_n: for every sample on the adversarial step the
+        gradient image `gx` becomes the momentum image m <- mu m + t / |t|_1, t the Gaussian-smoothed gx, and its row of `partial_ss`
+        the partial sums of ||m||^2; samples on the colour step keep gx, partial_ss and m bit for bit.  Two launches, no host read;
+        without `transfer` none."""
+        tr = self.transfer
+        if tr is None:
+            return
+        p = _lib.ptr
+        Hp, Wp = self.x.shape[1:3]
+        _lib.call('spaa_transfer_blur', p(gx), p(self.state), self._transfer_taps, tr.radius, p(self.transfer_t), p(self.transfer_l1),
+                  self.B, Hp, Wp)
+        _lib.call('spaa_transfer_momentum', p(self.transfer_t), p(self.transfer_l1), self.transfer_tiles, float(tr.momentum),
+                  p(self.state), p(self.momentum), p(gx), p(partial_ss), int(npartial), self.B, self.HWp)
 
     def _per_sample(self, targeted, d_thr, table=False):
         """The batch's (targeted, d_thr) as scalars when every sample agrees and the loss weights are uniform (the launches of a single
@@ -247,6 +277,7 @@ class AttackState:
         elif not self.ss_tiles:
             _lib.call('spaa_grad_sumsq_ps', p(gx), p(self.x), self.gray, p(prjl2_scale), p(self.state), p(self.partial_ss), B,
                       self.HWp)
+        self._shape_direction(gx, self.partial_ss, self.partial_ss.shape[1])
         _lib.call('spaa_step_and_track_n', p(self.x), p(gx), p(self.partial_ss), self.partial_ss.shape[1], p(self.state), float(adv_lr),
                   float(col_lr), p(self.x_best), p(y), p(self.cam_best), B, self.HWp, self.HWc,
                   p(self.clamp_bits) if self.clamp_bits is not None else None)       # :307,315,323-328
@@ -291,13 +322,13 @@ class EnsembleAttackState(AttackState):
     `ens_state`.  `focus`: a member that is already fooled rests (weight 0) until all are."""
 
     def __init__(self, pcnet, classifiers, target_idx, cam_scene, stealth_loss, setup_info, device, storage='f32', focus=False,
-                 attention=None):
+                 attention=None, transfer=None):
         self.members = _ensemble_members(classifiers, storage, 'EnsembleAttackState')
         if len(self.members) < 2:
             raise ValueError('EnsembleAttackState needs at least two classifiers (AttackState attacks one)')
         self.focus = bool(focus)
         super().__init__(pcnet, self.members[0], target_idx, cam_scene, stealth_loss, setup_info, device, storage=storage,
-                         attention=attention)
+                         attention=attention, transfer=transfer)
 
     def _build(self, pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, dev):
         super()._build(pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, dev)   # (leases member 0's engine: self.clf)
@@ -410,7 +441,7 @@ class MultiViewAttackState(AttackState):
     all are."""
 
     def __init__(self, pcnets, classifier, target_idx, cam_scenes, stealth_loss, setup_info, device, storage='f32', focus=False,
-                 attention=None):
+                 attention=None, transfer=None):
         views, scenes = _view_pcnets(pcnets, cam_scenes, 'MultiViewAttackState')
         if not isinstance(views, list):
             raise ValueError('MultiViewAttackState needs at least two views (AttackState attacks one)')
@@ -418,7 +449,7 @@ class MultiViewAttackState(AttackState):
         _views_supported(views, classifier, storage, 'MultiViewAttackState')
         self.pcnets, self._scenes, self.focus = views, scenes, bool(focus)
         super().__init__(views[0], classifier, target_idx, scenes[0], stealth_loss, setup_info, device, storage=storage,
-                         attention=attention)
+                         attention=attention, transfer=transfer)
 
     def _build(self, pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, dev):
         super()._build(pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, dev)   # (view 0: self.eng, self.clf, ...)
@@ -498,6 +529,7 @@ class MultiViewAttackState(AttackState):
                   self.HWp)
         _lib.call('spaa_grad_sumsq_ps', p(self.g), p(self.x), self.gray, p(self.ps_prjl2_scale), p(self.state), p(self.partial_ss), B,
                   self.HWp)
+        self._shape_direction(self.g, self.partial_ss, self.nblk_p)
         _lib.call('spaa_step_and_track_n', p(self.x), p(self.g), p(self.partial_ss), self.nblk_p, p(self.state), float(adv_lr),
                   float(col_lr), p(self.x_best), p(self._ys[0]), p(self.cam_best), B, self.HWp, self.HWc, None)   # :307,315,323-328
         _lib.call('spaa_views_track', _lib.ptr_array(self._ys), _lib.ptr_array(self.cam_bests), self.V, p(self.state), B, self.HWc)
@@ -595,6 +627,71 @@ def _attention_supported(attention, classifier, storage, jitter, who):
     _attention_checked(attention, storage, who)
 
 
+TRANSFER_RMAX = 7   # SPAA_TRANSFER_RMAX of include/spaa_hip.h
+
+
+@dataclasses.dataclass(frozen=True)
+class Transfer:
+    """The transferable adversarial step: what a sample on the adversarial step follows is not the raw gradient image
+    at the projector but m <- `momentum` m + t / |t|_1 (MI-FGSM), t the gradient image convolved with a Gaussian of `sigma` projector
+    pixels (TI-FGSM; radius ceil(3 sigma) <= TRANSFER_RMAX, zero beyond the border).  momentum = 0: no accumulation; sigma = 0: no
+    smoothing; both 0 is the plain attack and refused."""
+    momentum: float = 1.0
+    sigma: float = 0.0
+
+    def __post_init__(self):
+        for name in ('momentum', 'sigma'):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v):
+                raise ValueError(f'Transfer: {name} must be a finite number, got {v!r}')
+        if not 0 <= self.momentum <= 1:
+            raise ValueError(f'Transfer: momentum must be in [0, 1], got {self.momentum}')
+        if self.sigma < 0:
+            raise ValueError(f'Transfer: sigma must be >= 0, got {self.sigma}')
+        if self.radius > TRANSFER_RMAX:
+            raise ValueError(f'Transfer: sigma = {self.sigma} needs the radius ceil(3 sigma) = {self.radius}, at most {TRANSFER_RMAX} '
+                             f'(sigma <= {TRANSFER_RMAX}/3)')
+        if self.momentum == 0 and self.sigma == 0:
+            raise ValueError('Transfer(0, 0): no momentum and no smoothing is the plain attack (pass transfer=None)')
+
+    @property
+    def radius(self):
+        """r = ceil(3 sigma): the filter has 2 r + 1 taps per axis."""
+        return int(math.ceil(3 * self.sigma))
+
+    def weights(self):
+        """The 2 r + 1 taps exp(-i^2 / (2 sigma^2)), i = -r .. r, normalised to sum 1 in float64 and then rounded: a float32 tensor
+        ([1.0] for sigma = 0)."""
+        r = self.radius
+        if r == 0:
+            return torch.ones(1, dtype=torch.float32)
+        i = torch.arange(-r, r + 1, dtype=torch.float64)
+        w = torch.exp(-i * i / (2.0 * float(self.sigma) ** 2))
+        return (w / w.sum()).to(torch.float32)
+
+
+def _transfer_checked(transfer, storage, who):
+    """An attack state's own check of its `transfer` (the entry points say more, earlier: _transfer_supported)."""
+    if transfer is None:
+        return
+    if not isinstance(transfer, Transfer):
+        raise TypeError(f'{who}: transfer must be a spaa_amd.Transfer or None, got {type(transfer).__name__}')
+    if storage != 'f32':
+        raise NotImplementedError(f"{who}: storage={storage!r} is not implemented with transfer (the momentum image and the smoothed "
+                                  "gradient are fp32 and carry no loss scale); use storage='f32'")
+
+
+def _transfer_supported(transfer, classifier, storage, who):
+    """What a transferable attack does not serve, said before anything is allocated or launched.  `classifier`: as spaa() holds it
+    after its own checks (a Classifier, a checked list of several, or anything else)."""
+    if not isinstance(transfer, Transfer):
+        raise TypeError(f'{who}: transfer must be a spaa_amd.Transfer or None, got {type(transfer).__name__}')
+    if not isinstance(classifier, (Classifier, list)):
+        raise TypeError(f'{who}: a transferable attack needs a spaa_amd.Classifier, got {type(classifier).__name__} (the route of a '
+                        'foreign callable steps inside torch.autograd, where the fused direction kernels do not run)')
+    _transfer_checked(transfer, storage, who)
+
+
 class JitterAttackState(EnsembleAttackState):
     """One batched attack against J = jitter.draws randomly perturbed captures of the camera image per iteration (DESIGN.md,
     "Capture-robust attack"): EnsembleAttackState whose members are J leased engines of ONE classifier, member j looking at draw j
@@ -604,12 +701,13 @@ class JitterAttackState(EnsembleAttackState):
     spaa_jitter_fwd, and the members' gradient images are pulled back to y by spaa_jitter_bwd before they are combined.  `state`,
     `stats`, `ens_state`, `ens_stats` keep the ensemble's meaning with draws as members."""
 
-    def __init__(self, pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, device, jitter, storage='f32'):
+    def __init__(self, pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, device, jitter, storage='f32', transfer=None):
         pcnet, classifier = _unwrap(pcnet), _unwrap(classifier)
         _jitter_supported(jitter, pcnet, classifier, storage, False, 'JitterAttackState')
         self.jitter, self.focus = jitter, False
         self.members = [classifier] * int(jitter.draws)   # (EnsembleAttackState._build leases one engine per entry)
-        AttackState.__init__(self, pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, device, storage=storage)
+        AttackState.__init__(self, pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, device, storage=storage,
+                             transfer=transfer)
 
     def _build(self, pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, dev):
         super()._build(pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, dev)
@@ -636,23 +734,26 @@ class JitterAttackState(EnsembleAttackState):
 
 
 def _attack_state(pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, device, storage, focus, jitter=None,
-                  attention=None):
+                  attention=None, transfer=None):
     """AttackState for one Classifier, EnsembleAttackState for a checked list of several, MultiViewAttackState for a checked list of
-    PCNets (with their list of scenes), JitterAttackState for one Classifier with a CaptureJitter (which takes no `attention`)."""
+    PCNets (with their list of scenes), JitterAttackState for one Classifier with a CaptureJitter (which takes no `attention`).
+    Each of them takes `transfer`."""
     if jitter is not None:
-        return JitterAttackState(pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, device, jitter, storage=storage)
+        return JitterAttackState(pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, device, jitter, storage=storage,
+                                 transfer=transfer)
     if isinstance(pcnet, list):
         return MultiViewAttackState(pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, device, storage=storage,
-                                    focus=focus, attention=attention)
+                                    focus=focus, attention=attention, transfer=transfer)
     if isinstance(classifier, list):
         return EnsembleAttackState(pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, device, storage=storage,
-                                   focus=focus, attention=attention)
-    return AttackState(pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, device, storage=storage, attention=attention)
+                                   focus=focus, attention=attention, transfer=transfer)
+    return AttackState(pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, device, storage=storage, attention=attention,
+                       transfer=transfer)
 
 
 def spaa(pcnet, classifier, imagenet_labels, target_idx, targeted, cam_scene, d_thr, stealth_loss, device, setup_info,
          *, iters=50, adv_lr=2, col_lr=1, p_thresh=0.9, trace=None, verbose=False, storage='f32', focus=False, jitter=None,
-         attention=None):
+         attention=None, transfer=None):
     """Stealthy Projector-based Adversarial Attack (SPAA Algorithm 1) — see module docstring.
 
     :param pcnet: spaa_amd.PCNet (optionally wrapped in DataParallel-like `.module`), or a list / tuple of 2..4 of them: the same projector
@@ -669,6 +770,9 @@ def spaa(pcnet, classifier, imagenet_labels, target_idx, targeted, cam_scene, d_
     :param attention: an Attention: the classifier's gradient image is weighted by floor + (1 - floor) M, M the Grad-CAM map of the
         sample's class on the classifier crop (fp32 storage, a spaa_amd.Classifier, no `jitter`).  In an ensemble every
         member uses its own map, with several views every view its own.  None (default): the plain attack, launch for launch
+    :param transfer: a Transfer: the adversarial step follows the Gaussian-smoothed, momentum-accumulated gradient image at the projector
+        instead of the raw one (fp32 storage, a spaa_amd.Classifier).  Combines with ensembles, views, `focus`, `jitter`
+        and `attention`: it acts on the projector-side gradient after them.  None (default): the plain attack, launch for launch
     :param imagenet_labels: dict idx -> name (only used when verbose)
     :param target_idx: list of B class ids (true label if untargeted)
     :param targeted: bool
@@ -696,12 +800,15 @@ def spaa(pcnet, classifier, imagenet_labels, target_idx, targeted, cam_scene, d_
         _jitter_supported(jitter, pcnet, classifier, storage, focus, 'spaa')
     if attention is not None:
         _attention_supported(attention, classifier, storage, jitter, 'spaa')
+    if transfer is not None:
+        _transfer_supported(transfer, classifier, storage, 'spaa')
     if not isinstance(classifier, (Classifier, list)):
         if not callable(classifier):
             raise TypeError('classifier must be a spaa_amd.Classifier or a callable (im, crop_sz) -> (raw_score, p, idx)')
         return _spaa_foreign_classifier(pcnet, classifier, imagenet_labels, target_idx, targeted, cam_scene, d_thr,
                                         stealth_loss, device, setup_info, iters, adv_lr, col_lr, p_thresh, trace)
-    st = _attack_state(pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, device, storage, focus, jitter, attention)
+    st = _attack_state(pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, device, storage, focus, jitter, attention,
+                       transfer)
 
     def report(i):
         if i % 30 == 0 or i == iters - 1:
@@ -799,7 +906,7 @@ def split_sweep(samples, ncfg, chunk_results):
 
 
 def spaa_sweep(pcnet, classifier, imagenet_labels, cam_scene, setup_info, device, configs, *, iters=50, adv_lr=2, col_lr=1,
-               p_thresh=0.9, max_batch=64, storage='f32', trace=None, focus=False, jitter=None, attention=None):
+               p_thresh=0.9, max_batch=64, storage='f32', trace=None, focus=False, jitter=None, attention=None, transfer=None):
     """Several SPAA attacks on one PCNet, scene and classifier as few batched attacks (the reference's driver makes one spaa() call
     per configuration: projector_based_attack.py:24-148).  `configs`: [(stealth_loss, d_thr, targeted, target_idx), ...]; returns one
     (cam_infer_best, prj_adv_best) per config, in order -- what spaa(pcnet, classifier, imagenet_labels, target_idx, targeted,
@@ -812,7 +919,8 @@ def spaa_sweep(pcnet, classifier, imagenet_labels, cam_scene, setup_info, device
     in spaa(): every sample then attacks all views at once, each config's first return value is a list of one camera image batch
     per view, and the trace entries are (state, stats, view_state, view_stats).  `jitter`: a CaptureJitter, as in spaa(): every chunk
     is a jitter attack with that seed (the draws of a sample depend on its place in its chunk), the trace entries the ensemble's.
-    `attention`: an Attention, as in spaa(): every chunk is an attention-weighted attack."""
+    `attention`: an Attention, as in spaa(): every chunk is an attention-weighted attack.  `transfer`: a Transfer, as in spaa(): every
+    chunk's adversarial steps follow the smoothed, momentum-accumulated direction (each chunk's momentum starts at zero)."""
     samples, chunks = plan_sweep(configs, max_batch)
     pcnet, classifier = _unwrap(pcnet), _unwrap(classifier)
     if isinstance(pcnet, (list, tuple)):
@@ -829,6 +937,8 @@ def spaa_sweep(pcnet, classifier, imagenet_labels, cam_scene, setup_info, device
         _jitter_supported(jitter, pcnet, classifier, storage, focus, 'spaa_sweep')
     if attention is not None:
         _attention_supported(attention, classifier, storage, jitter, 'spaa_sweep')
+    if transfer is not None:
+        _transfer_supported(transfer, classifier, storage, 'spaa_sweep')
     if not isinstance(classifier, (Classifier, list)):
         raise TypeError('spaa_sweep needs a spaa_amd.Classifier')
     _require_gpu(device, 'spaa_sweep')
@@ -845,7 +955,7 @@ def spaa_sweep(pcnet, classifier, imagenet_labels, cam_scene, setup_info, device
     for a, b in chunks:
         part = samples[a:b]
         st = _attack_state(pcnet, classifier, [t for *_, t in part], sc, [s[1] for s in part], setup_info, device, storage, focus,
-                           jitter, attention)
+                           jitter, attention, transfer)
         tr = [] if trace is not None else None
         _run(st, [s[3] for s in part], [s[2] for s in part], iters, adv_lr, col_lr, p_thresh, tr)
         if trace is not None:
@@ -944,5 +1054,5 @@ from .attack_driver import (ATTACKERS, MODEL_TRAIN_CFG, AttackSetup, get_attacke
                             run_projector_based_attack, _run_one_pixel_de, project_capture_real_attack)
 from .attack_summary import (SUMMARY_STEALTH_LOSSES, SUMMARY_D_THRESHES, SUMMARY_CLASSIFIERS, SUMMARY_CHUNK,   # noqa: E402,F401
                              SUMMARY_COLUMNS, MONTAGE_CHUNK, attack_success, write_stats, _sorted_classes, _nonempty,
-                             attack_results, attack_transfer, capture_survival, summarize_single_attacker,
+                             attack_results, attack_transfer, capture_survival, transfer_success, summarize_single_attacker,
                              summarize_all_attackers)
