@@ -586,6 +586,35 @@ int spaa_adaptive_avgpool_fwd(const float* in, float* out, int B, int Hin, int W
 int spaa_adaptive_avgpool_bwd(const float* g_out, const float* gate_in, float* g_in, int B, int Hin, int Win, int C,
                               int Hout, int Wout, spaa_stream_t stream);
 
+/* ---- Depthwise 3 x 3 / ReLU6 layers of torchvision's MobileNetV2 (csrc/dwconv.hip; spaa_amd/mobilenet.py) --------------- */
+/* NHWC fp32, C % 4 == 0, B Hin Win C < 2^29 elements (every tensor below 2 GiB).  ReLU6 is torch's hardtanh(0, 6): the value is
+ * min(max(v, 0), 6), the gradient passes where 0 < v < 6, strictly on both sides.  Gate bytes have the format of
+ * spaa_tapconv_t.mask_out (one byte per 4 consecutive channels, bit e = channel 4 q + e passes), so a convolution's input-gradient
+ * launch takes them through `gate_bits` unchanged.  The clamp is fminf(fmaxf(v, 0), 6) like every ReLU epilogue of this library: a NaN
+ * becomes 0 with its gate bit clear (FINITE VALUES ONLY, see the pooling section above).  Invalid arguments (a null pointer other
+ * than the optional ones named below, C % 4 != 0, a stride other than 1 or 2, a size < 1 or over the limit) return
+ * hipErrorInvalidValue with nothing launched and nothing written.
+ *
+ * spaa_dwconv3_fwd: depthwise 3 x 3, padding 1, stride 1 or 2: in [B, Hin, Win, C] -> out [B, Hout, Wout, C], Hout = (Hin - 1) / stride
+ * + 1 (likewise Wout).  w [9][C] tap-major (tap = 3 ky + kx) with the BatchNorm folded in, bias [C].  in_relu6 != 0: `in` is a
+ * pre-activation and is clamped to [0, 6] as it is loaded (the ReLU6 of the layer before, which that launch then does not apply).  The
+ * accumulation order is fixed: acc = bias, then acc = fmaf(w, v, acc) over (ky, kx) in row-major order, taps outside the image skipped.
+ * The output is always ReLU6'd; mask_out [B, Hout, Wout, C / 4] (may be NULL) receives bit = (0 < acc < 6).
+ * spaa_dwconv3_bwd: its exact adjoint as a gather (no atomics; two runs are bitwise equal): g_in[y, x, c] = gate6(in_pre[y, x, c]) *
+ * sum over the taps (ky, kx), row-major, that reach an output pixel, of w[ky, kx, c] g_out[oy, ox, c] (acc = 0, then fmaf).  in_pre
+ * [B, Hin, Win, C]: the pre-activation the forward pass clamped on load (NULL: no gate).  g_out must arrive gated by the forward
+ * pass's mask_out (the projection's input-gradient launch does that through gate_bits). */
+int spaa_dwconv3_fwd(const float* in, int in_relu6, const float* w, const float* bias, float* out, uint8_t* mask_out, int B, int Hin,
+                     int Win, int C, int stride, spaa_stream_t stream);
+int spaa_dwconv3_bwd(const float* g_out, const float* w, const float* in_pre, float* g_in, int B, int Hin, int Win, int C, int stride,
+                     spaa_stream_t stream);
+/* In-place ReLU6 of act [M pixels][C], writing its gate bytes mask_out [M][C / 4] (may be NULL: a pass nobody differentiates):
+ * MobileNetV2's features.18, whose clamped output is also the feature map Grad-CAM reads. */
+int spaa_relu6_gate(float* act, uint8_t* mask_out, int64_t M, int C, spaa_stream_t stream);
+/* adaptive_avg_pool2d(1) backward under a ReLU6 gate: g_in[b, p, c] = bit(mask[b, p, c / 4], c % 4) ? g_feat[b, c] / HW : 0
+ * (spaa_avgpool_bwd gates on act > 0 only, which is wrong at 6). */
+int spaa_global_avgpool_bwd_bits(const float* g_feat, const uint8_t* mask, float* g_in, int B, int HW, int C, spaa_stream_t stream);
+
 /* ---- SPAA Algorithm 1 control on device (projector_based_attack.py:269-328) ------------------------------ */
 /* Per-sample decision, one workgroup per sample: softmax top-1 / argmax of logits (classifier.py:64-68), loss
  * reduction, masks (:290-299), best bookkeeping (:318-320), and the seed of the adversarial backward pass

@@ -171,6 +171,10 @@ _SIGNATURES = {
     'spaa_adaptive_avgpool_bwd': [_p, _p, _p] + [_i] * 6 + [_p],
     'spaa_avgpool_fwd': [_p, _p, _i, _i, _i, _p],
     'spaa_avgpool_bwd': [_p, _p, _p, _i, _i, _i, _p],
+    'spaa_dwconv3_fwd': [_p, _i, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p],
+    'spaa_dwconv3_bwd': [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p],
+    'spaa_relu6_gate': [_p, _p, _l, _i, _p],
+    'spaa_global_avgpool_bwd_bits': [_p, _p, _p, _i, _i, _i, _p],
     'spaa_decide': [_p, _i, _p, _i, _p, _i, _i, _p, _f, _f, _f, _f, _f, _f, _p, _p, _p, _i, _p],
     'spaa_decide_ps': [_p, _i, _p, _p, _i, _i, _p, _p, _p, _f, _f, _p, _p, _p, _i, _p],
     'spaa_select_grad': [_p, _p, _p, _p, _p, _i, _i, _p],

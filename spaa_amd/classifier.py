@@ -32,7 +32,7 @@ BODY_GATE_MASKS = os.environ.get('SPAA_BODY_MASKS', '1') != '0'   # 0: VGG-16 / 
 
 IMAGENET_MEAN = (0.485, 0.456, 0.406)
 IMAGENET_STD = (0.229, 0.224, 0.225)
-INPUT_SZ = {'resnet18': (224, 224), 'vgg16': (224, 224), 'inception_v3': (299, 299)}
+INPUT_SZ = {'resnet18': (224, 224), 'vgg16': (224, 224), 'inception_v3': (299, 299), 'mobilenet_v2': (224, 224)}
 
 
 @dataclasses.dataclass(frozen=True)
@@ -63,8 +63,8 @@ def _strip(sd):
 
 
 class ClassifierBody:
-    """What the three bodies share: the storage mode and its allocators, the layer-size and BatchNorm-folding helpers, the ReLU-gate
-    switches, the global-average-pool + `fc` head of ResNet-18 and Inception-v3, and flops_fwd() over `fwd_plans()`.
+    """What the bodies share: the storage mode and its allocators, the layer-size and BatchNorm-folding helpers, the ReLU-gate
+    switches, the global-average-pool + linear head of ResNet-18, Inception-v3 and MobileNetV2, and flops_fwd() over `fwd_plans()`.
     A body provides forward(x4) -> logits [B, ncls], backward(g_logits) -> gradient w.r.t. x4, refresh_masks(), fwd_plans() and
     attention_source()."""
     body_masks_switch = True   # SPAA_BODY_MASKS=0 applies (VGG-16, Inception-v3: the A/B switch never covered ResNet-18)
@@ -98,13 +98,13 @@ class ClassifierBody:
         sd = self.sd
         return cp.fold_bn(sd[conv + '.weight'], sd[bn + '.weight'], sd[bn + '.bias'], sd[bn + '.running_mean'], sd[bn + '.running_var'], eps=eps)
 
-    def build_head(self, c):
-        """adaptive_avg_pool2d(1) over `c` channels + `fc` (ResNet-18, Inception-v3)."""
+    def build_head(self, c, key='fc'):
+        """adaptive_avg_pool2d(1) over `c` channels + the linear layer `key` (ResNet-18, Inception-v3: 'fc'; MobileNetV2: 'classifier.1')."""
         sd, B = self.sd, self.B
-        self.ncls = sd['fc.weight'].shape[0]
+        self.ncls = sd[key + '.weight'].shape[0]
         self.pooled, self.g_pooled = self.zf(B, 1, 1, c), self.zf(B, 1, 1, c)
-        self.fc_f = cp.linear_fwd_plan(sd['fc.weight'], sd['fc.bias'], self.dev, 'fc')
-        self.fc_d = cp.linear_dgrad_plan(sd['fc.weight'], self.dev, 'fc_dgrad')
+        self.fc_f = cp.linear_fwd_plan(sd[key + '.weight'], sd[key + '.bias'], self.dev, 'fc')
+        self.fc_d = cp.linear_dgrad_plan(sd[key + '.weight'], self.dev, 'fc_dgrad')
         self.logits = self.zf(B, 1, 1, self.ncls)
 
     def head_fwd(self, last):
@@ -400,7 +400,13 @@ def _inception_body(sd, batch, in_hw, dev, storage='f32'):
     return InceptionV3Body(sd, batch, in_hw, dev, storage)
 
 
-BODIES = {'resnet18': ResNet18Body, 'vgg16': VGG16Body, 'inception_v3': _inception_body}
+def _mobilenet_body(sd, batch, in_hw, dev, storage='f32'):
+    from .mobilenet import MobileNetV2Body
+    return MobileNetV2Body(sd, batch, in_hw, dev, storage)
+
+
+BODIES = {'resnet18': ResNet18Body, 'vgg16': VGG16Body, 'inception_v3': _inception_body, 'mobilenet_v2': _mobilenet_body}
+LAST_LINEAR = {'vgg16': 'classifier.6', 'mobilenet_v2': 'classifier.1'}   # the last linear layer's key where it is not 'fc'
 
 
 class ClassifierEngine:
@@ -568,7 +574,7 @@ class Classifier(object):
     @property
     def num_classes(self):
         """Rows of the last linear layer (what an engine reports as `ncls`), read from the weights: no engine is built."""
-        return int(self.state_dict['classifier.6.weight' if self.name == 'vgg16' else 'fc.weight'].shape[0])
+        return int(self.state_dict[LAST_LINEAR.get(self.name, 'fc') + '.weight'].shape[0])
 
     def engine(self, batch, im_hw, crop_sz, owner=None, storage='f32'):
         """Cached engine for a batch size / geometry; an engine leased to an `owner` (attack state) is not handed to

@@ -262,6 +262,49 @@ def inception_v3_state_dict(seed=4, num_classes=1000, logit_gain=1.0):
     return sd
 
 
+def mobilenet_v2_state_dict(seed=6, num_classes=1000, logit_gain=1.0):
+    """Random-init MobileNetV2 (torchvision key names, width 1.0; the `num_batches_tracked` counters omitted as for the other bodies).
+    The BatchNorm in front of every ReLU6 has weight 0.8 U(0.5, 1.5) (the stem's: 4 U(0.5, 1.5), its input is the normalised image)
+    and bias U(-1.5, 1.5) + 3, so that both branches of the clamp (<= 0 and >= 6) are common at each of the 35 sites -- more than
+    10 % of the units each on random images -- while the network stays well conditioned: with weights 3 U(0.5, 1.5) at every site each
+    layer amplifies a perturbation ~3.5 times, 52 layers deep, and torch's own fp32 and float64 forward passes then differ by 30 % in
+    the logits (input gradients ~5e8); with these they differ by ~1e-6.  The projections' BatchNorms (no activation follows) have
+    unit scale."""
+    rng = np.random.default_rng(seed)
+    sd = {}
+
+    def conv(name, cout, cin_per_group, k):
+        sd[name + '.weight'] = _t(rng.standard_normal((cout, cin_per_group, k, k)) * math.sqrt(2.0 / (cin_per_group * k * k)))
+
+    def bn(prefix, c, relu6, scale=0.8):
+        sd[prefix + '.weight'] = _t(rng.uniform(0.5, 1.5, (c,)) * scale) if relu6 else _t(np.ones(c))
+        sd[prefix + '.bias'] = _t(rng.uniform(-1.5, 1.5, (c,)) + 3.0) if relu6 else _t(rng.uniform(-0.2, 0.2, (c,)))
+        sd[prefix + '.running_mean'] = _t(rng.uniform(-0.2, 0.2, (c,)))
+        sd[prefix + '.running_var'] = _t(rng.uniform(0.5, 1.5, (c,)))
+
+    conv('features.0.0', 32, 3, 3)
+    bn('features.0.1', 32, True, scale=4.0)
+    cin, idx = 32, 1
+    for t, c, n, s in ((1, 16, 1, 1), (6, 24, 2, 2), (6, 32, 3, 2), (6, 64, 4, 2), (6, 96, 3, 1), (6, 160, 3, 2), (6, 320, 1, 1)):
+        for _ in range(n):
+            p, hid, j = f'features.{idx}.conv', cin * t, 0
+            if t != 1:
+                conv(f'{p}.0.0', hid, cin, 1)
+                bn(f'{p}.0.1', hid, True)
+                j = 1
+            conv(f'{p}.{j}.0', hid, 1, 3)          # depthwise: groups = hid
+            bn(f'{p}.{j}.1', hid, True)
+            conv(f'{p}.{j + 1}', c, hid, 1)
+            bn(f'{p}.{j + 2}', c, False)
+            cin, idx = c, idx + 1
+    conv('features.18.0', 1280, cin, 1)
+    bn('features.18.1', 1280, True)
+    bound = 1.0 / math.sqrt(1280)
+    sd['classifier.1.weight'] = _t(rng.uniform(-bound, bound, (num_classes, 1280)) * logit_gain)
+    sd['classifier.1.bias'] = _t(rng.uniform(-bound, bound, (num_classes,)) * logit_gain)
+    return sd
+
+
 def scenes(seed=1, n=1, sz=(256, 256), box=8, lo=0.05, hi=0.95):
     """`n` smooth random camera scenes in [lo,hi]: U[0,1) low-pass filtered by a box x box mean."""
     rng = np.random.default_rng(seed)
