@@ -739,6 +739,34 @@ int spaa_jitter_fwd(const float* y, const float* jit, const uint32_t* key, int J
  * without atomics: run-to-run bitwise reproducible.  The pad channel of g_y is 0.  One launch. */
 int spaa_jitter_bwd(const float* const* g_out, const float* jit, const uint8_t* const* gate, int J, float* const* g_y, int B, int H,
                     int W, spaa_stream_t stream);
+/* spaa_jitter_fwd with an input image of its own per draw: out[j] and gate[j] from y[j] (J device pointers in a host array), by the
+ * same arithmetic; with J equal pointers the results are spaa_jitter_fwd's bit for bit.  One launch. */
+int spaa_jitter_fwd_each(const float* const* y, const float* jit, const uint32_t* key, int J, int quantize, float* const* out,
+                         uint8_t* const* gate, int B, int H, int W, spaa_stream_t stream);
+
+/* ---- pose-robust SPAA: one projection against J randomly warped copies of the camera image, 2 <= J <= SPAA_JITTER_MAX
+ * Conventions of the capture jitter above: host arrays of J device pointers, any other J / a null pointer / a size < 1 is
+ * hipErrorInvalidValue with nothing launched, images [B][H*W][4] fp32, no allocation, no sync, no atomics.
+ *
+ * A table row h[b][j][0..7] is the homography [[h0, h1, h2], [h3, h4, h5], [h6, h7, 1]] in centred pixel coordinates: output pixel
+ * (row, col) has u = col + 0.5 - W/2, v = row + 0.5 - H/2 and reads the source position, evaluated in fp32 in this order,
+ *   w = fmaf(h6, u, fmaf(h7, v, 1)),  xs = fmaf(h0, u, fmaf(h1, v, h2)) / w + (W/2 - 0.5),  ys = fmaf(h3, u, fmaf(h4, v, h5)) / w + (H/2 - 0.5).
+ *
+ * spaa_pose_draw: the rows of iteration t = counter[0] (device memory; t + 1 is stored after every thread of the one workgroup has
+ * read it): h = (s cos a, -s sin a, tx, s sin a, s cos a, ty, px / R, py / R), R = max(H, W) / 2, a = rotate (2u0 - 1) pi / 180,
+ * s = 1 + zoom (2u1 - 1), tx, ty = shift (2u2 - 1), shift (2u3 - 1), px, py = tilt (2u4 - 1), tilt (2u5 - 1); the u_i are
+ * spaa_jitter_draw's uniforms of (seed, t, b, j, i) with the first constant 0x85ebca6b in place of 0x9e3779b9.  clean0 != 0: draw 0
+ * of every sample is the identity row (1, 0, 0, 0, 1, 0, 0, 0).  table: [B][J][8]. */
+int spaa_pose_draw(uint32_t seed, int32_t* counter, float rotate, float zoom, float shift, float tilt, int clean0, float* table, int B,
+                   int J, int H, int W, spaa_stream_t stream);
+/* out[j] = the bilinear sample of y at (xs, ys), taps outside the image contributing 0 (torch's grid_sample, bilinear, zeros,
+ * align_corners = False); the pad channel of out is 0.  The identity row copies the colour channels of y bit for bit.  One launch. */
+int spaa_pose_fwd(const float* y, const float* table, int J, float* const* out, int B, int H, int W, spaa_stream_t stream);
+/* The exact adjoint as a gather: input pixel p sums g_out[j][m] w_m(p) over the output pixels m within 2 of round(H^-1 p) (a 5 x 5
+ * window, in row-major order), w_m(p) the forward's own weight of tap p at m recomputed by the identical fp32 expression.  The
+ * window holds every contribution while the row stays within 10 degrees, zoom 0.15 and tilt 0.1 (what spaa_pose_draw is given by
+ * PoseJitter); beyond them contributions are lost.  Run-to-run bitwise reproducible; the pad channel of g_y is 0.  One launch. */
+int spaa_pose_bwd(const float* const* g_out, const float* table, int J, float* const* g_y, int B, int H, int W, spaa_stream_t stream);
 
 /* ---- attention-weighted attack: Grad-CAM of the classifier weights its gradient image ---------------------------
  * No atomics and fixed summation orders: bitwise repeatable.  One launch each, none syncs. */

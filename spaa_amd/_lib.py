@@ -192,6 +192,10 @@ _SIGNATURES = {
     'spaa_jitter_draw': [C.c_uint32, _p, _f, _f, _f, _f, _i, _p, _p, _i, _i, _p],
     'spaa_jitter_fwd': [_p, _p, _p, _i, _i, _pp, _pp, _i, _i, _i, _p],
     'spaa_jitter_bwd': [_pp, _p, _pp, _i, _pp, _i, _i, _i, _p],
+    'spaa_jitter_fwd_each': [_pp, _p, _p, _i, _i, _pp, _pp, _i, _i, _i, _p],
+    'spaa_pose_draw': [C.c_uint32, _p, _f, _f, _f, _f, _i, _p, _i, _i, _i, _i, _p],
+    'spaa_pose_fwd': [_p, _p, _i, _pp, _i, _i, _i, _p],
+    'spaa_pose_bwd': [_pp, _p, _i, _pp, _i, _i, _i, _p],
     'spaa_cam_alpha': [_p, _p, _i, _i, _i, _i, _p],
     'spaa_cam_map': [_p, _p, _f, _p, _i, _p, _p, _p, _i, _i, _i, _p],
     'spaa_attention_apply': [_p, _p, _f, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p],

@@ -131,6 +131,68 @@ def capture_survival(ims, classifier, target_idx, targeted, crop_sz, jitter, *, 
     return (hits / int(draws)).numpy()
 
 
+def pose_survival(ims, classifier, target_idx, targeted, crop_sz, pose, *, draws=32, seed=0, jitter=None):
+    """The fraction of `draws` randomly warped captures of each camera image that still succeed: float [N], the arguments and the
+    success rule as in capture_survival.  The evaluation hook of a pose attack.  The captures are those of `pose` (a PoseJitter: its
+    ranges; its `draws` and `seed` belong to the attack) with the generator seeded by `seed`, none of them the unwarped one:
+    spaa_pose_draw + spaa_pose_fwd in rounds of four captures (round r is the generator's iteration r), on chunks of at most 64
+    images (an image's captures depend on its place in its chunk).  With `jitter` (a CaptureJitter: its ranges and `quantize`) every
+    warped capture is then jittered, none of them cleanly, by the jitter generator of the same `seed`."""
+    from .models import to_nhwc4
+    from .projector_based_attack import CaptureJitter, PoseJitter
+    if not isinstance(pose, PoseJitter):
+        raise TypeError(f'pose_survival: pose must be a spaa_amd.PoseJitter, got {type(pose).__name__}')
+    if jitter is not None and not isinstance(jitter, CaptureJitter):
+        raise TypeError(f'pose_survival: jitter must be a spaa_amd.CaptureJitter or None, got {type(jitter).__name__}')
+    n = ims.shape[0]
+    tgt = torch.as_tensor([int(t) for t in target_idx])
+    tg = torch.full((n,), bool(targeted)) if np.ndim(targeted) == 0 else torch.as_tensor([bool(t) for t in targeted])
+    if tuple(tgt.shape) != (n,) or tuple(tg.shape) != (n,) or int(draws) < 1:
+        raise ValueError(f'pose_survival: {n} images, {tgt.numel()} targets, {tg.numel()} targeted flags, {draws} draws')
+    dev = classifier.device
+    if dev.type != 'cuda':
+        raise RuntimeError(f'pose_survival runs on the GPU only (no CPU fallback); the classifier is on {dev}')
+    ps = PoseJitter(pose.rotate, pose.zoom, pose.shift, pose.tilt, SURVIVAL_ROUND, seed)
+    jt = None if jitter is None else CaptureJitter(jitter.gain, jitter.offset, jitter.shift, jitter.noise, jitter.quantize,
+                                                   SURVIVAL_ROUND, seed)
+    J, (H, W) = SURVIVAL_ROUND, ims.shape[-2:]
+    b = min(n, SURVIVAL_CHUNK)
+    hits = torch.zeros(n)
+    with _lib.on_device(dev):
+        eng = classifier.engine(b, (H, W), tuple(crop_sz))
+        table = torch.zeros(b, J, 8, device=dev)
+        outs = [torch.zeros(b, H, W, 4, device=dev) for _ in range(J)]
+        if jt is not None:
+            jit = torch.zeros(b, J, 8, device=dev)
+            key = torch.zeros(b, J, dtype=torch.int32, device=dev)
+            jouts = [torch.zeros(b, H, W, 4, device=dev) for _ in range(J)]
+            gates = [torch.zeros(b, H * W, dtype=torch.uint8, device=dev) for _ in range(J)]
+        for s in range(0, n, b):
+            part = ims[s:s + b].to(dev).float()
+            m = part.shape[0]
+            if m < b:   # (one engine geometry: the last chunk is padded)
+                part = torch.cat((part, part.new_zeros(b - m, *part.shape[1:])))
+            y4 = to_nhwc4(part.contiguous())
+            counter = torch.zeros(1, dtype=torch.int32, device=dev)
+            jcounter = torch.zeros(1, dtype=torch.int32, device=dev)
+            t_dev, tg_dev = tgt[s:s + m].to(dev), tg[s:s + m].to(dev)
+            count = torch.zeros(m, device=dev)
+            for done in range(0, int(draws), J):
+                ps.draw(counter, table, b, J, H, W, clean0=False)
+                _lib.call('spaa_pose_fwd', _lib.ptr(y4), _lib.ptr(table), J, _lib.ptr_array(outs), b, H, W)
+                seen = outs
+                if jt is not None:
+                    jt.draw(jcounter, jit, key, b, J, clean0=False)
+                    _lib.call('spaa_jitter_fwd_each', _lib.ptr_array(outs), _lib.ptr(jit), _lib.ptr(key), J, int(bool(jt.quantize)),
+                              _lib.ptr_array(jouts), _lib.ptr_array(gates), b, H, W)
+                    seen = jouts
+                for j in range(min(J, int(draws) - done)):
+                    top1 = eng.forward(seen[j], need_grad=False)[:m].argmax(dim=1)
+                    count += torch.where(tg_dev, top1 == t_dev, top1 != t_dev).float()
+            hits[s:s + m] = count.cpu()
+    return (hits / int(draws)).numpy()
+
+
 def transfer_success(cam, classifier, target_idx, targeted, crop_sz, p_thresh=0.9):
     """Which camera images `cam` [B,3,H,W] fool `classifier`, by the success rule of the attack's own decision (spaa_decide): bool [B];
     one class id per image in `target_idx` and `targeted` (one flag, or one per image): top-1 == target with p1 > `p_thresh`, else

@@ -4,6 +4,7 @@
 //
 //   spaa_jitter_draw   the per-(sample, draw) parameter rows and noise keys of iteration t = counter[0]; stores t + 1
 //   spaa_jitter_fwd    out_j = Q(clamp(gain_c S_j(y) + offset + sigma n, 0, 1)) for all J draws in one launch, and the clamp gate
+//   spaa_jitter_fwd_each  the same with an input image of its own per draw (behind the pose warp: DESIGN.md 7k)
 //   spaa_jitter_bwd    g_y_j = S_j^T(gain_c gate_c g_out_j) as a gather (no atomics: bitwise repeatable)
 //
 // The per-draw tensors arrive as HOST arrays of J device pointers and travel in a by-value kernel argument, as the ensemble's members do
@@ -96,10 +97,10 @@ __device__ __forceinline__ float normal_of(uint32_t a, uint32_t c) {
     return sqrtf(-2.f * logf(u1)) * cospif(2.f * u2);
 }
 
-// grid (ceil(HW / 256), J, B); one pixel of one draw per thread
-__global__ __launch_bounds__(256) void jitter_fwd_kernel(const float4* __restrict__ y, const float4* __restrict__ jit,
-                                                         const uint32_t* __restrict__ key, int quantize, const Draws<float> out,
-                                                         const Draws<uint8_t> gate, int H, int W) {
+// one pixel of one draw per thread: draw j of sample b from the image batch y (grid (ceil(HW / 256), J, B))
+__device__ __forceinline__ void jitter_fwd_pixel(const float4* __restrict__ y, const float4* __restrict__ jit,
+                                                 const uint32_t* __restrict__ key, int quantize, const Draws<float>& out,
+                                                 const Draws<uint8_t>& gate, int H, int W) {
     const int j = blockIdx.y, J = gridDim.y, b = blockIdx.z;
     const int HW = H * W;
     const int pix = blockIdx.x * 256 + threadIdx.x;
@@ -133,6 +134,20 @@ __global__ __launch_bounds__(256) void jitter_fwd_kernel(const float4* __restric
     }
     reinterpret_cast<float4*>(draw_ptr(out, j))[(size_t)b * HW + pix] = make_float4(o[0], o[1], o[2], 0.f);
     draw_ptr(gate, j)[(size_t)b * HW + pix] = (uint8_t)bits;
+}
+
+// every draw from the one image batch y
+__global__ __launch_bounds__(256) void jitter_fwd_kernel(const float4* __restrict__ y, const float4* __restrict__ jit,
+                                                         const uint32_t* __restrict__ key, int quantize, const Draws<float> out,
+                                                         const Draws<uint8_t> gate, int H, int W) {
+    jitter_fwd_pixel(y, jit, key, quantize, out, gate, H, W);
+}
+
+// draw j from its own image batch y[j]
+__global__ __launch_bounds__(256) void jitter_fwd_each_kernel(const Draws<const float> y, const float4* __restrict__ jit,
+                                                              const uint32_t* __restrict__ key, int quantize, const Draws<float> out,
+                                                              const Draws<uint8_t> gate, int H, int W) {
+    jitter_fwd_pixel(reinterpret_cast<const float4*>(draw_ptr(y, (int)blockIdx.y)), jit, key, quantize, out, gate, H, W);
 }
 
 // One axis of S^T as a gather: input index n receives from the output indices m in [lo, hi] those whose clamped taps land on n.
@@ -217,6 +232,19 @@ int spaa_jitter_fwd(const float* y, const float* jit, const uint32_t* key, int J
     if (!gather(o, out, J) || !gather(gt, gate, J) || !y || !jit || !key || !image_grid(B, J, H, W, grid)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(jitter_fwd_kernel, grid, dim3(256), 0, (hipStream_t)stream, (const float4*)y, (const float4*)jit, key, quantize,
                        o, gt, H, W);
+    return (int)hipGetLastError();
+}
+
+int spaa_jitter_fwd_each(const float* const* y, const float* jit, const uint32_t* key, int J, int quantize, float* const* out,
+                         uint8_t* const* gate, int B, int H, int W, spaa_stream_t stream) {
+    Draws<const float> in;
+    Draws<float> o;
+    Draws<uint8_t> gt;
+    dim3 grid;
+    if (!gather(in, y, J) || !gather(o, out, J) || !gather(gt, gate, J) || !jit || !key || !image_grid(B, J, H, W, grid))
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(jitter_fwd_each_kernel, grid, dim3(256), 0, (hipStream_t)stream, in, (const float4*)jit, key, quantize, o, gt, H,
+                       W);
     return (int)hipGetLastError();
 }
 

@@ -733,11 +733,136 @@ class JitterAttackState(EnsembleAttackState):
         return self.draw_grads
 
 
+POSE_MAX_ROTATE, POSE_MAX_ZOOM, POSE_MAX_TILT, POSE_MAX_SHIFT = 10.0, 0.15, 0.1, 32.0
+
+
+@dataclasses.dataclass(frozen=True)
+class PoseJitter:
+    """A small change of camera pose after the setup was captured (the camera bumped, re-mounted, zoomed a little), as ranges of a
+    random homography of the camera image: an in-plane rotation of +- `rotate` degrees, a scale of 1 +- `zoom`, a
+    translation of +- `shift` camera pixels per axis and a tilt of +- `tilt` per axis, the relative change of the projective
+    denominator from the image centre to the edge of the longer side.  What leaves the frame is not seen and what enters it is black.
+    `draws`: warped copies attacked at once per iteration (2..4; the first one is the unwarped capture), `seed`: of the counter-based
+    generator.  The defaults are a guess at "the camera was bumped", not a measurement.  `rotate` <= 10, `zoom` <= 0.15 and `tilt`
+    <= 0.1 are what bounds the window of the adjoint kernel (spaa_pose_bwd); `shift` <= 32."""
+    rotate: float = 2.0
+    zoom: float = 0.03
+    shift: float = 3.0
+    tilt: float = 0.02
+    draws: int = 3
+    seed: int = 0
+
+    def __post_init__(self):
+        if not 2 <= int(self.draws) <= JITTER_MAX:
+            raise ValueError(f'PoseJitter: draws must be 2..{JITTER_MAX}, got {self.draws}')
+        for name, most in (('rotate', POSE_MAX_ROTATE), ('zoom', POSE_MAX_ZOOM), ('shift', POSE_MAX_SHIFT), ('tilt', POSE_MAX_TILT)):
+            v = float(getattr(self, name))
+            if not v >= 0:
+                raise ValueError(f'PoseJitter: {name} must be >= 0, got {getattr(self, name)}')
+            if v > most:
+                raise ValueError(f'PoseJitter: {name} must be <= {most:g}, got {getattr(self, name)}')
+
+    def draw(self, counter, table, B, J, H, W, clean0):
+        """spaa_pose_draw of these ranges: fills table [B][J][8] for iteration counter[0] of an H x W image and advances the counter."""
+        _lib.call('spaa_pose_draw', int(self.seed) & 0xffffffff, _lib.ptr(counter), float(self.rotate), float(self.zoom),
+                  float(self.shift), float(self.tilt), int(bool(clean0)), _lib.ptr(table), B, J, H, W)
+
+
+def _pose_supported(pose, pcnet, classifier, storage, focus, attention, jitter, who):
+    """What a pose attack does not serve, said before anything is allocated or launched.  `pcnet` / `classifier`: as spaa() holds
+    them after its own checks; `jitter`: None or a checked CaptureJitter."""
+    if not isinstance(pose, PoseJitter):
+        raise TypeError(f'{who}: pose must be a spaa_amd.PoseJitter, got {type(pose).__name__}')
+    if isinstance(pcnet, list):
+        raise NotImplementedError(f'{who}: pose jitter against several views is not implemented; attack one view with pose')
+    if isinstance(classifier, list):
+        raise NotImplementedError(f'{who}: pose jitter against an ensemble of classifiers is not implemented; attack one classifier '
+                                  'with pose')
+    if not isinstance(classifier, Classifier):
+        raise TypeError(f'{who}: a pose attack needs a spaa_amd.Classifier, got {type(classifier).__name__} (a foreign callable can '
+                        'only be attacked without pose)')
+    if attention is not None:
+        raise NotImplementedError(f'{who}: attention together with pose jitter is not implemented (every draw would need a map of its '
+                                  'own, pulled back through the warp); use attention or pose')
+    if storage != 'f32':
+        raise NotImplementedError(f"{who}: storage={storage!r} is not implemented with pose (the draws' unit vectors need a loss scale "
+                                  "of their own); use storage='f32'")
+    if focus:
+        raise ValueError(f'{who}: focus=True has no meaning with pose (a sample must fool every draw of every iteration)')
+    if jitter is not None and int(jitter.draws) != int(pose.draws):
+        raise ValueError(f'{who}: pose and jitter are applied draw by draw and must name the same draws, got pose.draws = '
+                         f'{pose.draws} and jitter.draws = {jitter.draws}')
+
+
+class PoseAttackState(EnsembleAttackState):
+    """One batched attack against J = pose.draws randomly warped copies of the camera image per iteration:
+    EnsembleAttackState whose members are J leased engines of ONE classifier, member j looking at draw j of y = PCNet(x, s), as in
+    JitterAttackState.  Draw 0 is the unwarped capture (the identity row), so a sample counts as successful only when the unwarped
+    capture and every warped draw of that iteration are fooled; the stealth loss and `cam_best` stay the clean inference.  The
+    homographies come from spaa_pose_draw (a device-side counter: a replayed graph advances the sequence), the warp from
+    spaa_pose_fwd, and the members' gradient images are pulled back to y by spaa_pose_bwd before they are combined.  With `jitter`
+    (a CaptureJitter of the same `draws`) draw j is Jitter_j(Pose_j(y)): spaa_jitter_fwd_each behind the warp, spaa_jitter_bwd before
+    its adjoint.  `state`, `stats`, `ens_state`, `ens_stats` keep the ensemble's meaning with draws as members."""
+
+    def __init__(self, pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, device, pose, storage='f32', jitter=None,
+                 transfer=None):
+        pcnet, classifier = _unwrap(pcnet), _unwrap(classifier)
+        if jitter is not None:
+            _jitter_supported(jitter, pcnet, classifier, storage, False, 'PoseAttackState')
+        _pose_supported(pose, pcnet, classifier, storage, False, None, jitter, 'PoseAttackState')
+        self.pose, self.jitter, self.focus = pose, jitter, False
+        self.members = [classifier] * int(pose.draws)   # (EnsembleAttackState._build leases one engine per entry)
+        AttackState.__init__(self, pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, device, storage=storage,
+                             transfer=transfer)
+
+    def _build(self, pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, dev):
+        super()._build(pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, dev)
+        B, J = self.B, self.K
+        self.counter = torch.zeros(1, dtype=torch.int32, device=dev)        # the iteration number the next draw reads
+        self.table = torch.zeros(B, J, 8, device=dev)
+        self.pose_ims = [torch.zeros_like(self.g_adv) for _ in range(J)]
+        self.pose_grads = [torch.zeros_like(self.g_adv) for _ in range(J)]
+        if self.jitter is not None:
+            self.jitter_counter = torch.zeros(1, dtype=torch.int32, device=dev)
+            self.jit = torch.zeros(B, J, 8, device=dev)
+            self.key = torch.zeros(B, J, dtype=torch.int32, device=dev)     # (uint32 bit patterns)
+            self.draw_ims = [torch.zeros_like(self.g_adv) for _ in range(J)]
+            self.draw_gates = [torch.zeros(B, self.HWc, dtype=torch.uint8, device=dev) for _ in range(J)]
+            self.draw_grads = [torch.zeros_like(self.g_adv) for _ in range(J)]
+
+    def _member_logits(self, y):
+        jt, p, arr = self.jitter, _lib.ptr, _lib.ptr_array
+        Hc, Wc = self.eng.Hc, self.eng.Wc
+        self.pose.draw(self.counter, self.table, self.B, self.K, Hc, Wc, clean0=True)
+        _lib.call('spaa_pose_fwd', p(y), p(self.table), self.K, arr(self.pose_ims), self.B, Hc, Wc)
+        ims = self.pose_ims
+        if jt is not None:
+            jt.draw(self.jitter_counter, self.jit, self.key, self.B, self.K, clean0=True)
+            _lib.call('spaa_jitter_fwd_each', arr(ims), p(self.jit), p(self.key), self.K, int(bool(jt.quantize)), arr(self.draw_ims),
+                      arr(self.draw_gates), self.B, Hc, Wc)
+            ims = self.draw_ims
+        return [e.forward(im) for e, im in zip(self.clfs, ims)]                      # :266, once per draw
+
+    def _member_gradients(self):
+        p, arr = _lib.ptr, _lib.ptr_array
+        gs = super()._member_gradients()
+        if self.jitter is not None:
+            _lib.call('spaa_jitter_bwd', arr(gs), p(self.jit), arr(self.draw_gates), self.K, arr(self.draw_grads), self.B, self.eng.Hc,
+                      self.eng.Wc)
+            gs = self.draw_grads
+        _lib.call('spaa_pose_bwd', arr(gs), p(self.table), self.K, arr(self.pose_grads), self.B, self.eng.Hc, self.eng.Wc)
+        return self.pose_grads
+
+
 def _attack_state(pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, device, storage, focus, jitter=None,
-                  attention=None, transfer=None):
+                  attention=None, transfer=None, pose=None):
     """AttackState for one Classifier, EnsembleAttackState for a checked list of several, MultiViewAttackState for a checked list of
-    PCNets (with their list of scenes), JitterAttackState for one Classifier with a CaptureJitter (which takes no `attention`).
-    Each of them takes `transfer`."""
+    PCNets (with their list of scenes), JitterAttackState for one Classifier with a CaptureJitter (which takes no `attention`),
+    PoseAttackState for one Classifier with a PoseJitter (with or without a CaptureJitter; no `attention`).  Each of them takes
+    `transfer`."""
+    if pose is not None:
+        return PoseAttackState(pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, device, pose, storage=storage,
+                               jitter=jitter, transfer=transfer)
     if jitter is not None:
         return JitterAttackState(pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, device, jitter, storage=storage,
                                  transfer=transfer)
@@ -753,7 +878,7 @@ def _attack_state(pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_
 
 def spaa(pcnet, classifier, imagenet_labels, target_idx, targeted, cam_scene, d_thr, stealth_loss, device, setup_info,
          *, iters=50, adv_lr=2, col_lr=1, p_thresh=0.9, trace=None, verbose=False, storage='f32', focus=False, jitter=None,
-         attention=None, transfer=None):
+         attention=None, transfer=None, pose=None):
     """Stealthy Projector-based Adversarial Attack (SPAA Algorithm 1) — see module docstring.
 
     :param pcnet: spaa_amd.PCNet (optionally wrapped in DataParallel-like `.module`), or a list / tuple of 2..4 of them: the same projector
@@ -773,6 +898,10 @@ def spaa(pcnet, classifier, imagenet_labels, target_idx, targeted, cam_scene, d_
     :param transfer: a Transfer: the adversarial step follows the Gaussian-smoothed, momentum-accumulated gradient image at the projector
         instead of the raw one (fp32 storage, a spaa_amd.Classifier).  Combines with ensembles, views, `focus`, `jitter`
         and `attention`: it acts on the projector-side gradient after them.  None (default): the plain attack, launch for launch
+    :param pose: a PoseJitter: ONE projection against `pose.draws` randomly warped copies of the camera image per iteration (a small
+        random change of camera pose: rotation, zoom, translation, tilt), the first of them the unwarped one (PoseAttackState, DESIGN.md
+        7k; one PCNet, one Classifier, fp32 storage, no `focus`, no `attention`).  With `jitter` of the same `draws`, draw j is
+        Jitter_j(Pose_j(y)).  The trace entries are the ensemble's, with draws as members.  None (default): launch for launch as before
     :param imagenet_labels: dict idx -> name (only used when verbose)
     :param target_idx: list of B class ids (true label if untargeted)
     :param targeted: bool
@@ -798,6 +927,8 @@ def spaa(pcnet, classifier, imagenet_labels, target_idx, targeted, cam_scene, d_
         _views_supported(pcnet, classifier, storage, 'spaa')
     if jitter is not None:
         _jitter_supported(jitter, pcnet, classifier, storage, focus, 'spaa')
+    if pose is not None:
+        _pose_supported(pose, pcnet, classifier, storage, focus, attention, jitter, 'spaa')
     if attention is not None:
         _attention_supported(attention, classifier, storage, jitter, 'spaa')
     if transfer is not None:
@@ -808,7 +939,7 @@ def spaa(pcnet, classifier, imagenet_labels, target_idx, targeted, cam_scene, d_
         return _spaa_foreign_classifier(pcnet, classifier, imagenet_labels, target_idx, targeted, cam_scene, d_thr,
                                         stealth_loss, device, setup_info, iters, adv_lr, col_lr, p_thresh, trace)
     st = _attack_state(pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, device, storage, focus, jitter, attention,
-                       transfer)
+                       transfer, pose)
 
     def report(i):
         if i % 30 == 0 or i == iters - 1:
@@ -817,7 +948,8 @@ def spaa(pcnet, classifier, imagenet_labels, target_idx, targeted, cam_scene, d_
             if isinstance(st, MultiViewAttackState):   # (p = the least confident view's; y = how many views are fooled)
                 name = f'of {st.V} views fooled'
             elif isinstance(st, EnsembleAttackState):   # (p = the least confident member's / draw's; y = how many are fooled)
-                name = f'of {st.K} draws fooled' if isinstance(st, JitterAttackState) else f'of {st.K} members fooled'
+                draws = isinstance(st, (JitterAttackState, PoseAttackState))
+                name = f'of {st.K} draws fooled' if draws else f'of {st.K} members fooled'
             else:
                 name = imagenet_labels[int(s[v, 3])] if imagenet_labels else ''
             print(f'col_loss = {f[:, 3].mean():<9.4f} | prjl2 = {f[:, 4].mean() * 255:<9.4f} | caml2 = '
@@ -906,7 +1038,8 @@ def split_sweep(samples, ncfg, chunk_results):
 
 
 def spaa_sweep(pcnet, classifier, imagenet_labels, cam_scene, setup_info, device, configs, *, iters=50, adv_lr=2, col_lr=1,
-               p_thresh=0.9, max_batch=64, storage='f32', trace=None, focus=False, jitter=None, attention=None, transfer=None):
+               p_thresh=0.9, max_batch=64, storage='f32', trace=None, focus=False, jitter=None, attention=None, transfer=None,
+               pose=None):
     """Several SPAA attacks on one PCNet, scene and classifier as few batched attacks (the reference's driver makes one spaa() call
     per configuration: projector_based_attack.py:24-148).  `configs`: [(stealth_loss, d_thr, targeted, target_idx), ...]; returns one
     (cam_infer_best, prj_adv_best) per config, in order -- what spaa(pcnet, classifier, imagenet_labels, target_idx, targeted,
@@ -920,7 +1053,8 @@ def spaa_sweep(pcnet, classifier, imagenet_labels, cam_scene, setup_info, device
     per view, and the trace entries are (state, stats, view_state, view_stats).  `jitter`: a CaptureJitter, as in spaa(): every chunk
     is a jitter attack with that seed (the draws of a sample depend on its place in its chunk), the trace entries the ensemble's.
     `attention`: an Attention, as in spaa(): every chunk is an attention-weighted attack.  `transfer`: a Transfer, as in spaa(): every
-    chunk's adversarial steps follow the smoothed, momentum-accumulated direction (each chunk's momentum starts at zero)."""
+    chunk's adversarial steps follow the smoothed, momentum-accumulated direction (each chunk's momentum starts at zero).  `pose`: a
+    PoseJitter, as in spaa(): every chunk is a pose attack with that seed (the draws of a sample depend on its place in its chunk)."""
     samples, chunks = plan_sweep(configs, max_batch)
     pcnet, classifier = _unwrap(pcnet), _unwrap(classifier)
     if isinstance(pcnet, (list, tuple)):
@@ -935,6 +1069,8 @@ def spaa_sweep(pcnet, classifier, imagenet_labels, cam_scene, setup_info, device
         _views_supported(pcnet, classifier, storage, 'spaa_sweep')
     if jitter is not None:
         _jitter_supported(jitter, pcnet, classifier, storage, focus, 'spaa_sweep')
+    if pose is not None:
+        _pose_supported(pose, pcnet, classifier, storage, focus, attention, jitter, 'spaa_sweep')
     if attention is not None:
         _attention_supported(attention, classifier, storage, jitter, 'spaa_sweep')
     if transfer is not None:
@@ -955,7 +1091,7 @@ def spaa_sweep(pcnet, classifier, imagenet_labels, cam_scene, setup_info, device
     for a, b in chunks:
         part = samples[a:b]
         st = _attack_state(pcnet, classifier, [t for *_, t in part], sc, [s[1] for s in part], setup_info, device, storage, focus,
-                           jitter, attention, transfer)
+                           jitter, attention, transfer, pose)
         tr = [] if trace is not None else None
         _run(st, [s[3] for s in part], [s[2] for s in part], iters, adv_lr, col_lr, p_thresh, tr)
         if trace is not None:
@@ -1054,5 +1190,5 @@ from .attack_driver import (ATTACKERS, MODEL_TRAIN_CFG, AttackSetup, get_attacke
                             run_projector_based_attack, _run_one_pixel_de, project_capture_real_attack)
 from .attack_summary import (SUMMARY_STEALTH_LOSSES, SUMMARY_D_THRESHES, SUMMARY_CLASSIFIERS, SUMMARY_CHUNK,   # noqa: E402,F401
                              SUMMARY_COLUMNS, MONTAGE_CHUNK, attack_success, write_stats, _sorted_classes, _nonempty,
-                             attack_results, attack_transfer, capture_survival, transfer_success, summarize_single_attacker,
-                             summarize_all_attackers)
+                             attack_results, attack_transfer, capture_survival, pose_survival, transfer_success,
+                             summarize_single_attacker, summarize_all_attackers)
