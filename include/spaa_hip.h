@@ -615,6 +615,45 @@ int spaa_relu6_gate(float* act, uint8_t* mask_out, int64_t M, int C, spaa_stream
  * (spaa_avgpool_bwd gates on act > 0 only, which is wrong at 6). */
 int spaa_global_avgpool_bwd_bits(const float* g_feat, const uint8_t* mask, float* g_in, int B, int HW, int C, spaa_stream_t stream);
 
+/* ---- torchvision vit_b_16 (csrc/vit_ops.hip; spaa_amd/vit.py) ------------------------------------- */
+/* fp32 throughout, exact-fp32 VALU arithmetic, no atomics and a fixed accumulation order (two runs are bitwise equal), no allocation
+ * and no synchronisation.  Invalid arguments (a null pointer other than the optional `add`, a row length D or head width dh that is no
+ * multiple of 4, dh > 64, T > 256, a size < 1, a tensor of 2^29 elements or more) return hipErrorInvalidValue with nothing launched and
+ * nothing written.  Every pointer is 16-byte aligned and every row stride a multiple of 4 floats.
+ *
+ * spaa_vit_patchify: img [B, h, w, 4] -> patches [B n, 4 P P], n = (h / P)(w / P) tokens in row-major order of the patch grid, column
+ * (ky P + kx) 4 + c (h % P == w % P == 0): a P x P / stride P convolution becomes a 1 x 1 plan over K = 4 P P whose weight the host
+ * rearranges (zeros for c = 3).  spaa_vit_unpatchify: the adjoint, g_img[b, y, x] = g_patches[token, column]: one value per pixel.
+ * spaa_vit_assemble: x [B, T, D], T = n + 1 >= 2: row 0 = class_token [D] + pos[0], row 1 + i = emb [B, n, D] row i + pos [T, D] row
+ * 1 + i.  spaa_vit_assemble_bwd: g_emb[b, i] = g_x[b, 1 + i]. */
+int spaa_vit_patchify(const float* img, float* patches, int B, int h, int w, int P, spaa_stream_t stream);
+int spaa_vit_unpatchify(const float* g_patches, float* g_img, int B, int h, int w, int P, spaa_stream_t stream);
+int spaa_vit_assemble(const float* emb, const float* class_token, const float* pos, float* x, int B, int T, int D, spaa_stream_t stream);
+int spaa_vit_assemble_bwd(const float* g_x, float* g_emb, int B, int T, int D, spaa_stream_t stream);
+/* LayerNorm over `rows` rows of D floats, row r of a tensor at r * its stride (stride >= D floats: the head normalises only the
+ * class-token rows of [B, T, D] with stride T D).  Forward: mean first, then the biased variance as the mean of the centred squares;
+ * y = (x - mean) rstd gamma + beta, rstd = 1 / sqrt(var + eps); mean [rows] and rstd [rows] are written for the adjoint.
+ * Backward: gx = rstd (gh - mean(gh) - xh mean(gh xh)) (+ add where add != NULL: a residual gradient at no extra pass), gh = g gamma,
+ * xh = (x - mean) rstd.  gx may be `g` or `add` itself (a lane reads what it writes before it writes). */
+int spaa_layernorm_fwd(const float* x, int64_t x_stride, const float* gamma, const float* beta, float* y, int64_t y_stride, float* mean,
+                       float* rstd, int rows, int D, float eps, spaa_stream_t stream);
+int spaa_layernorm_bwd(const float* g, int64_t g_stride, const float* x, int64_t x_stride, const float* gamma, const float* mean,
+                       const float* rstd, const float* add, int64_t add_stride, float* gx, int64_t gx_stride, int rows, int D,
+                       spaa_stream_t stream);
+/* Exact GELU x Phi(x) over n floats (n % 4 == 0), Phi(x) = erfc(-x / sqrt 2) / 2; the adjoint is g (Phi(pre) + pre phi(pre)) with the
+ * PRE-activation the forward pass read (kept by the caller).  act may be pre, gx may be g (elementwise). */
+int spaa_gelu_fwd(const float* pre, float* act, int64_t n, spaa_stream_t stream);
+int spaa_gelu_bwd(const float* g, const float* pre, float* gx, int64_t n, spaa_stream_t stream);
+/* Multi-head softmax attention.  qkv [B, T, 3 D], D = heads dh: columns [0, D) the queries, [D, 2 D) the keys, [2 D, 3 D) the values,
+ * head h at columns h dh .. (h + 1) dh of each (torch.nn.MultiheadAttention's in_proj order).  ctx [B, T, D] (heads concatenated in
+ * order) = softmax_j(q_i . k_j / sqrt(dh)) v_j with the row maximum subtracted; lse [B, heads, T] = max + log(sum) is kept instead of
+ * the probabilities, which the adjoint recomputes as exp(s - lse).
+ * spaa_attn_bwd: g_qkv [B, T, 3 D] from g_ctx [B, T, D] in two launches: a query-parallel pass writes delta [B, heads, T] (a workspace
+ * of the caller's: delta_i = g_ctx_i . ctx_i) and g_q, a key-parallel pass g_k and g_v; every element of g_qkv is written. */
+int spaa_attn_fwd(const float* qkv, float* ctx, float* lse, int B, int T, int heads, int dh, spaa_stream_t stream);
+int spaa_attn_bwd(const float* qkv, const float* ctx, const float* lse, const float* g_ctx, float* g_qkv, float* delta, int B, int T,
+                  int heads, int dh, spaa_stream_t stream);
+
 /* ---- SPAA Algorithm 1 control on device (projector_based_attack.py:269-328) ------------------------------ */
 /* Per-sample decision, one workgroup per sample: softmax top-1 / argmax of logits (classifier.py:64-68), loss
  * reduction, masks (:290-299), best bookkeeping (:318-320), and the seed of the adversarial backward pass

@@ -175,6 +175,16 @@ _SIGNATURES = {
     'spaa_dwconv3_bwd': [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p],
     'spaa_relu6_gate': [_p, _p, _l, _i, _p],
     'spaa_global_avgpool_bwd_bits': [_p, _p, _p, _i, _i, _i, _p],
+    'spaa_vit_patchify': [_p, _p, _i, _i, _i, _i, _p],
+    'spaa_vit_unpatchify': [_p, _p, _i, _i, _i, _i, _p],
+    'spaa_vit_assemble': [_p, _p, _p, _p, _i, _i, _i, _p],
+    'spaa_vit_assemble_bwd': [_p, _p, _i, _i, _i, _p],
+    'spaa_layernorm_fwd': [_p, _l, _p, _p, _p, _l, _p, _p, _i, _i, _f, _p],
+    'spaa_layernorm_bwd': [_p, _l, _p, _l, _p, _p, _p, _p, _l, _p, _l, _i, _i, _p],
+    'spaa_gelu_fwd': [_p, _p, _l, _p],
+    'spaa_gelu_bwd': [_p, _p, _p, _l, _p],
+    'spaa_attn_fwd': [_p, _p, _p, _i, _i, _i, _i, _p],
+    'spaa_attn_bwd': [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p],
     'spaa_decide': [_p, _i, _p, _i, _p, _i, _i, _p, _f, _f, _f, _f, _f, _f, _p, _p, _p, _i, _p],
     'spaa_decide_ps': [_p, _i, _p, _p, _i, _i, _p, _p, _p, _f, _f, _p, _p, _p, _i, _p],
     'spaa_select_grad': [_p, _p, _p, _p, _p, _i, _i, _p],

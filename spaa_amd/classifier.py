@@ -32,7 +32,7 @@ BODY_GATE_MASKS = os.environ.get('SPAA_BODY_MASKS', '1') != '0'   # 0: VGG-16 / 
 
 IMAGENET_MEAN = (0.485, 0.456, 0.406)
 IMAGENET_STD = (0.229, 0.224, 0.225)
-INPUT_SZ = {'resnet18': (224, 224), 'vgg16': (224, 224), 'inception_v3': (299, 299), 'mobilenet_v2': (224, 224)}
+INPUT_SZ = {'resnet18': (224, 224), 'vgg16': (224, 224), 'inception_v3': (299, 299), 'mobilenet_v2': (224, 224), 'vit_b_16': (224, 224)}
 
 
 @dataclasses.dataclass(frozen=True)
@@ -405,8 +405,17 @@ def _mobilenet_body(sd, batch, in_hw, dev, storage='f32'):
     return MobileNetV2Body(sd, batch, in_hw, dev, storage)
 
 
-BODIES = {'resnet18': ResNet18Body, 'vgg16': VGG16Body, 'inception_v3': _inception_body, 'mobilenet_v2': _mobilenet_body}
-LAST_LINEAR = {'vgg16': 'classifier.6', 'mobilenet_v2': 'classifier.1'}   # the last linear layer's key where it is not 'fc'
+def _vit_body(sd, batch, in_hw, dev, storage='f32'):
+    from .vit import ViTB16Body
+    return ViTB16Body(sd, batch, in_hw, dev, storage)
+
+
+BODIES = {'resnet18': ResNet18Body, 'vgg16': VGG16Body, 'inception_v3': _inception_body, 'mobilenet_v2': _mobilenet_body,
+          'vit_b_16': _vit_body}
+LAST_LINEAR = {'vgg16': 'classifier.6', 'mobilenet_v2': 'classifier.1', 'vit_b_16': 'heads.head'}   # the last linear layer's key where it is not 'fc'
+
+
+NO_FEATURE_MAP = ('vit_b_16',)   # bodies without a convolutional feature map: Grad-CAM and attention= are refused for them
 
 
 class ClassifierEngine:
@@ -569,12 +578,23 @@ class Classifier(object):
         if not fix_params:
             raise NotImplementedError('spaa_amd classifiers are frozen (input gradients only)')
         self.state_dict = {k: v.detach().float().cpu() for k, v in _strip(state_dict).items()}
+        if model_name == 'vit_b_16':
+            # what the ViT body does not serve (input size against patch size and position embedding, width against the 12 heads): said
+            # here, on the CPU, before any engine is built
+            from . import vit
+            self.state_dict = vit.canonical(self.state_dict)
+            vit.check_geometry(self.state_dict, self.input_sz)
         self._engines = {}
 
     @property
     def num_classes(self):
         """Rows of the last linear layer (what an engine reports as `ncls`), read from the weights: no engine is built."""
         return int(self.state_dict[LAST_LINEAR.get(self.name, 'fc') + '.weight'].shape[0])
+
+    @property
+    def has_feature_map(self):
+        """Does the body end in a convolutional feature map that Grad-CAM can read?  (Every body but the vision transformer.)"""
+        return self.name not in NO_FEATURE_MAP
 
     def engine(self, batch, im_hw, crop_sz, owner=None, storage='f32'):
         """Cached engine for a batch size / geometry; an engine leased to an `owner` (attack state) is not handed to
@@ -616,6 +636,8 @@ class Classifier(object):
         """Where the classifier looks for `class_idx` (a list of B classes) in `im` [B, 3, H, W] on the GPU: the Grad-CAM map M of
         DESIGN.md 7h as float32 [B, 1, H, W] on the device, in [0, 1], 0 outside the classifier crop.  One forward pass and the
         head's part of the backward pass (the body's backward pass does not run)."""
+        if not self.has_feature_map:
+            raise NotImplementedError(f'grad_cam: Grad-CAM is not implemented for {self.name} (the body has no convolutional feature map)')
         if self.device.type != 'cuda':
             raise RuntimeError('spaa_amd.Classifier runs on the GPU only (no CPU fallback); got device=%s' % self.device)
         if im.dtype == torch.uint8:

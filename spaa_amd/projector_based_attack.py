@@ -624,6 +624,10 @@ def _attention_supported(attention, classifier, storage, jitter, who):
     if not isinstance(classifier, (Classifier, list)):
         raise TypeError(f'{who}: an attention-weighted attack needs a spaa_amd.Classifier, got {type(classifier).__name__} (a foreign '
                         'callable has no feature map to read)')
+    for c in classifier if isinstance(classifier, list) else [classifier]:
+        if isinstance(c, Classifier) and not c.has_feature_map:
+            raise NotImplementedError(f'{who}: attention is not implemented for {c.name} (Grad-CAM needs a convolutional feature map, which '
+                                      'this body does not have); attack it without attention=')
     _attention_checked(attention, storage, who)
 
 

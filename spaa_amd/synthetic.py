@@ -305,6 +305,48 @@ def mobilenet_v2_state_dict(seed=6, num_classes=1000, logit_gain=1.0):
     return sd
 
 
+def vit_b_16_state_dict(seed=7, num_classes=1000, logit_gain=1.0, dim=768, depth=12, mlp_dim=3072, patch=16, input_sz=(224, 224)):
+    """Random-init ViT (torchvision's vit_b_16 key names; the defaults are ViT-B/16 at 224 x 224, the keyword arguments shrink it for
+    tests: `dim` must be a multiple of 48, `input_sz` of `patch`).  LayerNorm weights U(0.5, 1.5) and biases U(-0.2, 0.2); linear
+    weights N(0, 1 / fan_in) with biases U(-0.2, 0.2), the q and k rows of in_proj_weight scaled by 1.5 so that the softmax is far from
+    uniform (mean row maximum 0.4 - 0.7); class_token and pos_embedding N(0, 0.25); conv_proj N(0, 1 / (3 P^2)); the head
+    U(+-1 / sqrt(dim)) x logit_gain.  Half the GELU inputs are negative and a third beyond |x| = 1, and torch's own fp32 pass stays
+    within 1e-6 of float64 in the logits (tests/test_vit_cpu.py re-establishes both)."""
+    rng = np.random.default_rng(seed)
+    h, w = input_sz
+    if dim % 48 or h % patch or w % patch:
+        raise ValueError(f'vit_b_16_state_dict: dim {dim} must be a multiple of 48 and input_sz {tuple(input_sz)} of the patch size {patch}')
+    T = (h // patch) * (w // patch) + 1
+    sd = {}
+
+    def linear(name, n, k, wkey='.weight', bkey='.bias'):
+        sd[name + wkey] = _t(rng.standard_normal((n, k)) / math.sqrt(k))
+        sd[name + bkey] = _t(rng.uniform(-0.2, 0.2, (n,)))
+
+    def ln(name):
+        sd[name + '.weight'] = _t(rng.uniform(0.5, 1.5, (dim,)))
+        sd[name + '.bias'] = _t(rng.uniform(-0.2, 0.2, (dim,)))
+
+    sd['conv_proj.weight'] = _t(rng.standard_normal((dim, 3, patch, patch)) / math.sqrt(3 * patch * patch))
+    sd['conv_proj.bias'] = _t(rng.uniform(-0.2, 0.2, (dim,)))
+    sd['class_token'] = _t(rng.standard_normal((1, 1, dim)) * 0.5)
+    sd['encoder.pos_embedding'] = _t(rng.standard_normal((1, T, dim)) * 0.5)
+    for i in range(depth):
+        p = f'encoder.layers.encoder_layer_{i}.'
+        ln(p + 'ln_1')
+        linear(p + 'self_attention.in_proj', 3 * dim, dim, '_weight', '_bias')
+        sd[p + 'self_attention.in_proj_weight'][:2 * dim] *= 1.5
+        linear(p + 'self_attention.out_proj', dim, dim)
+        ln(p + 'ln_2')
+        linear(p + 'mlp.0', mlp_dim, dim)
+        linear(p + 'mlp.3', dim, mlp_dim)
+    ln('encoder.ln')
+    bound = 1.0 / math.sqrt(dim)
+    sd['heads.head.weight'] = _t(rng.uniform(-bound, bound, (num_classes, dim)) * logit_gain)
+    sd['heads.head.bias'] = _t(rng.uniform(-bound, bound, (num_classes,)) * logit_gain)
+    return sd
+
+
 def scenes(seed=1, n=1, sz=(256, 256), box=8, lo=0.05, hi=0.95):
     """`n` smooth random camera scenes in [lo,hi]: U[0,1) low-pass filtered by a box x box mean."""
     rng = np.random.default_rng(seed)
