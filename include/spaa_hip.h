@@ -653,6 +653,22 @@ int spaa_gelu_bwd(const float* g, const float* pre, float* gx, int64_t n, spaa_s
 int spaa_attn_fwd(const float* qkv, float* ctx, float* lse, int B, int T, int heads, int dh, spaa_stream_t stream);
 int spaa_attn_bwd(const float* qkv, const float* ctx, const float* lse, const float* g_ctx, float* g_qkv, float* delta, int B, int T,
                   int heads, int dh, spaa_stream_t stream);
+/* Gradient-weighted attention rollout (Chefer, Gur and Wolf 2021): the class token's row rho [B, T] of
+ * R = (I + A_L) ... (I + A_1), A_l = mean over the heads of max(0, P_h * dP_h / seed), pushed down one layer per call while the backward
+ * pass visits that layer: P_h = exp(q k^T / sqrt(dh) - lse) and dP_h = g_ctx v^T are recomputed from what spaa_attn_bwd reads, and
+ * seed = g_logits[b][target[b]] (read on the device; g_logits [B, ncls], target int32 [B]) turns the loop's cotangent into the class
+ * logit's gradient.
+ * spaa_attn_relevance: rho_out[j] = rho_in[j] + (1 / heads) sum_h sum_i rho_in[i] max(0, P_h[i][j] dP_h[i][j] / seed), the same
+ * admissible shapes as the attention entry points.  rho_in == NULL stands for e_cls (the top layer; only query row 0 is read) and gives
+ * bitwise what an explicit e_cls gives; rho_out may be rho_in.  head_ws [B, heads, T] is a workspace of the caller's, written whole.
+ * Two launches; per head the queries are summed per lane in index order and then over the wave, the heads in index order, the mean
+ * is one division.  A sample whose seed is 0 or whose target is no class in [0, ncls) keeps rho_out = rho_in.
+ * spaa_relevance_map: c [B, T - 1] = max(0, rho[1:]) and cmax [B] = its maximum, both 0 for a sample without a seed: what spaa_cam_map
+ * leaves for spaa_attention_apply, with fh x fw the patch grid.  T >= 2. */
+int spaa_attn_relevance(const float* qkv, const float* lse, const float* g_ctx, const float* rho_in, const float* g_logits, int ncls,
+                        const int32_t* target, float* head_ws, float* rho_out, int B, int T, int heads, int dh, spaa_stream_t stream);
+int spaa_relevance_map(const float* rho, const float* g_logits, int ncls, const int32_t* target, float* c, float* cmax, int B, int T,
+                       spaa_stream_t stream);
 
 /* ---- SPAA Algorithm 1 control on device (projector_based_attack.py:269-328) ------------------------------ */
 /* Per-sample decision, one workgroup per sample: softmax top-1 / argmax of logits (classifier.py:64-68), loss

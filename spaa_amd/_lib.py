@@ -185,6 +185,8 @@ _SIGNATURES = {
     'spaa_gelu_bwd': [_p, _p, _p, _l, _p],
     'spaa_attn_fwd': [_p, _p, _p, _i, _i, _i, _i, _p],
     'spaa_attn_bwd': [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p],
+    'spaa_attn_relevance': [_p, _p, _p, _p, _p, _i, _p, _p, _p, _i, _i, _i, _i, _p],
+    'spaa_relevance_map': [_p, _p, _i, _p, _p, _p, _i, _i, _p],
     'spaa_decide': [_p, _i, _p, _i, _p, _i, _i, _p, _f, _f, _f, _f, _f, _f, _p, _p, _p, _i, _p],
     'spaa_decide_ps': [_p, _i, _p, _p, _i, _i, _p, _p, _p, _f, _f, _p, _p, _p, _i, _p],
     'spaa_select_grad': [_p, _p, _p, _p, _p, _i, _i, _p],

@@ -39,12 +39,17 @@ INPUT_SZ = {'resnet18': (224, 224), 'vgg16': (224, 224), 'inception_v3': (299, 2
 class Attention:
     """Attention-weighted attack: the classifier's gradient image at the camera is multiplied by floor + (1 - floor) M,
     M in [0, 1] the Grad-CAM map of the sample's class resampled onto the classifier crop.  `floor`: the weight where the classifier
-    does not look (0: the adversarial step puts nothing there; 1: the plain attack)."""
+    does not look (0: the adversarial step puts nothing there; 1: the plain attack).  `rollout`: a body without a
+    convolutional feature map (vit_b_16) takes the gradient-weighted attention rollout of its class token as M instead of being
+    refused; the convolutional bodies keep Grad-CAM either way."""
     floor: float = 0.0
+    rollout: bool = False
 
     def __post_init__(self):
         if isinstance(self.floor, bool) or not isinstance(self.floor, (int, float)) or not 0 <= float(self.floor) <= 1:
             raise ValueError(f'Attention: floor must be a number in [0, 1], got {self.floor!r}')
+        if not isinstance(self.rollout, bool):
+            raise ValueError(f'Attention: rollout must be a bool, got {self.rollout!r}')
 
 
 def center_crop_origin(h, w, size):
@@ -127,6 +132,11 @@ class ClassifierBody:
         that enters the head's average pool.  G: the ungated gradient there -- with `pooled`, as the head's g_pooled [B, 1, 1, C] (the
         gradient at every position is g_pooled / (h w)), else as the map [B, h, w, C] itself."""
         raise NotImplementedError
+
+    def relevance_grid(self):
+        """The (rows, columns) of the map that backward(g_logits, relevance=...) writes where the body has an attention rollout
+        (vit_b_16's patch grid); None for a body that hands Grad-CAM a feature map instead."""
+        return None
 
     def flops_fwd(self):
         return sum(plan.flops(self.B, h, w) for plan, (h, w) in self.fwd_plans())
@@ -416,6 +426,7 @@ LAST_LINEAR = {'vgg16': 'classifier.6', 'mobilenet_v2': 'classifier.1', 'vit_b_1
 
 
 NO_FEATURE_MAP = ('vit_b_16',)   # bodies without a convolutional feature map: Grad-CAM and attention= are refused for them
+ROLLOUT = ('vit_b_16',)          # ... of which these serve Attention(rollout=True) and Classifier.relevance with an attention rollout
 
 
 class ClassifierEngine:
@@ -460,16 +471,25 @@ class ClassifierEngine:
         self._grad_ready = self.body.write_masks = False
         return self.body.forward(self.pre)
 
-    def attention_buffers(self):
+    def attention_buffers(self, rollout=False):
         """Allocates what the Grad-CAM launches write (once; an attack state does it before its loop, so that a captured iteration
         allocates nothing): c [B, h w], its maximum [B], the channel means [B, C] where the body hands over a gradient map, and the
-        map M [B, H, W] in the camera frame that attention_map() renders."""
+        map M [B, H, W] in the camera frame that attention_map() renders.  `rollout` (Attention.rollout): a body with an attention
+        rollout (relevance_grid()) gets c over its patch grid and the body's own workspaces instead; without it such a
+        body is refused as before (its attention_source() raises)."""
         if self.storage != 'f32':
             raise NotImplementedError(f"ClassifierEngine: attention with storage={self.storage!r} is not implemented (the feature map and "
                                       "its gradient are read as fp32); use storage='f32'")
+        grid = self.body.relevance_grid()
+        if grid is not None and not rollout:
+            self.body.attention_source()
         if self._cam is None:
-            A, G, pooled = self.body.attention_source()
-            b, h, w, c = A.shape
+            if grid is not None:
+                b, (h, w), pooled = self.B, grid, True
+                self.body.relevance_buffers()
+            else:
+                A, G, pooled = self.body.attention_source()
+                b, h, w, c = A.shape
             self._cam = dict(c=torch.zeros(b, h * w, device=self.dev), max=torch.zeros(b, device=self.dev),
                              alpha=None if pooled else torch.zeros(b, c, device=self.dev),
                              M=torch.zeros(b, self.H, self.W, device=self.dev), hw=(h, w), valid=False)
@@ -509,13 +529,25 @@ class ClassifierEngine:
                   self.H, self.W, self.cy0, self.cx0, self.ch, self.cw, fh, fw)
 
     def attention_map(self):
-        """M of the last grad_cam() in the camera frame, [B, 1, H, W] (0 outside the classifier crop): a copy."""
-        self.attention_apply(0.0, None, self.attention_buffers()['M'])
-        return self._cam['M'].view(self.B, 1, self.H, self.W).clone()
+        """M of the last grad_cam() (or rollout) in the camera frame, [B, 1, H, W] (0 outside the classifier crop): a copy."""
+        cam = self._cam if self._cam is not None else self.attention_buffers()
+        self.attention_apply(0.0, None, cam['M'])
+        return cam['M'].view(self.B, 1, self.H, self.W).clone()
+
+    def _relevance_args(self, g_logits, target):
+        """What body.backward(..., relevance=) takes: (target, c, cmax) of the rollout buffers, after the checks grad_cam() makes."""
+        cam = self.attention_buffers(rollout=True)
+        _lib.check_dev(g_logits)
+        if target.dtype != torch.int32 or tuple(target.shape) != (self.B,) or tuple(g_logits.shape) != (self.B, self.ncls):
+            raise ValueError(f'ClassifierEngine.backward: target must be int32 [{self.B}] and g_logits [{self.B}, {self.ncls}] (got '
+                             f'{target.dtype} {tuple(target.shape)}, {tuple(g_logits.shape)})')
+        _lib._same_device(target)
+        return target, cam['c'], cam['max']
 
     def backward(self, g_logits, attention=None, target=None):
         """The gradient image at the camera frame.  `attention` (an Attention; with `target`, the samples' classes as int32 [B]): the
-        image is weighted by floor + (1 - floor) M, M the Grad-CAM map of this pass (attention_map() returns it)."""
+        image is weighted by floor + (1 - floor) M, M the Grad-CAM map of this pass (attention_map() returns it) -- for a body with an
+        attention rollout and `attention.rollout`, the rollout map that the body's backward pass writes on its way."""
         if attention is not None and not isinstance(attention, Attention):
             raise TypeError(f'ClassifierEngine.backward: attention must be a spaa_amd.Attention or None, got {type(attention).__name__}')
         if attention is not None and target is None:
@@ -524,11 +556,17 @@ class ClassifierEngine:
             # (a need_grad=False pass overwrote the activations but left the ReLU-gate masks / pool arg-max bytes of the pass before it)
             raise RuntimeError('ClassifierEngine.backward(): the last forward() ran with need_grad=False (its gate masks were not '
                                'written); run forward(..., need_grad=True) first')
-        g_pre = self.body.backward(g_logits)
+        rollout = attention is not None and attention.rollout and self.body.relevance_grid() is not None
+        if rollout:
+            g_pre = self.body.backward(g_logits, relevance=self._relevance_args(g_logits, target))
+            self._cam['valid'] = True
+        else:
+            g_pre = self.body.backward(g_logits)
         _lib.call('spaa_preproc_bwd', _lib.ptr(g_pre), _lib.ptr(self.g_y), self.B, self.H, self.W, self.cy0, self.cx0,
                   self.ch, self.cw, self.oh, self.ow, self._std)
         if attention is not None:
-            self.grad_cam(g_logits, target)
+            if not rollout:
+                self.grad_cam(g_logits, target)
             self.attention_apply(attention.floor, g_y=self.g_y)
         return self.g_y
 
@@ -596,6 +634,11 @@ class Classifier(object):
         """Does the body end in a convolutional feature map that Grad-CAM can read?  (Every body but the vision transformer.)"""
         return self.name not in NO_FEATURE_MAP
 
+    @property
+    def has_rollout(self):
+        """Does the body write an attention-rollout map in its backward pass?  (The vision transformer.)"""
+        return self.name in ROLLOUT
+
     def engine(self, batch, im_hw, crop_sz, owner=None, storage='f32'):
         """Cached engine for a batch size / geometry; an engine leased to an `owner` (attack state) is not handed to
         anyone else while the owner lives (see PCNet.engine).  `storage`: 'f32' or 'f16' (fp16 activations in HBM)."""
@@ -638,26 +681,55 @@ class Classifier(object):
         head's part of the backward pass (the body's backward pass does not run)."""
         if not self.has_feature_map:
             raise NotImplementedError(f'grad_cam: Grad-CAM is not implemented for {self.name} (the body has no convolutional feature map)')
+        im, classes = self._map_inputs('grad_cam', im, class_idx)
+        b, _, h, w = im.shape
+        with _lib.on_device(im.device):
+            eng = self.engine(b, (h, w), tuple(crop_sz))
+            eng.attention_buffers()
+            eng.forward(to_nhwc4(im.float().contiguous()), need_grad=False)
+            seed, target = self._one_hot(classes, eng.ncls, im.device)
+            eng.body.head_grad(seed)
+            eng.grad_cam(seed, target)
+            return eng.attention_map()
+
+    def _map_inputs(self, who, im, class_idx):
+        """The checks grad_cam() and relevance() share: (im as float [B, 3, H, W] on the device, the classes as ints)."""
         if self.device.type != 'cuda':
             raise RuntimeError('spaa_amd.Classifier runs on the GPU only (no CPU fallback); got device=%s' % self.device)
         if im.dtype == torch.uint8:
             im = im.type(torch.float32) / 255
         if im.ndim != 4 or im.shape[1] != 3:
-            raise ValueError(f'grad_cam: im must be [B, 3, H, W], got {tuple(im.shape)}')
+            raise ValueError(f'{who}: im must be [B, 3, H, W], got {tuple(im.shape)}')
         classes = [int(c) for c in class_idx]
-        b, _, h, w = im.shape
+        b = im.shape[0]
         if len(classes) != b or any(not 0 <= c < self.num_classes for c in classes):
-            raise ValueError(f'grad_cam: class_idx must hold {b} classes in [0, {self.num_classes}), got {classes}')
-        im = im.to(self.device)
+            raise ValueError(f'{who}: class_idx must hold {b} classes in [0, {self.num_classes}), got {classes}')
+        return im.to(self.device), classes
+
+    @staticmethod
+    def _one_hot(classes, ncls, dev):
+        """(seed [B, ncls] with 1 at each sample's class, target int32 [B]) on `dev`."""
+        target = torch.tensor(classes, dtype=torch.int32, device=dev)
+        seed = torch.zeros(len(classes), ncls, device=dev)
+        seed[torch.arange(len(classes), device=dev), target.long()] = 1.0
+        return seed, target
+
+    def relevance(self, im, class_idx, crop_sz=(240, 240)):
+        """Where the classifier looks for `class_idx`, whatever its body: float32 [B, 1, H, W] on the device, in [0, 1], 0 outside the
+        classifier crop.  For vit_b_16 the gradient-weighted attention rollout of the class token over the patch
+        grid, resampled onto the crop as Grad-CAM's map is: one forward and one backward pass of the body.  For a convolutional
+        body grad_cam()'s map."""
+        if not self.has_rollout:
+            return self.grad_cam(im, class_idx, crop_sz)
+        im, classes = self._map_inputs('relevance', im, class_idx)
+        b, _, h, w = im.shape
         with _lib.on_device(im.device):
             eng = self.engine(b, (h, w), tuple(crop_sz))
-            eng.attention_buffers()
-            eng.forward(to_nhwc4(im.float().contiguous()), need_grad=False)
-            target = torch.tensor(classes, dtype=torch.int32, device=im.device)
-            seed = torch.zeros(b, eng.ncls, device=im.device)
-            seed[torch.arange(b, device=im.device), target.long()] = 1.0
-            eng.body.head_grad(seed)
-            eng.grad_cam(seed, target)
+            eng.attention_buffers(rollout=True)
+            eng.forward(to_nhwc4(im.float().contiguous()))
+            seed, target = self._one_hot(classes, eng.ncls, im.device)
+            eng.body.backward(seed, relevance=eng._relevance_args(seed, target))
+            eng._cam['valid'] = True
             return eng.attention_map()
 
 

@@ -16,6 +16,9 @@
 // index for the scores (at most ATT_SLOTS = 4 per lane: T <= 256) and over dh for the weighted sums, the weights broadcast from the
 // lane that holds them by v_readlane.  The probabilities are never stored: the forward pass keeps lse = max + log(sum), both adjoint
 // passes recompute p = exp(s - lse).
+//
+// Relevance rollout: one layer's step of the class token's row, in the form of the key-parallel adjoint pass without its
+// weighted sums (Q and g_ctx staged, a wave owns key j, two dot products per query), then a small pass that adds the heads in index order.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -470,6 +473,118 @@ inline bool att_ok(int B, int T, int heads, int dh) {
            small((int64_t)B * T * 3 * heads * dh) && (int64_t)B * heads < 65536;
 }
 
+// ---- relevance rollout ----------------------------------------------------------------------------------------------
+// One layer's step of the class token's row of the gradient-weighted attention rollout, pushed down through the layer:
+//   rho_out[j] = rho_in[j] + (1 / heads) sum_h sum_i rho_in[i] max(0, P_h[i][j] dP_h[i][j] / seed)
+// with P_h[i][j] = exp(scale q_i . k_j - lse[h][i]) and dP_h[i][j] = g_ctx_i . v_j recomputed as in the key-parallel adjoint pass (Q
+// and g_ctx staged, a wave owns key j), and seed = g_logits[b][target[b]] the cotangent the backward pass was seeded with.  Two
+// launches: relevance_kernel writes the per-head sums w [B, heads, T], relevance_sum_kernel adds the heads in index order.
+struct RelArgs {
+    const float* qkv;       // [B, T, 3 D]
+    const float* lse;       // [B, heads, T]
+    const float* g_ctx;     // [B, T, D]
+    const float* rho_in;    // [B, T], or NULL: e_cls (only query row 0 is staged and read)
+    const float* g_logits;  // [B, ncls]
+    const int32_t* target;  // [B]
+    float* w;               // [B, heads, T]
+    int T, heads, dh, D, ncls;
+    float scale;
+};
+
+// the seed of sample b: 0 where the target is no class
+__device__ __forceinline__ float seed_of(const float* __restrict__ g_logits, const int32_t* __restrict__ target, const int ncls, const int b) {
+    const int t = target[b];
+    return (unsigned)t < (unsigned)ncls ? g_logits[(int64_t)b * ncls + t] : 0.f;
+}
+
+// TCAP bounds the QUERY rows staged: T, or 1 where rho_in == NULL
+template <int TCAP>
+__global__ __launch_bounds__(ATT_WAVES * 64) void relevance_kernel(const RelArgs a) {
+    __shared__ __attribute__((aligned(16))) float As[TCAP * (ATT_MAXDH + ATT_PAD)];
+    __shared__ __attribute__((aligned(16))) float Bs[TCAP * (ATT_MAXDH + ATT_PAD)];
+    __shared__ __attribute__((aligned(16))) float av[ATT_WAVES][ATT_MAXDH];
+    __shared__ __attribute__((aligned(16))) float bv[ATT_WAVES][ATT_MAXDH];
+    const int bh = blockIdx.y, b = bh / a.heads, h = bh - b * a.heads;
+    const int T = a.T, dh = a.dh, D = a.D, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int Tq = a.rho_in != nullptr ? T : 1;
+    const int64_t ld = 3 * (int64_t)D;
+    const float* base = a.qkv + (int64_t)b * T * ld + h * dh;
+    const float* gc = a.g_ctx + (int64_t)b * T * D + h * dh;
+    const float* lse = a.lse + (int64_t)bh * T;
+    float* w = a.w + (int64_t)bh * T;
+    const int i0 = blockIdx.x * ATT_ROWS, i1 = min(T, i0 + ATT_ROWS);
+    const float seed = seed_of(a.g_logits, a.target, a.ncls, b);
+    if (seed == 0.f) {   // (workgroup-uniform) no class to explain: the step is the identity
+        for (int i = i0 + threadIdx.x; i < i1; i += ATT_WAVES * 64) w[i] = 0.f;
+        return;
+    }
+    const float inv = 1.f / seed;
+    stage(As, base, ld, Tq, dh);
+    stage(Bs, gc, D, Tq, dh);
+    __syncthreads();
+    float rho[ATT_SLOTS], l[ATT_SLOTS];
+#pragma unroll
+    for (int e = 0; e < ATT_SLOTS; ++e) {
+        const int r = lane + 64 * e;
+        rho[e] = r < Tq ? (a.rho_in != nullptr ? a.rho_in[(int64_t)b * T + r] : 1.f) : 0.f;
+        l[e] = r < Tq ? lse[r] : 0.f;
+    }
+    for (int i = i0 + wave; i < i1; i += ATT_WAVES) {   // (wave-uniform: no workgroup barrier below)
+        if (lane < dh) {
+            av[wave][lane] = base[(int64_t)i * ld + D + lane];
+            bv[wave][lane] = base[(int64_t)i * ld + 2 * D + lane];
+        }
+        __builtin_amdgcn_wave_barrier();
+        float s[ATT_SLOTS], t[ATT_SLOTS];
+        row_dots<true>(As, Bs, av[wave], bv[wave], Tq, dh, lane, s, t);
+        float acc = 0.f;
+#pragma unroll
+        for (int e = 0; e < ATT_SLOTS; ++e) {
+            if (lane + 64 * e < Tq) {
+                const float x = expf(s[e] * a.scale - l[e]) * t[e] * inv;
+                acc = fmaf(rho[e], x > 0.f ? x : 0.f, acc);
+            }
+        }
+        acc = wave_sum(acc);
+        if (lane == 0) w[i] = acc;
+        __builtin_amdgcn_wave_barrier();
+    }
+}
+
+// rho_out[b][j] = rho_in[b][j] (NULL: e_cls) + (sum_h w[b][h][j]) / heads, the heads in index order
+__global__ __launch_bounds__(256) void relevance_sum_kernel(const float* __restrict__ w, const float* rho_in, float* rho_out, const int T,
+                                                            const int heads, const int total) {
+    const int idx = blockIdx.x * 256 + threadIdx.x;   // (b, j)
+    if (idx >= total) return;
+    const int b = idx / T, j = idx - b * T;
+    const float* wb = w + (int64_t)b * heads * T + j;
+    float acc = 0.f;
+    for (int h = 0; h < heads; ++h) acc += wb[(int64_t)h * T];
+    const float r = rho_in != nullptr ? rho_in[idx] : (j == 0 ? 1.f : 0.f);
+    rho_out[idx] = r + acc / (float)heads;
+}
+
+// c[b][i] = max(0, rho[b][1 + i]) and cmax[b] = max_i c[b][i] (both 0 where the seed is 0), as spaa_cam_map leaves them.  One
+// workgroup of four waves per sample.
+__global__ __launch_bounds__(256) void relevance_map_kernel(const float* __restrict__ rho, const float* __restrict__ g_logits, const int ncls,
+                                                            const int32_t* __restrict__ target, float* __restrict__ c,
+                                                            float* __restrict__ cmax, const int T) {
+    __shared__ float red[4];
+    const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const bool live = seed_of(g_logits, target, ncls, b) != 0.f;
+    float mx = 0.f;
+    for (int i = threadIdx.x; i < T - 1; i += 256) {
+        const float v = rho[(int64_t)b * T + 1 + i];
+        const float cv = live && v > 0.f ? v : 0.f;
+        c[(int64_t)b * (T - 1) + i] = cv;
+        mx = fmaxf(mx, cv);
+    }
+    mx = wave_max(mx);
+    if (lane == 0) red[wave] = mx;
+    __syncthreads();
+    if (threadIdx.x == 0) cmax[b] = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+}
+
 }  // namespace
 
 extern "C" {
@@ -565,6 +680,30 @@ int spaa_attn_bwd(const float* qkv, const float* ctx, const float* lse, const fl
     int rc = (int)hipGetLastError();
     if (rc) return rc;
     ATT_LAUNCH(ATT_BWD_K, a, B, stream);
+    return (int)hipGetLastError();
+}
+
+int spaa_attn_relevance(const float* qkv, const float* lse, const float* g_ctx, const float* rho_in, const float* g_logits, int ncls,
+                        const int32_t* target, float* head_ws, float* rho_out, int B, int T, int heads, int dh, spaa_stream_t stream) {
+    if (!qkv || !lse || !g_ctx || !g_logits || !target || !head_ws || !rho_out || ncls < 1 || !att_ok(B, T, heads, dh))
+        return hipErrorInvalidValue;
+    const RelArgs a{qkv, lse, g_ctx, rho_in, g_logits, target, head_ws, T, heads, dh, heads * dh, ncls, 1.f / sqrtf((float)dh)};
+    const dim3 grid((T + ATT_ROWS - 1) / ATT_ROWS, B * heads), block(ATT_WAVES * 64);
+    const int tq = rho_in ? T : 1;   // query rows staged
+    if (tq <= 64) hipLaunchKernelGGL((relevance_kernel<64>), grid, block, 0, (hipStream_t)stream, a);
+    else if (tq <= 128) hipLaunchKernelGGL((relevance_kernel<128>), grid, block, 0, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL((relevance_kernel<256>), grid, block, 0, (hipStream_t)stream, a);
+    const int rc = (int)hipGetLastError();
+    if (rc) return rc;
+    hipLaunchKernelGGL(relevance_sum_kernel, dim3(nb((int64_t)B * T)), dim3(256), 0, (hipStream_t)stream, head_ws, rho_in, rho_out, T, heads,
+                       B * T);
+    return (int)hipGetLastError();
+}
+
+int spaa_relevance_map(const float* rho, const float* g_logits, int ncls, const int32_t* target, float* c, float* cmax, int B, int T,
+                       spaa_stream_t stream) {
+    if (!rho || !g_logits || !target || !c || !cmax || ncls < 1 || B < 1 || T < 2 || !small((int64_t)B * T)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(relevance_map_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, rho, g_logits, ncls, target, c, cmax, T);
     return (int)hipGetLastError();
 }
 

@@ -102,7 +102,7 @@ class AttackState:
             raise ValueError(f'cam_scene is {tuple(cam_scene.shape[-2:])} but PCNet outputs {(Hc, Wc)}')
         self.clf = classifier.engine(B, (Hc, Wc), self.cp_sz, owner=self, storage=self.storage)
         if self.attention is not None:
-            self.clf.attention_buffers()
+            self.clf.attention_buffers(self.attention.rollout)
         # fp16 gradients need a loss scale (fp16's smallest normal is 6e-5; the per-pixel loss gradients are ~1/(B*H*W)).
         # Each sample's gradient is normalised before the step (:307, :315), so a positive per-branch scale changes
         # nothing but the fp16 rounding: stealth branch: 1/16 per pixel instead of 1/(B*H*W); adversarial branch: +-16
@@ -338,7 +338,7 @@ class EnsembleAttackState(AttackState):
                                   for c in self.members[1:]]
         if self.attention is not None:
             for e in self.clfs[1:]:
-                e.attention_buffers()
+                e.attention_buffers(self.attention.rollout)
         self.ens_g_logits = [self.g_logits] + [torch.zeros_like(self.g_logits) for _ in range(K - 1)]
         self.ens_state = torch.zeros(B, K, 2, dtype=torch.int32, device=dev)
         self.ens_stats = torch.zeros(B, K, 2, device=dev)
@@ -479,7 +479,7 @@ class MultiViewAttackState(AttackState):
             self.engs.append(eng)
             self.clfs.append(classifier.engine(B, (Hc, Wc), self.cp_sz, owner=self, storage=self.storage))
             if self.attention is not None:
-                self.clfs[-1].attention_buffers()
+                self.clfs[-1].attention_buffers(self.attention.rollout)
             self.scene4s.append(scene4)
             self.scene_labs.append(lab)
             self.g_cols.append(torch.zeros_like(self.g_col))
@@ -615,7 +615,8 @@ def _attention_checked(attention, storage, who):
 
 def _attention_supported(attention, classifier, storage, jitter, who):
     """What an attention-weighted attack does not serve, said before anything is allocated or launched.  `classifier`: as spaa() holds
-    it after its own checks (a Classifier, a checked list of several, or anything else)."""
+    it after its own checks (a Classifier, a checked list of several, or anything else).  A body without a feature map passes only
+    with attention.rollout, where it has an attention rollout to offer instead."""
     if not isinstance(attention, Attention):
         raise TypeError(f'{who}: attention must be a spaa_amd.Attention or None, got {type(attention).__name__}')
     if jitter is not None:
@@ -625,7 +626,7 @@ def _attention_supported(attention, classifier, storage, jitter, who):
         raise TypeError(f'{who}: an attention-weighted attack needs a spaa_amd.Classifier, got {type(classifier).__name__} (a foreign '
                         'callable has no feature map to read)')
     for c in classifier if isinstance(classifier, list) else [classifier]:
-        if isinstance(c, Classifier) and not c.has_feature_map:
+        if isinstance(c, Classifier) and not c.has_feature_map and not (attention.rollout and c.has_rollout):
             raise NotImplementedError(f'{who}: attention is not implemented for {c.name} (Grad-CAM needs a convolutional feature map, which '
                                       'this body does not have); attack it without attention=')
     _attention_checked(attention, storage, who)
@@ -898,7 +899,9 @@ def spaa(pcnet, classifier, imagenet_labels, target_idx, targeted, cam_scene, d_
         are the ensemble's, with draws as members.  None (default): the attack on the noiseless inferred capture
     :param attention: an Attention: the classifier's gradient image is weighted by floor + (1 - floor) M, M the Grad-CAM map of the
         sample's class on the classifier crop (fp32 storage, a spaa_amd.Classifier, no `jitter`).  In an ensemble every
-        member uses its own map, with several views every view its own.  None (default): the plain attack, launch for launch
+        member uses its own map, with several views every view its own.  vit_b_16 has no such map and is refused, unless
+        `attention.rollout` is set: then its M is the attention rollout of its class token, written in the backward
+        pass itself, and convolutional members keep Grad-CAM.  None (default): the plain attack, launch for launch
     :param transfer: a Transfer: the adversarial step follows the Gaussian-smoothed, momentum-accumulated gradient image at the projector
         instead of the raw one (fp32 storage, a spaa_amd.Classifier).  Combines with ensembles, views, `focus`, `jitter`
         and `attention`: it acts on the projector-side gradient after them.  None (default): the plain attack, launch for launch

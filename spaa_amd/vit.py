@@ -24,7 +24,9 @@ Saved per layer for the backward pass: the block input x, x_mid (after the atten
 lse and the MLP's pre-activation: (6 D + M) floats per token, 0.39 GB per layer and 4.6 GB in all at B = 64 with the real widths.
 The probabilities are not kept (119 MB per layer at B = 64): the attention adjoint recomputes them from lse.
 
-Grad-CAM has no meaning here (there is no convolutional feature map): attention_source() raises.  fp16 storage is not implemented.
+Grad-CAM has no meaning here (there is no convolutional feature map): attention_source() raises.  What the body offers instead is the
+gradient-weighted attention rollout of its class token (Chefer, Gur and Wolf 2021), written by backward(g_logits,
+relevance=...) on its way down the layers from what the attention adjoint reads anyway.  fp16 storage is not implemented.
 """
 import torch
 
@@ -145,6 +147,7 @@ class ViTB16Body(ClassifierBody):
         self.fc_d = cp.linear_dgrad_plan(sd['heads.head.weight'], dev, 'heads.head_dgrad')
         self.logits = zf(B, 1, 1, self.ncls)
         self.g_in = zf(B, h, w, 4)
+        self.rho = self.rho_heads = None   # the rollout's workspaces (relevance_buffers())
 
     # ---- the launches of csrc/vit_ops.hip ------------------------------------------------------------------------------------------
     def ln_fwd(self, x, wb, y, st, rows=None, x_stride=None):
@@ -183,10 +186,26 @@ class ViTB16Body(ClassifierBody):
         self.fc_d.run(g_logits.view(self.B, 1, 1, self.ncls), self.g_hn)
         return self.g_hn
 
-    def backward(self, g_logits):
-        """g_logits [B, ncls] -> gradient w.r.t. the normalised input [B, h, w, 4]."""
+    def relevance_grid(self):
+        return self.in_hw[0] // self.P, self.in_hw[1] // self.P
+
+    def relevance_buffers(self):
+        """The rollout's workspaces (allocated once, by the engine's attention_buffers() before an attack's loop): the two rho [B, T]
+        that the layers alternate between and the per-head sums [B, heads, T]."""
+        if self.rho is None:
+            self.rho, self.rho_heads = (self.zf(self.B, self.T), self.zf(self.B, self.T)), self.zf(self.B, HEADS, self.T)
+        return self.rho
+
+    def backward(self, g_logits, relevance=None):
+        """g_logits [B, ncls] -> gradient w.r.t. the normalised input [B, h, w, 4].  `relevance` = (target int32 [B], c [B, T - 1],
+        cmax [B]): the pass also writes the class token's attention-rollout map of each sample's class `target` into c
+        and its maximum into cmax -- one spaa_attn_relevance after each layer's attention adjoint, whose inputs it shares, and
+        spaa_relevance_map at the end.  g_logits must be zero but at the targets (the seed is divided out)."""
         p, B, T, D = _lib.ptr, self.B, self.T, self.D
         h, w = self.in_hw
+        if relevance is not None:
+            target, c, cmax = relevance
+            rho, rho_in = self.relevance_buffers(), None
         self.ln_bwd(self.head_grad(g_logits), self.layers[-1]['out'], self.ln, self.st_head, None, self.g_top, rows=B, wide=T * D)
         g = self.g_top
         for i in range(self.depth - 1, -1, -1):
@@ -197,9 +216,15 @@ class ViTB16Body(ClassifierBody):
             self.ln_bwd(self.g_n, ly['x_mid'], ly['ln2'], ly['st2'], g, self.g_mid)
             ly['out_d'].run(self.g_mid, self.g_ctx)
             _lib.call('spaa_attn_bwd', p(ly['qkv']), p(ly['ctx']), p(ly['lse']), p(self.g_ctx), p(self.g_qkv), p(self.delta), B, T, HEADS, self.dh)
+            if relevance is not None:
+                _lib.call('spaa_attn_relevance', p(ly['qkv']), p(ly['lse']), p(self.g_ctx), p(rho_in), p(g_logits), self.ncls, p(target),
+                          p(self.rho_heads), p(rho[i & 1]), B, T, HEADS, self.dh)
+                rho_in = rho[i & 1]
             ly['in_d'].run(self.g_qkv, self.g_n)
             self.ln_bwd(self.g_n, ly['x'], ly['ln1'], ly['st1'], self.g_mid, self.g_x[i & 1])
             g = self.g_x[i & 1]
+        if relevance is not None:
+            _lib.call('spaa_relevance_map', p(rho_in), p(g_logits), self.ncls, p(target), p(c), p(cmax), B, T)
         _lib.call('spaa_vit_assemble_bwd', p(g), p(self.g_emb), B, T, D)
         self.proj_d.run(self.g_emb, self.g_patches)
         _lib.call('spaa_vit_unpatchify', p(self.g_patches), p(self.g_in), B, h, w, self.P)
