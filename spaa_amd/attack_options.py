@@ -1,0 +1,305 @@
+"""What an attack can be asked for besides the plain SPAA loop -- the option values CaptureJitter, PoseJitter and Transfer (Attention is
+spaa_amd.classifier's), the limits of include/spaa_hip.h -- and the check of a request, made before anything is allocated or launched:
+`checked_request` for spaa() and spaa_sweep(), the `_supported` functions for the attack states that are built directly."""
+import dataclasses
+import math
+
+import torch
+
+from . import _lib
+from .models import PCNet
+from .classifier import Attention, Classifier
+
+ENS_MAX = VIEWS_MAX = JITTER_MAX = 4   # SPAA_ENS_MAX, SPAA_VIEWS_MAX, SPAA_JITTER_MAX of include/spaa_hip.h
+TRANSFER_RMAX = 7   # SPAA_TRANSFER_RMAX of include/spaa_hip.h
+POSE_MAX_ROTATE, POSE_MAX_ZOOM, POSE_MAX_TILT, POSE_MAX_SHIFT = 10.0, 0.15, 0.1, 32.0
+
+
+@dataclasses.dataclass(frozen=True)
+class CaptureJitter:
+    """What separates a real capture from the inferred one, as ranges of a random perturbation of the camera image (DESIGN.md,
+    "Capture-robust attack"): exposure / white balance `gain` (per channel, 1 +- gain) and `offset` (+- offset), a misregistration of
+    +- `shift` camera pixels per axis, sensor noise of standard deviation `noise`, the camera's 8-bit step (`quantize`).  `draws`:
+    captures attacked at once per iteration (2..4; the first one is the clean capture), `seed`: of the counter-based generator.
+    `shift` <= 2 and `noise` <= 0.1 are what the adjoint kernel's border loop and the tests' noise tolerance assume."""
+    gain: float = 0.1
+    offset: float = 0.03
+    shift: float = 0.75
+    noise: float = 0.01
+    quantize: bool = True
+    draws: int = 3
+    seed: int = 0
+
+    def __post_init__(self):
+        if not 2 <= int(self.draws) <= JITTER_MAX:
+            raise ValueError(f'CaptureJitter: draws must be 2..{JITTER_MAX}, got {self.draws}')
+        for name in ('gain', 'offset', 'shift', 'noise'):
+            if not float(getattr(self, name)) >= 0:
+                raise ValueError(f'CaptureJitter: {name} must be >= 0, got {getattr(self, name)}')
+        if self.gain >= 1:
+            raise ValueError(f'CaptureJitter: gain must be < 1 (a channel gain stays positive), got {self.gain}')
+        if self.shift > 2:
+            raise ValueError(f'CaptureJitter: shift must be <= 2 camera pixels, got {self.shift}')
+        if self.noise > 0.1:
+            raise ValueError(f'CaptureJitter: noise must be <= 0.1, got {self.noise}')
+
+    def draw(self, counter, jit, key, B, J, clean0):
+        """spaa_jitter_draw of these ranges: fills jit [B][J][8] / key [B][J] for iteration counter[0] and advances the counter."""
+        _lib.call('spaa_jitter_draw', int(self.seed) & 0xffffffff, _lib.ptr(counter), float(self.gain), float(self.offset),
+                  float(self.shift), float(self.noise), int(bool(clean0)), _lib.ptr(jit), _lib.ptr(key), B, J)
+
+
+@dataclasses.dataclass(frozen=True)
+class PoseJitter:
+    """A small change of camera pose after the setup was captured (the camera bumped, re-mounted, zoomed a little), as ranges of a
+    random homography of the camera image: an in-plane rotation of +- `rotate` degrees, a scale of 1 +- `zoom`, a
+    translation of +- `shift` camera pixels per axis and a tilt of +- `tilt` per axis, the relative change of the projective
+    denominator from the image centre to the edge of the longer side.  What leaves the frame is not seen and what enters it is black.
+    `draws`: warped copies attacked at once per iteration (2..4; the first one is the unwarped capture), `seed`: of the counter-based
+    generator.  The defaults are a guess at "the camera was bumped", not a measurement.  `rotate` <= 10, `zoom` <= 0.15 and `tilt`
+    <= 0.1 are what bounds the window of the adjoint kernel (spaa_pose_bwd); `shift` <= 32."""
+    rotate: float = 2.0
+    zoom: float = 0.03
+    shift: float = 3.0
+    tilt: float = 0.02
+    draws: int = 3
+    seed: int = 0
+
+    def __post_init__(self):
+        if not 2 <= int(self.draws) <= JITTER_MAX:
+            raise ValueError(f'PoseJitter: draws must be 2..{JITTER_MAX}, got {self.draws}')
+        for name, most in (('rotate', POSE_MAX_ROTATE), ('zoom', POSE_MAX_ZOOM), ('shift', POSE_MAX_SHIFT), ('tilt', POSE_MAX_TILT)):
+            v = float(getattr(self, name))
+            if not v >= 0:
+                raise ValueError(f'PoseJitter: {name} must be >= 0, got {getattr(self, name)}')
+            if v > most:
+                raise ValueError(f'PoseJitter: {name} must be <= {most:g}, got {getattr(self, name)}')
+
+    def draw(self, counter, table, B, J, H, W, clean0):
+        """spaa_pose_draw of these ranges: fills table [B][J][8] for iteration counter[0] of an H x W image and advances the counter."""
+        _lib.call('spaa_pose_draw', int(self.seed) & 0xffffffff, _lib.ptr(counter), float(self.rotate), float(self.zoom),
+                  float(self.shift), float(self.tilt), int(bool(clean0)), _lib.ptr(table), B, J, H, W)
+
+
+@dataclasses.dataclass(frozen=True)
+class Transfer:
+    """The transferable adversarial step: what a sample on the adversarial step follows is not the raw gradient image
+    at the projector but m <- `momentum` m + t / |t|_1 (MI-FGSM), t the gradient image convolved with a Gaussian of `sigma` projector
+    pixels (TI-FGSM; radius ceil(3 sigma) <= TRANSFER_RMAX, zero beyond the border).  momentum = 0: no accumulation; sigma = 0: no
+    smoothing; both 0 is the plain attack and refused."""
+    momentum: float = 1.0
+    sigma: float = 0.0
+
+    def __post_init__(self):
+        for name in ('momentum', 'sigma'):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v):
+                raise ValueError(f'Transfer: {name} must be a finite number, got {v!r}')
+        if not 0 <= self.momentum <= 1:
+            raise ValueError(f'Transfer: momentum must be in [0, 1], got {self.momentum}')
+        if self.sigma < 0:
+            raise ValueError(f'Transfer: sigma must be >= 0, got {self.sigma}')
+        if self.radius > TRANSFER_RMAX:
+            raise ValueError(f'Transfer: sigma = {self.sigma} needs the radius ceil(3 sigma) = {self.radius}, at most {TRANSFER_RMAX} '
+                             f'(sigma <= {TRANSFER_RMAX}/3)')
+        if self.momentum == 0 and self.sigma == 0:
+            raise ValueError('Transfer(0, 0): no momentum and no smoothing is the plain attack (pass transfer=None)')
+
+    @property
+    def radius(self):
+        """r = ceil(3 sigma): the filter has 2 r + 1 taps per axis."""
+        return int(math.ceil(3 * self.sigma))
+
+    def weights(self):
+        """The 2 r + 1 taps exp(-i^2 / (2 sigma^2)), i = -r .. r, normalised to sum 1 in float64 and then rounded: a float32 tensor
+        ([1.0] for sigma = 0)."""
+        r = self.radius
+        if r == 0:
+            return torch.ones(1, dtype=torch.float32)
+        i = torch.arange(-r, r + 1, dtype=torch.float64)
+        w = torch.exp(-i * i / (2.0 * float(self.sigma) ** 2))
+        return (w / w.sum()).to(torch.float32)
+
+
+def _unwrap(m):
+    return m.module if hasattr(m, 'module') and not isinstance(m, (PCNet, Classifier)) else m
+
+
+def _ensemble_members(classifier, storage, who):
+    """The members of a list / tuple `classifier`, checked: each a spaa_amd.Classifier (no foreign-callable route for ensembles), at most
+    ENS_MAX of them, no object twice, one number of classes; fp32 storage."""
+    members = [_unwrap(c) for c in classifier]
+    if not members:
+        raise ValueError(f'{who}: the classifier sequence is empty')
+    for c in members:
+        if not isinstance(c, Classifier):
+            raise TypeError(f'{who}: every member of a classifier ensemble must be a spaa_amd.Classifier, got {type(c).__name__} '
+                            '(a foreign callable can only be attacked alone)')
+    if len(members) > ENS_MAX:
+        raise ValueError(f'{who}: an ensemble holds at most {ENS_MAX} classifiers, got {len(members)}')
+    if len({id(c) for c in members}) != len(members):
+        raise ValueError(f'{who}: the same Classifier object is listed twice in the ensemble')
+    ncls = [c.num_classes for c in members]
+    if any(n != ncls[0] for n in ncls):
+        raise ValueError(f'{who}: the members of an ensemble must have the same number of classes, got {ncls}')
+    if len(members) >= 2:
+        _need_f32('for an ensemble', _OWN_SCALE.format('members'), storage, who)
+    return members
+
+
+def _view_pcnets(pcnet, cam_scene, who):
+    """The views of a list / tuple `pcnet`, checked: each a spaa_amd.PCNet, 2 to VIEWS_MAX of them, no object twice, and `cam_scene` a
+    list / tuple of as many scenes.  Returns (list of PCNets, list of scenes); a sequence of one PCNet is that PCNet: (PCNet, its
+    scene)."""
+    views = [_unwrap(m) for m in pcnet]
+    for m in views:
+        if not isinstance(m, PCNet):
+            raise TypeError(f'{who}: every view must be a spaa_amd.PCNet, got {type(m).__name__} (the HIP path has no generic PCNet '
+                            'fallback)')
+    if not views:
+        raise ValueError(f'{who}: the pcnet sequence is empty')
+    if len(views) == 1:
+        if isinstance(cam_scene, (list, tuple)):
+            if len(cam_scene) != 1:
+                raise ValueError(f'{who}: {len(cam_scene)} scenes for one view')
+            cam_scene = cam_scene[0]
+        return views[0], cam_scene
+    if len(views) > VIEWS_MAX:
+        raise ValueError(f'{who}: a multi-view attack holds at most {VIEWS_MAX} views, got {len(views)}')
+    if len({id(m) for m in views}) != len(views):
+        raise ValueError(f'{who}: the same PCNet object is listed twice among the views')
+    if not isinstance(cam_scene, (list, tuple)) or len(cam_scene) != len(views):
+        n = len(cam_scene) if isinstance(cam_scene, (list, tuple)) else 'one tensor'
+        raise ValueError(f'{who}: cam_scene must be a list of one scene per view ({len(views)}), got {n}')
+    return views, list(cam_scene)
+
+
+# The refusals that the features share, each stated once; a feature's function below passes its own words.
+_OWN_SCALE = "the {}' unit vectors need a loss scale of their own"
+
+
+def _need_f32(where, why, storage, who):
+    if storage != 'f32':
+        raise NotImplementedError(f"{who}: storage={storage!r} is not implemented {where} ({why}); use storage='f32'")
+
+
+def _need_classifier(attack, why, classifier, who, kinds=Classifier):   # (`classifier`: a Classifier, a checked list, or anything else)
+    if not isinstance(classifier, kinds):
+        raise TypeError(f'{who}: {attack} needs a spaa_amd.Classifier, got {type(classifier).__name__} ({why})')
+
+
+def _need_one_of_each(what, short, pcnet, classifier, who):   # (draws: of one camera image, through one classifier)
+    if isinstance(pcnet, list):
+        raise NotImplementedError(f'{who}: {what} against several views is not implemented; attack one view with {short}')
+    if isinstance(classifier, list):
+        raise NotImplementedError(f'{who}: {what} against an ensemble of classifiers is not implemented; attack one classifier with '
+                                  f'{short}')
+
+
+def _no_focus(short, focus, who):
+    if focus:
+        raise ValueError(f'{who}: focus=True has no meaning with {short} (a sample must fool every draw of every iteration)')
+
+
+def _is_a(value, name, kind, who, or_none=''):
+    if not isinstance(value, kind):
+        raise TypeError(f'{who}: {name} must be a spaa_amd.{kind.__name__}{or_none}, got {type(value).__name__}')
+
+
+def _views_supported(views, classifier, storage, who):
+    """What a multi-view attack does not serve.  `classifier`: as spaa() holds it after its own checks."""
+    if isinstance(classifier, list):
+        raise NotImplementedError(f'{who}: an ensemble of classifiers against several views is not implemented; attack one '
+                                  'classifier from several views, or several classifiers from one')
+    _need_classifier('a multi-view attack', 'a foreign callable can only be attacked from one view', classifier, who)
+    _need_f32('for several views', _OWN_SCALE.format('views'), storage, who)
+    sizes = [tuple(m.warping_net.out_size) for m in views]
+    if any(sz != sizes[0] for sz in sizes):
+        raise ValueError(f'{who}: the views must have the same camera size, got {sizes}')
+
+
+def _jitter_supported(jitter, pcnet, classifier, storage, focus, who):
+    """What a jitter attack does not serve.  `pcnet` / `classifier`: as spaa() holds them after its own checks."""
+    _is_a(jitter, 'jitter', CaptureJitter, who)
+    _need_one_of_each('capture jitter', 'jitter', pcnet, classifier, who)
+    _need_classifier('a jitter attack', 'a foreign callable can only be attacked without jitter', classifier, who)
+    _need_f32('with jitter', _OWN_SCALE.format('draws'), storage, who)
+    _no_focus('jitter', focus, who)
+
+
+def _pose_supported(pose, pcnet, classifier, storage, focus, attention, jitter, who):
+    """What a pose attack does not serve.  `pcnet` / `classifier`: as spaa() holds them after its own checks; `jitter`: None or a checked
+    CaptureJitter."""
+    _is_a(pose, 'pose', PoseJitter, who)
+    _need_one_of_each('pose jitter', 'pose', pcnet, classifier, who)
+    _need_classifier('a pose attack', 'a foreign callable can only be attacked without pose', classifier, who)
+    if attention is not None:
+        raise NotImplementedError(f'{who}: attention together with pose jitter is not implemented (every draw would need a map of its '
+                                  'own, pulled back through the warp); use attention or pose')
+    _need_f32('with pose', _OWN_SCALE.format('draws'), storage, who)
+    _no_focus('pose', focus, who)
+    if jitter is not None and int(jitter.draws) != int(pose.draws):
+        raise ValueError(f'{who}: pose and jitter are applied draw by draw and must name the same draws, got pose.draws = '
+                         f'{pose.draws} and jitter.draws = {jitter.draws}')
+
+
+def _attention_checked(attention, storage, who):
+    """An attack state's own check of its `attention` (the entry points say more, earlier: _attention_supported)."""
+    if attention is not None:
+        _is_a(attention, 'attention', Attention, who, ' or None')
+        _need_f32('with attention', 'the feature map and its gradient are read as fp32', storage, who)
+
+
+def _attention_supported(attention, classifier, storage, jitter, who):
+    """What an attention-weighted attack does not serve.  `classifier`: as spaa() holds it after its own checks.  A body without a
+    feature map passes only with attention.rollout, where it has an attention rollout to offer instead."""
+    _is_a(attention, 'attention', Attention, who, ' or None')
+    if jitter is not None:
+        raise NotImplementedError(f'{who}: attention together with capture jitter is not implemented (every draw would need a map of '
+                                  'its own, pulled back through the jitter); use attention or jitter')
+    _need_classifier('an attention-weighted attack', 'a foreign callable has no feature map to read', classifier, who, (Classifier, list))
+    for c in classifier if isinstance(classifier, list) else [classifier]:
+        if isinstance(c, Classifier) and not c.has_feature_map and not (attention.rollout and c.has_rollout):
+            raise NotImplementedError(f'{who}: attention is not implemented for {c.name} (Grad-CAM needs a convolutional feature map, which '
+                                      'this body does not have); attack it without attention=')
+    _attention_checked(attention, storage, who)
+
+
+def _transfer_checked(transfer, storage, who):
+    """An attack state's own check of its `transfer` (the entry points say more, earlier: _transfer_supported)."""
+    if transfer is not None:
+        _is_a(transfer, 'transfer', Transfer, who, ' or None')
+        _need_f32('with transfer', 'the momentum image and the smoothed gradient are fp32 and carry no loss scale', storage, who)
+
+
+def _transfer_supported(transfer, classifier, storage, who):
+    """What a transferable attack does not serve.  `classifier`: as spaa() holds it after its own checks."""
+    _is_a(transfer, 'transfer', Transfer, who, ' or None')
+    _need_classifier('a transferable attack', 'the route of a foreign callable steps inside torch.autograd, where the fused direction '
+                     'kernels do not run', classifier, who, (Classifier, list))
+    _transfer_checked(transfer, storage, who)
+
+
+def checked_request(who, pcnet, classifier, cam_scene, storage, focus, jitter, pose, attention, transfer):
+    """The request of spaa() / spaa_sweep() (`who`), checked in the one order that decides which error a caller sees; returns the
+    normalised (pcnet, classifier, cam_scene): unwrapped, a sequence of one collapsed, a list where there are several."""
+    pcnet, classifier = _unwrap(pcnet), _unwrap(classifier)
+    if isinstance(pcnet, (list, tuple)):
+        pcnet, cam_scene = _view_pcnets(pcnet, cam_scene, who)
+    if not isinstance(pcnet, (PCNet, list)):
+        raise TypeError(f"{'spaa_amd.spaa' if who == 'spaa' else who} needs a spaa_amd.PCNet (the HIP path has no generic PCNet fallback)")
+    if isinstance(classifier, (list, tuple)):
+        classifier = _ensemble_members(classifier, storage, who)
+        if len(classifier) == 1:
+            classifier = classifier[0]
+    if isinstance(pcnet, list):
+        _views_supported(pcnet, classifier, storage, who)
+    if jitter is not None:
+        _jitter_supported(jitter, pcnet, classifier, storage, focus, who)
+    if pose is not None:
+        _pose_supported(pose, pcnet, classifier, storage, focus, attention, jitter, who)
+    if attention is not None:
+        _attention_supported(attention, classifier, storage, jitter, who)
+    if transfer is not None:
+        _transfer_supported(transfer, classifier, storage, who)
+    return pcnet, classifier, cam_scene

@@ -1,0 +1,559 @@
+"""The device-side states of the batched SPAA attack: AttackState (one PCNet, one classifier), EnsembleAttackState (several classifiers),
+MultiViewAttackState (several PCNets) and DrawAttackState (random draws of the camera image through a chain of stages:
+JitterAttackState, PoseAttackState).  Lines quoted as :NNN are the reference's projector_based_attack.py."""
+import ctypes
+
+import torch
+
+from . import _lib
+from .models import to_nhwc4, to_nchw
+from .attack_options import (_unwrap, _ensemble_members, _view_pcnets, _views_supported, _jitter_supported, _pose_supported,
+                             _attention_checked, _transfer_checked)
+
+
+def _is_scalar(v):
+    return isinstance(v, (bool, int, float)) or (isinstance(v, torch.Tensor) and v.ndim == 0) or getattr(v, 'ndim', None) == 0
+
+
+def _require_gpu(device, who):
+    """torch.device(device), which must be a GPU: `who` names the entry point in the error."""
+    dev = torch.device(device)
+    if dev.type != 'cuda':
+        raise RuntimeError(f'spaa_amd.{who} runs on the GPU only (no CPU fallback); got device={device}')
+    return dev
+
+
+def _scene_batch(cam_scene, B):
+    """`cam_scene` ([3,H,W], [1,3,H,W] or [B,3,H,W]) as float [B,3,H,W]; one scene is broadcast (a view).  Any other shape comes back
+    as it is: the caller checks it and words its own error."""
+    sc = cam_scene.detach().float()
+    while sc.ndim < 4:
+        sc = sc[None]
+    return sc.expand(B, -1, -1, -1) if sc.ndim == 4 and sc.shape[0] == 1 else sc
+
+
+class AttackState:
+    """Device-side state of one batched attack (everything the loop touches, allocated once)."""
+    label = None   # what spaa()'s report counts in state[:, 3]: 'members', 'draws', 'views'; None: the plain attack prints the class
+
+    def __init__(self, pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, device, storage='f32', attention=None,
+                 transfer=None):
+        """`storage`: 'f32' (default; results identical to the reference to rounding) or 'f16' (fp16-storage mode of
+        BASELINE.json configs[4]: network activations and their gradients are fp16 in HBM, images / losses / dE2000 /
+        norms / accumulation fp32).  `attention`: an Attention (fp32 storage): every classifier engine of the state
+        weights its gradient image by its own Grad-CAM map; attention_maps() returns the maps of the last iteration.  `transfer`: a
+        Transfer (fp32 storage): the adversarial step follows the smoothed, momentum-accumulated gradient image
+        `momentum` [B,Hp,Wp,4] instead of the raw one."""
+        _attention_checked(attention, storage, type(self).__name__)
+        _transfer_checked(transfer, storage, type(self).__name__)
+        self.storage, self.attention, self.transfer = storage, attention, transfer
+        dev = _require_gpu(device, 'spaa')
+        if dev.index is None:
+            dev = torch.device('cuda', torch.cuda.current_device())
+        with _lib.on_device(dev):  # kernels launch on the current device: make it the one the state lives on
+            self._build(pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, dev)
+
+    def _lease_view(self, pcnet, classifier, cam_scene, setup_info, whose=''):
+        """One camera view: a leased PCNet engine holding the view's scene batch and a leased classifier engine looking at its output;
+        returns (PCNet engine, classifier engine, scene [B,Hc,Wc,4], its Lab image).  Further views have the first one's camera size."""
+        B = self.B
+        sc = _scene_batch(cam_scene, B)
+        if sc.shape[0] != B:
+            raise ValueError(f'{whose}cam_scene must hold 1 or len(target_idx) scenes')
+        eng = pcnet.engine(B, tuple(setup_info['prj_im_sz']), owner=self, storage=self.storage)
+        Hc, Wc = eng.Hc, eng.Wc
+        first = getattr(self, 'eng', eng)
+        if (first.Hc, first.Wc) != (Hc, Wc):
+            raise ValueError(f'the views must have the same camera size, got {(first.Hc, first.Wc)} and {(Hc, Wc)}')
+        if tuple(sc.shape[-2:]) != (Hc, Wc):
+            raise ValueError(f'cam_scene is {tuple(sc.shape[-2:])} but PCNet outputs {(Hc, Wc)}')
+        clf = classifier.engine(B, (Hc, Wc), self.cp_sz, owner=self, storage=self.storage)
+        if self.attention is not None:
+            clf.attention_buffers(self.attention.rollout)
+        scene4 = to_nhwc4(sc.contiguous().to(self.dev))
+        eng.set_scene(scene4)
+        scene_lab = torch.zeros_like(scene4)
+        _lib.call('spaa_rgb2lab', _lib.ptr(scene4), _lib.ptr(scene_lab), B * Hc * Wc)
+        return eng, clf, scene4, scene_lab
+
+    def _build(self, pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, dev):
+        from .projector_based_attack import CLAMP_BITS, loss_weights   # (the switches live with the entry points)
+        B = len(target_idx)
+        if B < 1:
+            raise ValueError('target_idx is empty: nothing to attack')
+        self.B, self.dev = B, dev
+        prj_sz = tuple(setup_info['prj_im_sz'])
+        self.cp_sz = tuple(setup_info['classifier_crop_sz'])
+        self.gray = float(setup_info['prj_brightness'])
+        self.eng, self.clf, self.scene4, self.scene_lab = self._lease_view(pcnet, classifier, cam_scene, setup_info)
+        self.clfs = [self.clf]   # (one engine per member / view where there are several)
+        Hc, Wc = self.eng.Hc, self.eng.Wc
+        # fp16 gradients need a loss scale (fp16's smallest normal is 6e-5; the per-pixel loss gradients are ~1/(B*H*W)).
+        # Each sample's gradient is normalised before the step (:307, :315), so a positive per-branch scale changes
+        # nothing but the fp16 rounding: stealth branch: 1/16 per pixel instead of 1/(B*H*W); adversarial branch: +-16
+        # at the target logit instead of 1/B.
+        self.gs_col, self.gs_adv = ((B * Hc * Wc) / 16.0, 16.0 * B) if self.storage == 'f16' else (1.0, 1.0)
+        Hp, Wp = prj_sz
+        self.HWp, self.HWc = Hp * Wp, Hc * Wc
+        self.x = torch.zeros(B, Hp, Wp, 4, device=dev)
+        self.x[..., :3] = self.gray
+        self.x_best, self.cam_best = self.x.clone(), self.scene4.clone()
+        self.state = torch.zeros(B, 4, dtype=torch.int32, device=dev)
+        self.stats = torch.zeros(B, 8, device=dev)
+        self.stats[:, 5] = 1e6
+        self.nblk_c, self.nblk_p = (self.HWc + 255) // 256, (self.HWp + 255) // 256
+        self.partial_loss = torch.zeros(B, self.nblk_c, 3, device=dev)
+        # ||g_b||^2 partial sums: per 256-pixel block (spaa_grad_sumsq), or per 16 x 16 projector tile when the tiled grid_sample
+        # adjoint computes them in its epilogue
+        self.ss_tiles = self.eng.sumsq_tiles()
+        self.partial_ss = torch.zeros(B, self.ss_tiles or self.nblk_p, device=dev)
+        # The clamp gate of x.clamp(0, 1) (:265) for the backward pass as one byte per projector pixel, written by the step that writes x:
+        # the grid_sample adjoint then reads 1 byte per pixel instead of x's 16.  The bytes describe self.x as long as nobody else has
+        # written it: `_bits_version` remembers torch's version counter of self.x (in-place torch writes -- tests that inject an x --
+        # bump it, this module's own kernels go through raw pointers and do not): a mismatch falls back to the comparisons on x.
+        self.clamp_bits = torch.zeros(B, self.HWp, dtype=torch.uint8, device=dev) if self.ss_tiles and CLAMP_BITS else None
+        self._bits_version = -1
+        self.g_col = torch.zeros(B, Hc, Wc, 4, device=dev)
+        self.gP = torch.zeros(B, Hc, Wc, 4, device=dev)
+        self.g_logits = torch.zeros(B, self.clf.ncls, device=dev)
+        self.prjl2 = torch.zeros(B, device=dev)
+        self.target = torch.tensor([int(t) for t in target_idx], dtype=torch.int32, device=dev)
+        # `stealth_loss`: one string for the batch, or one per sample (spaa_sweep).  self.prjl2_w / caml2_w / camdE_w are the batch's
+        # weights when every sample has the same ones, else None: the per-sample table of the _ps launches carries them.
+        losses = [stealth_loss] * B if isinstance(stealth_loss, str) else list(stealth_loss)
+        if len(losses) != B:
+            raise ValueError(f'stealth_loss: {len(losses)} strings for {B} samples')
+        self.loss_w = [loss_weights(s) for s in losses]
+        uniform = all(w == self.loss_w[0] for w in self.loss_w)
+        self.prjl2_w, self.caml2_w, self.camdE_w = self.loss_w[0] if uniform else (None, None, None)
+        self.any_prjl2 = any(w[0] for w in self.loss_w)
+        self._ps_key = None      # (targeted, d_thr) per sample of the uploaded table, None: scalar launches
+        self.ps_params = torch.zeros(B, 4, device=dev)
+        self.ps_flags = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.ps_prjl2_scale = torch.zeros(B, device=dev)
+        if self.transfer is not None:
+            # the momentum image m (zero: the first adversarial step is the smoothed gradient's), the smoothed gradient t and its |.|
+            # sums per tile of the blur launch; the taps travel in the launch's arguments
+            self.momentum = torch.zeros(B, Hp, Wp, 4, device=dev)
+            self.transfer_t = torch.zeros(B, Hp, Wp, 4, device=dev)
+            self.transfer_tiles = _lib.load().spaa_transfer_tiles(Hp, Wp)
+            self.transfer_l1 = torch.zeros(B, self.transfer_tiles, device=dev)
+            taps = self.transfer.weights().tolist()
+            self._transfer_taps = (ctypes.c_float * len(taps))(*taps)
+
+    def _shape_direction(self, gx, partial_ss, npartial):
+        """The transferable step, directly before spaa_step_and_track_n: for every sample on the adversarial step the
+        gradient image `gx` becomes the momentum image m <- mu m + t / |t|_1, t the Gaussian-smoothed gx, and its row of `partial_ss`
+        the partial sums of ||m||^2; samples on the colour step keep gx, partial_ss and m bit for bit.  Two launches, no host read;
+        without `transfer` none."""
+        tr = self.transfer
+        if tr is None:
+            return
+        p = _lib.ptr
+        Hp, Wp = self.x.shape[1:3]
+        _lib.call('spaa_transfer_blur', p(gx), p(self.state), self._transfer_taps, tr.radius, p(self.transfer_t), p(self.transfer_l1),
+                  self.B, Hp, Wp)
+        _lib.call('spaa_transfer_momentum', p(self.transfer_t), p(self.transfer_l1), self.transfer_tiles, float(tr.momentum),
+                  p(self.state), p(self.momentum), p(gx), p(partial_ss), int(npartial), self.B, self.HWp)
+
+    def _per_sample(self, targeted, d_thr, table=False):
+        """The batch's (targeted, d_thr) as scalars when every sample agrees and the loss weights are uniform (the launches of a single
+        attack, unchanged); else, or with `table` always, uploads the per-sample table (once per distinct setting: a captured graph
+        replays the table it read) and returns None."""
+        B = self.B
+        tg = [bool(targeted)] * B if _is_scalar(targeted) else [bool(t) for t in targeted]
+        dt = [float(d_thr)] * B if _is_scalar(d_thr) else [float(d) for d in d_thr]
+        if len(tg) != B or len(dt) != B:
+            raise ValueError(f'targeted / d_thr: one value or {B} values')
+        if not table and self.caml2_w is not None and all(t == tg[0] for t in tg) and all(d == dt[0] for d in dt):
+            return tg[0], dt[0]
+        key = (tuple(tg), tuple(dt))
+        if key != self._ps_key:
+            params = torch.tensor([list(w) + [d] for w, d in zip(self.loss_w, dt)], dtype=torch.float32)
+            self.ps_params.copy_(params)
+            self.ps_flags.copy_(torch.tensor([int(t) for t in tg], dtype=torch.int32))
+            self.ps_prjl2_scale.copy_(params[:, 0] / (B * self.HWp) * self.gs_col)
+            self._ps_key = key
+        return None
+
+    def iteration(self, targeted, d_thr, adv_lr, col_lr, p_thresh, adv_w=1.0):
+        """One pass of the loop body (projector_based_attack.py:264-328), ~90 kernel launches, no host sync.  `targeted` and `d_thr`:
+        one value for the batch or one per sample."""
+        with torch.cuda.device(self.dev):
+            self._forward_decide(targeted, d_thr, p_thresh, adv_w)
+            self._backward_step(adv_lr, col_lr)
+
+    def forward_decide(self, targeted, d_thr, p_thresh, adv_w=1.0):
+        """First half of `iteration` (:265-299): forward passes, losses and their gradient at the camera image, masks."""
+        with torch.cuda.device(self.dev):
+            self._forward_decide(targeted, d_thr, p_thresh, adv_w)
+
+    def backward_step(self, adv_lr, col_lr):
+        """Second half of `iteration` (:302-328): the backward pass, the normalised step and the best-so-far bookkeeping.
+        (The halves are separate entry points so that the parity tests can compare / exchange the ReLU gates in between.)"""
+        with torch.cuda.device(self.dev):
+            self._backward_step(adv_lr, col_lr)
+
+    def _prjl2_fwd(self):
+        """prjl2 of the per-sample table route, where any sample weights it; returns the pointer the decision takes (or None)."""
+        if self.any_prjl2:
+            _lib.call('spaa_prjl2_fwd', _lib.ptr(self.x), self.gray, _lib.ptr(self.prjl2), self.B, self.HWp)
+        return _lib.ptr(self.prjl2) if self.any_prjl2 else None
+
+    def _stealth_loss_ps(self, y, v=None):
+        """The stealth loss of camera image y (the state's own view, or view v) and its gradient, weighted by the per-sample table."""
+        p = _lib.ptr
+        scene4, lab, g_col, partial = ((self.scene4, self.scene_lab, self.g_col, self.partial_loss) if v is None else
+                                       (self.scene4s[v], self.scene_labs[v], self.g_cols[v], self.partial_losses[v]))
+        _lib.call('spaa_stealth_loss_fwd_bwd_ps', p(y), p(scene4), p(lab), p(self.ps_params), self.gs_col / (self.B * self.HWc),
+                  p(g_col), None, p(partial), self.B, self.HWc)
+
+    def _forward_decide(self, targeted, d_thr, p_thresh, adv_w):
+        B, p = self.B, _lib.ptr
+        uni = self._per_sample(targeted, d_thr)
+        y = self.eng.forward(self.x, clamp01=True)                                   # :265
+        logits = self.clf.forward(y)                                                 # :266
+        self._y, self._uniform = y, uni is not None
+        if uni is None:   # several attack configurations in one batch: the same kernels, their parameters per sample
+            prjl2 = self._prjl2_fwd()
+            self._stealth_loss_ps(y)
+            _lib.call('spaa_decide_ps', p(logits), self.clf.ncls, p(self.target), p(self.partial_loss), self.nblk_c, self.HWc,
+                      prjl2, p(self.ps_params), p(self.ps_flags), float(p_thresh), adv_w / B * self.gs_adv,
+                      p(self.state), p(self.stats), p(self.g_logits), B)
+            return
+        targeted, d_thr = uni
+        if self.prjl2_w:
+            _lib.call('spaa_prjl2_fwd', p(self.x), self.gray, p(self.prjl2), B, self.HWp)    # :275
+        _lib.call('spaa_stealth_loss_fwd_bwd', p(y), p(self.scene4), p(self.scene_lab), self.caml2_w, self.camdE_w,
+                  self.gs_col / (B * self.HWc), p(self.g_col), None, p(self.partial_loss), B, self.HWc)   # :279-287 + bwd
+        _lib.call('spaa_decide', p(logits), self.clf.ncls, p(self.target), int(bool(targeted)), p(self.partial_loss),
+                  self.nblk_c, self.HWc, p(self.prjl2) if self.prjl2_w else None, self.prjl2_w, self.caml2_w,
+                  self.camdE_w, float(d_thr), float(p_thresh), adv_w / B * self.gs_adv, p(self.state), p(self.stats),
+                  p(self.g_logits), B)                                               # :269-272, :290-299, :318-320
+
+    def _adv_gradient(self):
+        """The adversarial loss's gradient at the camera image [B,Hc,Wc,4]: the classifier's backward pass from the seed of the decision."""
+        return self.clf.backward(self.g_logits, self.attention, self.target)         # :302 (classifier part)
+
+    def _engine_maps(self, engines):
+        if self.attention is None:
+            raise RuntimeError('attention_maps(): this attack runs without attention (pass attention=Attention(...))')
+        with torch.cuda.device(self.dev):
+            return [e.attention_map() for e in engines]
+
+    def attention_maps(self):
+        """The Grad-CAM map M of the last iteration in the camera frame, [B, 1, Hc, Wc] in [0, 1] and 0 outside the classifier crop
+        (EnsembleAttackState: a list of one per member, MultiViewAttackState: of one per view)."""
+        maps = self._engine_maps(self.clfs)
+        return maps if self.label else maps[0]
+
+    def trace_entry(self):
+        """What spaa()'s `trace` records per iteration (copies; no sync)."""
+        return self.state.clone(), self.stats.clone()
+
+    def _pcnet_backward(self, eng, g_adv, g_col, gP, sumsq=None, clamp_bits=None):
+        """The PCNet part of the backward pass for one engine (:302 / :310), from each sample's choice between g_adv and g_col: the
+        choice and the clamp gate as the first phase of the fused head kernel where the engine has it, else as a launch into gP."""
+        if eng.can_select():
+            return eng.backward(None, select=(g_adv, g_col, self.state), sumsq=sumsq, clamp_bits=clamp_bits)
+        p = _lib.ptr
+        _lib.call('spaa_select_grad', p(g_adv), p(g_col), p(self.state), p(eng.a['Ypre']), p(gP), self.B, self.HWc)
+        return eng.backward(gP, sumsq=sumsq, clamp_bits=clamp_bits)
+
+    def _step_and_track(self, gx, adv_lr, col_lr):
+        """The normalised step along gx (||gx||^2 per sample in partial_ss) and the best-so-far bookkeeping (:307,315,323-328)."""
+        p, n = _lib.ptr, self.partial_ss.shape[1]
+        self._shape_direction(gx, self.partial_ss, n)
+        _lib.call('spaa_step_and_track_n', p(self.x), p(gx), p(self.partial_ss), n, p(self.state), float(adv_lr), float(col_lr),
+                  p(self.x_best), p(self._y), p(self.cam_best), self.B, self.HWp, self.HWc, p(self.clamp_bits))
+        self._bits_version = self.x._version
+
+    def _backward_step(self, adv_lr, col_lr):
+        B, p = self.B, _lib.ptr
+        g_adv = self._adv_gradient()
+        # (mixed configurations: the prjl2 scale is a [B] device tensor, and the sums of squares take the _ps launches)
+        prjl2_scale = self.prjl2_w / (B * self.HWp) * self.gs_col if self._uniform else self.ps_prjl2_scale
+        ss = (self.partial_ss, self.gray, prjl2_scale, self.state) if self.ss_tiles else None   # (||g||^2 from the adjoint's epilogue)
+        bits = self.clamp_bits if (self.clamp_bits is not None and self._bits_version == self.x._version) else None
+        gx = self._pcnet_backward(self.eng, g_adv, self.g_col, self.gP, ss, bits)
+        if not self.ss_tiles and self._uniform:
+            _lib.call('spaa_grad_sumsq', p(gx), p(self.x), self.gray, prjl2_scale, p(self.state), p(self.partial_ss), B, self.HWp)
+        elif not self.ss_tiles:
+            _lib.call('spaa_grad_sumsq_ps', p(gx), p(self.x), self.gray, p(prjl2_scale), p(self.state), p(self.partial_ss), B,
+                      self.HWp)
+        self._step_and_track(gx, adv_lr, col_lr)
+
+    def results(self):
+        with torch.cuda.device(self.dev):
+            return to_nchw(self.cam_best), to_nchw(self.x_best, clamp01=True)        # :337
+
+
+class EnsembleAttackState(AttackState):
+    """One batched attack against K = 2..ENS_MAX classifiers that see the same camera image ("Ensemble attack"): AttackState
+    with one leased engine per member, the decision over all members (spaa_decide_ens) and, as adversarial cotangent, the weighted sum
+    of the members' unit gradient images (spaa_ens_sumsq + spaa_ens_combine).  PCNet's passes, the stealth loss, the colour step, the
+    normalised step and the best tracking are AttackState's.  `state[:, 3]` counts the fooled members; each member's top-1 is in
+    `ens_state`.  `focus`: a member that is already fooled rests (weight 0) until all are."""
+    label = 'members'
+
+    def __init__(self, pcnet, classifiers, target_idx, cam_scene, stealth_loss, setup_info, device, storage='f32', focus=False,
+                 attention=None, transfer=None):
+        self.members, self.focus = self._members(classifiers, storage), bool(focus)   # (one engine is leased per member)
+        super().__init__(pcnet, self.members[0], target_idx, cam_scene, stealth_loss, setup_info, device, storage=storage,
+                         attention=attention, transfer=transfer)
+
+    def _members(self, classifiers, storage):   # (the checked list of the members' classifiers)
+        members = _ensemble_members(classifiers, storage, 'EnsembleAttackState')
+        if len(members) < 2:
+            raise ValueError('EnsembleAttackState needs at least two classifiers (AttackState attacks one)')
+        return members
+
+    def _build(self, pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, dev):
+        super()._build(pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, dev)   # (leases member 0's engine: self.clf)
+        B, K = self.B, len(self.members)
+        self.K = K
+        self.clfs = [self.clf] + [c.engine(B, (self.eng.Hc, self.eng.Wc), self.cp_sz, owner=self, storage=self.storage)
+                                  for c in self.members[1:]]
+        for e in self.clfs[1:] if self.attention is not None else []:
+            e.attention_buffers(self.attention.rollout)
+        self.ens_g_logits = [self.g_logits] + [torch.zeros_like(self.g_logits) for _ in range(K - 1)]
+        self.ens_state = torch.zeros(B, K, 2, dtype=torch.int32, device=dev)
+        self.ens_stats = torch.zeros(B, K, 2, device=dev)
+        self.ens_w = torch.ones(B, K, device=dev)
+        self.ens_partial = torch.zeros(B, K, self.nblk_c, device=dev)
+        self.g_adv = torch.zeros(B, self.eng.Hc, self.eng.Wc, 4, device=dev)
+
+    def _forward_decide(self, targeted, d_thr, p_thresh, adv_w):
+        p = _lib.ptr
+        self._per_sample(targeted, d_thr, table=True)   # (the ensemble decision has the per-sample table form only)
+        y = self.eng.forward(self.x, clamp01=True)                                   # :265
+        logits = self._member_logits(y)
+        self._y, self._uniform = y, False
+        prjl2 = self._prjl2_fwd()
+        self._stealth_loss_ps(y)
+        _lib.call('spaa_decide_ens', _lib.ptr_array(logits), self.K, self.clf.ncls, p(self.target), p(self.partial_loss), self.nblk_c,
+                  self.HWc, prjl2, p(self.ps_params), p(self.ps_flags), float(p_thresh), int(self.focus), p(self.state), p(self.stats),
+                  p(self.ens_state), p(self.ens_stats), p(self.ens_w),
+                  _lib.ptr_array(self.ens_g_logits), self.B)
+
+    def _member_logits(self, y):
+        """Every member's logits of the camera image y."""
+        return [e.forward(y) for e in self.clfs]                                     # :266, once per member
+
+    def _member_gradients(self):
+        """Every member's gradient image at the camera image, from its seed of the decision."""
+        return [e.backward(g, self.attention, self.target) for e, g in zip(self.clfs, self.ens_g_logits)]   # (each its own map)
+
+    def _adv_gradient(self):
+        gs = _lib.ptr_array(self._member_gradients())
+        _lib.call('spaa_ens_sumsq', gs, self.K, _lib.ptr(self.ens_partial), self.B, self.HWc)
+        _lib.call('spaa_ens_combine', gs, self.K, _lib.ptr(self.ens_partial), self.nblk_c, _lib.ptr(self.ens_w), _lib.ptr(self.g_adv),
+                  self.B, self.HWc)
+        return self.g_adv
+
+    def trace_entry(self):
+        return super().trace_entry() + (self.ens_state.clone(), self.ens_stats.clone())
+
+
+class MultiViewAttackState(AttackState):
+    """One batched attack against V = 2..VIEWS_MAX camera views of the same projector and scene ("Multi-view attack"): one
+    projector image x through V PCNets, each with its own scene, and one classifier looking at each of the V camera images.
+    AttackState (view 0's engines and buffers are its own) with one leased PCNet engine and one leased engine of the classifier per
+    further view, the decision over all views (spaa_decide_views), the V backward passes down to the projector image and their
+    combination there (spaa_ens_sumsq + spaa_views_combine): the mean of the views' stealth gradients on the colour step, the weighted
+    sum of the views' unit gradient images on the adversarial step.  `state[:, 3]` counts the fooled views; each view's top-1 is in
+    `view_state`, its p1, target logit, caml2 and camdE in `view_stats`.  `focus`: a view that is already fooled rests (weight 0) until
+    all are."""
+    label = 'views'
+
+    def __init__(self, pcnets, classifier, target_idx, cam_scenes, stealth_loss, setup_info, device, storage='f32', focus=False,
+                 attention=None, transfer=None):
+        views, scenes = _view_pcnets(pcnets, cam_scenes, 'MultiViewAttackState')
+        if not isinstance(views, list):
+            raise ValueError('MultiViewAttackState needs at least two views (AttackState attacks one)')
+        classifier = _unwrap(classifier)
+        _views_supported(views, classifier, storage, 'MultiViewAttackState')
+        self.pcnets, self._scenes, self.focus = views, scenes, bool(focus)
+        super().__init__(views[0], classifier, target_idx, scenes[0], stealth_loss, setup_info, device, storage=storage,
+                         attention=attention, transfer=transfer)
+
+    def _build(self, pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, dev):
+        super()._build(pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, dev)   # (view 0: self.eng, self.clf, ...)
+        B, V = self.B, len(self.pcnets)
+        self.V = V
+        # ||g||^2 of the COMBINED gradient comes from spaa_grad_sumsq_ps (a view's adjoint cannot sum it in its epilogue), and the
+        # views' backward passes read the clamp gate from x
+        self.ss_tiles, self.clamp_bits = 0, None
+        self.partial_ss = torch.zeros(B, self.nblk_p, device=dev)
+        more = [self._lease_view(m, classifier, sc, setup_info, whose="every view's ") for m, sc in zip(self.pcnets[1:], self._scenes[1:])]
+        self.engs, self.clfs, self.scene4s, self.scene_labs = ([own] + [view[i] for view in more] for i, own in
+                                                               enumerate((self.eng, self.clf, self.scene4, self.scene_lab)))
+        self.g_cols, self.gPs, self.partial_losses, self.view_g_logits = ([own] + [torch.zeros_like(own) for _ in more] for own in
+                                                                          (self.g_col, self.gP, self.partial_loss, self.g_logits))
+        self.cam_bests = [self.cam_best] + [scene4.clone() for scene4 in self.scene4s[1:]]
+        self.view_state = torch.zeros(B, V, 2, dtype=torch.int32, device=dev)
+        self.view_stats = torch.zeros(B, V, 4, device=dev)
+        self.view_w = torch.ones(B, V, device=dev)
+        self.views_partial = torch.zeros(B, V, self.nblk_p, device=dev)
+        self.g = torch.zeros(B, self.x.shape[1], self.x.shape[2], 4, device=dev)
+        self._ys = None
+
+    def _forward_decide(self, targeted, d_thr, p_thresh, adv_w):
+        B, p = self.B, _lib.ptr
+        self._per_sample(targeted, d_thr, table=True)   # (the decision over views has the per-sample table form only)
+        ys, logits = [], []
+        for v in range(self.V):
+            y = self.engs[v].forward(self.x, clamp01=True)                           # :265, once per view
+            logits.append(self.clfs[v].forward(y))                                   # :266
+            self._stealth_loss_ps(y, v)
+            ys.append(y)
+        self._ys, self._y, self._uniform = ys, ys[0], False
+        prjl2 = self._prjl2_fwd()
+        _lib.call('spaa_decide_views', _lib.ptr_array(logits), self.V, self.clf.ncls, p(self.target),
+                  _lib.ptr_array(self.partial_losses), self.nblk_c, self.HWc, prjl2, p(self.ps_params), p(self.ps_flags),
+                  float(p_thresh), adv_w / B * self.gs_adv, int(self.focus), p(self.state),
+                  p(self.stats), p(self.view_state), p(self.view_stats), p(self.view_w), _lib.ptr_array(self.view_g_logits), B)
+
+    def _backward_step(self, adv_lr, col_lr):
+        B, p = self.B, _lib.ptr
+        gxs = []
+        for v, eng in enumerate(self.engs):
+            g_adv = self.clfs[v].backward(self.view_g_logits[v], self.attention, self.target)   # :302 (classifier part), view v's seed and map
+            gxs.append(self._pcnet_backward(eng, g_adv, self.g_cols[v], self.gPs[v]))
+        gs = _lib.ptr_array(gxs)
+        _lib.call('spaa_ens_sumsq', gs, self.V, p(self.views_partial), B, self.HWp)
+        _lib.call('spaa_views_combine', gs, self.V, p(self.views_partial), self.nblk_p, p(self.view_w), p(self.state), p(self.g), B,
+                  self.HWp)
+        _lib.call('spaa_grad_sumsq_ps', p(self.g), p(self.x), self.gray, p(self.ps_prjl2_scale), p(self.state), p(self.partial_ss), B,
+                  self.HWp)
+        self._step_and_track(self.g, adv_lr, col_lr)
+        _lib.call('spaa_views_track', _lib.ptr_array(self._ys), _lib.ptr_array(self.cam_bests), self.V, p(self.state), B, self.HWc)
+
+    def trace_entry(self):
+        return super().trace_entry() + (self.view_state.clone(), self.view_stats.clone())
+
+    def results(self):
+        with torch.cuda.device(self.dev):
+            return [to_nchw(c) for c in self.cam_bests], to_nchw(self.x_best, clamp01=True)
+
+
+class JitterStage:
+    """Capture jitter as a stage of a draw chain ("Capture-robust attack"): its device-side counter, the rows `jit` and noise
+    keys `key` of spaa_jitter_draw, J images with their clamp gates, J gradient images; `build` returns them by their names on the state."""
+
+    def __init__(self, jitter):
+        self.options, self.draws = jitter, int(jitter.draws)
+
+    def build(self, st, first):
+        B, J, dev = st.B, st.K, st.dev
+        self.counter = torch.zeros(1, dtype=torch.int32, device=dev)        # the iteration number the next draw reads
+        self.jit = torch.zeros(B, J, 8, device=dev)
+        self.key = torch.zeros(B, J, dtype=torch.int32, device=dev)         # (uint32 bit patterns)
+        self.ims = [torch.zeros_like(st.g_adv) for _ in range(J)]
+        self.gates = [torch.zeros(B, st.HWc, dtype=torch.uint8, device=dev) for _ in range(J)]
+        self.grads = [torch.zeros_like(st.g_adv) for _ in range(J)]
+        return dict(jit=self.jit, key=self.key, draw_ims=self.ims, draw_gates=self.gates, draw_grads=self.grads,
+                    **{'counter' if first else 'jitter_counter': self.counter})
+
+    def forward(self, st, src):
+        """Draws this iteration's rows, then draw j of `src`: the camera image y, or (behind another stage) that stage's image j."""
+        jt, p, arr = self.options, _lib.ptr, _lib.ptr_array
+        jt.draw(self.counter, self.jit, self.key, st.B, st.K, clean0=True)
+        each = isinstance(src, list)
+        _lib.call('spaa_jitter_fwd_each' if each else 'spaa_jitter_fwd', arr(src) if each else p(src), p(self.jit), p(self.key), st.K,
+                  int(bool(jt.quantize)), arr(self.ims), arr(self.gates), st.B, st.eng.Hc, st.eng.Wc)
+        return self.ims
+
+    def backward(self, st, gs):
+        _lib.call('spaa_jitter_bwd', _lib.ptr_array(gs), _lib.ptr(self.jit), _lib.ptr_array(self.gates), st.K, _lib.ptr_array(self.grads),
+                  st.B, st.eng.Hc, st.eng.Wc)
+        return self.grads
+
+
+class PoseStage:
+    """Camera-pose jitter as a stage of a draw chain: its device-side counter, the homography rows `table` of
+    spaa_pose_draw, the J warped images, the J gradient images of its adjoint.  The first stage only: the warp launches from y."""
+
+    def __init__(self, pose):
+        self.options, self.draws = pose, int(pose.draws)
+
+    def build(self, st, first):
+        assert first, 'the pose warp has no launch form behind another stage'
+        self.counter = torch.zeros(1, dtype=torch.int32, device=st.dev)     # the iteration number the next draw reads
+        self.table = torch.zeros(st.B, st.K, 8, device=st.dev)
+        self.ims = [torch.zeros_like(st.g_adv) for _ in range(st.K)]
+        self.grads = [torch.zeros_like(st.g_adv) for _ in range(st.K)]
+        return dict(counter=self.counter, table=self.table, pose_ims=self.ims, pose_grads=self.grads)
+
+    def forward(self, st, y):
+        self.options.draw(self.counter, self.table, st.B, st.K, st.eng.Hc, st.eng.Wc, clean0=True)
+        _lib.call('spaa_pose_fwd', _lib.ptr(y), _lib.ptr(self.table), st.K, _lib.ptr_array(self.ims), st.B, st.eng.Hc, st.eng.Wc)
+        return self.ims
+
+    def backward(self, st, gs):
+        _lib.call('spaa_pose_bwd', _lib.ptr_array(gs), _lib.ptr(self.table), st.K, _lib.ptr_array(self.grads), st.B, st.eng.Hc,
+                  st.eng.Wc)
+        return self.grads
+
+
+class DrawAttackState(EnsembleAttackState):
+    """One batched attack against J random draws of the camera image per iteration: EnsembleAttackState whose members are J leased
+    engines of ONE classifier, member j looking at draw j of y = PCNet(x, s).  The draws come from a chain of `stages` applied to y,
+    each drawing its parameters directly before its transform (a device-side counter per stage: a replayed graph advances the
+    sequences); the members' gradient images go back to y through the stages' adjoints in reverse order before they are combined.
+    Draw 0 is the identity row of every stage, so a sample counts as successful only when the clean capture and every other draw of
+    that iteration are fooled; the stealth loss and `cam_best` stay the clean inference.  `state`, `stats`, `ens_state`, `ens_stats` keep
+    the ensemble's meaning with draws as members; the stages' buffers are attributes of the state (`counter`: the first stage's)."""
+    label = 'draws'
+
+    def __init__(self, pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, device, stages, storage='f32', transfer=None):
+        self.stages = stages
+        super().__init__(pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, device, storage=storage, transfer=transfer)
+
+    def _members(self, classifier, storage):
+        return [classifier] * self.stages[0].draws
+
+    def _build(self, pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, dev):
+        super()._build(pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, dev)
+        for i, stage in enumerate(self.stages):
+            vars(self).update(stage.build(self, first=i == 0))
+
+    def _member_logits(self, y):
+        ims = y
+        for stage in self.stages:
+            ims = stage.forward(self, ims)
+        return [e.forward(im) for e, im in zip(self.clfs, ims)]                      # :266, once per draw
+
+    def _member_gradients(self):
+        gs = super()._member_gradients()
+        for stage in reversed(self.stages):
+            gs = stage.backward(self, gs)
+        return gs
+
+
+class JitterAttackState(DrawAttackState):
+    """The draw attack of one stage, capture jitter: J = jitter.draws perturbed captures per iteration (spaa_jitter_draw,
+    spaa_jitter_fwd, spaa_jitter_bwd)."""
+
+    def __init__(self, pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, device, jitter, storage='f32', transfer=None):
+        pcnet, classifier = _unwrap(pcnet), _unwrap(classifier)
+        _jitter_supported(jitter, pcnet, classifier, storage, False, 'JitterAttackState')
+        self.jitter = jitter
+        super().__init__(pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, device, [JitterStage(jitter)], storage,
+                         transfer)
+
+
+class PoseAttackState(DrawAttackState):
+    """The draw attack through random homographies: J = pose.draws warped copies per iteration (spaa_pose_draw, spaa_pose_fwd,
+    spaa_pose_bwd).  With `jitter` (a CaptureJitter of the same `draws`) draw j is Jitter_j(Pose_j(y)): spaa_jitter_fwd_each behind the
+    warp, spaa_jitter_bwd before its adjoint."""
+
+    def __init__(self, pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, device, pose, storage='f32', jitter=None,
+                 transfer=None):
+        pcnet, classifier = _unwrap(pcnet), _unwrap(classifier)
+        if jitter is not None:
+            _jitter_supported(jitter, pcnet, classifier, storage, False, 'PoseAttackState')
+        _pose_supported(pose, pcnet, classifier, storage, False, None, jitter, 'PoseAttackState')
+        self.pose, self.jitter = pose, jitter
+        stages = [PoseStage(pose)] + ([JitterStage(jitter)] if jitter is not None else [])
+        super().__init__(pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, device, stages, storage, transfer)

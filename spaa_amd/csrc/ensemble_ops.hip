@@ -1,31 +1,20 @@
 // ensemble_ops.hip — SPAA against K classifiers (2 <= K <= SPAA_ENS_MAX) that see the same camera image: the decision step over the
 // K members' logits, and the adversarial cotangent  g_adv_b = sum_k a_bk g_bk / ||g_bk||_2  from the members' own gradient images.
 //
-// The member tensors arrive as HOST arrays of K device pointers (as mean3 / std3 of spaa_preproc_fwd are host pointers); the launchers
-// copy them into a kernel argument passed by value, so there is no device pointer table and a captured graph holds no copy.
+// The member tensors arrive as HOST arrays of K device pointers (as mean3 / std3 of spaa_preproc_fwd are host pointers) and travel in a
+// by-value kernel argument (ptr_table.hpp).
 // The per-sample tables state [B][4] / stats [B][8] keep the meaning the rest of the loop reads ("Ensemble attack").
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/spaa_hip.h"
 #include "device_util.hpp"
 #include "decide_util.hpp"
+#include "ptr_table.hpp"
 
 namespace {
 
-struct EnsIn {
-    const float* p[SPAA_ENS_MAX];
-};
-struct EnsOut {
-    float* p[SPAA_ENS_MAX];
-};
-
-// member k's pointer (k is uniform per workgroup; selects, so that the argument struct stays in the kernel-argument segment)
-__device__ __forceinline__ const float* member(const EnsIn& t, int k) {
-    return k == 0 ? t.p[0] : k == 1 ? t.p[1] : k == 2 ? t.p[2] : t.p[3];
-}
-__device__ __forceinline__ float* member(const EnsOut& t, int k) {
-    return k == 0 ? t.p[0] : k == 1 ? t.p[1] : k == 2 ? t.p[2] : t.p[3];
-}
+using EnsIn = PtrTable<const float, SPAA_ENS_MAX>;
+using EnsOut = PtrTable<float, SPAA_ENS_MAX>;
 
 // One workgroup per sample.  Member k: top1, p1 and the target logit as decide_kernel computes them (decide_util.hpp);
 // succ_k = (top1 == target) if targeted else (top1 != target); fooled_k = succ_k && p1 > p_thresh if targeted else succ_k.
@@ -48,7 +37,7 @@ __global__ __launch_bounds__(256) void decide_ens_kernel(const EnsIn logits, int
     unsigned fooled_bits = 0;
     float p_min = INFINITY, tl_sum = 0.f;
     for (int k = 0; k < K; ++k) {
-        const float* lg = member(logits, k) + (size_t)b * ncls;
+        const float* lg = ptr_of(logits, k) + (size_t)b * ncls;
         int am;
         float p1;
         decide_top1(lg, ncls, lds, am, p1);
@@ -68,7 +57,7 @@ __global__ __launch_bounds__(256) void decide_ens_kernel(const EnsIn logits, int
             ens_stats[r + 1] = tl;
         }
         // the seed of member k's backward pass: g_logits_k[b][c] = (c == target_b) ? -/+1 : 0
-        float* gl = member(g_logits, k) + (size_t)b * ncls;
+        float* gl = ptr_of(g_logits, k) + (size_t)b * ncls;
         for (int i = threadIdx.x; i < ncls; i += 256) gl[i] = (i == tgt) ? seed : 0.f;
     }
     float a, d;
@@ -103,7 +92,7 @@ __global__ __launch_bounds__(256) void ens_sumsq_kernel(const EnsIn g, float* __
     const int pix = blockIdx.x * 256 + threadIdx.x;
     float ss = 0.f;
     if (pix < HW) {
-        const float4 v = reinterpret_cast<const float4*>(member(g, k))[(size_t)b * HW + pix];
+        const float4 v = reinterpret_cast<const float4*>(ptr_of(g, k))[(size_t)b * HW + pix];
         ss = v.x * v.x + v.y * v.y + v.z * v.z;
     }
     ss = block_sum(ss, red);
@@ -126,23 +115,13 @@ __global__ __launch_bounds__(256) void ens_combine_kernel(const EnsIn g, int K, 
         const float nrm = sqrtf(a);
         const float w = ens_w[(size_t)b * K + k];
         if (pix < HW && nrm > 0.f && w != 0.f) {
-            const float4 v = reinterpret_cast<const float4*>(member(g, k))[(size_t)b * HW + pix];
+            const float4 v = reinterpret_cast<const float4*>(ptr_of(g, k))[(size_t)b * HW + pix];
             acc.x += w * (v.x / nrm);
             acc.y += w * (v.y / nrm);
             acc.z += w * (v.z / nrm);
         }
     }
     if (pix < HW) g_adv[(size_t)b * HW + pix] = acc;
-}
-
-template <typename T, typename P>
-bool gather(T& t, P* const* host, int K) {
-    if (!host || K < 2 || K > SPAA_ENS_MAX) return false;
-    for (int k = 0; k < SPAA_ENS_MAX; ++k) {
-        t.p[k] = k < K ? host[k] : nullptr;
-        if (k < K && !host[k]) return false;
-    }
-    return true;
 }
 
 }  // namespace

@@ -13,40 +13,18 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/spaa_hip.h"
+#include "ptr_table.hpp"
+#include "draw_rng.hpp"
 
 namespace {
 
 template <typename T>
-struct Draws {
-    T* p[SPAA_JITTER_MAX];
-};
-
-// draw j's pointer (j is uniform per workgroup; selects, so that the argument struct stays in the kernel-argument segment)
-template <typename T>
-__device__ __forceinline__ T* draw_ptr(const Draws<T>& t, int j) {
-    return j == 0 ? t.p[0] : j == 1 ? t.p[1] : j == 2 ? t.p[2] : t.p[3];
-}
-
-__host__ __device__ __forceinline__ uint32_t mix32(uint32_t x) {
-    x ^= x >> 16;
-    x *= 0x7feb352du;
-    x ^= x >> 15;
-    x *= 0x846ca68bu;
-    x ^= x >> 16;
-    return x;
-}
+using Draws = PtrTable<T, SPAA_JITTER_MAX>;
 
 // the word of (seed, t, b, j, parameter index i)
 __device__ __forceinline__ uint32_t draw_word(uint32_t seed, uint32_t t, uint32_t b, uint32_t j, uint32_t i) {
-    uint32_t h = mix32(seed ^ 0x9e3779b9u);
-    h = mix32(h ^ t);
-    h = mix32(h ^ b);
-    h = mix32(h ^ j);
-    return mix32(h ^ i);
+    return draw_word(0x9e3779b9u, seed, t, b, j, i);
 }
-
-// 2 u - 1 with u = (h >> 8) 2^-24: exact in fp32
-__device__ __forceinline__ float signed_unit(uint32_t h) { return (float)((int32_t)(h >> 8) * 2 - (1 << 24)) * 0x1p-24f; }
 
 enum { JIT_GAIN = 0, JIT_OFFSET = 3, JIT_DX = 4, JIT_DY = 5, JIT_SIGMA = 6, JIT_KEY = 7 };   // parameter indices = columns of a row
 
@@ -132,8 +110,8 @@ __device__ __forceinline__ void jitter_fwd_pixel(const float4* __restrict__ y, c
         if (quantize) v = floorf(v * 255.f) / 255.f;
         o[c] = v;
     }
-    reinterpret_cast<float4*>(draw_ptr(out, j))[(size_t)b * HW + pix] = make_float4(o[0], o[1], o[2], 0.f);
-    draw_ptr(gate, j)[(size_t)b * HW + pix] = (uint8_t)bits;
+    reinterpret_cast<float4*>(ptr_of(out, j))[(size_t)b * HW + pix] = make_float4(o[0], o[1], o[2], 0.f);
+    ptr_of(gate, j)[(size_t)b * HW + pix] = (uint8_t)bits;
 }
 
 // every draw from the one image batch y
@@ -147,7 +125,7 @@ __global__ __launch_bounds__(256) void jitter_fwd_kernel(const float4* __restric
 __global__ __launch_bounds__(256) void jitter_fwd_each_kernel(const Draws<const float> y, const float4* __restrict__ jit,
                                                               const uint32_t* __restrict__ key, int quantize, const Draws<float> out,
                                                               const Draws<uint8_t> gate, int H, int W) {
-    jitter_fwd_pixel(reinterpret_cast<const float4*>(draw_ptr(y, (int)blockIdx.y)), jit, key, quantize, out, gate, H, W);
+    jitter_fwd_pixel(reinterpret_cast<const float4*>(ptr_of(y, (int)blockIdx.y)), jit, key, quantize, out, gate, H, W);
 }
 
 // One axis of S^T as a gather: input index n receives from the output indices m in [lo, hi] those whose clamped taps land on n.
@@ -175,8 +153,8 @@ __global__ __launch_bounds__(256) void jitter_bwd_kernel(const Draws<const float
     const Axis ax = axis_of(hi.x), ay = axis_of(hi.y);
     const int r = pix / W, q = pix - r * W;
     const Span sr = span_of(r, ay.k, H), sq = span_of(q, ax.k, W);
-    const float4* gb = reinterpret_cast<const float4*>(draw_ptr(g_out, j)) + (size_t)b * HW;
-    const uint8_t* tb = draw_ptr(gate, j) + (size_t)b * HW;
+    const float4* gb = reinterpret_cast<const float4*>(ptr_of(g_out, j)) + (size_t)b * HW;
+    const uint8_t* tb = ptr_of(gate, j) + (size_t)b * HW;
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
     for (int mi = sr.lo; mi <= sr.hi; ++mi) {
         const float wr = tap_weight(mi, r, ay, H);
@@ -193,23 +171,7 @@ __global__ __launch_bounds__(256) void jitter_bwd_kernel(const Draws<const float
         acc.y += wr * line.y;
         acc.z += wr * line.z;
     }
-    reinterpret_cast<float4*>(draw_ptr(g_y, j))[(size_t)b * HW + pix] = acc;
-}
-
-template <typename T>
-bool gather(Draws<T>& t, T* const* host, int J) {
-    if (!host || J < 2 || J > SPAA_JITTER_MAX) return false;
-    for (int j = 0; j < SPAA_JITTER_MAX; ++j) {
-        t.p[j] = j < J ? host[j] : nullptr;
-        if (j < J && !host[j]) return false;
-    }
-    return true;
-}
-
-bool image_grid(int B, int J, int H, int W, dim3& grid) {
-    if (B < 1 || B > 65535 || H < 1 || W < 1 || (int64_t)H * W > (int64_t)1 << 30) return false;
-    grid = dim3((unsigned)((H * W + 255) / 256), (unsigned)J, (unsigned)B);
-    return true;
+    reinterpret_cast<float4*>(ptr_of(g_y, j))[(size_t)b * HW + pix] = acc;
 }
 
 }  // namespace

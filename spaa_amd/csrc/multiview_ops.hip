@@ -2,31 +2,19 @@
 // views' logits and stealth losses, the combination of the V input gradients at the projector image, and the best-image tracking of
 // the views after the first.
 //
-// Per-view tensors arrive as HOST arrays of V device pointers, copied into a kernel argument passed by value (as ensemble_ops.hip: no
-// device pointer table, a captured graph holds no copy).  The per-sample tables state [B][4] / stats [B][8] keep the meaning the rest
+// Per-view tensors arrive as HOST arrays of V device pointers and travel in a by-value kernel argument (ptr_table.hpp).  The per-sample tables state [B][4] / stats [B][8] keep the meaning the rest
 // of the loop reads ("Multi-view attack").  All reductions run in a fixed order: no atomics.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/spaa_hip.h"
 #include "device_util.hpp"
 #include "decide_util.hpp"
+#include "ptr_table.hpp"
 
 namespace {
 
-struct ViewsIn {
-    const float* p[SPAA_VIEWS_MAX];
-};
-struct ViewsOut {
-    float* p[SPAA_VIEWS_MAX];
-};
-
-// view v's pointer (v is uniform per workgroup; selects, so that the argument struct stays in the kernel-argument segment)
-__device__ __forceinline__ const float* view(const ViewsIn& t, int v) {
-    return v == 0 ? t.p[0] : v == 1 ? t.p[1] : v == 2 ? t.p[2] : t.p[3];
-}
-__device__ __forceinline__ float* view(const ViewsOut& t, int v) {
-    return v == 0 ? t.p[0] : v == 1 ? t.p[1] : v == 2 ? t.p[2] : t.p[3];
-}
+using ViewsIn = PtrTable<const float, SPAA_VIEWS_MAX>;
+using ViewsOut = PtrTable<float, SPAA_VIEWS_MAX>;
 
 // One workgroup per sample.  View v: top1, p1, the target logit and the loss means as decide_kernel computes them (decide_util.hpp);
 // succ_v = (top1 == target) if targeted else (top1 != target); fooled_v = succ_v && p1 > p_thresh if targeted else succ_v.
@@ -50,11 +38,11 @@ __global__ __launch_bounds__(256) void decide_views_kernel(const ViewsIn logits,
     unsigned fooled_bits = 0;
     float p_min = INFINITY, tl_sum = 0.f, caml2_sum = 0.f, camdE_sum = 0.f;
     for (int v = 0; v < V; ++v) {
-        const float* lg = view(logits, v) + (size_t)b * ncls;
+        const float* lg = ptr_of(logits, v) + (size_t)b * ncls;
         int am;
         float p1, a, d;
         decide_top1(lg, ncls, lds, am, p1);
-        decide_loss_sums(view(partial, v) + 3 * (size_t)b * nblk, nblk, lds, a, d);
+        decide_loss_sums(ptr_of(partial, v) + 3 * (size_t)b * nblk, nblk, lds, a, d);
         // this view's means caml2_v, camdE_v (decide_losses with the weights off: tmp[1], tmp[2])
         float tmp[5], col_v;
         decide_losses(a, d, HW, 0.f, 0.f, 0.f, 0.f, 0.f, tmp, col_v);
@@ -78,7 +66,7 @@ __global__ __launch_bounds__(256) void decide_views_kernel(const ViewsIn logits,
             view_stats[4 * r + 3] = tmp[2];
         }
         // the seed of view v's classifier backward pass, as decide_kernel writes it
-        float* gl = view(g_logits, v) + (size_t)b * ncls;
+        float* gl = ptr_of(g_logits, v) + (size_t)b * ncls;
         for (int i = threadIdx.x; i < ncls; i += 256) gl[i] = (i == tgt) ? seed : 0.f;
     }
     if (threadIdx.x == 0) {
@@ -119,7 +107,7 @@ __global__ __launch_bounds__(256) void views_combine_kernel(const ViewsIn g, int
     if (state[4 * b + 1] != 0) {   // (uniform per workgroup)
         if (pix < HW) {
             for (int v = 0; v < V; ++v) {
-                const float4 t = reinterpret_cast<const float4*>(view(g, v))[idx];
+                const float4 t = reinterpret_cast<const float4*>(ptr_of(g, v))[idx];
                 acc.x += t.x;
                 acc.y += t.y;
                 acc.z += t.z;
@@ -138,7 +126,7 @@ __global__ __launch_bounds__(256) void views_combine_kernel(const ViewsIn g, int
             const float nrm = sqrtf(a);
             const float w = view_w[(size_t)b * V + v];
             if (pix < HW && nrm > 0.f && w != 0.f) {
-                const float4 t = reinterpret_cast<const float4*>(view(g, v))[idx];
+                const float4 t = reinterpret_cast<const float4*>(ptr_of(g, v))[idx];
                 acc.x += w * (t.x / nrm);
                 acc.y += w * (t.y / nrm);
                 acc.z += w * (t.z / nrm);
@@ -155,18 +143,7 @@ __global__ __launch_bounds__(256) void views_track_kernel(const ViewsIn cam, con
     const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (idx >= (int64_t)B * HW) return;
     const int b = (int)(idx / HW);
-    if (state[4 * b] != 0) reinterpret_cast<float4*>(view(cam_best, v))[idx] = reinterpret_cast<const float4*>(view(cam, v))[idx];
-}
-
-// the V host pointers into the kernel argument; entries from `first` on must be set
-template <typename T, typename P>
-bool gather(T& t, P* const* host, int V, int first = 0) {
-    if (!host || V < 2 || V > SPAA_VIEWS_MAX) return false;
-    for (int v = 0; v < SPAA_VIEWS_MAX; ++v) {
-        t.p[v] = (v >= first && v < V) ? host[v] : nullptr;
-        if (v >= first && v < V && !host[v]) return false;
-    }
-    return true;
+    if (state[4 * b] != 0) reinterpret_cast<float4*>(ptr_of(cam_best, v))[idx] = reinterpret_cast<const float4*>(ptr_of(cam, v))[idx];
 }
 
 }  // namespace

@@ -13,41 +13,19 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/spaa_hip.h"
+#include "ptr_table.hpp"
+#include "draw_rng.hpp"
 
 namespace {
 
 template <typename T>
-struct Draws {
-    T* p[SPAA_JITTER_MAX];
-};
-
-// draw j's pointer (j is uniform per workgroup; selects, so that the argument struct stays in the kernel-argument segment)
-template <typename T>
-__device__ __forceinline__ T* draw_ptr(const Draws<T>& t, int j) {
-    return j == 0 ? t.p[0] : j == 1 ? t.p[1] : j == 2 ? t.p[2] : t.p[3];
-}
-
-__device__ __forceinline__ uint32_t mix32(uint32_t x) {
-    x ^= x >> 16;
-    x *= 0x7feb352du;
-    x ^= x >> 15;
-    x *= 0x846ca68bu;
-    x ^= x >> 16;
-    return x;
-}
+using Draws = PtrTable<T, SPAA_JITTER_MAX>;
 
 // the word of (seed, t, b, j, parameter index i): jitter's chain behind another first constant, so that a pose table and a jitter
 // table of one seed are independent
 __device__ __forceinline__ uint32_t draw_word(uint32_t seed, uint32_t t, uint32_t b, uint32_t j, uint32_t i) {
-    uint32_t h = mix32(seed ^ 0x85ebca6bu);
-    h = mix32(h ^ t);
-    h = mix32(h ^ b);
-    h = mix32(h ^ j);
-    return mix32(h ^ i);
+    return draw_word(0x85ebca6bu, seed, t, b, j, i);
 }
-
-// 2 u - 1 with u = (h >> 8) 2^-24: exact in fp32
-__device__ __forceinline__ float signed_unit(uint32_t h) { return (float)((int32_t)(h >> 8) * 2 - (1 << 24)) * 0x1p-24f; }
 
 enum { POSE_ROT = 0, POSE_ZOOM = 1, POSE_TX = 2, POSE_TY = 3, POSE_PX = 4, POSE_PY = 5 };   // parameter indices of the generator
 
@@ -131,7 +109,7 @@ __global__ __launch_bounds__(256) void pose_fwd_kernel(const float4* __restrict_
         if (y1 && x0) add_tap(acc, s.w10, yb[(s.y0 + 1) * W + s.x0]);
         if (y1 && x1) add_tap(acc, s.w11, yb[(s.y0 + 1) * W + s.x0 + 1]);
     }
-    reinterpret_cast<float4*>(draw_ptr(out, j))[(size_t)b * HW + pix] = acc;
+    reinterpret_cast<float4*>(ptr_of(out, j))[(size_t)b * HW + pix] = acc;
 }
 
 enum { POSE_WINDOW = 2 };   // the adjoint looks at the output pixels within 2 of round(H^-1 p): what the ranges of PoseJitter bound
@@ -164,7 +142,7 @@ __global__ __launch_bounds__(256) void pose_bwd_kernel(const Draws<const float> 
         const int mc = (int)fc, mr = (int)fr;
         const int c_lo = max(mc - POSE_WINDOW, 0), c_hi = min(mc + POSE_WINDOW, W - 1);
         const int r_lo = max(mr - POSE_WINDOW, 0), r_hi = min(mr + POSE_WINDOW, H - 1);
-        const float4* gb = reinterpret_cast<const float4*>(draw_ptr(g_out, j)) + (size_t)b * HW;
+        const float4* gb = reinterpret_cast<const float4*>(ptr_of(g_out, j)) + (size_t)b * HW;
         for (int mi = r_lo; mi <= r_hi; ++mi) {
             for (int mk = c_lo; mk <= c_hi; ++mk) {
                 const Source s = source_of(lo, hi, mi, mk, H, W);
@@ -176,23 +154,7 @@ __global__ __launch_bounds__(256) void pose_bwd_kernel(const Draws<const float> 
             }
         }
     }
-    reinterpret_cast<float4*>(draw_ptr(g_y, j))[(size_t)b * HW + pix] = acc;
-}
-
-template <typename T>
-bool gather(Draws<T>& t, T* const* host, int J) {
-    if (!host || J < 2 || J > SPAA_JITTER_MAX) return false;
-    for (int j = 0; j < SPAA_JITTER_MAX; ++j) {
-        t.p[j] = j < J ? host[j] : nullptr;
-        if (j < J && !host[j]) return false;
-    }
-    return true;
-}
-
-bool image_grid(int B, int J, int H, int W, dim3& grid) {
-    if (B < 1 || B > 65535 || H < 1 || W < 1 || (int64_t)H * W > (int64_t)1 << 30) return false;
-    grid = dim3((unsigned)((H * W + 255) / 256), (unsigned)J, (unsigned)B);
-    return true;
+    reinterpret_cast<float4*>(ptr_of(g_y, j))[(size_t)b * HW + pix] = acc;
 }
 
 }  // namespace

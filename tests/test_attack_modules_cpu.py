@@ -1,4 +1,5 @@
-"""CPU: the attack's three modules -- projector_based_attack (the attack, and the import surface), attack_driver and attack_summary:
+"""CPU: the attack's modules -- projector_based_attack (the entry points, and the import surface), attack_options, attack_state,
+attack_driver and attack_summary:
 every public name stays reachable where it always was, importing the attack does not import pandas, AttackSetup reads a setup as the
 drivers did, and the deep-learning driver's host logic (what it hands the attack, what it saves, in which order) with the attack
 stubbed."""
@@ -18,7 +19,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FACADE = {
     'CLAMP_BITS': 'projector_based_attack', 'GRAPH_MAX_PIXELS': 'projector_based_attack', 'LAST_RUN': 'projector_based_attack',
     'LOSS_TERMS': 'projector_based_attack', 'loss_weights': 'projector_based_attack',
-    'AttackState': 'projector_based_attack', 'spaa': 'projector_based_attack', 'spaa_attack': 'projector_based_attack',
+    'spaa': 'projector_based_attack', 'spaa_attack': 'projector_based_attack', '_attack_state': 'projector_based_attack',
+    'AttackState': 'attack_state', 'EnsembleAttackState': 'attack_state', 'MultiViewAttackState': 'attack_state',
+    'JitterAttackState': 'attack_state', 'PoseAttackState': 'attack_state',
+    'CaptureJitter': 'attack_options', 'PoseJitter': 'attack_options', 'Transfer': 'attack_options', 'ENS_MAX': 'attack_options',
+    'VIEWS_MAX': 'attack_options', 'JITTER_MAX': 'attack_options', 'TRANSFER_RMAX': 'attack_options', 'POSE_MAX_ROTATE': 'attack_options',
+    '_attention_supported': 'attack_options', '_attention_checked': 'attack_options',
     'plan_sweep': 'projector_based_attack', 'split_sweep': 'projector_based_attack', 'spaa_sweep': 'projector_based_attack',
     'ATTACKERS': 'attack_driver', 'MODEL_TRAIN_CFG': 'attack_driver', 'get_attacker_cfg': 'attack_driver',
     'to_attacker_cfg_str': 'attack_driver',
