@@ -866,6 +866,37 @@ int spaa_transfer_blur(const float* g, const int32_t* state, const float* taps, 
 int spaa_transfer_momentum(const float* t, const float* partial_l1, int tiles, float mu, const int32_t* state, float* m, float* g,
                            float* partial_ss, int npartial, int B, int HW, spaa_stream_t stream);
 
+/* ---- SSIM stealth term of the attack loop, 'camssim'  --------------------------------------------------------------
+ * SSIM_b(y, scene) as pytorch_ssim._ssim(size_average=False): the 11-tap Gaussian (sigma 1.5) along both axes after replicate padding
+ * by 5, C1 = 0.01^2, C2 = 0.03^2, each colour channel on its own, the mean over the 3 H W values of the map S.  Images and maps are
+ * [B][H][W][4] fp32; the pad channel is never read into a result and is written 0 in the maps.  `taps` is a HOST array of 11 floats,
+ * copied into the launch's arguments.  w_ps [B] (device): per-sample weights; a sample with weight 0 is skipped by spaa_ssim_fwd,
+ * spaa_ssim_bwd and spaa_ssim_value: none of its rows of the maps, partial, g_y or ssim is read or written.  fp32 with fused
+ * multiply-adds, taps in index order, rows first; no atomics and fixed summation orders: bitwise repeatable.  One launch each, none
+ * syncs.  A null pointer, a non-positive size, B > 65535 or H W > 2^30: hipErrorInvalidValue and nothing is launched. */
+#define SPAA_SSIM_TILE_H 16
+#define SPAA_SSIM_TILE_W 32
+/* tiles per image (SPAA_SSIM_TILE_H x SPAA_SSIM_TILE_W pixels, row-major); 0 for sizes that the launches refuse */
+int spaa_ssim_tiles(int H, int W);
+/* the window statistics of the scene alone, for every sample (F: replicate-pad, rows, then columns): the window mean and second moment
+ * of scene - c, c per tile and channel the scene's value at the tile's first pixel: mu2 = F (scene - c), e22 = F (scene - c)^2.
+ * spaa_ssim_fwd accumulates its three statistics about the same constants and shifts the means back, so that the variances do not
+ * cancel in fp32; S and the maps are those of the unshifted definition. */
+int spaa_ssim_scene_stats(const float* scene, const float* taps, float* mu2, float* e22, int B, int H, int W, spaa_stream_t stream);
+/* mu1 = F y, e11 = F y^2, e12 = F (y scene); per pixel and channel
+ *   S = A1 A2 / (B1 B2), A1 = 2 mu1 mu2 + C1, A2 = 2 (e12 - mu1 mu2) + C2, B1 = mu1^2 + mu2^2 + C1, B2 = (e11 - mu1^2) + (e22 - mu2^2) + C2
+ * and m_mu = dS/dmu1, m_11 = dS/de11, m_12 = dS/de12 (the algebra of spaa_train_loss_fwd_bwd); partial [B][tiles] = each tile's sum of
+ * S over its pixels and colour channels (the fixed-order block sum), tiles = spaa_ssim_tiles(H, W). */
+int spaa_ssim_fwd(const float* y, const float* scene, const float* mu2, const float* e22, const float* taps, const float* w_ps, float* m_mu,
+                  float* m_11, float* m_12, float* partial, int B, int H, int W, spaa_stream_t stream);
+/* g_y[q] += -gscale w_ps[b] (F^T m_mu + 2 y[q] F^T m_11 + scene[q] F^T m_12)[q] on the three colour channels: gscale w_ps[b] times the
+ * gradient of 3 H W (1 - SSIM_b) at y.  F^T is the adjoint of F: an edge pixel also collects the taps of the pad cells that copy it. */
+int spaa_ssim_bwd(const float* y, const float* scene, const float* m_mu, const float* m_11, const float* m_12, const float* taps,
+                  const float* w_ps, float gscale, float* g_y, int B, int H, int W, spaa_stream_t stream);
+/* ssim [B]: ssim[b] = (sum of partial[b][0 .. tiles - 1] in index order, in double) / (3 H W), rounded once to fp32;
+ * tiles must be spaa_ssim_tiles(H, W) */
+int spaa_ssim_value(const float* partial, const float* w_ps, int tiles, int H, int W, float* ssim, int B, spaa_stream_t stream);
+
 /* ---- PerC_AL.adversary_projector (perc_al/__init__.py:133-256) ------------------------------------------ */
 /* x = a + b (inputs + delta), NHWC4 */
 int spaa_add_nhwc4(const float* a, const float* b, float* x, int npix, spaa_stream_t stream);

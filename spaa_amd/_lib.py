@@ -213,6 +213,10 @@ _SIGNATURES = {
     'spaa_attention_apply': [_p, _p, _f, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p],
     'spaa_transfer_blur': [_p, _p, C.POINTER(C.c_float), _i, _p, _p, _i, _i, _i, _p],
     'spaa_transfer_momentum': [_p, _p, _i, _f, _p, _p, _p, _p, _i, _i, _i, _p],
+    'spaa_ssim_scene_stats': [_p, C.POINTER(C.c_float), _p, _p, _i, _i, _i, _p],
+    'spaa_ssim_fwd': [_p, _p, _p, _p, C.POINTER(C.c_float), _p, _p, _p, _p, _p, _i, _i, _i, _p],
+    'spaa_ssim_bwd': [_p, _p, _p, _p, _p, C.POINTER(C.c_float), _p, _f, _p, _i, _i, _i, _p],
+    'spaa_ssim_value': [_p, _p, _i, _i, _i, _p, _i, _p],
     'spaa_onepixel_preproc': [_p, _p, _i, _i, _i, _p, _i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_float), C.POINTER(C.c_float), _p],
     'spaa_onepixel_score': [_p, _i, _i, _i, _p, _p, _p, _i, _p],
     'spaa_onepixel_warp': [_p, _p, _i, _i, _i, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p],
@@ -230,7 +234,7 @@ _SIGNATURES = {
 }
 
 EXPORTS = sorted(list(_SIGNATURES) + ['spaa_version', 'spaa_tapconv_sizeof', 'spaa_tapconv_offsetof', 'spaa_tapconv_wino_plan', 'spaa_tapconv_h16p_plan',
-                                         'spaa_tapconv_tile_info', 'spaa_tapconv_check', 'spaa_transfer_tiles'])
+                                         'spaa_tapconv_tile_info', 'spaa_tapconv_check', 'spaa_transfer_tiles', 'spaa_ssim_tiles'])
 
 _lib = None
 
@@ -262,6 +266,8 @@ def load():
     lib.spaa_tapconv_check.restype = C.c_int
     lib.spaa_transfer_tiles.argtypes = [C.c_int, C.c_int]                              # (host-side query: no stream)
     lib.spaa_transfer_tiles.restype = C.c_int
+    lib.spaa_ssim_tiles.argtypes = [C.c_int, C.c_int]                                  # (host-side query: no stream)
+    lib.spaa_ssim_tiles.restype = C.c_int
     _lib = lib
     return lib
 

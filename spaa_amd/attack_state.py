@@ -74,10 +74,14 @@ class AttackState:
         eng.set_scene(scene4)
         scene_lab = torch.zeros_like(scene4)
         _lib.call('spaa_rgb2lab', _lib.ptr(scene4), _lib.ptr(scene_lab), B * Hc * Wc)
+        if self.any_ssim:   # the window statistics of the scene alone: once per attack and view
+            mu2, e22 = torch.zeros_like(scene4), torch.zeros_like(scene4)
+            _lib.call('spaa_ssim_scene_stats', _lib.ptr(scene4), self._ssim_taps, _lib.ptr(mu2), _lib.ptr(e22), B, Hc, Wc)
+            self.ssim_scene_stats.append((mu2, e22))
         return eng, clf, scene4, scene_lab
 
     def _build(self, pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, dev):
-        from .projector_based_attack import CLAMP_BITS, loss_weights   # (the switches live with the entry points)
+        from .projector_based_attack import CLAMP_BITS, loss_weights, ssim_weight   # (the switches live with the entry points)
         B = len(target_idx)
         if B < 1:
             raise ValueError('target_idx is empty: nothing to attack')
@@ -85,9 +89,27 @@ class AttackState:
         prj_sz = tuple(setup_info['prj_im_sz'])
         self.cp_sz = tuple(setup_info['classifier_crop_sz'])
         self.gray = float(setup_info['prj_brightness'])
+        # `stealth_loss`: one string for the batch, or one per sample (spaa_sweep)
+        losses = [stealth_loss] * B if isinstance(stealth_loss, str) else list(stealth_loss)
+        # the SSIM term has its own launches with a weight per sample; without it in any string nothing of it exists
+        ssim_w = [ssim_weight(s) for s in losses]
+        self.any_ssim, self.ssim, self.ssims = any(ssim_w), None, None
+        if self.any_ssim:
+            from .metrics import ssim_taps
+            self._ssim_taps = (ctypes.c_float * 11)(*ssim_taps().tolist())
+            self.ssim_scene_stats = []   # (mu2, e22) per view, in the order of the views
         self.eng, self.clf, self.scene4, self.scene_lab = self._lease_view(pcnet, classifier, cam_scene, setup_info)
         self.clfs = [self.clf]   # (one engine per member / view where there are several)
         Hc, Wc = self.eng.Hc, self.eng.Wc
+        if self.any_ssim:
+            # the three maps of dS/d(window statistics) are shared by the views (forward and adjoint run back to back), the tile sums
+            # of S and the per-sample SSIM of the last iteration are per view: `ssims[v]`, `ssim` = `ssims[0]`
+            self.ssim_w = torch.tensor(ssim_w, dtype=torch.float32, device=dev)
+            self.ssim_maps = [torch.zeros(B, Hc, Wc, 4, device=dev) for _ in range(3)]
+            self.ssim_tiles = _lib.load().spaa_ssim_tiles(Hc, Wc)
+            self.ssim_partials = [torch.zeros(B, self.ssim_tiles, device=dev)]
+            self.ssims = [torch.zeros(B, device=dev)]
+            self.ssim = self.ssims[0]
         # fp16 gradients need a loss scale (fp16's smallest normal is 6e-5; the per-pixel loss gradients are ~1/(B*H*W)).
         # Each sample's gradient is normalised before the step (:307, :315), so a positive per-branch scale changes
         # nothing but the fp16 rounding: stealth branch: 1/16 per pixel instead of 1/(B*H*W); adversarial branch: +-16
@@ -118,9 +140,8 @@ class AttackState:
         self.g_logits = torch.zeros(B, self.clf.ncls, device=dev)
         self.prjl2 = torch.zeros(B, device=dev)
         self.target = torch.tensor([int(t) for t in target_idx], dtype=torch.int32, device=dev)
-        # `stealth_loss`: one string for the batch, or one per sample (spaa_sweep).  self.prjl2_w / caml2_w / camdE_w are the batch's
-        # weights when every sample has the same ones, else None: the per-sample table of the _ps launches carries them.
-        losses = [stealth_loss] * B if isinstance(stealth_loss, str) else list(stealth_loss)
+        # self.prjl2_w / caml2_w / camdE_w are the batch's weights when every sample has the same ones, else None: the per-sample table
+        # of the _ps launches carries them.
         if len(losses) != B:
             raise ValueError(f'stealth_loss: {len(losses)} strings for {B} samples')
         self.loss_w = [loss_weights(s) for s in losses]
@@ -208,6 +229,23 @@ class AttackState:
         _lib.call('spaa_stealth_loss_fwd_bwd_ps', p(y), p(scene4), p(lab), p(self.ps_params), self.gs_col / (self.B * self.HWc),
                   p(g_col), None, p(partial), self.B, self.HWc)
 
+    def _ssim_term(self, y, v=None):
+        """The SSIM term of camera image y (the state's own view, or view v), directly behind the stealth-loss launch that has written
+        g_col: for every sample with 'camssim' in its string, g_col += gscale d(1 - SSIM_b)/dy with gscale = gs_col / B (the loop's
+        batch mean and loss scale; the SSIM mean over 3 Hc Wc is the launch's), and ssims[v] = SSIM_b.  The other samples' rows are
+        not touched.  Three launches, no host read; without the term in any string none."""
+        if not self.any_ssim:
+            return
+        p, v = _lib.ptr, v or 0
+        scene4, g_col = (self.scene4, self.g_col) if not v else (self.scene4s[v], self.g_cols[v])
+        (mu2, e22), (m_mu, m_11, m_12), partial = self.ssim_scene_stats[v], self.ssim_maps, self.ssim_partials[v]
+        Hc, Wc = self.eng.Hc, self.eng.Wc
+        _lib.call('spaa_ssim_fwd', p(y), p(scene4), p(mu2), p(e22), self._ssim_taps, p(self.ssim_w), p(m_mu), p(m_11), p(m_12),
+                  p(partial), self.B, Hc, Wc)
+        _lib.call('spaa_ssim_bwd', p(y), p(scene4), p(m_mu), p(m_11), p(m_12), self._ssim_taps, p(self.ssim_w),
+                  self.gs_col / (self.B * 3 * self.HWc), p(g_col), self.B, Hc, Wc)
+        _lib.call('spaa_ssim_value', p(partial), p(self.ssim_w), self.ssim_tiles, Hc, Wc, p(self.ssims[v]), self.B)
+
     def _forward_decide(self, targeted, d_thr, p_thresh, adv_w):
         B, p = self.B, _lib.ptr
         uni = self._per_sample(targeted, d_thr)
@@ -217,6 +255,7 @@ class AttackState:
         if uni is None:   # several attack configurations in one batch: the same kernels, their parameters per sample
             prjl2 = self._prjl2_fwd()
             self._stealth_loss_ps(y)
+            self._ssim_term(y)
             _lib.call('spaa_decide_ps', p(logits), self.clf.ncls, p(self.target), p(self.partial_loss), self.nblk_c, self.HWc,
                       prjl2, p(self.ps_params), p(self.ps_flags), float(p_thresh), adv_w / B * self.gs_adv,
                       p(self.state), p(self.stats), p(self.g_logits), B)
@@ -226,6 +265,7 @@ class AttackState:
             _lib.call('spaa_prjl2_fwd', p(self.x), self.gray, p(self.prjl2), B, self.HWp)    # :275
         _lib.call('spaa_stealth_loss_fwd_bwd', p(y), p(self.scene4), p(self.scene_lab), self.caml2_w, self.camdE_w,
                   self.gs_col / (B * self.HWc), p(self.g_col), None, p(self.partial_loss), B, self.HWc)   # :279-287 + bwd
+        self._ssim_term(y)
         _lib.call('spaa_decide', p(logits), self.clf.ncls, p(self.target), int(bool(targeted)), p(self.partial_loss),
                   self.nblk_c, self.HWc, p(self.prjl2) if self.prjl2_w else None, self.prjl2_w, self.caml2_w,
                   self.camdE_w, float(d_thr), float(p_thresh), adv_w / B * self.gs_adv, p(self.state), p(self.stats),
@@ -331,6 +371,7 @@ class EnsembleAttackState(AttackState):
         self._y, self._uniform = y, False
         prjl2 = self._prjl2_fwd()
         self._stealth_loss_ps(y)
+        self._ssim_term(y)
         _lib.call('spaa_decide_ens', _lib.ptr_array(logits), self.K, self.clf.ncls, p(self.target), p(self.partial_loss), self.nblk_c,
                   self.HWc, prjl2, p(self.ps_params), p(self.ps_flags), float(p_thresh), int(self.focus), p(self.state), p(self.stats),
                   p(self.ens_state), p(self.ens_stats), p(self.ens_w),
@@ -391,6 +432,9 @@ class MultiViewAttackState(AttackState):
         self.g_cols, self.gPs, self.partial_losses, self.view_g_logits = ([own] + [torch.zeros_like(own) for _ in more] for own in
                                                                           (self.g_col, self.gP, self.partial_loss, self.g_logits))
         self.cam_bests = [self.cam_best] + [scene4.clone() for scene4 in self.scene4s[1:]]
+        if self.any_ssim:
+            self.ssim_partials += [torch.zeros_like(self.ssim_partials[0]) for _ in more]
+            self.ssims += [torch.zeros_like(self.ssim) for _ in more]
         self.view_state = torch.zeros(B, V, 2, dtype=torch.int32, device=dev)
         self.view_stats = torch.zeros(B, V, 4, device=dev)
         self.view_w = torch.ones(B, V, device=dev)
@@ -406,6 +450,7 @@ class MultiViewAttackState(AttackState):
             y = self.engs[v].forward(self.x, clamp01=True)                           # :265, once per view
             logits.append(self.clfs[v].forward(y))                                   # :266
             self._stealth_loss_ps(y, v)
+            self._ssim_term(y, v)
             ys.append(y)
         self._ys, self._y, self._uniform = ys, ys[0], False
         prjl2 = self._prjl2_fwd()

@@ -36,6 +36,12 @@ def _window(window_size=11, sigma=1.5):
     return g.mm(g.t()).float().reshape(-1).contiguous()
 
 
+def ssim_taps(window_size=11, sigma=1.5):
+    """pytorch_ssim/__init__.py:9-12 (gaussian): the normalised 1-D Gaussian in float32, whose outer product `_window` is."""
+    g = torch.Tensor([math.exp(-(i - window_size // 2) ** 2 / float(2 * sigma ** 2)) for i in range(window_size)])
+    return g / g.sum()
+
+
 def center_crop_origin(h, w, size):
     """img_proc.py:126-132 (center_crop): the crop's top-left corner (Python's round, as the reference)."""
     th, tw = size

@@ -41,6 +41,12 @@ def loss_weights(stealth_loss):
             1.0 if 'camdE' in stealth_loss else 0.0)
 
 
+def ssim_weight(stealth_loss):
+    """The weight of the SSIM term 1 - SSIM(cam_infer, cam_scene) of a stealth-loss string: 1.0 when 'camssim' occurs in it, else 0.0
+    (not a term of the reference, so not one of loss_weights()'s three)."""
+    return 1.0 if 'camssim' in stealth_loss else 0.0
+
+
 def _attack_state(pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, device, storage, focus, jitter=None,
                   attention=None, transfer=None, pose=None):
     """AttackState for one Classifier, EnsembleAttackState for a checked list of several, MultiViewAttackState for a checked list of
@@ -91,7 +97,8 @@ def spaa(pcnet, classifier, imagenet_labels, target_idx, targeted, cam_scene, d_
     :param targeted: bool
     :param cam_scene: [3,H,W] / [1,3,H,W] / [B,3,H,W] in [0,1]
     :param d_thr: SPAA Algorithm 1's threshold on the mean per-pixel L2 perturbation (x255)
-    :param stealth_loss: string containing any of 'prjl2', 'caml2', 'camdE'
+    :param stealth_loss: string containing any of 'prjl2', 'caml2', 'camdE', 'camssim' (the last: 1 - SSIM of the inferred capture
+        against the scene joins the colour loss; a spaa_amd.Classifier only)
     :param setup_info: {'classifier_crop_sz', 'prj_brightness', 'prj_im_sz'}
     :param trace: optional list; receives per-iteration (state, stats) device tensors (no sync inside the loop); for an ensemble
         (state, stats, ens_state, ens_stats), where state[:, 3] counts the fooled members and ens_state holds each member's top-1;
@@ -170,8 +177,8 @@ def plan_sweep(configs, max_batch=64):
             loss, d_thr, targeted, target_idx = cfg
         except (TypeError, ValueError):
             raise ValueError(f'configs[{i}]: expected (stealth_loss, d_thr, targeted, target_idx), got {cfg!r}') from None
-        if not isinstance(loss, str) or not loss or any(t not in LOSS_TERMS for t in loss.split('_')):
-            raise ValueError(f'configs[{i}]: unknown stealth loss {loss!r} (terms joined by "_": {", ".join(LOSS_TERMS)})')
+        if not isinstance(loss, str) or not loss or any(t not in LOSS_TERMS + ('camssim',) for t in loss.split('_')):
+            raise ValueError(f'configs[{i}]: unknown stealth loss {loss!r} (terms joined by "_": {", ".join(LOSS_TERMS)}, camssim)')
         target_idx = list(target_idx)
         if not target_idx:
             raise ValueError(f'configs[{i}]: target_idx is empty: nothing to attack')
@@ -277,6 +284,8 @@ def _spaa_foreign_classifier(pcnet, classifier, imagenet_labels, target_idx, tar
     body, so this route keeps PCNet (forward + input gradient) and the stealth loss on the HIP kernels, lets torch.autograd
     carry the gradient through the foreign classifier, and follows the reference's loop :264-328 step by step — with one
     backward pass of the per-sample-selected loss instead of two (samples are independent, see AttackState)."""
+    if ssim_weight(stealth_loss):
+        raise NotImplementedError("spaa(): the 'camssim' term runs in the fused loop only: pass a spaa_amd.Classifier, not a callable")
     dev = _require_gpu(device, 'spaa')
     B = len(target_idx)
     with _lib.on_device(dev):
