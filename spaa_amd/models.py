@@ -390,6 +390,19 @@ def pack_s2f_x6(w_eff):
     return cp.split_planes(img).permute(1, 2, 0, 3, 4, 5).contiguous()                    # [3][ks][9][...] -> [ks][9][3][rb][64][8]
 
 
+def pack_tail(w_transconv2, w_conv6, f16):
+    """Weight images of the fused tail and head (csrc/shading_tail.hip) from transConv2's [64, 32, 2, 2] and conv6's [3, 32, 3, 3] weights,
+    on the CPU: w2 / w2t the transposed convolution as a GEMM matrix and its transpose, w6 conv6's taps channel-last, w6t its adjoint's."""
+    wt, w6 = w_transconv2.detach().float().cpu(), w_conv6.detach().float().cpu()
+    assert wt.shape == (64, 32, 2, 2) and w6.shape == (3, 32, 3, 3)
+    mat = (lambda w: w.half().contiguous()) if f16 else cp.split_planes   # fp16 storage: rounded to fp16 (one MFMA per product, as every layer of the mode)
+    w6p = w6.permute(0, 2, 3, 1).reshape(3, 9, 32).contiguous()
+    return dict(w2=mat(wt.permute(2, 3, 1, 0).reshape(128, 64)),        # ([3])[32 (2 py + px) + c][k]
+                w2t=mat(wt.permute(0, 2, 3, 1).reshape(64, 128)),       # ([3])[n][32 (2 py + px) + c]
+                w6=(w6p.half() if f16 else w6p),                        # [o][3 ky + kx][c]
+                w6t=w6.flip(2, 3).permute(2, 3, 0, 1).reshape(27, 32).contiguous())  # [3 t + o][c], taps mirrored
+
+
 def pack_pair1_bwd(w_conv1, w_conv1_s):
     """MFMA A operands of spaa_conv1_pair_bwd_f16 (include/spaa_hip.h): [2 sources][4 operands (r, q)][64 lanes][8] fp16.  Lane = (row
     4 (2 cy + cx) + c, 8-channel chunk g); element e = weight[n = 8 g + e][c (+ 3: conv1_s's rough input channels)][ky][kx] of the tap
@@ -538,14 +551,7 @@ def pcnet_routes(sn, use_rough, batch, cam_size, storage='f32', fuse_skip2=None,
             r.pair1_bwd = pack_pair1_bwd(sn.conv1.weight, sn.conv1_s.weight).to(dev)
     # tail / head (csrc/shading_tail.hip): transConv2 + conv6 and their adjoints as one launch each, X7 and its gradient never reach
     # HBM.  Needs the byte gate masks; the training step (weight gradients read X7 and P7) passes fuse_tail=False
-    wt, w6 = sn.transConv2.weight.detach().float().cpu(), sn.conv6.weight.detach().float().cpu()
-    assert wt.shape == (64, 32, 2, 2) and w6.shape == (3, 32, 3, 3)
-    mat = (lambda w: w.half().contiguous()) if f16 else cp.split_planes   # fp16 storage: rounded to fp16 (one MFMA per product, as every layer of the mode)
-    w6p = w6.permute(0, 2, 3, 1).reshape(3, 9, 32).contiguous()
-    r.tail = dict(w2=mat(wt.permute(2, 3, 1, 0).reshape(128, 64)).to(dev),      # ([3])[32 (2 py + px) + c][k]
-                  w2t=mat(wt.permute(0, 2, 3, 1).reshape(64, 128)).to(dev),     # ([3])[n][32 (2 py + px) + c]
-                  w6=(w6p.half() if f16 else w6p).to(dev),              # [o][3 ky + kx][c]
-                  w6t=w6.flip(2, 3).permute(2, 3, 0, 1).reshape(27, 32).contiguous().to(dev),  # [3 t + o][c], taps mirrored
+    r.tail = dict({k: v.to(dev) for k, v in pack_tail(sn.transConv2.weight, sn.conv6.weight, f16).items()},
                   b2=fbias('transConv2'), b6=fbias('conv6'))
     if FUSE_TAIL and fuse_tail is not False and byte_gates:
         packed('transConv2', 'conv6')
