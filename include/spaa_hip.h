@@ -755,7 +755,9 @@ int spaa_ens_combine(const float* const* g, int K, const float* partial, int nbl
  *   view_state int32 [B][V][2] = (bit 0 succ | bit 1 fooled, top1)    view_stats float [B][V][4] = (p1, target logit, caml2_v, camdE_v)
  *   view_w float [B][V]: the view weights of spaa_views_combine -- 1, or with focus != 0: 0 for a fooled view unless all are fooled
  *   g_logits: V seeds [B][ncls], (c == target_b) ? -adv_scale (targeted) / +adv_scale : 0
- * With V identical views (V a power of two) state[.][0..2], stats[.][1..5] and the seeds are bitwise those of spaa_decide_ps. */
+ * With V identical views (V a power of two) state[.][0..2], stats[.][1..5] and the seeds are bitwise those of spaa_decide_ps.
+ * spaa_decide_ens is the same kernel with one loss table for all members: given that table V times (V a power of two) and
+ * adv_scale = 1, state, stats, the weights, the seeds, view_state and view_stats[..][0..1] are bitwise spaa_decide_ens's. */
 int spaa_decide_views(const float* const* logits, int V, int ncls, const int32_t* target, const float* const* partial, int nblk, int HW,
                       const float* prjl2, const float* params, const int32_t* flags, float p_thresh, float adv_scale, int focus,
                       int32_t* state, float* stats, int32_t* view_state, float* view_stats, float* view_w, float* const* g_logits,
@@ -764,7 +766,8 @@ int spaa_decide_views(const float* const* logits, int V, int ncls, const int32_t
  * g_out_b = (sum over v in index order of g_bv) * (1 / V), the gradient of the mean of the views' stealth losses, not normalised (the
  * prjl2 term that spaa_grad_sumsq adds afterwards keeps its scale); for every other sample g_out_b = sum over v in index order of
  * view_w[b][v] * g_bv / ||g_bv||_2, a view with zero norm contributing 0.  The pad channel of g_out [B][HW][4] is 0.  partial
- * [B][V][nblk] from spaa_ens_sumsq with the same HW, nblk = ceil(HW / 256); run-to-run bitwise reproducible */
+ * [B][V][nblk] from spaa_ens_sumsq with the same HW, nblk = ceil(HW / 256); run-to-run bitwise reproducible.  Where no sample is on
+ * the colour step, g_out is bitwise spaa_ens_combine's (one kernel) */
 int spaa_views_combine(const float* const* g, int V, const float* partial, int nblk, const float* view_w, const int32_t* state,
                        float* g_out, int B, int HW, spaa_stream_t stream);
 /* cam_best[v]_b = cam[v]_b where state[b][0] != 0 (succ), for the views v = 1 .. V-1 in one launch: what spaa_step_and_track_n does

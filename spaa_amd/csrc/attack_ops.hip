@@ -36,33 +36,20 @@ __global__ __launch_bounds__(256) void decide_kernel(const float* __restrict__ l
         targeted = flags[b] & 1;
     }
     const float* lg = logits + (size_t)b * ncls;
-    // argmax (first maximum), softmax top-1 probability and the loss sums (fixed order): decide_util.hpp, shared with the ensemble form
+    // argmax (first maximum), softmax top-1 probability, the loss sums (fixed order), the success rules (:269-272, :290-299), the
+    // seed row and the commit: decide_util.hpp, shared with the group form
     int am;
     float p1, a, d;
     decide_top1(lg, ncls, lds, am, p1);
     decide_loss_sums(partial + 3 * (size_t)b * nblk, nblk, lds, a, d);
-    const int tgt = target[b];
-    // d adv_loss / d logits: adv_loss = -/+ mean_b logit[b, target_b]   (:269-272)
-    for (int i = threadIdx.x; i < ncls; i += 256)
-        g_logits[(size_t)b * ncls + i] = (i == tgt) ? (targeted ? -adv_scale : adv_scale) : 0.f;
+    const DecideMember m = decide_member(lg, ncls, target[b], targeted, am, p1, p_thresh, adv_scale, g_logits + (size_t)b * ncls);
     if (threadIdx.x == 0) {
         // (per-sample mode: a sample without the prjl2 term reads 0, as the scalar launch whose caller passes prjl2 = NULL)
         const float pl2 = (prjl2 != nullptr && (params == nullptr || prjl2_w != 0.f)) ? prjl2[b] : 0.f;
         float* st = stats + 8 * (size_t)b;
         float col;
         const bool high_pert = decide_losses(a, d, HW, pl2, prjl2_w, caml2_w, camdE_w, d_thr, st, col);
-        const bool high_conf = p1 > p_thresh;
-        const bool succ = targeted ? (am == tgt) : (am != tgt);
-        const bool best_adv = targeted ? (succ && high_conf && high_pert) : (succ && high_pert);
-        const bool best = best_adv && (col < st[5]);
-        if (best) st[5] = col;
-        st[0] = p1;
-        st[6] = lg[tgt];
-        int32_t* s = state + 4 * (size_t)b;
-        s[0] = succ;
-        s[1] = best_adv;
-        s[2] = best;
-        s[3] = am;
+        decide_commit(m.succ, m.fooled, high_pert, col, p1, m.tl, am, state + 4 * (size_t)b, st);
     }
 }
 

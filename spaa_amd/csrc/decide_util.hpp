@@ -1,8 +1,9 @@
-// decide_util.hpp — the per-sample arithmetic of SPAA's decision step, shared by decide_kernel (attack_ops.hip: one classifier),
-// decide_ens_kernel (ensemble_ops.hip: K classifiers on the same camera image) and decide_views_kernel (multiview_ops.hip: one
-// classifier on V camera images): a classifier's first-maximum arg-max and softmax top-1 probability, and the stealth-loss sums with
-// the colour loss built from them.  One copy, so that a member of an ensemble, or a view, gets bitwise what spaa_decide /
-// spaa_decide_ps give that classifier and camera image alone.  Workgroups of 256 threads.
+// decide_util.hpp — the per-sample arithmetic and rules of SPAA's decision step, shared by decide_kernel (attack_ops.hip: one
+// classifier) and decide_group_kernel (group_ops.hip: the members of an ensemble, the views or the draws of a sample): a classifier's
+// first-maximum arg-max and softmax top-1 probability, the stealth-loss sums with the colour loss built from them, a member's succ /
+// fooled rule and seed row, and the sample's best_adv / best rule with the state and stats words.  One copy, so that a member of an
+// ensemble, or a view, gets bitwise what spaa_decide / spaa_decide_ps give that classifier and camera image alone.  Workgroups of 256
+// threads.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -84,6 +85,42 @@ __device__ __forceinline__ bool decide_losses(float a, float d, int HW, float pl
     st[3] = col;
     st[4] = pl2;
     return caml2 * 255.f > d_thr;
+}
+
+// One classifier's outcome on one image (the plain form's, an ensemble member's, a view's, a draw's), valid in every thread
+struct DecideMember {
+    bool succ;     // top-1 is the target (targeted) / is not the true class (untargeted)
+    bool fooled;   // succ, and for a targeted sample also confident: p1 > p_thresh
+    float tl;      // the target logit
+};
+
+// The outcome from decide_top1's `am` and `p1`, and the seed row of this classifier's backward pass:
+// d adv_loss / d logits, adv_loss = -/+ logit[target]:  gl[c] = (c == tgt) ? -seed_mag (targeted) / +seed_mag : 0   (all threads)
+__device__ __forceinline__ DecideMember decide_member(const float* __restrict__ lg, int ncls, int tgt, int targeted, int am, float p1,
+                                                      float p_thresh, float seed_mag, float* __restrict__ gl) {
+    DecideMember m;
+    m.succ = targeted ? (am == tgt) : (am != tgt);
+    m.fooled = targeted ? (m.succ && p1 > p_thresh) : m.succ;
+    m.tl = lg[tgt];
+    const float seed = targeted ? -seed_mag : seed_mag;
+    for (int i = threadIdx.x; i < ncls; i += 256) gl[i] = (i == tgt) ? seed : 0.f;
+    return m;
+}
+
+// One thread's commit of the sample after decide_losses has filled st[1..4]: best_adv, best and the best colour loss so far (st[5]),
+// the four state words s[0..3] and st[0], st[6].  all_succ / all_fooled: over the sample's classifiers (the plain form has one);
+// p_stat, tl_stat: p1 and the target logit, or their min / mean over a group; state3: top-1 (plain) or the number fooled (group).
+__device__ __forceinline__ void decide_commit(bool all_succ, bool all_fooled, bool high_pert, float col, float p_stat, float tl_stat,
+                                              int state3, int32_t* __restrict__ s, float* __restrict__ st) {
+    const bool best_adv = all_fooled && high_pert;
+    const bool best = best_adv && (col < st[5]);
+    if (best) st[5] = col;
+    st[0] = p_stat;
+    st[6] = tl_stat;
+    s[0] = all_succ;
+    s[1] = best_adv;
+    s[2] = best;
+    s[3] = state3;
 }
 
 }  // namespace

@@ -8,7 +8,7 @@
 //   spaa_jitter_bwd    g_y_j = S_j^T(gain_c gate_c g_out_j) as a gather (no atomics: bitwise repeatable)
 //
 // The per-draw tensors arrive as HOST arrays of J device pointers and travel in a by-value kernel argument, as the ensemble's members do
-// (ensemble_ops.hip).  The generator is counter-based: 32-bit integer mixing of (seed, t, b, j, parameter) / (key, pixel, channel), no
+// (group_ops.hip).  The generator is counter-based: 32-bit integer mixing of (seed, t, b, j, parameter) / (key, pixel, channel), no
 // state; tests/jitter_oracle.py restates it in Python integers.
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -1,5 +1,5 @@
 // ptr_table.hpp — the per-member / per-view / per-draw tensors of the ensemble, multi-view, jitter and pose entry points (one copy for
-// ensemble_ops.hip, multiview_ops.hip, jitter_ops.hip, pose_ops.hip).  They arrive as HOST arrays of n device pointers; the launchers
+// group_ops.hip, jitter_ops.hip, pose_ops.hip).  They arrive as HOST arrays of n device pointers; the launchers
 // copy them into a kernel argument passed by value, so there is no device pointer table and a captured graph holds no copy.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -28,7 +28,7 @@ def test_entry_points_are_declared_and_exported():
         assert hasattr(lib, name), f'{name} is not exported by libspaa_hip.so'
         assert name in _lib.EXPORTS and name in _lib._SIGNATURES
     assert re.search(r'#define\s+SPAA_ENS_MAX\s+4\b', hdr) and A.ENS_MAX == 4
-    assert 'ensemble_ops.hip' in open(os.path.join(ROOT, 'spaa_amd', 'csrc', 'Makefile')).read()
+    assert 'group_ops.hip' in open(os.path.join(ROOT, 'spaa_amd', 'csrc', 'Makefile')).read()
 
 
 @pytest.mark.parametrize('targeted', [True, False])

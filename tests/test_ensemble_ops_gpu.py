@@ -1,4 +1,4 @@
-"""GPU: the ensemble kernels (csrc/ensemble_ops.hip) one by one against their float64 restatement (tests/ensemble_oracle.py):
+"""GPU: the ensemble entry points (csrc/group_ops.hip) one by one against their float64 restatement (tests/ensemble_oracle.py):
 spaa_decide_ens on planted logits that hold every decision case, and spaa_ens_sumsq + spaa_ens_combine on gradient images with a
 zero member, a zero weight, garbage in the pad channel and magnitudes 1e6 apart."""
 import ctypes as C

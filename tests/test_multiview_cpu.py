@@ -29,7 +29,7 @@ def test_entry_points_are_declared_and_exported():
         assert hasattr(lib, name), f'{name} is not exported by libspaa_hip.so'
         assert name in _lib.EXPORTS and name in _lib._SIGNATURES
     assert re.search(r'#define\s+SPAA_VIEWS_MAX\s+4\b', hdr) and A.VIEWS_MAX == 4
-    assert 'multiview_ops.hip' in open(os.path.join(ROOT, 'spaa_amd', 'csrc', 'Makefile')).read()
+    assert 'group_ops.hip' in open(os.path.join(ROOT, 'spaa_amd', 'csrc', 'Makefile')).read()
     assert spaa_amd.MultiViewAttackState is A.MultiViewAttackState and issubclass(A.MultiViewAttackState, A.AttackState)
 
 

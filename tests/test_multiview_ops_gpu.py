@@ -1,4 +1,4 @@
-"""GPU: the three entry points of csrc/multiview_ops.hip through the C-ABI against float64 (tests/multiview_oracle.py):
+"""GPU: the three multi-view entry points of csrc/group_ops.hip through the C-ABI against float64 (tests/multiview_oracle.py):
 spaa_decide_views on engineered logits and loss tables, spaa_views_combine on every size around the 256-pixel block, and
 spaa_views_track's gated copies."""
 import numpy as np
