@@ -826,6 +826,41 @@ int spaa_pose_fwd(const float* y, const float* table, int J, float* const* out, 
  * PoseJitter); beyond them contributions are lost.  Run-to-run bitwise reproducible; the pad channel of g_y is 0.  One launch. */
 int spaa_pose_bwd(const float* const* g_out, const float* table, int J, float* const* g_y, int B, int H, int W, spaa_stream_t stream);
 
+/* ---- JPEG-robust SPAA: one projection against J codec round trips of the camera image, 2 <= J <= SPAA_JITTER_MAX ----
+ * Conventions of the capture jitter above: host arrays of J device pointers, any other J / a null pointer / a size < 1 / another
+ * subsampling code is hipErrorInvalidValue with nothing launched, images [B][H*W][4] fp32, no allocation, no sync, no atomics.
+ *
+ * A table row is (Q, 0, 0, 0), row [B][J][4]: Q in 1..100 is the codec's quality, Q = 0 the identity row.  The round trip of an image y
+ * at quality Q: p = 255 clamp(y, 0, 1); JFIF full-range YCbCr; padding by edge replication to a multiple of the MCU (8 for 4:4:4, 16
+ * for 4:2:0); 4:2:0: Cb, Cr become their 2 x 2 means; per 8 x 8 block c = D (b - 128) D^T with the orthonormal DCT-II matrix D,
+ * k = rint(c / T), c^ = k T, b^ = D^T c^ D + 128, with T = clamp((base s + 50) / 100, 1, 255) in integers, s = 5000 / Q below 50 and
+ * 200 - 2 Q from 50 on, base the ITU-T T.81 Annex K luminance table for Y and chrominance table for Cb, Cr in natural order; 4:2:0:
+ * Cb, Cr back to full resolution over the padded planes by the separable triangle filter (3 near + far) / 4 with edge replication;
+ * v = RGB by the JFIF inverse (1.402, 0.344136, 0.714136, 1.772); out = rint(clamp(v, 0, 255)) / 255 cropped to H x W, pad channel 0.
+ * The planes are not rounded to 8 bits in between (libjpeg does).  The identity row: out = y bit for bit in the colour channels.
+ * The gate byte of a pixel: bit c = (0 <= y_c <= 1), bit 4 + c = (0 <= v_c <= 255); 0x77 in an identity row. */
+#define SPAA_JPEG_444 0
+#define SPAA_JPEG_420 2
+/* The rows of iteration t = counter[0] (device memory; t + 1 is stored after every thread of the one workgroup has read it):
+ * Q = q_lo + (((h >> 8) (q_hi - q_lo + 1)) >> 24), h spaa_jitter_draw's word of (seed, t, b, j, 0) with the first constant 0xc2b2ae35
+ * in place of 0x9e3779b9; 1 <= q_lo <= q_hi <= 100.  clean0 != 0: draw 0 of every sample is the identity row. */
+int spaa_jpeg_draw(uint32_t seed, int32_t* counter, int q_lo, int q_hi, int clean0, float* row, int B, int J, spaa_stream_t stream);
+/* The floats of workspace spaa_jpeg_fwd needs (host-side query): 0 for 4:4:4; J B Hp Wp 3/2 for 4:2:0, Hp and Wp the sides rounded up
+ * to 16: the decoded planes between its two launches (Y [Hp][Wp], Cb and Cr [Hp/2][Wp/2] per draw and sample). */
+int64_t spaa_jpeg_ws_floats(int subsampling, int J, int B, int H, int W);
+/* out[j], gate[j] = the round trip of y[j] at the qualities row[b][j]; there is always one input pointer per draw (J equal pointers
+ * where every draw starts from the same image: the results are then those of J distinct copies bit for bit).  4:4:4 is one launch
+ * and reads no workspace (ws may be NULL); 4:2:0 is two with `ws` between them (the triangle filter reads across tile borders). */
+int spaa_jpeg_fwd(const float* const* y, const float* row, int J, int subsampling, float* const* out, uint8_t* const* gate, float* ws,
+                  int B, int H, int W, spaa_stream_t stream);
+/* The adjoint: g_y[j] = the exact transpose of the chain's linear parts applied to g_out[j] -- the 8-bit step straight-through, both
+ * gates, both colour matrices, the triangle filter, DCT and IDCT, the 1/4 spread of the 2 x 2 mean, the padding cells' gradients
+ * summed into their edge pixel -- with the coefficient rounding replaced by the factor phi: 1 (soft == 0), or 3 r^2 with
+ * r = c / T - rint(c / T) (soft != 0), c recomputed from y[j] (no residues are stored; soft == 0 does not read y).  The identity row
+ * passes g_out through.  A gather without atomics: run-to-run bitwise reproducible.  The pad channel of g_y is 0.  One launch. */
+int spaa_jpeg_bwd(const float* const* g_out, const float* const* y, const float* row, int J, int subsampling, int soft,
+                  const uint8_t* const* gate, float* const* g_y, int B, int H, int W, spaa_stream_t stream);
+
 /* ---- attention-weighted attack: Grad-CAM of the classifier weights its gradient image ---------------------------
  * No atomics and fixed summation orders: bitwise repeatable.  One launch each, none syncs. */
 /* alpha [B][C] = the spatial mean of a gradient map G [B][HW][cstride] (channels 0 .. C - 1 of each position), positions added in

@@ -208,6 +208,9 @@ _SIGNATURES = {
     'spaa_pose_draw': [C.c_uint32, _p, _f, _f, _f, _f, _i, _p, _i, _i, _i, _i, _p],
     'spaa_pose_fwd': [_p, _p, _i, _pp, _i, _i, _i, _p],
     'spaa_pose_bwd': [_pp, _p, _i, _pp, _i, _i, _i, _p],
+    'spaa_jpeg_draw': [C.c_uint32, _p, _i, _i, _i, _p, _i, _i, _p],
+    'spaa_jpeg_fwd': [_pp, _p, _i, _i, _pp, _pp, _p, _i, _i, _i, _p],
+    'spaa_jpeg_bwd': [_pp, _pp, _p, _i, _i, _i, _pp, _pp, _i, _i, _i, _p],
     'spaa_cam_alpha': [_p, _p, _i, _i, _i, _i, _p],
     'spaa_cam_map': [_p, _p, _f, _p, _i, _p, _p, _p, _i, _i, _i, _p],
     'spaa_attention_apply': [_p, _p, _f, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p],
@@ -234,7 +237,7 @@ _SIGNATURES = {
 }
 
 EXPORTS = sorted(list(_SIGNATURES) + ['spaa_version', 'spaa_tapconv_sizeof', 'spaa_tapconv_offsetof', 'spaa_tapconv_wino_plan', 'spaa_tapconv_h16p_plan',
-                                         'spaa_tapconv_tile_info', 'spaa_tapconv_check', 'spaa_transfer_tiles', 'spaa_ssim_tiles'])
+                                         'spaa_tapconv_tile_info', 'spaa_tapconv_check', 'spaa_transfer_tiles', 'spaa_ssim_tiles', 'spaa_jpeg_ws_floats'])
 
 _lib = None
 
@@ -268,6 +271,8 @@ def load():
     lib.spaa_transfer_tiles.restype = C.c_int
     lib.spaa_ssim_tiles.argtypes = [C.c_int, C.c_int]                                  # (host-side query: no stream)
     lib.spaa_ssim_tiles.restype = C.c_int
+    lib.spaa_jpeg_ws_floats.argtypes = [C.c_int] * 5                                   # (host-side query: no stream)
+    lib.spaa_jpeg_ws_floats.restype = C.c_int64
     _lib = lib
     return lib
 

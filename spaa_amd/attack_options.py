@@ -1,4 +1,4 @@
-"""What an attack can be asked for besides the plain SPAA loop -- the option values CaptureJitter, PoseJitter and Transfer (Attention is
+"""What an attack can be asked for besides the plain SPAA loop -- the option values CaptureJitter, PoseJitter, JpegCapture and Transfer (Attention is
 spaa_amd.classifier's), the limits of include/spaa_hip.h -- and the check of a request, made before anything is allocated or launched:
 `checked_request` for spaa() and spaa_sweep(), the `_supported` functions for the attack states that are built directly."""
 import dataclasses
@@ -79,6 +79,54 @@ class PoseJitter:
         """spaa_pose_draw of these ranges: fills table [B][J][8] for iteration counter[0] of an H x W image and advances the counter."""
         _lib.call('spaa_pose_draw', int(self.seed) & 0xffffffff, _lib.ptr(counter), float(self.rotate), float(self.zoom),
                   float(self.shift), float(self.tilt), int(bool(clean0)), _lib.ptr(table), B, J, H, W)
+
+
+JPEG_SUBSAMPLINGS = {'4:4:4': 0, '4:2:0': 2}   # SPAA_JPEG_444, SPAA_JPEG_420 of include/spaa_hip.h
+JPEG_GRADIENTS = ('soft', 'straight')
+
+
+def jpeg_quality_range(quality, who='JpegCapture'):
+    """(lo, hi) of a quality that is one integer or an ordered pair of integers, each in 1..100."""
+    pair = tuple(quality) if isinstance(quality, (tuple, list)) else (quality, quality)
+    if len(pair) != 2 or any(isinstance(q, bool) or not isinstance(q, int) for q in pair):
+        raise ValueError(f'{who}: quality must be an integer or a pair of integers, got {quality!r}')
+    if not 1 <= pair[0] <= pair[1] <= 100:
+        raise ValueError(f'{who}: quality must be in 1..100 and an ordered pair (low, high), got {quality!r}')
+    return pair
+
+
+@dataclasses.dataclass(frozen=True)
+class JpegCapture:
+    """The camera's codec as the last thing that happens to a capture: a JPEG round trip at a `quality` drawn
+    uniformly from the integers of the range (one integer: that quality), with `subsampling` '4:2:0' (phones, DSLRs) or '4:4:4'.
+    `gradient`: what stands for the derivative of the coefficient rounding in the backward pass: 'soft' (3 r^2, r the rounding
+    residue: it mutes the frequencies the codec deletes) or 'straight' (1).  `draws`: round trips attacked at once per iteration
+    (2..4; the first one is the uncompressed capture), `seed`: of the counter-based generator."""
+    quality: object = (60, 95)
+    subsampling: str = '4:2:0'
+    gradient: str = 'soft'
+    draws: int = 3
+    seed: int = 0
+
+    def __post_init__(self):
+        if not 2 <= int(self.draws) <= JITTER_MAX:
+            raise ValueError(f'JpegCapture: draws must be 2..{JITTER_MAX}, got {self.draws}')
+        jpeg_quality_range(self.quality)
+        if isinstance(self.quality, list):
+            object.__setattr__(self, 'quality', tuple(self.quality))   # (hashable)
+        if self.subsampling not in JPEG_SUBSAMPLINGS:
+            raise ValueError(f"JpegCapture: subsampling must be one of {', '.join(map(repr, JPEG_SUBSAMPLINGS))}, got {self.subsampling!r}")
+        if self.gradient not in JPEG_GRADIENTS:
+            raise ValueError(f"JpegCapture: gradient must be one of {', '.join(map(repr, JPEG_GRADIENTS))}, got {self.gradient!r}")
+
+    @property
+    def quality_range(self):
+        return jpeg_quality_range(self.quality)
+
+    def draw(self, counter, row, B, J, clean0):
+        """spaa_jpeg_draw of this range: fills row [B][J][4] for iteration counter[0] and advances the counter."""
+        lo, hi = self.quality_range
+        _lib.call('spaa_jpeg_draw', int(self.seed) & 0xffffffff, _lib.ptr(counter), lo, hi, int(bool(clean0)), _lib.ptr(row), B, J)
 
 
 @dataclasses.dataclass(frozen=True)
@@ -243,6 +291,23 @@ def _pose_supported(pose, pcnet, classifier, storage, focus, attention, jitter, 
                          f'{pose.draws} and jitter.draws = {jitter.draws}')
 
 
+def _jpeg_supported(jpeg, pcnet, classifier, storage, focus, attention, jitter, pose, who):
+    """What a JPEG attack does not serve.  `pcnet` / `classifier`: as spaa() holds them after its own checks; `jitter` / `pose`: None or
+    checked values."""
+    _is_a(jpeg, 'jpeg', JpegCapture, who)
+    _need_one_of_each('camera JPEG', 'jpeg', pcnet, classifier, who)
+    _need_classifier('a JPEG attack', 'a foreign callable can only be attacked without jpeg', classifier, who)
+    if attention is not None:
+        raise NotImplementedError(f'{who}: attention together with camera JPEG is not implemented (every draw would need a map of its '
+                                  'own, pulled back through the codec); use attention or jpeg')
+    _need_f32('with jpeg', _OWN_SCALE.format('draws'), storage, who)
+    _no_focus('jpeg', focus, who)
+    for name, other in (('pose', pose), ('jitter', jitter)):
+        if other is not None and int(other.draws) != int(jpeg.draws):
+            raise ValueError(f'{who}: {name} and jpeg are applied draw by draw and must name the same draws, got {name}.draws = '
+                             f'{other.draws} and jpeg.draws = {jpeg.draws}')
+
+
 def _attention_checked(attention, storage, who):
     """An attack state's own check of its `attention` (the entry points say more, earlier: _attention_supported)."""
     if attention is not None:
@@ -280,7 +345,7 @@ def _transfer_supported(transfer, classifier, storage, who):
     _transfer_checked(transfer, storage, who)
 
 
-def checked_request(who, pcnet, classifier, cam_scene, storage, focus, jitter, pose, attention, transfer):
+def checked_request(who, pcnet, classifier, cam_scene, storage, focus, jitter, pose, attention, transfer, jpeg=None):
     """The request of spaa() / spaa_sweep() (`who`), checked in the one order that decides which error a caller sees; returns the
     normalised (pcnet, classifier, cam_scene): unwrapped, a sequence of one collapsed, a list where there are several."""
     pcnet, classifier = _unwrap(pcnet), _unwrap(classifier)
@@ -298,6 +363,8 @@ def checked_request(who, pcnet, classifier, cam_scene, storage, focus, jitter, p
         _jitter_supported(jitter, pcnet, classifier, storage, focus, who)
     if pose is not None:
         _pose_supported(pose, pcnet, classifier, storage, focus, attention, jitter, who)
+    if jpeg is not None:
+        _jpeg_supported(jpeg, pcnet, classifier, storage, focus, attention, jitter, pose, who)
     if attention is not None:
         _attention_supported(attention, classifier, storage, jitter, who)
     if transfer is not None:

@@ -1,14 +1,14 @@
 """The device-side states of the batched SPAA attack: AttackState (one PCNet, one classifier), EnsembleAttackState (several classifiers),
 MultiViewAttackState (several PCNets) and DrawAttackState (random draws of the camera image through a chain of stages:
-JitterAttackState, PoseAttackState).  Lines quoted as :NNN are the reference's projector_based_attack.py."""
+JitterAttackState, PoseAttackState, JpegAttackState).  Lines quoted as :NNN are the reference's projector_based_attack.py."""
 import ctypes
 
 import torch
 
 from . import _lib
 from .models import to_nhwc4, to_nchw
-from .attack_options import (_unwrap, _ensemble_members, _view_pcnets, _views_supported, _jitter_supported, _pose_supported,
-                             _attention_checked, _transfer_checked)
+from .attack_options import (JPEG_SUBSAMPLINGS, _unwrap, _ensemble_members, _view_pcnets, _views_supported, _jitter_supported,
+                             _pose_supported, _jpeg_supported, _attention_checked, _transfer_checked)
 
 
 def _is_scalar(v):
@@ -541,6 +541,42 @@ class PoseStage:
         return self.grads
 
 
+class JpegStage:
+    """The camera's JPEG codec as a stage of a draw chain, always the last one: its device-side counter, the quality rows
+    `jpeg_rows` of spaa_jpeg_draw, J round-tripped images with their gate bytes, J gradient images, and for 4:2:0 the workspace
+    between the two launches of spaa_jpeg_fwd.  It remembers its J input images: the 'soft' adjoint recomputes the coefficients."""
+
+    def __init__(self, jpeg):
+        self.options, self.draws = jpeg, int(jpeg.draws)
+        self.code, self.soft = JPEG_SUBSAMPLINGS[jpeg.subsampling], int(jpeg.gradient == 'soft')
+
+    def build(self, st, first):
+        B, J, dev = st.B, st.K, st.dev
+        self.counter = torch.zeros(1, dtype=torch.int32, device=dev)        # the iteration number the next draw reads
+        self.rows = torch.zeros(B, J, 4, device=dev)
+        self.ims = [torch.zeros_like(st.g_adv) for _ in range(J)]
+        self.gates = [torch.zeros(B, st.HWc, dtype=torch.uint8, device=dev) for _ in range(J)]
+        self.grads = [torch.zeros_like(st.g_adv) for _ in range(J)]
+        floats = _lib.load().spaa_jpeg_ws_floats(self.code, J, B, st.eng.Hc, st.eng.Wc)
+        self.ws = torch.zeros(floats, device=dev) if floats else None
+        self.src = None
+        return dict(jpeg_rows=self.rows, jpeg_ims=self.ims, jpeg_gates=self.gates, jpeg_grads=self.grads,
+                    **{'counter' if first else 'jpeg_counter': self.counter})
+
+    def forward(self, st, src):
+        """Draws this iteration's qualities, then draw j of `src`: the camera image y, or (behind another stage) that stage's image j."""
+        self.options.draw(self.counter, self.rows, st.B, st.K, clean0=True)
+        self.src = src if isinstance(src, list) else [src] * st.K
+        _lib.call('spaa_jpeg_fwd', _lib.ptr_array(self.src), _lib.ptr(self.rows), st.K, self.code, _lib.ptr_array(self.ims),
+                  _lib.ptr_array(self.gates), _lib.ptr(self.ws), st.B, st.eng.Hc, st.eng.Wc)
+        return self.ims
+
+    def backward(self, st, gs):
+        _lib.call('spaa_jpeg_bwd', _lib.ptr_array(gs), _lib.ptr_array(self.src), _lib.ptr(self.rows), st.K, self.code, self.soft,
+                  _lib.ptr_array(self.gates), _lib.ptr_array(self.grads), st.B, st.eng.Hc, st.eng.Wc)
+        return self.grads
+
+
 class DrawAttackState(EnsembleAttackState):
     """One batched attack against J random draws of the camera image per iteration: EnsembleAttackState whose members are J leased
     engines of ONE classifier, member j looking at draw j of y = PCNet(x, s).  The draws come from a chain of `stages` applied to y,
@@ -602,3 +638,22 @@ class PoseAttackState(DrawAttackState):
         self.pose, self.jitter = pose, jitter
         stages = [PoseStage(pose)] + ([JitterStage(jitter)] if jitter is not None else [])
         super().__init__(pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, device, stages, storage, transfer)
+
+
+class JpegAttackState(DrawAttackState):
+    """The draw attack through the camera's JPEG codec: J = jpeg.draws round trips per iteration at drawn qualities (spaa_jpeg_draw,
+    spaa_jpeg_fwd, spaa_jpeg_bwd).  With `pose` and / or `jitter` (of the same `draws`) draw j is Jpeg_j(Jitter_j(Pose_j(y))), the order
+    a camera applies them in."""
+
+    def __init__(self, pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, device, jpeg, storage='f32', pose=None,
+                 jitter=None, transfer=None):
+        pcnet, classifier = _unwrap(pcnet), _unwrap(classifier)
+        if jitter is not None:
+            _jitter_supported(jitter, pcnet, classifier, storage, False, 'JpegAttackState')
+        if pose is not None:
+            _pose_supported(pose, pcnet, classifier, storage, False, None, jitter, 'JpegAttackState')
+        _jpeg_supported(jpeg, pcnet, classifier, storage, False, None, jitter, pose, 'JpegAttackState')
+        self.pose, self.jitter, self.jpeg = pose, jitter, jpeg
+        stages = ([PoseStage(pose)] if pose is not None else []) + ([JitterStage(jitter)] if jitter is not None else [])
+        super().__init__(pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, device, stages + [JpegStage(jpeg)], storage,
+                         transfer)

@@ -193,6 +193,29 @@ def pose_survival(ims, classifier, target_idx, targeted, crop_sz, pose, *, draws
     return (hits / int(draws)).numpy()
 
 
+def jpeg_survival(ims, classifier, target_idx, targeted, crop_sz, *, qualities=(95, 90, 75, 50, 30), subsampling='4:2:0'):
+    """Which camera images still succeed behind a JPEG re-encode: bool [len(qualities), N] for the images `ims` [N,3,H,W], one class id
+    per image in `target_idx` and `targeted` (one flag, or one per image), by the success rule of capture_survival.  The evaluation
+    hook of a JPEG attack, and the answer to a classifier that sits behind the input-transformation defence.  Row q is the round trip
+    of every image at qualities[q] (spaa_jpeg_fwd through jpeg_roundtrip).  Deterministic: nothing is drawn."""
+    from .jpeg import jpeg_roundtrip
+    n = ims.shape[0]
+    tgt = np.asarray([int(t) for t in target_idx])
+    tg = np.full(n, bool(targeted)) if np.ndim(targeted) == 0 else np.asarray([bool(t) for t in targeted])
+    if tgt.shape != (n,) or tg.shape != (n,) or len(qualities) < 1:
+        raise ValueError(f'jpeg_survival: {n} images, {tgt.size} targets, {tg.size} targeted flags, {len(qualities)} qualities')
+    dev = classifier.device
+    if dev.type != 'cuda':
+        raise RuntimeError(f'jpeg_survival runs on the GPU only (no CPU fallback); the classifier is on {dev}')
+    out = np.zeros((len(qualities), n), dtype=bool)
+    with _lib.on_device(dev):
+        y = ims.to(dev).float()
+        for q, quality in enumerate(qualities):
+            top1 = _sorted_classes(classifier, [jpeg_roundtrip(y, int(quality), subsampling)], crop_sz)[0][:, 0]
+            out[q] = np.where(tg, top1 == tgt, top1 != tgt)
+    return out
+
+
 def transfer_success(cam, classifier, target_idx, targeted, crop_sz, p_thresh=0.9):
     """Which camera images `cam` [B,3,H,W] fool `classifier`, by the success rule of the attack's own decision (spaa_decide): bool [B];
     one class id per image in `target_idx` and `targeted` (one flag, or one per image): top-1 == target with p1 > `p_thresh`, else

@@ -21,11 +21,11 @@ from . import _lib
 from .models import PCNet, to_nhwc4, to_nchw   # noqa: F401
 from .classifier import Attention, Classifier   # noqa: F401  (Attention: re-exported)
 from .attack_options import (ENS_MAX, VIEWS_MAX, JITTER_MAX, TRANSFER_RMAX, POSE_MAX_ROTATE, POSE_MAX_ZOOM, POSE_MAX_TILT,   # noqa: F401
-                             POSE_MAX_SHIFT, CaptureJitter, PoseJitter, Transfer, checked_request, _unwrap, _ensemble_members,
-                             _view_pcnets, _views_supported, _jitter_supported, _pose_supported, _attention_checked,
+                             POSE_MAX_SHIFT, CaptureJitter, PoseJitter, JpegCapture, Transfer, checked_request, _unwrap, _ensemble_members,
+                             _view_pcnets, _views_supported, _jitter_supported, _pose_supported, _jpeg_supported, _attention_checked,
                              _attention_supported, _transfer_checked, _transfer_supported)
 from .attack_state import (AttackState, EnsembleAttackState, MultiViewAttackState, DrawAttackState, JitterAttackState,   # noqa: F401
-                           PoseAttackState, JitterStage, PoseStage, _is_scalar, _require_gpu, _scene_batch)
+                           PoseAttackState, JpegAttackState, JitterStage, PoseStage, JpegStage, _is_scalar, _require_gpu, _scene_batch)
 
 # B * Hc * Wc up to which spaa() replays the iteration as a captured HIP graph (0 disables); above it the GPU is busy for
 # longer than the host needs to enqueue an iteration and eager launches lose nothing (measured: < 1 % at B = 64, 256 x 256)
@@ -48,11 +48,14 @@ def ssim_weight(stealth_loss):
 
 
 def _attack_state(pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, device, storage, focus, jitter=None,
-                  attention=None, transfer=None, pose=None):
+                  attention=None, transfer=None, pose=None, jpeg=None):
     """AttackState for one Classifier, EnsembleAttackState for a checked list of several, MultiViewAttackState for a checked list of
     PCNets (with their list of scenes), JitterAttackState for one Classifier with a CaptureJitter, PoseAttackState for one Classifier
-    with a PoseJitter (with or without a CaptureJitter); the last two take no `attention`.  Each of them takes `transfer`."""
+    with a PoseJitter (with or without a CaptureJitter), JpegAttackState for one Classifier with a JpegCapture (with or without either of
+    the other two); the last three take no `attention`.  Each of them takes `transfer`."""
     args = (pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, device)
+    if jpeg is not None:
+        return JpegAttackState(*args, jpeg, storage=storage, pose=pose, jitter=jitter, transfer=transfer)
     if pose is not None:
         return PoseAttackState(*args, pose, storage=storage, jitter=jitter, transfer=transfer)
     if jitter is not None:
@@ -66,7 +69,7 @@ def _attack_state(pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_
 
 def spaa(pcnet, classifier, imagenet_labels, target_idx, targeted, cam_scene, d_thr, stealth_loss, device, setup_info,
          *, iters=50, adv_lr=2, col_lr=1, p_thresh=0.9, trace=None, verbose=False, storage='f32', focus=False, jitter=None,
-         attention=None, transfer=None, pose=None):
+         attention=None, transfer=None, pose=None, jpeg=None):
     """Stealthy Projector-based Adversarial Attack (SPAA Algorithm 1) — see module docstring.
 
     :param pcnet: spaa_amd.PCNet (optionally wrapped in DataParallel-like `.module`), or a list / tuple of 2..4 of them: the same projector
@@ -92,6 +95,11 @@ def spaa(pcnet, classifier, imagenet_labels, target_idx, targeted, cam_scene, d_
         random change of camera pose: rotation, zoom, translation, tilt), the first of them the unwarped one (PoseAttackState, DESIGN.md
         7k; one PCNet, one Classifier, fp32 storage, no `focus`, no `attention`).  With `jitter` of the same `draws`, draw j is
         Jitter_j(Pose_j(y)).  The trace entries are the ensemble's, with draws as members.  None (default): launch for launch as before
+    :param jpeg: a JpegCapture: ONE projection against `jpeg.draws` JPEG round trips of the camera image per iteration, each at a
+        quality drawn from `jpeg.quality`, the first of them the uncompressed capture (JpegAttackState; one PCNet, one
+        Classifier, fp32 storage, no `focus`, no `attention`).  With `pose` and / or `jitter` of the same `draws` the codec comes last:
+        draw j is Jpeg_j(Jitter_j(Pose_j(y))).  The decision's stealth loss and `cam_best` stay the clean inference's.  None
+        (default): launch for launch as before
     :param imagenet_labels: dict idx -> name (only used when verbose)
     :param target_idx: list of B class ids (true label if untargeted)
     :param targeted: bool
@@ -105,14 +113,15 @@ def spaa(pcnet, classifier, imagenet_labels, target_idx, targeted, cam_scene, d_
         for several views (state, stats, view_state, view_stats) in the same way
     :return: (cam_infer_best [B,3,Hc,Wc], prj_adv_best [B,3,Hp,Wp] in [0,1]); for several views ([cam_infer_best per view], prj_adv_best)
     """
-    pcnet, classifier, cam_scene = checked_request('spaa', pcnet, classifier, cam_scene, storage, focus, jitter, pose, attention, transfer)
+    pcnet, classifier, cam_scene = checked_request('spaa', pcnet, classifier, cam_scene, storage, focus, jitter, pose, attention, transfer,
+                                                   jpeg)
     if not isinstance(classifier, (Classifier, list)):
         if not callable(classifier):
             raise TypeError('classifier must be a spaa_amd.Classifier or a callable (im, crop_sz) -> (raw_score, p, idx)')
         return _spaa_foreign_classifier(pcnet, classifier, imagenet_labels, target_idx, targeted, cam_scene, d_thr,
                                         stealth_loss, device, setup_info, iters, adv_lr, col_lr, p_thresh, trace)
     st = _attack_state(pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, device, storage, focus, jitter, attention,
-                       transfer, pose)
+                       transfer, pose, jpeg)
 
     def report(i):
         if i % 30 == 0 or i == iters - 1:
@@ -206,7 +215,7 @@ def split_sweep(samples, ncfg, chunk_results):
 
 def spaa_sweep(pcnet, classifier, imagenet_labels, cam_scene, setup_info, device, configs, *, iters=50, adv_lr=2, col_lr=1,
                p_thresh=0.9, max_batch=64, storage='f32', trace=None, focus=False, jitter=None, attention=None, transfer=None,
-               pose=None):
+               pose=None, jpeg=None):
     """Several SPAA attacks on one PCNet, scene and classifier as few batched attacks (the reference's driver makes one spaa() call
     per configuration: projector_based_attack.py:24-148).  `configs`: [(stealth_loss, d_thr, targeted, target_idx), ...]; returns one
     (cam_infer_best, prj_adv_best) per config, in order -- what spaa(pcnet, classifier, imagenet_labels, target_idx, targeted,
@@ -221,10 +230,11 @@ def spaa_sweep(pcnet, classifier, imagenet_labels, cam_scene, setup_info, device
     is a jitter attack with that seed (the draws of a sample depend on its place in its chunk), the trace entries the ensemble's.
     `attention`: an Attention, as in spaa(): every chunk is an attention-weighted attack.  `transfer`: a Transfer, as in spaa(): every
     chunk's adversarial steps follow the smoothed, momentum-accumulated direction (each chunk's momentum starts at zero).  `pose`: a
-    PoseJitter, as in spaa(): every chunk is a pose attack with that seed (the draws of a sample depend on its place in its chunk)."""
+    PoseJitter, as in spaa(): every chunk is a pose attack with that seed (the draws of a sample depend on its place in its chunk).
+    `jpeg`: a JpegCapture, as in spaa(): every chunk is a JPEG attack with that seed, in the same way."""
     samples, chunks = plan_sweep(configs, max_batch)
     pcnet, classifier, cam_scene = checked_request('spaa_sweep', pcnet, classifier, cam_scene, storage, focus, jitter, pose, attention,
-                                                   transfer)
+                                                   transfer, jpeg)
     if not isinstance(classifier, (Classifier, list)):
         raise TypeError('spaa_sweep needs a spaa_amd.Classifier')
     _require_gpu(device, 'spaa_sweep')
@@ -241,7 +251,7 @@ def spaa_sweep(pcnet, classifier, imagenet_labels, cam_scene, setup_info, device
     for a, b in chunks:
         part = samples[a:b]
         st = _attack_state(pcnet, classifier, [t for *_, t in part], sc, [s[1] for s in part], setup_info, device, storage, focus,
-                           jitter, attention, transfer, pose)
+                           jitter, attention, transfer, pose, jpeg)
         tr = [] if trace is not None else None
         _run(st, [s[3] for s in part], [s[2] for s in part], iters, adv_lr, col_lr, p_thresh, tr)
         if trace is not None:
@@ -340,7 +350,8 @@ spaa_attack = spaa  # name used by BASELINE.json's north_star
 # objects).  Neither module imports this one at import time: they reach the attack through it when they are called.
 from .attack_driver import (ATTACKERS, MODEL_TRAIN_CFG, AttackSetup, get_attacker_cfg, to_attacker_cfg_str,   # noqa: E402,F401
                             run_projector_based_attack, _run_one_pixel_de, project_capture_real_attack)
+from .jpeg import jpeg_roundtrip, quant_tables   # noqa: E402,F401
 from .attack_summary import (SUMMARY_STEALTH_LOSSES, SUMMARY_D_THRESHES, SUMMARY_CLASSIFIERS, SUMMARY_CHUNK,   # noqa: E402,F401
                              SUMMARY_COLUMNS, MONTAGE_CHUNK, attack_success, write_stats, _sorted_classes, _nonempty,
-                             attack_results, attack_transfer, capture_survival, pose_survival, transfer_success,
+                             attack_results, attack_transfer, capture_survival, pose_survival, jpeg_survival, transfer_success,
                              summarize_single_attacker, summarize_all_attackers)
