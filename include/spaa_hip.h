@@ -670,6 +670,27 @@ int spaa_attn_relevance(const float* qkv, const float* lse, const float* g_ctx, 
 int spaa_relevance_map(const float* rho, const float* g_logits, int ncls, const int32_t* target, float* c, float* cmax, int B, int T,
                        spaa_stream_t stream);
 
+/* ---- Depthwise 7 x 7 layers of torchvision's ConvNeXt (csrc/convnext_ops.hip; spaa_amd/convnext.py) -------------- */
+/* NHWC fp32, stride 1, zero padding 3 (the output has the size of the input), any H, W >= 1.  w [49][C] tap-major (tap = 7 ky + kx),
+ * the convention of spaa_dwconv3_*.  Exact-fp32 VALU arithmetic in a fixed order, no atomics (two runs are bitwise equal), no
+ * allocation and no synchronisation.  Invalid arguments (a null pointer other than `add`, C % 4 != 0, a size < 1, B H W C >= 2^29)
+ * return hipErrorInvalidValue with nothing launched and nothing written.
+ * spaa_dwconv7_fwd: out[y, x, c] = bias[c] + sum w[ky, kx, c] in[y - 3 + ky, x - 3 + kx, c]: acc = bias, then acc = fmaf(w, v, acc)
+ * over (ky, kx) in row-major order; a tap outside the image contributes nothing (a column outside it is multiplied as a 0, which for
+ * finite weights leaves acc as it is: FINITE VALUES ONLY).
+ * spaa_dwconv7_bwd: its exact adjoint as a gather: g_in[y, x, c] = add[y, x, c] + sum over the taps (ky, kx), row-major, that reach an
+ * output pixel, of w[ky, kx, c] g_out[y + 3 - ky, x + 3 - kx, c] (acc = 0, then fmaf; `add`, which may be NULL, is added last: the
+ * residual gradient of a ConvNeXt block at no extra pass).  g_in may be `add` itself (a lane reads what it writes before it writes),
+ * not g_out. */
+int spaa_dwconv7_fwd(const float* in, const float* w, const float* bias, float* out, int B, int H, int W, int C, spaa_stream_t stream);
+int spaa_dwconv7_bwd(const float* g_out, const float* w, const float* add, float* g_in, int B, int H, int W, int C,
+                     spaa_stream_t stream);
+/* Measurement and test switch (host side, no stream, nothing launched): which of the kernel's two forms the two entry points above
+ * launch from now on -- 0 the library's own choice by shape (the default), 1 strips of 4 columns and runs of at least 7 rows, 2 strips
+ * of 2 columns and runs of at least 4 rows.  Both forms accumulate in the same order: their outputs are bitwise equal.  Returns the
+ * value before the call; any other argument changes nothing. */
+int spaa_dwconv7_form(int form);
+
 /* ---- SPAA Algorithm 1 control on device (projector_based_attack.py:269-328) ------------------------------ */
 /* Per-sample decision, one workgroup per sample: softmax top-1 / argmax of logits (classifier.py:64-68), loss
  * reduction, masks (:290-299), best bookkeeping (:318-320), and the seed of the adversarial backward pass

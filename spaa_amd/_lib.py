@@ -175,6 +175,8 @@ _SIGNATURES = {
     'spaa_dwconv3_bwd': [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p],
     'spaa_relu6_gate': [_p, _p, _l, _i, _p],
     'spaa_global_avgpool_bwd_bits': [_p, _p, _p, _i, _i, _i, _p],
+    'spaa_dwconv7_fwd': [_p, _p, _p, _p, _i, _i, _i, _i, _p],
+    'spaa_dwconv7_bwd': [_p, _p, _p, _p, _i, _i, _i, _i, _p],
     'spaa_vit_patchify': [_p, _p, _i, _i, _i, _i, _p],
     'spaa_vit_unpatchify': [_p, _p, _i, _i, _i, _i, _p],
     'spaa_vit_assemble': [_p, _p, _p, _p, _i, _i, _i, _p],
@@ -237,7 +239,8 @@ _SIGNATURES = {
 }
 
 EXPORTS = sorted(list(_SIGNATURES) + ['spaa_version', 'spaa_tapconv_sizeof', 'spaa_tapconv_offsetof', 'spaa_tapconv_wino_plan', 'spaa_tapconv_h16p_plan',
-                                         'spaa_tapconv_tile_info', 'spaa_tapconv_check', 'spaa_transfer_tiles', 'spaa_ssim_tiles', 'spaa_jpeg_ws_floats'])
+                                         'spaa_tapconv_tile_info', 'spaa_tapconv_check', 'spaa_transfer_tiles', 'spaa_ssim_tiles', 'spaa_jpeg_ws_floats',
+                                         'spaa_dwconv7_form'])
 
 _lib = None
 
@@ -273,6 +276,8 @@ def load():
     lib.spaa_ssim_tiles.restype = C.c_int
     lib.spaa_jpeg_ws_floats.argtypes = [C.c_int] * 5                                   # (host-side query: no stream)
     lib.spaa_jpeg_ws_floats.restype = C.c_int64
+    lib.spaa_dwconv7_form.argtypes = [C.c_int]                                         # (host-side switch: no stream)
+    lib.spaa_dwconv7_form.restype = C.c_int
     _lib = lib
     return lib
 

@@ -32,7 +32,8 @@ BODY_GATE_MASKS = os.environ.get('SPAA_BODY_MASKS', '1') != '0'   # 0: VGG-16 / 
 
 IMAGENET_MEAN = (0.485, 0.456, 0.406)
 IMAGENET_STD = (0.229, 0.224, 0.225)
-INPUT_SZ = {'resnet18': (224, 224), 'vgg16': (224, 224), 'inception_v3': (299, 299), 'mobilenet_v2': (224, 224), 'vit_b_16': (224, 224)}
+INPUT_SZ = {'resnet18': (224, 224), 'vgg16': (224, 224), 'inception_v3': (299, 299), 'mobilenet_v2': (224, 224), 'vit_b_16': (224, 224),
+            'convnext_tiny': (224, 224)}
 
 
 @dataclasses.dataclass(frozen=True)
@@ -420,9 +421,14 @@ def _vit_body(sd, batch, in_hw, dev, storage='f32'):
     return ViTB16Body(sd, batch, in_hw, dev, storage)
 
 
+def _convnext_body(sd, batch, in_hw, dev, storage='f32'):
+    from .convnext import ConvNeXtBody
+    return ConvNeXtBody(sd, batch, in_hw, dev, storage)
+
+
 BODIES = {'resnet18': ResNet18Body, 'vgg16': VGG16Body, 'inception_v3': _inception_body, 'mobilenet_v2': _mobilenet_body,
-          'vit_b_16': _vit_body}
-LAST_LINEAR = {'vgg16': 'classifier.6', 'mobilenet_v2': 'classifier.1', 'vit_b_16': 'heads.head'}   # the last linear layer's key where it is not 'fc'
+          'vit_b_16': _vit_body, 'convnext_tiny': _convnext_body}
+LAST_LINEAR = {'vgg16': 'classifier.6', 'mobilenet_v2': 'classifier.1', 'vit_b_16': 'heads.head', 'convnext_tiny': 'classifier.2'}   # the last linear layer's key where it is not 'fc'
 
 
 NO_FEATURE_MAP = ('vit_b_16',)   # bodies without a convolutional feature map: Grad-CAM and attention= are refused for them
@@ -622,6 +628,10 @@ class Classifier(object):
             from . import vit
             self.state_dict = vit.canonical(self.state_dict)
             vit.check_geometry(self.state_dict, self.input_sz)
+        if model_name == 'convnext_tiny':
+            # likewise: input size against the stem and the downsamples, widths against the channel quads of the kernels
+            from . import convnext
+            convnext.check_geometry(self.state_dict, self.input_sz)
         self._engines = {}
 
     @property

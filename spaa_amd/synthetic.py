@@ -347,6 +347,47 @@ def vit_b_16_state_dict(seed=7, num_classes=1000, logit_gain=1.0, dim=768, depth
     return sd
 
 
+def convnext_tiny_state_dict(seed=8, num_classes=1000, logit_gain=1.0, dims=(96, 192, 384, 768), depths=(3, 3, 9, 3)):
+    """Random-init ConvNeXt (torchvision's convnext_tiny key names; the defaults are ConvNeXt-Tiny, `dims` -- multiples of 4 -- and
+    `depths` shrink it for tests).  LayerNorm weights U(0.5, 1.5) and biases U(-0.2, 0.2); convolution and linear weights
+    N(0, 1 / fan_in) with biases U(-0.2, 0.2) (the depthwise layers: fan_in = 49); the head U(+-1 / sqrt(C)) x logit_gain.
+    `layer_scale` is U(0.5, 1.5), not torchvision's initial 1e-6: with that value every block is the identity to six digits and a test
+    sees nothing of it.  The branch of a block ends in a LayerNorm-fed MLP, so its output stays of order 1 whatever its input and the
+    residual stream grows by addition only."""
+    rng = np.random.default_rng(seed)
+    if len(dims) != len(depths) or not dims or any(c % 4 or c < 4 for c in dims):
+        raise ValueError(f'convnext_tiny_state_dict: dims {tuple(dims)} must be multiples of 4, one per entry of depths {tuple(depths)}')
+    sd = {}
+
+    def dense(name, shape, fan_in):
+        sd[name + '.weight'] = _t(rng.standard_normal(shape) / math.sqrt(fan_in))
+        sd[name + '.bias'] = _t(rng.uniform(-0.2, 0.2, (shape[0],)))
+
+    def ln(name, c):
+        sd[name + '.weight'] = _t(rng.uniform(0.5, 1.5, (c,)))
+        sd[name + '.bias'] = _t(rng.uniform(-0.2, 0.2, (c,)))
+
+    dense('features.0.0', (dims[0], 3, 4, 4), 48)
+    ln('features.0.1', dims[0])
+    for si, (c, depth) in enumerate(zip(dims, depths)):
+        s = 2 * si + 1
+        if si > 0:
+            ln(f'features.{s - 1}.0', dims[si - 1])
+            dense(f'features.{s - 1}.1', (c, dims[si - 1], 2, 2), 4 * dims[si - 1])
+        for i in range(depth):
+            p = f'features.{s}.{i}.'
+            dense(p + 'block.0', (c, 1, 7, 7), 49)
+            ln(p + 'block.2', c)
+            dense(p + 'block.3', (4 * c, c), c)
+            dense(p + 'block.5', (c, 4 * c), 4 * c)
+            sd[p + 'layer_scale'] = _t(rng.uniform(0.5, 1.5, (c, 1, 1)))
+    ln('classifier.0', dims[-1])
+    bound = 1.0 / math.sqrt(dims[-1])
+    sd['classifier.2.weight'] = _t(rng.uniform(-bound, bound, (num_classes, dims[-1])) * logit_gain)
+    sd['classifier.2.bias'] = _t(rng.uniform(-bound, bound, (num_classes,)) * logit_gain)
+    return sd
+
+
 def scenes(seed=1, n=1, sz=(256, 256), box=8, lo=0.05, hi=0.95):
     """`n` smooth random camera scenes in [lo,hi]: U[0,1) low-pass filtered by a box x box mean."""
     rng = np.random.default_rng(seed)
