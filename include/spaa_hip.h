@@ -795,6 +795,35 @@ int spaa_views_combine(const float* const* g, int V, const float* partial, int n
  * for the one camera image it is given (view 0's).  cam, cam_best: V pointers each to [B][HW][4]; entry 0 is not read */
 int spaa_views_track(const float* const* cam, float* const* cam_best, int V, const int32_t* state, int B, int HW, spaa_stream_t stream);
 
+/* ---- universal SPAA: one projection for a group of N scenes, 2 <= N <= SPAA_UNIVERSAL_MAX ------------------------------------- */
+#define SPAA_UNIVERSAL_MAX 64
+/* A batch of B samples is U = B / N groups; group u is the samples uN .. uN+N-1, whose N rows hold the same projector image and whose
+ * parameters (params, flags) are uniform.  The members are rows of the ordinary [B][...] tensors: no pointer arrays.  Both entry points
+ * return hipErrorInvalidValue and launch nothing on a null pointer (prjl2 alone may be NULL), N outside 2..SPAA_UNIVERSAL_MAX,
+ * B % N != 0, B > 65535 or HW < 1; the decision also on need outside 1..N and nblk != ceil(HW / 256).
+ *
+ * The decision (logits, target, partial, nblk, HW, prjl2, params, flags, p_thresh, adv_scale as spaa_decide_ps).  Member b, by the
+ * arithmetic of spaa_decide_ps on sample b alone (bitwise): top1, p1, the target logit, succ, fooled, its own means caml2_b, camdE_b and
+ * its seed row g_logits[b].  Group: nsucc, nfooled; caml2 = (sum over members in index order of caml2_b) / N, camdE likewise; prjl2 is
+ * member 0's; col_loss = prjl2_w prjl2 + caml2_w caml2 + camdE_w camdE.  Outputs, the group's words in EACH of its N rows:
+ *   state [B][4]: 0 nsucc >= need, 1 best_adv = nfooled >= need && caml2 * 255 > d_thr, 2 best, 3 nfooled
+ *   stats [B][8]: 0 min over members of p1, 6 mean over members of the target logit, 1..5 as spaa_decide on the group's values
+ *   uni_state int32 [B][2] = (bit 0 succ | bit 1 fooled, top1)    uni_stats float [B][4] = (p1, target logit, caml2_b, camdE_b)
+ *   uni_w float [B]: the member weights of spaa_universal_combine -- 1, or with focus != 0: 0 for a fooled member unless
+ *   nfooled >= need
+ * With need == N this is spaa_decide_views with members in the place of views. */
+int spaa_decide_universal(const float* logits, int ncls, const int32_t* target, const float* partial, int nblk, int HW, const float* prjl2,
+                          const float* params, const int32_t* flags, int N, int need, float p_thresh, float adv_scale, int focus,
+                          int32_t* state, float* stats, int32_t* uni_state, float* uni_stats, float* uni_w, float* g_logits, int B,
+                          spaa_stream_t stream);
+/* The B per-sample gradient images at the projector, g [B][HW][4], combined group by group into g_out [B][HW][4] (another buffer), the
+ * result in all N rows of the group, its pad channel 0: for a group on the colour step (state[uN][1] != 0) (sum over members in index
+ * order of g_b) * (1 / N); for any other the sum over members in index order of coef_b g_b with coef_b = uni_w_b / ||g_b||_2, and 0
+ * where the norm or the weight is 0.  Workspaces: partial float [B][ceil(HW / 256)] (block partials of ||g_b||^2) and coef float [B].
+ * Run-to-run bitwise reproducible */
+int spaa_universal_combine(const float* g, int N, const float* uni_w, const int32_t* state, float* partial, float* coef, float* g_out,
+                           int B, int HW, spaa_stream_t stream);
+
 /* ---- capture-robust SPAA: one projection against J randomly jittered captures of the camera image, 2 <= J <= SPAA_JITTER_MAX -- */
 #define SPAA_JITTER_MAX 4
 /* Per-draw tensors are passed as HOST arrays of J device pointers, as the ensemble's member tensors.  Any other J, or a null

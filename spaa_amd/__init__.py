@@ -19,7 +19,8 @@ def __getattr__(name):
                 'to_attacker_cfg_str', 'summarize_single_attacker', 'summarize_all_attackers', 'project_capture_real_attack',
                 'attack_results', 'EnsembleAttackState', 'MultiViewAttackState', 'attack_transfer', 'CaptureJitter', 'JitterAttackState',
                 'capture_survival', 'Attention', 'Transfer', 'transfer_success', 'PoseJitter', 'PoseAttackState', 'pose_survival',
-                'JpegCapture', 'JpegAttackState', 'jpeg_survival', 'jpeg_roundtrip', 'quant_tables'):
+                'JpegCapture', 'JpegAttackState', 'jpeg_survival', 'jpeg_roundtrip', 'quant_tables', 'Universal',
+                'UniversalAttackState', 'universal_success'):
         from . import projector_based_attack
         return getattr(projector_based_attack, name)
     if name in ('rgb2lab_diff', 'ciede2000_diff', 'deltaE', 'stealth_loss_with_grad'):

@@ -203,6 +203,8 @@ _SIGNATURES = {
     'spaa_decide_views': [_pp, _i, _i, _p, _pp, _i, _i, _p, _p, _p, _f, _f, _i, _p, _p, _p, _p, _p, _pp, _i, _p],
     'spaa_views_combine': [_pp, _i, _p, _i, _p, _p, _p, _i, _i, _p],
     'spaa_views_track': [_pp, _pp, _i, _p, _i, _i, _p],
+    'spaa_decide_universal': [_p, _i, _p, _p, _i, _i, _p, _p, _p, _i, _i, _f, _f, _i, _p, _p, _p, _p, _p, _p, _i, _p],
+    'spaa_universal_combine': [_p, _i, _p, _p, _p, _p, _p, _i, _i, _p],
     'spaa_jitter_draw': [C.c_uint32, _p, _f, _f, _f, _f, _i, _p, _p, _i, _i, _p],
     'spaa_jitter_fwd': [_p, _p, _p, _i, _i, _pp, _pp, _i, _i, _i, _p],
     'spaa_jitter_bwd': [_pp, _p, _pp, _i, _pp, _i, _i, _i, _p],

@@ -1,4 +1,4 @@
-"""What an attack can be asked for besides the plain SPAA loop -- the option values CaptureJitter, PoseJitter, JpegCapture and Transfer (Attention is
+"""What an attack can be asked for besides the plain SPAA loop -- the option values CaptureJitter, PoseJitter, JpegCapture, Transfer and Universal (Attention is
 spaa_amd.classifier's), the limits of include/spaa_hip.h -- and the check of a request, made before anything is allocated or launched:
 `checked_request` for spaa() and spaa_sweep(), the `_supported` functions for the attack states that are built directly."""
 import dataclasses
@@ -167,6 +167,48 @@ class Transfer:
         i = torch.arange(-r, r + 1, dtype=torch.float64)
         w = torch.exp(-i * i / (2.0 * float(self.sigma) ** 2))
         return (w / w.sum()).to(torch.float32)
+
+
+UNIVERSAL_MAX = 64   # SPAA_UNIVERSAL_MAX of include/spaa_hip.h
+
+
+@dataclasses.dataclass(frozen=True)
+class Universal:
+    """A universal projection: the batch is cut into groups of `size` consecutive samples, each with its own scene, and
+    every group shares ONE projector image (2 <= size <= UNIVERSAL_MAX, the batch a multiple of it).  A group counts as fooled when
+    ceil(`rate` * size) of its members are (`rate` in (0, 1]; 1: all of them, the multi-view rule with members in the place of views)."""
+    size: int
+    rate: float = 1.0
+
+    def __post_init__(self):
+        if isinstance(self.size, bool) or not isinstance(self.size, int):
+            raise ValueError(f'Universal: size must be an integer, got {self.size!r}')
+        if not 2 <= self.size <= UNIVERSAL_MAX:
+            raise ValueError(f'Universal: size must be 2..{UNIVERSAL_MAX}, got {self.size}')
+        r = self.rate
+        if isinstance(r, bool) or not isinstance(r, (int, float)) or not math.isfinite(r) or not 0 < r <= 1:
+            raise ValueError(f'Universal: rate must be in (0, 1], got {r!r}')
+
+    @property
+    def need(self):
+        """The number of fooled members that makes a group fooled: ceil(rate * size) (a product that is an integer but for its
+        rounding, as 0.3 * 10, is that integer)."""
+        return min(self.size, max(1, int(math.ceil(float(self.rate) * self.size - 1e-9))))
+
+    def groups(self, B, who='Universal'):
+        """U = B / size, the number of groups of a batch of B samples."""
+        if B < self.size or B % self.size:
+            raise ValueError(f'{who}: a batch of {B} samples does not divide into groups of universal.size = {self.size}')
+        return B // self.size
+
+    def check_uniform(self, name, values, who='Universal'):
+        """`values` (one per sample) must be equal within every group; the error names the first group that mixes them."""
+        n = self.size
+        for u in range(len(values) // n):
+            row = values[u * n:(u + 1) * n]
+            if any(v != row[0] for v in row):
+                raise ValueError(f'{who}: {name} must be uniform within a universal group; group {u} (samples {u * n}..'
+                                 f'{(u + 1) * n - 1}) holds {sorted(set(row), key=str)}')
 
 
 def _unwrap(m):
@@ -345,7 +387,20 @@ def _transfer_supported(transfer, classifier, storage, who):
     _transfer_checked(transfer, storage, who)
 
 
-def checked_request(who, pcnet, classifier, cam_scene, storage, focus, jitter, pose, attention, transfer, jpeg=None):
+def _universal_supported(universal, pcnet, classifier, storage, jitter, pose, jpeg, who):
+    """What a universal attack does not serve.  `pcnet` / `classifier`: as spaa() holds them after its own checks; `jitter` / `pose` /
+    `jpeg`: None or checked values.  (`attention`, `transfer`, `focus` and every stealth-loss string combine with it.)"""
+    _is_a(universal, 'universal', Universal, who, ' or None')
+    _need_one_of_each('a universal projection', 'universal', pcnet, classifier, who)
+    for name, other in (('jitter', jitter), ('pose', pose), ('jpeg', jpeg)):
+        if other is not None:
+            raise NotImplementedError(f'{who}: universal together with {name} is not implemented (the draws of a sample and the members '
+                                      f'of a group would need a rule of their own); use universal or {name}')
+    _need_classifier('a universal attack', 'a foreign callable can only be attacked scene by scene', classifier, who)
+    _need_f32('for a universal projection', _OWN_SCALE.format('members'), storage, who)
+
+
+def checked_request(who, pcnet, classifier, cam_scene, storage, focus, jitter, pose, attention, transfer, jpeg=None, universal=None):
     """The request of spaa() / spaa_sweep() (`who`), checked in the one order that decides which error a caller sees; returns the
     normalised (pcnet, classifier, cam_scene): unwrapped, a sequence of one collapsed, a list where there are several."""
     pcnet, classifier = _unwrap(pcnet), _unwrap(classifier)
@@ -369,4 +424,6 @@ def checked_request(who, pcnet, classifier, cam_scene, storage, focus, jitter, p
         _attention_supported(attention, classifier, storage, jitter, who)
     if transfer is not None:
         _transfer_supported(transfer, classifier, storage, who)
+    if universal is not None:
+        _universal_supported(universal, pcnet, classifier, storage, jitter, pose, jpeg, who)
     return pcnet, classifier, cam_scene

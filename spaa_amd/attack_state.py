@@ -1,5 +1,5 @@
 """The device-side states of the batched SPAA attack: AttackState (one PCNet, one classifier), EnsembleAttackState (several classifiers),
-MultiViewAttackState (several PCNets) and DrawAttackState (random draws of the camera image through a chain of stages:
+MultiViewAttackState (several PCNets), UniversalAttackState (groups of samples that share their projector image) and DrawAttackState (random draws of the camera image through a chain of stages:
 JitterAttackState, PoseAttackState, JpegAttackState).  Lines quoted as :NNN are the reference's projector_based_attack.py."""
 import ctypes
 
@@ -8,7 +8,7 @@ import torch
 from . import _lib
 from .models import to_nhwc4, to_nchw
 from .attack_options import (JPEG_SUBSAMPLINGS, _unwrap, _ensemble_members, _view_pcnets, _views_supported, _jitter_supported,
-                             _pose_supported, _jpeg_supported, _attention_checked, _transfer_checked)
+                             _pose_supported, _jpeg_supported, _attention_checked, _transfer_checked, _universal_supported)
 
 
 def _is_scalar(v):
@@ -480,6 +480,85 @@ class MultiViewAttackState(AttackState):
     def results(self):
         with torch.cuda.device(self.dev):
             return [to_nchw(c) for c in self.cam_bests], to_nchw(self.x_best, clamp01=True)
+
+
+class UniversalAttackState(AttackState):
+    """One batched attack in which every group of N = universal.size consecutive samples shares ONE projector image:
+    AttackState -- one PCNet engine, one classifier engine, one scene per sample, the ordinary per-sample forward and backward passes --
+    with the decision per group (spaa_decide_universal: the multi-view rule with members in the place of views, a group fooled when
+    universal.need of its members are) and the B gradient images at the projector combined group by group (spaa_universal_combine: the
+    mean on the colour step, the weighted sum of the members' unit images on the adversarial step) into `g`, whose N equal rows per
+    group then take the ordinary step.  The N rows of a group hold the same `x`, `x_best`, `state` and `stats` words at every iteration,
+    bitwise.  `state[:, 3]` counts the group's fooled members; each sample's own top-1 is in `uni_state`, its p1, target logit, caml2
+    and camdE in `uni_stats`.  `focus`: a member that is already fooled rests (weight 0) until the group is fooled."""
+    label = 'members'
+
+    def __init__(self, pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, device, universal, storage='f32', focus=False,
+                 attention=None, transfer=None):
+        pcnet, classifier = _unwrap(pcnet), _unwrap(classifier)
+        _universal_supported(universal, pcnet, classifier, storage, None, None, None, 'UniversalAttackState')
+        B = len(target_idx)
+        universal.groups(B, 'UniversalAttackState')
+        if not isinstance(stealth_loss, str) and len(stealth_loss) == B:
+            universal.check_uniform('stealth_loss', list(stealth_loss), 'UniversalAttackState')
+        self.universal, self.N, self.need, self.focus = universal, int(universal.size), universal.need, bool(focus)
+        super().__init__(pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, device, storage=storage,
+                         attention=attention, transfer=transfer)
+
+    def _build(self, pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, dev):
+        super()._build(pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, dev)
+        B = self.B
+        # ||g||^2 of the COMBINED gradient comes from spaa_grad_sumsq_ps (the adjoint's epilogue sums a member's), and the backward
+        # pass reads the clamp gate from x
+        self.ss_tiles, self.clamp_bits = 0, None
+        self.partial_ss = torch.zeros(B, self.nblk_p, device=dev)
+        self.uni_state = torch.zeros(B, 2, dtype=torch.int32, device=dev)
+        self.uni_stats = torch.zeros(B, 4, device=dev)
+        self.uni_w = torch.ones(B, device=dev)
+        self.uni_partial = torch.zeros(B, self.nblk_p, device=dev)
+        self.uni_coef = torch.zeros(B, device=dev)
+        self.g = torch.zeros(B, self.x.shape[1], self.x.shape[2], 4, device=dev)
+
+    def _per_sample(self, targeted, d_thr, table=False):
+        """The per-sample table, always; a new (targeted, d_thr) setting must be uniform within every group."""
+        before = self._ps_key
+        super()._per_sample(targeted, d_thr, table=True)
+        if self._ps_key != before:
+            tg, dt = self._ps_key
+            self._ps_key = None   # (a refused setting is checked again when it comes again)
+            self.universal.check_uniform('targeted', list(tg), 'UniversalAttackState')
+            self.universal.check_uniform('d_thr', list(dt), 'UniversalAttackState')
+            self._ps_key = (tg, dt)
+
+    def _forward_decide(self, targeted, d_thr, p_thresh, adv_w):
+        B, p = self.B, _lib.ptr
+        self._per_sample(targeted, d_thr)
+        y = self.eng.forward(self.x, clamp01=True)                                   # :265, every sample its own scene
+        logits = self.clf.forward(y)                                                 # :266
+        self._y, self._uniform = y, False
+        prjl2 = self._prjl2_fwd()
+        self._stealth_loss_ps(y)
+        self._ssim_term(y)
+        _lib.call('spaa_decide_universal', p(logits), self.clf.ncls, p(self.target), p(self.partial_loss), self.nblk_c, self.HWc, prjl2,
+                  p(self.ps_params), p(self.ps_flags), self.N, self.need, float(p_thresh), adv_w / B * self.gs_adv, int(self.focus),
+                  p(self.state), p(self.stats), p(self.uni_state), p(self.uni_stats), p(self.uni_w), p(self.g_logits), B)
+
+    def _backward_step(self, adv_lr, col_lr):
+        B, p = self.B, _lib.ptr
+        g_adv = self._adv_gradient()
+        gx = self._pcnet_backward(self.eng, g_adv, self.g_col, self.gP)              # the B members' own gradient images
+        _lib.call('spaa_universal_combine', p(gx), self.N, p(self.uni_w), p(self.state), p(self.uni_partial), p(self.uni_coef), p(self.g),
+                  B, self.HWp)
+        _lib.call('spaa_grad_sumsq_ps', p(self.g), p(self.x), self.gray, p(self.ps_prjl2_scale), p(self.state), p(self.partial_ss), B,
+                  self.HWp)
+        self._step_and_track(self.g, adv_lr, col_lr)
+
+    def attention_maps(self):
+        """[B, 1, Hc, Wc]: every sample's own map (the members are rows of the one classifier engine)."""
+        return self._engine_maps(self.clfs)[0]
+
+    def trace_entry(self):
+        return super().trace_entry() + (self.uni_state.clone(), self.uni_stats.clone())
 
 
 class JitterStage:

@@ -231,6 +231,29 @@ def transfer_success(cam, classifier, target_idx, targeted, crop_sz, p_thresh=0.
     return np.where(tg, (top1 == tgt) & (p1[0] > np.float32(p_thresh)), top1 != tgt)
 
 
+def universal_success(pcnet, classifier, prj_adv, cam_scenes, target_idx, targeted, crop_sz, p_thresh=0.9):
+    """A universal projection on scenes it may never have seen: `prj_adv` ([3,Hp,Wp] / [1,3,Hp,Wp]: one projector image for all, or
+    [M,3,Hp,Wp]: one per scene) is projected onto the scenes `cam_scenes` [M,3,H,W] through `pcnet`, and `classifier` looks at the M
+    inferred captures.  Returns (success bool [M] by transfer_success's rule, cam_infer [M,3,H,W]); one class id per scene in
+    `target_idx` (its true class if untargeted) and `targeted` (one flag, or one per scene).  The evaluation hook of a universal attack
+    (Universal): the mean of the first return value over scenes held out from the attack is its fooling rate.  GPU only."""
+    scenes = cam_scenes.detach().float()
+    if scenes.ndim != 4 or scenes.shape[1] != 3:
+        raise ValueError(f'universal_success: cam_scenes must be [M,3,H,W], got {tuple(cam_scenes.shape)}')
+    m = scenes.shape[0]
+    prj = prj_adv.detach().float()
+    while prj.ndim < 4:
+        prj = prj[None]
+    if prj.shape[0] == 1:
+        prj = prj.expand(m, -1, -1, -1)
+    if prj.shape[0] != m:
+        raise ValueError(f'universal_success: {prj.shape[0]} projector images for {m} scenes (one for all, or one per scene)')
+    dev = next(pcnet.parameters()).device
+    with torch.no_grad(), _lib.on_device(dev):
+        cam = pcnet(torch.clamp(prj.to(dev), 0, 1).contiguous(), scenes.to(dev).contiguous()).detach()
+        return transfer_success(cam, classifier, target_idx, targeted, crop_sz, p_thresh), cam
+
+
 def write_stats(table, path):
     """The reference's table files: tab-separated, 4 decimals (stats.txt, stats_all.txt)."""
     table.to_csv(path, index=False, float_format='%.4f', sep='\t')

@@ -20,12 +20,14 @@ import torch
 from . import _lib
 from .models import PCNet, to_nhwc4, to_nchw   # noqa: F401
 from .classifier import Attention, Classifier   # noqa: F401  (Attention: re-exported)
-from .attack_options import (ENS_MAX, VIEWS_MAX, JITTER_MAX, TRANSFER_RMAX, POSE_MAX_ROTATE, POSE_MAX_ZOOM, POSE_MAX_TILT,   # noqa: F401
-                             POSE_MAX_SHIFT, CaptureJitter, PoseJitter, JpegCapture, Transfer, checked_request, _unwrap, _ensemble_members,
+from .attack_options import (ENS_MAX, VIEWS_MAX, JITTER_MAX, TRANSFER_RMAX, UNIVERSAL_MAX, POSE_MAX_ROTATE, POSE_MAX_ZOOM,   # noqa: F401
+                             POSE_MAX_TILT, POSE_MAX_SHIFT, CaptureJitter, PoseJitter, JpegCapture, Transfer, Universal,
+                             checked_request, _unwrap, _ensemble_members, _universal_supported,
                              _view_pcnets, _views_supported, _jitter_supported, _pose_supported, _jpeg_supported, _attention_checked,
                              _attention_supported, _transfer_checked, _transfer_supported)
-from .attack_state import (AttackState, EnsembleAttackState, MultiViewAttackState, DrawAttackState, JitterAttackState,   # noqa: F401
-                           PoseAttackState, JpegAttackState, JitterStage, PoseStage, JpegStage, _is_scalar, _require_gpu, _scene_batch)
+from .attack_state import (AttackState, EnsembleAttackState, MultiViewAttackState, UniversalAttackState, DrawAttackState,   # noqa: F401
+                           JitterAttackState, PoseAttackState, JpegAttackState, JitterStage, PoseStage, JpegStage, _is_scalar, _require_gpu,
+                           _scene_batch)
 
 # B * Hc * Wc up to which spaa() replays the iteration as a captured HIP graph (0 disables); above it the GPU is busy for
 # longer than the host needs to enqueue an iteration and eager launches lose nothing (measured: < 1 % at B = 64, 256 x 256)
@@ -48,12 +50,15 @@ def ssim_weight(stealth_loss):
 
 
 def _attack_state(pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, device, storage, focus, jitter=None,
-                  attention=None, transfer=None, pose=None, jpeg=None):
+                  attention=None, transfer=None, pose=None, jpeg=None, universal=None):
     """AttackState for one Classifier, EnsembleAttackState for a checked list of several, MultiViewAttackState for a checked list of
     PCNets (with their list of scenes), JitterAttackState for one Classifier with a CaptureJitter, PoseAttackState for one Classifier
     with a PoseJitter (with or without a CaptureJitter), JpegAttackState for one Classifier with a JpegCapture (with or without either of
-    the other two); the last three take no `attention`.  Each of them takes `transfer`."""
+    the other two); the last three take no `attention`; UniversalAttackState for one PCNet and one Classifier with a Universal.  Each of
+    them takes `transfer`."""
     args = (pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, device)
+    if universal is not None:
+        return UniversalAttackState(*args, universal, storage=storage, focus=focus, attention=attention, transfer=transfer)
     if jpeg is not None:
         return JpegAttackState(*args, jpeg, storage=storage, pose=pose, jitter=jitter, transfer=transfer)
     if pose is not None:
@@ -69,7 +74,7 @@ def _attack_state(pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_
 
 def spaa(pcnet, classifier, imagenet_labels, target_idx, targeted, cam_scene, d_thr, stealth_loss, device, setup_info,
          *, iters=50, adv_lr=2, col_lr=1, p_thresh=0.9, trace=None, verbose=False, storage='f32', focus=False, jitter=None,
-         attention=None, transfer=None, pose=None, jpeg=None):
+         attention=None, transfer=None, pose=None, jpeg=None, universal=None):
     """Stealthy Projector-based Adversarial Attack (SPAA Algorithm 1) — see module docstring.
 
     :param pcnet: spaa_amd.PCNet (optionally wrapped in DataParallel-like `.module`), or a list / tuple of 2..4 of them: the same projector
@@ -78,8 +83,8 @@ def spaa(pcnet, classifier, imagenet_labels, target_idx, targeted, cam_scene, d_
         camera image batch per view.  A sequence of one is that PCNet.
     :param classifier: spaa_amd.Classifier, or a list / tuple of 2..4 of them with the same classes: ONE projection against all of them
         (EnsembleAttackState; fp32 storage only).  A sequence of one is that classifier.
-    :param focus: ensembles and views only: members / views that are already fooled rest until all are (default: every one pulls all
-        the time)
+    :param focus: ensembles, views and universal groups only: members / views that are already fooled rest until all are (a universal
+        group: until enough are) (default: every one pulls all the time)
     :param jitter: a CaptureJitter: ONE projection against `jitter.draws` randomly perturbed captures of the camera image per iteration,
         the first of them the clean one (JitterAttackState; one PCNet, one Classifier, fp32 storage, no `focus`).  The trace entries
         are the ensemble's, with draws as members.  None (default): the attack on the noiseless inferred capture
@@ -100,6 +105,16 @@ def spaa(pcnet, classifier, imagenet_labels, target_idx, targeted, cam_scene, d_
         Classifier, fp32 storage, no `focus`, no `attention`).  With `pose` and / or `jitter` of the same `draws` the codec comes last:
         draw j is Jpeg_j(Jitter_j(Pose_j(y))).  The decision's stealth loss and `cam_best` stay the clean inference's.  None
         (default): launch for launch as before
+    :param universal: a Universal: the batch is cut into groups of `universal.size` consecutive samples, each sample with its own scene
+        (`cam_scene` [B,3,H,W]) and its own class in `target_idx`, and every group shares ONE projector image: the light pattern that
+        fools the classifier whatever scene of the group stands in front of the projector (UniversalAttackState; one
+        PCNet, one Classifier, fp32 storage, no `jitter`, `pose` or `jpeg`; B a multiple of the size; `targeted`, `d_thr` and the
+        stealth loss uniform within a group).  A group is fooled when ceil(universal.rate * size) of its members are; the members'
+        gradient images meet at the projector as the views' of a multi-view attack do.  Combines with `attention`, `transfer` and
+        `focus` (a fooled member rests until its group is fooled).  The return shapes stay: the rows of a group in `prj_adv_best`
+        are equal, `cam_infer_best` is per sample; the trace entries are (state, stats, uni_state, uni_stats), where state[:, 3]
+        counts the group's fooled members.  attack_summary.universal_success projects the result onto scenes held out from the
+        attack.  None (default): launch for launch as before
     :param imagenet_labels: dict idx -> name (only used when verbose)
     :param target_idx: list of B class ids (true label if untargeted)
     :param targeted: bool
@@ -114,20 +129,24 @@ def spaa(pcnet, classifier, imagenet_labels, target_idx, targeted, cam_scene, d_
     :return: (cam_infer_best [B,3,Hc,Wc], prj_adv_best [B,3,Hp,Wp] in [0,1]); for several views ([cam_infer_best per view], prj_adv_best)
     """
     pcnet, classifier, cam_scene = checked_request('spaa', pcnet, classifier, cam_scene, storage, focus, jitter, pose, attention, transfer,
-                                                   jpeg)
+                                                   jpeg, universal)
+    if universal is not None:   # (`targeted` / `d_thr` may be one per sample here: groups may differ from each other, not within)
+        for name, value in (('targeted', targeted), ('d_thr', d_thr)):
+            if not _is_scalar(value):
+                universal.check_uniform(name, list(value), 'spaa')
     if not isinstance(classifier, (Classifier, list)):
         if not callable(classifier):
             raise TypeError('classifier must be a spaa_amd.Classifier or a callable (im, crop_sz) -> (raw_score, p, idx)')
         return _spaa_foreign_classifier(pcnet, classifier, imagenet_labels, target_idx, targeted, cam_scene, d_thr,
                                         stealth_loss, device, setup_info, iters, adv_lr, col_lr, p_thresh, trace)
     st = _attack_state(pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, device, storage, focus, jitter, attention,
-                       transfer, pose, jpeg)
+                       transfer, pose, jpeg, universal)
 
     def report(i):
         if i % 30 == 0 or i == iters - 1:
             s, f = st.state.cpu(), st.stats.cpu()
             v = 7 if (targeted and st.B > 7) else 0
-            name = f'of {len(st.clfs)} {st.label} fooled' if st.label else (imagenet_labels[int(s[v, 3])] if imagenet_labels else '')
+            name = f'of {getattr(st, "N", len(st.clfs))} {st.label} fooled' if st.label else (imagenet_labels[int(s[v, 3])] if imagenet_labels else '')
             print(f'col_loss = {f[:, 3].mean():<9.4f} | prjl2 = {f[:, 4].mean() * 255:<9.4f} | caml2 = '
                   f'{f[:, 1].mean() * 255:<9.4f} | camdE = {f[:, 2].mean():<9.4f} | p = {f[v, 0]:.4f} | y = '
                   f'{int(s[v, 3]):3d} ({name})')
@@ -215,7 +234,7 @@ def split_sweep(samples, ncfg, chunk_results):
 
 def spaa_sweep(pcnet, classifier, imagenet_labels, cam_scene, setup_info, device, configs, *, iters=50, adv_lr=2, col_lr=1,
                p_thresh=0.9, max_batch=64, storage='f32', trace=None, focus=False, jitter=None, attention=None, transfer=None,
-               pose=None, jpeg=None):
+               pose=None, jpeg=None, universal=None):
     """Several SPAA attacks on one PCNet, scene and classifier as few batched attacks (the reference's driver makes one spaa() call
     per configuration: projector_based_attack.py:24-148).  `configs`: [(stealth_loss, d_thr, targeted, target_idx), ...]; returns one
     (cam_infer_best, prj_adv_best) per config, in order -- what spaa(pcnet, classifier, imagenet_labels, target_idx, targeted,
@@ -231,7 +250,11 @@ def spaa_sweep(pcnet, classifier, imagenet_labels, cam_scene, setup_info, device
     `attention`: an Attention, as in spaa(): every chunk is an attention-weighted attack.  `transfer`: a Transfer, as in spaa(): every
     chunk's adversarial steps follow the smoothed, momentum-accumulated direction (each chunk's momentum starts at zero).  `pose`: a
     PoseJitter, as in spaa(): every chunk is a pose attack with that seed (the draws of a sample depend on its place in its chunk).
-    `jpeg`: a JpegCapture, as in spaa(): every chunk is a JPEG attack with that seed, in the same way."""
+    `jpeg`: a JpegCapture, as in spaa(): every chunk is a JPEG attack with that seed, in the same way.  `universal` is refused: the
+    sweep batches configurations of ONE scene, a universal projection is over several."""
+    if universal is not None:
+        raise NotImplementedError('spaa_sweep: universal= is not implemented (the sweep batches the configurations of one scene; a '
+                                  'universal projection shares one image among several scenes): call spaa(..., universal=...)')
     samples, chunks = plan_sweep(configs, max_batch)
     pcnet, classifier, cam_scene = checked_request('spaa_sweep', pcnet, classifier, cam_scene, storage, focus, jitter, pose, attention,
                                                    transfer, jpeg)
@@ -354,4 +377,5 @@ from .jpeg import jpeg_roundtrip, quant_tables   # noqa: E402,F401
 from .attack_summary import (SUMMARY_STEALTH_LOSSES, SUMMARY_D_THRESHES, SUMMARY_CLASSIFIERS, SUMMARY_CHUNK,   # noqa: E402,F401
                              SUMMARY_COLUMNS, MONTAGE_CHUNK, attack_success, write_stats, _sorted_classes, _nonempty,
                              attack_results, attack_transfer, capture_survival, pose_survival, jpeg_survival, transfer_success,
+                             universal_success,
                              summarize_single_attacker, summarize_all_attackers)
