@@ -1033,6 +1033,38 @@ int spaa_onepixel_warp(const float* base, const int32_t* cand, int P, int npix, 
 int spaa_capture_preproc(const float* y, float* out, int B, int H, int W, int cy0, int cx0, int ch, int cw, int oh, int ow,
                          const float* mean3, const float* std3, int quantize, spaa_stream_t stream);
 
+/* ---- Square Attack on the projector image (Andriushchenko et al., ECCV 2020; spaa_amd/square_attack.py) ----------
+ * Sample b's current projector image x_u8 [B][Hp][Wp]: one packed word per pixel, R | G << 8 | B << 16, top byte 0; its float value
+ * is u8 / 255.0f (true division).  A perturbed value is clamp(c0 +/- eps8, 0, 255), c0 in 0..255, eps8 in 1..127.  Words come from
+ * draw_rng.hpp's draw_word behind two first constants of their own; the sample index of a word is b_off + b.  1 <= K <= 8,
+ * B <= 65535, Hp, Wp >= 2.  state int32 [B][4] = (accepted, k*, done, queries), best_loss float [B]: zeros and +inf before
+ * iteration 0. */
+/* the vertical stripes: column w, channel ch of sample b = c0 + eps8 where bit 0 of the word (seed, 0, b_off + b, w, ch) is set,
+ * else c0 - eps8 */
+int spaa_square_init(uint32_t seed, int b_off, int c0, int eps8, uint32_t* x_u8, int B, int Hp, int Wp, spaa_stream_t stream);
+/* prop int32 [B][K][8] = (r, c, h, R, G, B, 0, 0): r = word(seed, t, b_off + b, k, 0) % (Hp - h + 1), c = word(.., 1) % (Wp - h + 1),
+ * R / G / B = c0 +/- eps8 by bits 0 / 1 / 2 of word(.., 2).  0 <= h <= min(Hp, Wp) - 1.  A sample with state[b][2] != 0 (resting), and
+ * every sample when h == 0 (iteration 0: the stripes themselves), gets rows of zeros, which paint nothing. */
+int spaa_square_propose(uint32_t seed, int t, int b_off, int h, int c0, int eps8, const int32_t* state, int32_t* prop, int B, int K, int Hp,
+                        int Wp, spaa_stream_t stream);
+/* spaa_onepixel_warp with a per-sample base: xw [B*K][Hc][Wc][4], row b K + k = bitwise spaa_warp_fwd_taps of x_u8[b] / 255 with the
+ * square [r, r + h) x [c, c + h) of prop[b][k] painted (R, G, B) / 255; taps outside the image (0x7fffffff) read 0; the proposal words are
+ * compared, never used as addresses.  cat8 (may be NULL) [B*K][Hc][Wc][8] as spaa_onepixel_warp writes it, scene [Hc][Wc][4] shared. */
+int spaa_square_warp(const uint32_t* x_u8, const int32_t* prop, int B, int K, const int32_t* tap_src, const float* tap_wgt,
+                     const float* scene, float* xw, float* cat8, int Hp, int Wp, int Hc, int Wc, spaa_stream_t stream);
+/* Two launches.  rows float [B*K][4] = (loss, top-1, p1, 0) of logits [B*K][ncls], ncls >= 2: top-1 the first maximum, p1 = 1 / sum
+ * exp(l - max); loss = l[y] - max_{j != y} l[j] (targeted[b] == 0) or logsumexp(l) - l[y] (targeted[b] != 0), y = label[b]; a label
+ * outside [0, ncls) gives NaN.  Then per sample: k* = the smallest loss of its first `count` rows (1 <= count <= K: K captures per
+ * iteration, 1 for the stripes), ties to the lowest k, NaN never (k* = 0 when every loss is NaN); accepted iff that loss < best_loss[b]
+ * (strict), which then takes it; done = the accepted row's top-1 != y, or, targeted, == y with p1 > p_thresh; queries += count.  A
+ * sample with done != 0 keeps k*, done, queries and best_loss; its accepted word becomes 0. */
+int spaa_square_score(const float* logits, int ncls, const int32_t* label, const int32_t* targeted, float p_thresh, int count, float* rows,
+                      float* best_loss, int32_t* state, int B, int K, spaa_stream_t stream);
+/* accepted samples (state[b][0] != 0): the square of prop[b][k*] into x_u8[b] and y[b K + k*] ([B*K][Hc][Wc][4]) into cam_best[b]
+ * ([B][Hc][Wc][4]); a square that does not lie inside the image is not painted.  The others are left as they are. */
+int spaa_square_commit(const int32_t* state, const int32_t* prop, const float* y, uint32_t* x_u8, float* cam_best, int B, int K, int Hp,
+                       int Wp, int Hc, int Wc, spaa_stream_t stream);
+
 /* ---- direct-light mask of a camera view (train_network.py:68-80 load_data, img_proc.py:13-65 threshold_im) ---- */
 /* Nayar's separation of N >= 2 shifted-checkerboard captures cb [N][3][H][W] (planar fp32, projector backlight b in [0, 1)):
  * per pixel and channel l1 = max_n, l2 = min_n, direct = (l1 - l2) / (float)(1 - b), indirect = 2 (l2 - (float)b l1) /

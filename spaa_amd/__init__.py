@@ -39,6 +39,9 @@ def __getattr__(name):
     if name in ('DigitalOnePixelAttacker', 'ProjectorOnePixelAttacker', 'SimulatedCapture', 'perturb_image'):
         from . import one_pixel_attacker
         return getattr(one_pixel_attacker, name)
+    if name in ('ProjectorSquareAttacker',):
+        from . import square_attack
+        return getattr(square_attack, name)
     if name in ('calc_img_dists', 'img_stats', 'dists_from_sums'):
         from . import metrics
         return getattr(metrics, name)

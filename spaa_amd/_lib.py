@@ -228,6 +228,11 @@ _SIGNATURES = {
     'spaa_onepixel_score': [_p, _i, _i, _i, _p, _p, _p, _i, _p],
     'spaa_onepixel_warp': [_p, _p, _i, _i, _i, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p],
     'spaa_capture_preproc': [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_float), C.POINTER(C.c_float), _i, _p],
+    'spaa_square_init': [C.c_uint32, _i, _i, _i, _p, _i, _i, _i, _p],
+    'spaa_square_propose': [C.c_uint32, _i, _i, _i, _i, _i, _p, _p, _i, _i, _i, _i, _p],
+    'spaa_square_warp': [_p, _p, _i, _i, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p],
+    'spaa_square_score': [_p, _i, _p, _p, _f, _i, _p, _p, _p, _i, _i, _p],
+    'spaa_square_commit': [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p],
     'spaa_cb_direct_gray': [_p, _i, _i, _i, _d, _p, _p, _p, _p],
     'spaa_mask_blur_hist': [_p, _i, _i, _p, _p, _p],
     'spaa_otsu_mask_bbox': [_p, _p, _i, _i, _p, _p, _p],

@@ -14,6 +14,7 @@ from .classifier import load_imagenet_labels
 from .img_proc import center_crop, expand_4d
 
 ATTACKERS = ('SPAA', 'PerC-AL+CompenNet++', 'One-pixel_DE')
+QUERY_ATTACKERS = ('Square',)    # attackers of this project that the reference lacks: the driver runs them, the summary step does not read them
 MODEL_TRAIN_CFG = dict(loss='l1+ssim', num_train=500, batch_size=24, max_iters=2000)   # get_model_train_cfg's defaults (train_network.py)
 
 
@@ -27,12 +28,15 @@ def get_attacker_cfg(attacker_name, data_root, setup_list, device_ids=[0], load_
         cfg.stealth_losses, cfg.d_threshes = ['camdE'], [11]
     elif attacker_name == 'One-pixel_DE':
         cfg.stealth_losses, cfg.d_threshes = ['-'], ['-']
+    elif attacker_name == 'Square':
+        # square_eps8 (the budget in 8-bit projector levels) has no default: see ProjectorSquareAttacker.attack
+        cfg.stealth_losses, cfg.d_threshes, cfg.square_eps8, cfg.square_iters, cfg.square_proposals = ['-'], ['-'], None, 1000, 1
     return cfg
 
 
 def to_attacker_cfg_str(attacker_name):
     """projector_based_attack.py:195-209: (attacker_cfg_str, model_cfg_str), the result folders' names."""
-    if attacker_name not in ATTACKERS:
+    if attacker_name not in ATTACKERS + QUERY_ATTACKERS:
         raise ValueError(f'{attacker_name} not supported!')
     m = MODEL_TRAIN_CFG
     tail = f'{m["loss"]}_{m["num_train"]}_{m["batch_size"]}_{m["max_iters"]}'
@@ -176,8 +180,13 @@ def run_projector_based_attack(cfg, *, models=None, classifiers=None, iters=50, 
     (captures go under cam/raw/adv): see _run_one_pixel_de."""
     from . import perc_al, projector_based_attack as core
     name = cfg.attacker_name
-    if name not in ATTACKERS:
+    if name not in ATTACKERS + QUERY_ATTACKERS:
         raise ValueError(f'{name} not supported!')
+    if name == 'Square':
+        if capture is None:
+            raise NotImplementedError('Square attacks the real scene through a projector and a camera; pass capture=\'model\' (a trained '
+                                      'PCNet in `models` simulates the capture) or capture=<function setup_info -> capture callable>')
+        return _run_square(cfg, models, classifiers, capture)
     if name == 'One-pixel_DE':
         if capture is None:
             raise NotImplementedError('One-pixel_DE attacks the real scene through a projector and a camera; use '
@@ -281,6 +290,46 @@ def _run_one_pixel_de(cfg, models, classifiers, capture):
     if simulated:
         print(f'\nThe next step is to project and capture [One-pixel_DE] generated adversarial projections in '
               f'{setup.prj_adv(attacker_cfg_str)}')
+    else:
+        print(f'\nThe next step is to inspect the camera-captured adversarial projections in {cam_adv(attacker_cfg_str)}')
+    return cfg
+
+
+def _run_square(cfg, models, classifiers, capture):
+    """The Square Attack (spaa_amd.square_attack) on one setup, with One-pixel_DE's capture rules.  Per classifier the ten targeted
+    attacks and the untargeted one on the scene's top-1 run as ONE batch of 11 samples (sample i draws the words of sample i).
+    Projector images go under prj/adv/Square/-/-/<classifier>/ (1-10 targeted, 11 untargeted); captures of a real `capture` under
+    cam/raw/adv/..., those of capture='model' under cam/infer/adv/...  cfg.square_eps8 is required (no default: see
+    ProjectorSquareAttacker.attack); cfg.square_iters, cfg.square_proposals and an optional cfg.seed are handed on."""
+    from .square_attack import ProjectorSquareAttacker
+    setup_name = _one_setup(cfg, 'Square: ')
+    _check_capture(capture)
+    _require_classifiers(cfg, classifiers)
+    if cfg.get('square_eps8') is None:
+        raise ValueError('Square: set cfg.square_eps8, the L-infinity budget in 8-bit projector levels (1..127); it has no default')
+    setup = AttackSetup(cfg.data_root, setup_name)
+    cam_scene = setup.cam_scene()
+    cap, simulated = _resolve_capture(capture, 'run_projector_based_attack', models, setup, cam_scene)
+    cam_adv = setup.cam_infer_adv if simulated else setup.cam_raw_adv
+    imagenet_labels = setup.imagenet_labels()
+    n = 10
+    target_idx = setup.target_idx(n)
+    square = ProjectorSquareAttacker(imagenet_labels, setup.info, capture=cap)
+    attacker_cfg_str = to_attacker_cfg_str('Square')[0]
+    for stealth_loss, d_thr, classifier_name in itertools.product(cfg.stealth_losses, cfg.d_threshes, cfg.classifier_names):
+        folder = (attacker_cfg_str, stealth_loss, d_thr, classifier_name)
+        classifier = classifiers[classifier_name]
+        true_idx, p = _scene_top1(classifier, cam_scene, setup.crop_sz)
+        print(f'\n-------------------- [Square] attacking [{classifier_name}], original prediction: ({imagenet_labels[true_idx]}, '
+              f'p={p.max():.2f}), eps8: [{cfg.square_eps8}] --------')
+        prj, cam, info = square.attack(classifier, list(target_idx) + [true_idx], [True] * n + [False], eps8=cfg.square_eps8,
+                                       n_iters=cfg.get('square_iters', 1000), proposals=cfg.get('square_proposals', 1),
+                                       seed=cfg.get('seed', 0))
+        print(f'success {info["success"].astype(int).tolist()}, queries {info["queries"].tolist()}')
+        io.save_imgs(cam, cam_adv(*folder))
+        io.save_imgs(prj, setup.prj_adv(*folder))
+    if simulated:
+        print(f'\nThe next step is to project and capture [Square] generated adversarial projections in {setup.prj_adv(attacker_cfg_str)}')
     else:
         print(f'\nThe next step is to inspect the camera-captured adversarial projections in {cam_adv(attacker_cfg_str)}')
     return cfg
