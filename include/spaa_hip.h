@@ -911,6 +911,43 @@ int spaa_jpeg_fwd(const float* const* y, const float* row, int J, int subsamplin
 int spaa_jpeg_bwd(const float* const* g_out, const float* const* y, const float* row, int J, int subsampling, int soft,
                   const uint8_t* const* gate, float* const* g_y, int B, int H, int W, spaa_stream_t stream);
 
+/* ---- defocus-robust SPAA: one projection against J lens blurs of the camera image, 2 <= J <= SPAA_JITTER_MAX ----------
+ * Conventions of the capture jitter above: host arrays of J device pointers, any other J / a null pointer / a size < 1 is
+ * hipErrorInvalidValue with nothing launched, images [B][H*W][4] fp32, no allocation, no sync, no atomics, run-to-run bitwise
+ * reproducible.
+ *
+ * A row is 12 floats (sigma, r, w_0 .. w_8, 0), row [B][J][12]: the half kernel of a symmetric filter of 2 r + 1 taps, entries beyond
+ * w_r are 0.  The row of a sigma (camera pixels), in fp32: r = min(SPAA_BLUR_RMAX, (int)ceilf(3.0f * sigma)), w_0 = 1 (set, not
+ * computed), w_i = expf(-(i i) / (2 sigma sigma)) for i = 1..r, all divided by w_0 + 2 (w_1 + .. + w_r) summed in index order.
+ * sigma == 0 gives the identity row (0, 0, 1, 0, ...).  The sigmas of spaa_blur_rows lie in device memory, so the entry point cannot
+ * refuse one: a sigma that is not > 0 (negative, NaN) gives the identity row, and a sigma above 2.5 gives r = SPAA_BLUR_RMAX with the
+ * Gaussian truncated there (the 17 taps still normalised to sum 1); callers check the range on the host, as gaussian_blur() does.  The
+ * image kernels read r and the taps of a row, never its sigma; an r outside 0..SPAA_BLUR_RMAX is taken as the nearer end. */
+#define SPAA_BLUR_RMAX 8
+/* The tile of one workgroup of spaa_blur_fwd / spaa_blur_bwd (columns x rows): what the tests place their shapes around. */
+#define SPAA_BLUR_TILE_W 32
+#define SPAA_BLUR_TILE_H 16
+/* The rows of n sigmas from device memory: row [n][12] of sigma [n]; 1 <= n <= 2^24.  One launch. */
+int spaa_blur_rows(const float* sigma, float* row, int n, spaa_stream_t stream);
+/* The rows of iteration t = counter[0] (device memory; t + 1 is stored after every thread of the one workgroup has read it):
+ * sigma = fmaf(hi - lo, u, lo), u = (h >> 8) 2^-24, h spaa_jitter_draw's word of (seed, t, b, j, 0) with the first constant 0x2545f491
+ * in place of 0x9e3779b9; lo == hi gives exactly lo.  0 <= lo <= hi <= 2.5, both finite, else hipErrorInvalidValue.  clean0 != 0: draw
+ * 0 of every sample is the identity row. */
+int spaa_blur_draw(uint32_t seed, int32_t* counter, float lo, float hi, int clean0, float* row, int B, int J, spaa_stream_t stream);
+/* out[j][b] = the separable filter of y[j][b] with the taps of row[b][j] along both axes, border replicated: per axis
+ * out[m] = w_0 in[m] + sum_{i=1..r} w_i (in[clamp(m - i, 0, n - 1)] + in[clamp(m + i, 0, n - 1)]), i ascending, each colour channel on
+ * its own in fp32, along the rows (W) first, then along the columns (H).  The pad channel of out is 0.  No clamp and no gate: the filter
+ * is linear and its taps sum to 1.  The identity row copies the colour channels bit for bit.  There is always one input pointer per
+ * draw (J equal pointers give the bits of J distinct copies).  One launch, both passes through LDS. */
+int spaa_blur_fwd(const float* const* y, const float* row, int J, float* const* out, int B, int H, int W, spaa_stream_t stream);
+/* The exact transpose as a gather.  Replicate padding is not self-adjoint: the taps that left the frame come back into the edge pixel.
+ * Per axis, with g zero outside [0, n): z_e = sum_{k=-r..r} w_|k| g_{e-k} for e = -r .. n - 1 + r; g_in[p] = z_p for 0 < p < n - 1,
+ * g_in[0] = sum_{e <= 0} z_e, g_in[n - 1] = sum_{e >= n - 1} z_e (n == 1: every z_e lands in the one pixel).  An edge pixel
+ * evaluates its sum regrouped by input, sum_{m=0..r} T_m g_m with the tail sums T_m = w_m + .. + w_r (mirrored at n - 1; n == 1:
+ * (2 T_0 - w_0) g_0): the same value to rounding at r + 1 products.  The identity row passes g_out through bit for bit.  Along the
+ * columns first, then along the rows.  The pad channel of g_y is 0.  One launch. */
+int spaa_blur_bwd(const float* const* g_out, const float* row, int J, float* const* g_y, int B, int H, int W, spaa_stream_t stream);
+
 /* ---- attention-weighted attack: Grad-CAM of the classifier weights its gradient image ---------------------------
  * No atomics and fixed summation orders: bitwise repeatable.  One launch each, none syncs. */
 /* alpha [B][C] = the spatial mean of a gradient map G [B][HW][cstride] (channels 0 .. C - 1 of each position), positions added in

@@ -20,6 +20,7 @@ def __getattr__(name):
                 'attack_results', 'EnsembleAttackState', 'MultiViewAttackState', 'attack_transfer', 'CaptureJitter', 'JitterAttackState',
                 'capture_survival', 'Attention', 'Transfer', 'transfer_success', 'PoseJitter', 'PoseAttackState', 'pose_survival',
                 'JpegCapture', 'JpegAttackState', 'jpeg_survival', 'jpeg_roundtrip', 'quant_tables', 'Universal',
+                'CaptureBlur', 'BlurAttackState', 'blur_survival', 'gaussian_blur',
                 'UniversalAttackState', 'universal_success'):
         from . import projector_based_attack
         return getattr(projector_based_attack, name)

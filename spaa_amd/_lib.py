@@ -215,6 +215,10 @@ _SIGNATURES = {
     'spaa_jpeg_draw': [C.c_uint32, _p, _i, _i, _i, _p, _i, _i, _p],
     'spaa_jpeg_fwd': [_pp, _p, _i, _i, _pp, _pp, _p, _i, _i, _i, _p],
     'spaa_jpeg_bwd': [_pp, _pp, _p, _i, _i, _i, _pp, _pp, _i, _i, _i, _p],
+    'spaa_blur_rows': [_p, _p, _i, _p],
+    'spaa_blur_draw': [C.c_uint32, _p, _f, _f, _i, _p, _i, _i, _p],
+    'spaa_blur_fwd': [_pp, _p, _i, _pp, _i, _i, _i, _p],
+    'spaa_blur_bwd': [_pp, _p, _i, _pp, _i, _i, _i, _p],
     'spaa_cam_alpha': [_p, _p, _i, _i, _i, _i, _p],
     'spaa_cam_map': [_p, _p, _f, _p, _i, _p, _p, _p, _i, _i, _i, _p],
     'spaa_attention_apply': [_p, _p, _f, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p],

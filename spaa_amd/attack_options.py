@@ -1,4 +1,4 @@
-"""What an attack can be asked for besides the plain SPAA loop -- the option values CaptureJitter, PoseJitter, JpegCapture, Transfer and Universal (Attention is
+"""What an attack can be asked for besides the plain SPAA loop -- the option values CaptureJitter, PoseJitter, JpegCapture, CaptureBlur, Transfer and Universal (Attention is
 spaa_amd.classifier's), the limits of include/spaa_hip.h -- and the check of a request, made before anything is allocated or launched:
 `checked_request` for spaa() and spaa_sweep(), the `_supported` functions for the attack states that are built directly."""
 import dataclasses
@@ -127,6 +127,51 @@ class JpegCapture:
         """spaa_jpeg_draw of this range: fills row [B][J][4] for iteration counter[0] and advances the counter."""
         lo, hi = self.quality_range
         _lib.call('spaa_jpeg_draw', int(self.seed) & 0xffffffff, _lib.ptr(counter), lo, hi, int(bool(clean0)), _lib.ptr(row), B, J)
+
+
+BLUR_RMAX = 8          # SPAA_BLUR_RMAX of include/spaa_hip.h
+BLUR_SIGMA_MAX = 2.5   # the largest sigma whose radius ceil(3 sigma) fits BLUR_RMAX
+
+
+def blur_sigma_range(sigma, who='CaptureBlur'):
+    """(lo, hi) of a sigma that is one number or an ordered pair of numbers, 0 <= lo <= hi <= BLUR_SIGMA_MAX."""
+    pair = tuple(sigma) if isinstance(sigma, (tuple, list)) else (sigma, sigma)
+    if len(pair) != 2 or any(isinstance(s, bool) or not isinstance(s, (int, float)) or not math.isfinite(s) for s in pair):
+        raise ValueError(f'{who}: sigma must be a finite number or a pair of finite numbers, got {sigma!r}')
+    if not 0 <= pair[0] <= pair[1] <= BLUR_SIGMA_MAX:
+        raise ValueError(f'{who}: sigma must be in 0..{BLUR_SIGMA_MAX:g} camera pixels (the radius ceil(3 sigma) is at most {BLUR_RMAX}) '
+                         f'and an ordered pair (low, high), got {sigma!r}')
+    return float(pair[0]), float(pair[1])
+
+
+@dataclasses.dataclass(frozen=True)
+class CaptureBlur:
+    """The camera's lens out of focus: the capture convolved with a Gaussian of `sigma` camera pixels along both axes,
+    the border replicated, sigma drawn uniformly from the range (one number: that sigma; radius ceil(3 sigma) <= BLUR_RMAX, so sigma
+    <= BLUR_SIGMA_MAX).  `draws`: blurred copies attacked at once per iteration (2..4; the first one is the sharp capture), `seed`: of
+    the counter-based generator.  The default range is a guess at "slightly out of focus", not a measurement.  A range that ends at 0
+    is the plain attack and refused."""
+    sigma: object = (0.5, 2.0)
+    draws: int = 3
+    seed: int = 0
+
+    def __post_init__(self):
+        if not 2 <= int(self.draws) <= JITTER_MAX:
+            raise ValueError(f'CaptureBlur: draws must be 2..{JITTER_MAX}, got {self.draws}')
+        _, hi = blur_sigma_range(self.sigma)
+        if isinstance(self.sigma, list):
+            object.__setattr__(self, 'sigma', tuple(self.sigma))   # (hashable)
+        if hi == 0:
+            raise ValueError('CaptureBlur(0): a sigma of 0 is no blur, the plain attack (pass blur=None)')
+
+    @property
+    def sigma_range(self):
+        return blur_sigma_range(self.sigma)
+
+    def draw(self, counter, rows, B, J, clean0):
+        """spaa_blur_draw of this range: fills rows [B][J][12] for iteration counter[0] and advances the counter."""
+        lo, hi = self.sigma_range
+        _lib.call('spaa_blur_draw', int(self.seed) & 0xffffffff, _lib.ptr(counter), lo, hi, int(bool(clean0)), _lib.ptr(rows), B, J)
 
 
 @dataclasses.dataclass(frozen=True)
@@ -350,6 +395,26 @@ def _jpeg_supported(jpeg, pcnet, classifier, storage, focus, attention, jitter, 
                              f'{other.draws} and jpeg.draws = {jpeg.draws}')
 
 
+def _blur_supported(blur, pcnet, classifier, storage, focus, attention, jitter, pose, jpeg, universal, who):
+    """What a blur attack does not serve.  `pcnet` / `classifier`: as spaa() holds them after its own checks; `jitter` / `pose` / `jpeg`:
+    None or checked values; `universal`: None or what the caller passed."""
+    _is_a(blur, 'blur', CaptureBlur, who)
+    _need_one_of_each('lens blur', 'blur', pcnet, classifier, who)
+    _need_classifier('a blur attack', 'a foreign callable can only be attacked without blur', classifier, who)
+    if attention is not None:
+        raise NotImplementedError(f'{who}: attention together with lens blur is not implemented (every draw would need a map of its '
+                                  'own, pulled back through the blur); use attention or blur')
+    _need_f32('with blur', _OWN_SCALE.format('draws'), storage, who)
+    _no_focus('blur', focus, who)
+    for name, other in (('pose', pose), ('jitter', jitter), ('jpeg', jpeg)):
+        if other is not None and int(other.draws) != int(blur.draws):
+            raise ValueError(f'{who}: {name} and blur are applied draw by draw and must name the same draws, got {name}.draws = '
+                             f'{other.draws} and blur.draws = {blur.draws}')
+    if universal is not None:
+        raise NotImplementedError(f'{who}: universal together with blur is not implemented (the draws of a sample and the members '
+                                  'of a group would need a rule of their own); use universal or blur')
+
+
 def _attention_checked(attention, storage, who):
     """An attack state's own check of its `attention` (the entry points say more, earlier: _attention_supported)."""
     if attention is not None:
@@ -400,7 +465,8 @@ def _universal_supported(universal, pcnet, classifier, storage, jitter, pose, jp
     _need_f32('for a universal projection', _OWN_SCALE.format('members'), storage, who)
 
 
-def checked_request(who, pcnet, classifier, cam_scene, storage, focus, jitter, pose, attention, transfer, jpeg=None, universal=None):
+def checked_request(who, pcnet, classifier, cam_scene, storage, focus, jitter, pose, attention, transfer, jpeg=None, universal=None,
+                    blur=None):
     """The request of spaa() / spaa_sweep() (`who`), checked in the one order that decides which error a caller sees; returns the
     normalised (pcnet, classifier, cam_scene): unwrapped, a sequence of one collapsed, a list where there are several."""
     pcnet, classifier = _unwrap(pcnet), _unwrap(classifier)
@@ -420,6 +486,8 @@ def checked_request(who, pcnet, classifier, cam_scene, storage, focus, jitter, p
         _pose_supported(pose, pcnet, classifier, storage, focus, attention, jitter, who)
     if jpeg is not None:
         _jpeg_supported(jpeg, pcnet, classifier, storage, focus, attention, jitter, pose, who)
+    if blur is not None:
+        _blur_supported(blur, pcnet, classifier, storage, focus, attention, jitter, pose, jpeg, universal, who)
     if attention is not None:
         _attention_supported(attention, classifier, storage, jitter, who)
     if transfer is not None:

@@ -1,6 +1,6 @@
 """The device-side states of the batched SPAA attack: AttackState (one PCNet, one classifier), EnsembleAttackState (several classifiers),
 MultiViewAttackState (several PCNets), UniversalAttackState (groups of samples that share their projector image) and DrawAttackState (random draws of the camera image through a chain of stages:
-JitterAttackState, PoseAttackState, JpegAttackState).  Lines quoted as :NNN are the reference's projector_based_attack.py."""
+JitterAttackState, PoseAttackState, JpegAttackState, BlurAttackState).  Lines quoted as :NNN are the reference's projector_based_attack.py."""
 import ctypes
 
 import torch
@@ -8,7 +8,7 @@ import torch
 from . import _lib
 from .models import to_nhwc4, to_nchw
 from .attack_options import (JPEG_SUBSAMPLINGS, _unwrap, _ensemble_members, _view_pcnets, _views_supported, _jitter_supported,
-                             _pose_supported, _jpeg_supported, _attention_checked, _transfer_checked, _universal_supported)
+                             _pose_supported, _jpeg_supported, _blur_supported, _attention_checked, _transfer_checked, _universal_supported)
 
 
 def _is_scalar(v):
@@ -656,6 +656,35 @@ class JpegStage:
         return self.grads
 
 
+class BlurStage:
+    """The camera's lens blur as a stage of a draw chain, behind the pose warp and in front of the sensor and the codec:
+    its device-side counter, the tap rows `blur_rows` of spaa_blur_draw, J blurred images, J gradient images.  The filter is linear:
+    its adjoint needs neither its input nor a gate."""
+
+    def __init__(self, blur):
+        self.options, self.draws = blur, int(blur.draws)
+
+    def build(self, st, first):
+        B, J, dev = st.B, st.K, st.dev
+        self.counter = torch.zeros(1, dtype=torch.int32, device=dev)        # the iteration number the next draw reads
+        self.rows = torch.zeros(B, J, 12, device=dev)
+        self.ims = [torch.zeros_like(st.g_adv) for _ in range(J)]
+        self.grads = [torch.zeros_like(st.g_adv) for _ in range(J)]
+        return dict(blur_rows=self.rows, blur_ims=self.ims, blur_grads=self.grads,
+                    **{'counter' if first else 'blur_counter': self.counter})
+
+    def forward(self, st, src):
+        """Draws this iteration's sigmas, then draw j of `src`: the camera image y, or (behind another stage) that stage's image j."""
+        self.options.draw(self.counter, self.rows, st.B, st.K, clean0=True)
+        src = src if isinstance(src, list) else [src] * st.K
+        _lib.call('spaa_blur_fwd', _lib.ptr_array(src), _lib.ptr(self.rows), st.K, _lib.ptr_array(self.ims), st.B, st.eng.Hc, st.eng.Wc)
+        return self.ims
+
+    def backward(self, st, gs):
+        _lib.call('spaa_blur_bwd', _lib.ptr_array(gs), _lib.ptr(self.rows), st.K, _lib.ptr_array(self.grads), st.B, st.eng.Hc, st.eng.Wc)
+        return self.grads
+
+
 class DrawAttackState(EnsembleAttackState):
     """One batched attack against J random draws of the camera image per iteration: EnsembleAttackState whose members are J leased
     engines of ONE classifier, member j looking at draw j of y = PCNet(x, s).  The draws come from a chain of `stages` applied to y,
@@ -736,3 +765,24 @@ class JpegAttackState(DrawAttackState):
         stages = ([PoseStage(pose)] if pose is not None else []) + ([JitterStage(jitter)] if jitter is not None else [])
         super().__init__(pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, device, stages + [JpegStage(jpeg)], storage,
                          transfer)
+
+
+class BlurAttackState(DrawAttackState):
+    """The draw attack through the camera's lens blur: J = blur.draws defocused copies per iteration at drawn sigmas (spaa_blur_draw,
+    spaa_blur_fwd, spaa_blur_bwd).  With `pose`, `jitter` and / or `jpeg` (of the same `draws`) draw j is
+    Jpeg_j(Jitter_j(Blur_j(Pose_j(y)))), the optical order: geometry, lens, sensor, codec."""
+
+    def __init__(self, pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, device, blur, storage='f32', pose=None,
+                 jitter=None, jpeg=None, transfer=None):
+        pcnet, classifier = _unwrap(pcnet), _unwrap(classifier)
+        if jitter is not None:
+            _jitter_supported(jitter, pcnet, classifier, storage, False, 'BlurAttackState')
+        if pose is not None:
+            _pose_supported(pose, pcnet, classifier, storage, False, None, jitter, 'BlurAttackState')
+        if jpeg is not None:
+            _jpeg_supported(jpeg, pcnet, classifier, storage, False, None, jitter, pose, 'BlurAttackState')
+        _blur_supported(blur, pcnet, classifier, storage, False, None, jitter, pose, jpeg, None, 'BlurAttackState')
+        self.pose, self.jitter, self.jpeg, self.blur = pose, jitter, jpeg, blur
+        stages = (([PoseStage(pose)] if pose is not None else []) + [BlurStage(blur)] +
+                  ([JitterStage(jitter)] if jitter is not None else []) + ([JpegStage(jpeg)] if jpeg is not None else []))
+        super().__init__(pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, device, stages, storage, transfer)

@@ -216,6 +216,30 @@ def jpeg_survival(ims, classifier, target_idx, targeted, crop_sz, *, qualities=(
     return out
 
 
+def blur_survival(ims, classifier, target_idx, targeted, crop_sz, *, sigmas=(0.5, 1.0, 1.5, 2.0, 2.5)):
+    """Which camera images still succeed through a defocused lens: bool [len(sigmas), N] for the images `ims` [N,3,H,W], one class id
+    per image in `target_idx` and `targeted` (one flag, or one per image), by the success rule of capture_survival.  The evaluation
+    hook of a blur attack, and the answer to a classifier that sits behind Gaussian smoothing of its input.  Row s is every image
+    through the Gaussian of sigmas[s] camera pixels (spaa_blur_fwd through gaussian_blur).  Deterministic: nothing is
+    drawn."""
+    from .blur import gaussian_blur
+    n = ims.shape[0]
+    tgt = np.asarray([int(t) for t in target_idx])
+    tg = np.full(n, bool(targeted)) if np.ndim(targeted) == 0 else np.asarray([bool(t) for t in targeted])
+    if tgt.shape != (n,) or tg.shape != (n,) or len(sigmas) < 1:
+        raise ValueError(f'blur_survival: {n} images, {tgt.size} targets, {tg.size} targeted flags, {len(sigmas)} sigmas')
+    dev = classifier.device
+    if dev.type != 'cuda':
+        raise RuntimeError(f'blur_survival runs on the GPU only (no CPU fallback); the classifier is on {dev}')
+    out = np.zeros((len(sigmas), n), dtype=bool)
+    with _lib.on_device(dev):
+        y = ims.to(dev).float()
+        for s, sigma in enumerate(sigmas):
+            top1 = _sorted_classes(classifier, [gaussian_blur(y, float(sigma))], crop_sz)[0][:, 0]
+            out[s] = np.where(tg, top1 == tgt, top1 != tgt)
+    return out
+
+
 def transfer_success(cam, classifier, target_idx, targeted, crop_sz, p_thresh=0.9):
     """Which camera images `cam` [B,3,H,W] fool `classifier`, by the success rule of the attack's own decision (spaa_decide): bool [B];
     one class id per image in `target_idx` and `targeted` (one flag, or one per image): top-1 == target with p1 > `p_thresh`, else

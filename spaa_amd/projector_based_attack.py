@@ -21,12 +21,15 @@ from . import _lib
 from .models import PCNet, to_nhwc4, to_nchw   # noqa: F401
 from .classifier import Attention, Classifier   # noqa: F401  (Attention: re-exported)
 from .attack_options import (ENS_MAX, VIEWS_MAX, JITTER_MAX, TRANSFER_RMAX, UNIVERSAL_MAX, POSE_MAX_ROTATE, POSE_MAX_ZOOM,   # noqa: F401
-                             POSE_MAX_TILT, POSE_MAX_SHIFT, CaptureJitter, PoseJitter, JpegCapture, Transfer, Universal,
+                             POSE_MAX_TILT, POSE_MAX_SHIFT, CaptureJitter, PoseJitter, JpegCapture, CaptureBlur, Transfer, Universal,
+                             BLUR_RMAX, BLUR_SIGMA_MAX,
                              checked_request, _unwrap, _ensemble_members, _universal_supported,
-                             _view_pcnets, _views_supported, _jitter_supported, _pose_supported, _jpeg_supported, _attention_checked,
+                             _view_pcnets, _views_supported, _jitter_supported, _pose_supported, _jpeg_supported, _blur_supported,
+                             _attention_checked,
                              _attention_supported, _transfer_checked, _transfer_supported)
 from .attack_state import (AttackState, EnsembleAttackState, MultiViewAttackState, UniversalAttackState, DrawAttackState,   # noqa: F401
-                           JitterAttackState, PoseAttackState, JpegAttackState, JitterStage, PoseStage, JpegStage, _is_scalar, _require_gpu,
+                           JitterAttackState, PoseAttackState, JpegAttackState, BlurAttackState, JitterStage, PoseStage, JpegStage, BlurStage,
+                           _is_scalar, _require_gpu,
                            _scene_batch)
 
 # B * Hc * Wc up to which spaa() replays the iteration as a captured HIP graph (0 disables); above it the GPU is busy for
@@ -50,13 +53,16 @@ def ssim_weight(stealth_loss):
 
 
 def _attack_state(pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, device, storage, focus, jitter=None,
-                  attention=None, transfer=None, pose=None, jpeg=None, universal=None):
+                  attention=None, transfer=None, pose=None, jpeg=None, universal=None, blur=None):
     """AttackState for one Classifier, EnsembleAttackState for a checked list of several, MultiViewAttackState for a checked list of
     PCNets (with their list of scenes), JitterAttackState for one Classifier with a CaptureJitter, PoseAttackState for one Classifier
     with a PoseJitter (with or without a CaptureJitter), JpegAttackState for one Classifier with a JpegCapture (with or without either of
-    the other two); the last three take no `attention`; UniversalAttackState for one PCNet and one Classifier with a Universal.  Each of
+    the other two), BlurAttackState for one Classifier with a CaptureBlur (with or without any of the other three); the last four take no
+    `attention`; UniversalAttackState for one PCNet and one Classifier with a Universal.  Each of
     them takes `transfer`."""
     args = (pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, device)
+    if blur is not None:
+        return BlurAttackState(*args, blur, storage=storage, pose=pose, jitter=jitter, jpeg=jpeg, transfer=transfer)
     if universal is not None:
         return UniversalAttackState(*args, universal, storage=storage, focus=focus, attention=attention, transfer=transfer)
     if jpeg is not None:
@@ -74,7 +80,7 @@ def _attack_state(pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_
 
 def spaa(pcnet, classifier, imagenet_labels, target_idx, targeted, cam_scene, d_thr, stealth_loss, device, setup_info,
          *, iters=50, adv_lr=2, col_lr=1, p_thresh=0.9, trace=None, verbose=False, storage='f32', focus=False, jitter=None,
-         attention=None, transfer=None, pose=None, jpeg=None, universal=None):
+         attention=None, transfer=None, pose=None, jpeg=None, universal=None, blur=None):
     """Stealthy Projector-based Adversarial Attack (SPAA Algorithm 1) — see module docstring.
 
     :param pcnet: spaa_amd.PCNet (optionally wrapped in DataParallel-like `.module`), or a list / tuple of 2..4 of them: the same projector
@@ -115,6 +121,13 @@ def spaa(pcnet, classifier, imagenet_labels, target_idx, targeted, cam_scene, d_
         are equal, `cam_infer_best` is per sample; the trace entries are (state, stats, uni_state, uni_stats), where state[:, 3]
         counts the group's fooled members.  attack_summary.universal_success projects the result onto scenes held out from the
         attack.  None (default): launch for launch as before
+    :param blur: a CaptureBlur: ONE projection against `blur.draws` defocused copies of the camera image per iteration, each through a
+        Gaussian lens blur of a sigma drawn from `blur.sigma` (camera pixels, border replicated), the first of them the sharp capture
+        (BlurAttackState; one PCNet, one Classifier, fp32 storage, no `focus`, no `attention`, no `universal`).  With
+        `pose`, `jitter` and / or `jpeg` of the same `draws` the stages run in the optical order, geometry, lens, sensor, codec: draw j
+        is Jpeg_j(Jitter_j(Blur_j(Pose_j(y)))).  Combines with `transfer` and every stealth-loss string; the decision's stealth loss
+        and `cam_best` stay the clean inference's.  attack_summary.blur_survival replays a result through fixed sigmas.  None
+        (default): launch for launch as before
     :param imagenet_labels: dict idx -> name (only used when verbose)
     :param target_idx: list of B class ids (true label if untargeted)
     :param targeted: bool
@@ -129,7 +142,7 @@ def spaa(pcnet, classifier, imagenet_labels, target_idx, targeted, cam_scene, d_
     :return: (cam_infer_best [B,3,Hc,Wc], prj_adv_best [B,3,Hp,Wp] in [0,1]); for several views ([cam_infer_best per view], prj_adv_best)
     """
     pcnet, classifier, cam_scene = checked_request('spaa', pcnet, classifier, cam_scene, storage, focus, jitter, pose, attention, transfer,
-                                                   jpeg, universal)
+                                                   jpeg, universal, blur)
     if universal is not None:   # (`targeted` / `d_thr` may be one per sample here: groups may differ from each other, not within)
         for name, value in (('targeted', targeted), ('d_thr', d_thr)):
             if not _is_scalar(value):
@@ -140,7 +153,7 @@ def spaa(pcnet, classifier, imagenet_labels, target_idx, targeted, cam_scene, d_
         return _spaa_foreign_classifier(pcnet, classifier, imagenet_labels, target_idx, targeted, cam_scene, d_thr,
                                         stealth_loss, device, setup_info, iters, adv_lr, col_lr, p_thresh, trace)
     st = _attack_state(pcnet, classifier, target_idx, cam_scene, stealth_loss, setup_info, device, storage, focus, jitter, attention,
-                       transfer, pose, jpeg, universal)
+                       transfer, pose, jpeg, universal, blur=blur)
 
     def report(i):
         if i % 30 == 0 or i == iters - 1:
@@ -234,7 +247,7 @@ def split_sweep(samples, ncfg, chunk_results):
 
 def spaa_sweep(pcnet, classifier, imagenet_labels, cam_scene, setup_info, device, configs, *, iters=50, adv_lr=2, col_lr=1,
                p_thresh=0.9, max_batch=64, storage='f32', trace=None, focus=False, jitter=None, attention=None, transfer=None,
-               pose=None, jpeg=None, universal=None):
+               pose=None, jpeg=None, universal=None, blur=None):
     """Several SPAA attacks on one PCNet, scene and classifier as few batched attacks (the reference's driver makes one spaa() call
     per configuration: projector_based_attack.py:24-148).  `configs`: [(stealth_loss, d_thr, targeted, target_idx), ...]; returns one
     (cam_infer_best, prj_adv_best) per config, in order -- what spaa(pcnet, classifier, imagenet_labels, target_idx, targeted,
@@ -250,14 +263,14 @@ def spaa_sweep(pcnet, classifier, imagenet_labels, cam_scene, setup_info, device
     `attention`: an Attention, as in spaa(): every chunk is an attention-weighted attack.  `transfer`: a Transfer, as in spaa(): every
     chunk's adversarial steps follow the smoothed, momentum-accumulated direction (each chunk's momentum starts at zero).  `pose`: a
     PoseJitter, as in spaa(): every chunk is a pose attack with that seed (the draws of a sample depend on its place in its chunk).
-    `jpeg`: a JpegCapture, as in spaa(): every chunk is a JPEG attack with that seed, in the same way.  `universal` is refused: the
+    `jpeg`: a JpegCapture, as in spaa(): every chunk is a JPEG attack with that seed, in the same way.  `blur`: a CaptureBlur, as in spaa(): every chunk is a blur attack with that seed, in the same way.  `universal` is refused: the
     sweep batches configurations of ONE scene, a universal projection is over several."""
     if universal is not None:
         raise NotImplementedError('spaa_sweep: universal= is not implemented (the sweep batches the configurations of one scene; a '
                                   'universal projection shares one image among several scenes): call spaa(..., universal=...)')
     samples, chunks = plan_sweep(configs, max_batch)
     pcnet, classifier, cam_scene = checked_request('spaa_sweep', pcnet, classifier, cam_scene, storage, focus, jitter, pose, attention,
-                                                   transfer, jpeg)
+                                                   transfer, jpeg, None, blur)
     if not isinstance(classifier, (Classifier, list)):
         raise TypeError('spaa_sweep needs a spaa_amd.Classifier')
     _require_gpu(device, 'spaa_sweep')
@@ -274,7 +287,7 @@ def spaa_sweep(pcnet, classifier, imagenet_labels, cam_scene, setup_info, device
     for a, b in chunks:
         part = samples[a:b]
         st = _attack_state(pcnet, classifier, [t for *_, t in part], sc, [s[1] for s in part], setup_info, device, storage, focus,
-                           jitter, attention, transfer, pose, jpeg)
+                           jitter, attention, transfer, pose, jpeg, blur=blur)
         tr = [] if trace is not None else None
         _run(st, [s[3] for s in part], [s[2] for s in part], iters, adv_lr, col_lr, p_thresh, tr)
         if trace is not None:
@@ -374,8 +387,9 @@ spaa_attack = spaa  # name used by BASELINE.json's north_star
 from .attack_driver import (ATTACKERS, MODEL_TRAIN_CFG, AttackSetup, get_attacker_cfg, to_attacker_cfg_str,   # noqa: E402,F401
                             run_projector_based_attack, _run_one_pixel_de, project_capture_real_attack)
 from .jpeg import jpeg_roundtrip, quant_tables   # noqa: E402,F401
+from .blur import gaussian_blur   # noqa: E402,F401
 from .attack_summary import (SUMMARY_STEALTH_LOSSES, SUMMARY_D_THRESHES, SUMMARY_CLASSIFIERS, SUMMARY_CHUNK,   # noqa: E402,F401
                              SUMMARY_COLUMNS, MONTAGE_CHUNK, attack_success, write_stats, _sorted_classes, _nonempty,
-                             attack_results, attack_transfer, capture_survival, pose_survival, jpeg_survival, transfer_success,
+                             attack_results, attack_transfer, capture_survival, pose_survival, jpeg_survival, blur_survival, transfer_success,
                              universal_success,
                              summarize_single_attacker, summarize_all_attackers)
